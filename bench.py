@@ -365,6 +365,63 @@ def forcing_algorithmic_bytes(st):
 PARITY_COLS = ["cx", "cy", "alpha", "u", "v", "xi", "height", "mass", "moment", "p_dxdt", "p_dydt", "p_dalphadt", "p_dudt", "p_dvdt",
                "p_dxidt", "fxOA", "fyOA", "trqOA", "overarea", "coll_fx", "coll_fy", "coll_trq", "stress_accum", "stress_instant", "strain"]
 
+DUMP_COLS = PARITY_COLS + ["area", "rmax", "hflx_factor"]
+DUMP_MAX_BYTES = 64 << 20
+
+
+def floe_outputs(hw, n):
+    """what a caller of the timed path receives for floes 0..n-1 of a context: the state columns, the ids and status,
+    and the rings (vertex count per floe + coordinates), as float64 host arrays"""
+    import numpy as np
+    out = {f: np.asarray(hw.get(f)[:n], np.float64) for f in DUMP_COLS}
+    fid, _, status = hw.ids()
+    out["id"] = fid[:n].astype(np.float64); out["status"] = status[:n].astype(np.float64)
+    off, vx, vy = hw.rings()
+    out["ring_n"] = np.diff(off[:n + 1]).astype(np.float64)
+    out["ring_x"] = np.asarray(vx[off[0]:off[n]], np.float64); out["ring_y"] = np.asarray(vy[off[0]:off[n]], np.float64)
+    return out
+
+
+def order_floe_outputs(parts):
+    """the owned floes of every tile (dicts of floe_outputs + "gidx") merged into one field in global floe order"""
+    import numpy as np
+    g = np.concatenate([p_["gidx"] for p_ in parts]); order = np.argsort(g, kind="stable")
+    out = {k: np.concatenate([p_[k] for p_ in parts])[order] for k in parts[0] if k not in ("gidx", "ring_x", "ring_y")}
+    cnt = np.concatenate([p_["ring_n"] for p_ in parts]).astype(np.int64)
+    start = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+    idx = np.concatenate([np.arange(s, s + c) for s, c in zip(start[order], cnt[order])]) if len(cnt) else np.zeros(0, np.int64)
+    for k in ("ring_x", "ring_y"):
+        out[k] = np.concatenate([p_[k] for p_ in parts])[idx]
+    return out
+
+
+def write_outputs(dirname, out, grids=None, seed=20240917):
+    """DIR/<name>.npy for every floe array (and every grid of `grids`); above DUMP_MAX_BYTES in all, a fixed seeded sample of
+    the floes (their indices in floe_sample.npy) is written instead of the whole field"""
+    import numpy as np
+    grids = grids or {}
+    n = len(out["cx"])
+    per_floe = sum(a.nbytes for k, a in out.items() if k not in ("ring_x", "ring_y")) / max(n, 1)
+    per_vert = 16.0
+    total = sum(a.nbytes for a in out.values()) + sum(a.nbytes for a in grids.values())
+    sample = None
+    if total > DUMP_MAX_BYTES:
+        budget = 0.95 * DUMP_MAX_BYTES - sum(a.nbytes for a in grids.values())
+        mean_verts = len(out["ring_x"]) / max(n, 1)
+        k = max(1, min(n, int(budget / (per_floe + 8 + per_vert * mean_verts * 1.25))))
+        sample = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, k, replace=False))
+        cnt = out["ring_n"].astype(np.int64); start = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+        vidx = np.concatenate([np.arange(start[i], start[i] + cnt[i]) for i in sample])
+        out = {k_: (a[vidx] if k_ in ("ring_x", "ring_y") else a[sample]) for k_, a in out.items()}
+        out["floe_sample"] = sample.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    written = 0
+    for k_, a in list(out.items()) + list(grids.items()):
+        np.save(os.path.join(dirname, k_ + ".npy"), np.ascontiguousarray(a, np.float64))
+        written += a.size * 8
+    return {"dir": dirname, "arrays": len(out) + len(grids), "bytes": written, "floes": n,
+            "floes_written": n if sample is None else int(len(sample))}
+
 
 def oracle_parity(cfg, device, steps=2, coupling_dt=1):
     """Parity evidence for the very field the bench times (N = 1 line): add_ghosts! + timestep_collisions! of the HIP engine against the
@@ -451,6 +508,9 @@ def main():
                     "in one context on this GPU -- the denominator of the strong-scaling curve, which the N > 1 lines are measured on")
     ap.add_argument("--parity-steps", type=int, default=3, help="tiled runs: steps after which the owned columns of all ranks are compared with a "
                     "single-context run of the same field on rank 0 (tiled_parity in the line); 0: skip")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path computed in its last "
+                    "step (floe state columns, ids / status, rings; with --two-way the ocean stress grids) as DIR/<name>.npy, float64, at most "
+                    "64 MB in all (a fixed seeded sample of the floes above that); the inputs are fixed by the arguments")
     args = ap.parse_args()
 
     # `python3 bench.py --gpus N` with no launcher around it: this process becomes the launcher -- N fresh children, one per GPU, before
@@ -643,6 +703,27 @@ def main():
             el = float(t.item())
         blocks.append(el)
         log(f"block {rep}: {1e3 * el / args.steps:.4f} ms/step")
+    dumped = None
+    if args.dump_outputs:
+        # the state the timed path leaves after its last step, read back before anything else runs on the context
+        if not tiled:
+            if rank == 0:
+                grids = {}
+                if args.two_way:
+                    grids = dict(zip(("ocean_tau_x", "ocean_tau_y", "ocean_si_frac", "ocean_hflx_factor"), hw.ocean_stress()))
+                dumped = write_outputs(args.dump_outputs, floe_outputs(hw, hw.M), grids)
+        else:
+            mine = floe_outputs(hw, len(tw.gidx)); mine["gidx"] = tw.gidx.copy()
+            if dist is not None:
+                parts = [None] * world if rank == 0 else None
+                dist.gather_object(mine, parts, dst=0)
+            else:
+                parts = [mine]
+            if rank == 0:
+                dumped = write_outputs(args.dump_outputs, order_floe_outputs(parts))
+            del mine, parts
+        if rank == 0:
+            log(f"outputs of the last timed step: {dumped}")
     el = float(np.median(blocks))
     if kt is None:                            # (the event-timed block was the last one)
         kt = hw.kernel_times(); st_ev = hw.stats(); forcing_where = hw.forcing_launch()
@@ -747,6 +828,8 @@ def main():
         }
         if parity_line is not None:
             out["parity"] = parity_line
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if tiled_parity is not None:
             out["tiled_parity"] = tiled_parity
         if one_gpu is not None:
