@@ -1756,7 +1756,9 @@ bool pipeline_eligible(const sz_ctx* c, int nsteps, bool coll, bool sg, bool gi,
 // A batch of pipelined steps: L1(s) = narrow(s) | GEO(s) | forcings(s), L2(s) = VEL(s) | search(s + 1).  Same contract as the loop of sz_step
 // it replaces: h = the counter block after the batch, *done = the steps that ran; the context's state is complete when it returns (rows of
 // the last step assembled, strain evaluated, ghosts detached).
-int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling_dt, int flags, bool periodic, bool gi, int* h, int* done_out) {
+// *rest_out: the lists grew past what the pipelined launches are compiled for (MAXNB); the batch handed back the state at step *done_out and the
+// caller runs the rest on the three-launch steps.
+int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling_dt, int flags, bool periodic, bool gi, int* h, int* done_out, bool* rest_out) {
   State& S0 = c->S;
   const int N = c->hostN;
   const bool user_stop = !(flags & SZ_NO_STOP);
@@ -1895,6 +1897,19 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
         (void)hipMemsetAsync(S0.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream); (void)hipMemsetAsync(S0.cnt + C_STOP, 0, sizeof(int), c->stream);
         (void)hipMemsetAsync(S0.cnt + C_FRCSTOP, 0, sizeof(int), c->stream);
         (void)hipMemsetAsync(c->facc_buf, 0, (size_t)FX_WORDS * S0.capM * sizeof(long long), c->stream);
+        if (S0.maxnb > MAXNB) {
+          // the prologue's and the L2 launch's neighbour search are instantiated for MAXNB-wide rows (neighbors_body's row stride): with the
+          // wider lists the steps from sr on are the three-launch ones.  The state of step sr is set par(sr)'s (adopted above); the ghost links
+          // GEO(sr - 1) made go, the caller's batch seeds its own from the parents as they lie (as sz_step does after growing its lists)
+          Clears cl(c);
+          for (int b = 0; b < 2; b++) { cl.add(c->pb[b].ngh, (size_t)S0.capM * sizeof(int)); cl.add(c->pb[b].gh, (size_t)MAX_GHOSTS * S0.capM * sizeof(int), 0xff); }
+          cl.launch(c);
+          HIPCHK(c, hipStreamSynchronize(c->stream));
+          if (getenv("SZ_VERBOSE")) fprintf(stderr, "[subzero-hip] pipelined batch: lists outgrew its neighbour capacity in step %d of %d, the rest on the three-launch steps\n", sr + 1, nsteps);
+          c->grid_live = false; c->crec_current = false; c->callid = callid0 + sr;
+          *done_out = sr; *rest_out = true;
+          return leave(SZ_OK);
+        }
         s0 = sr; need_prologue = true;
         continue;
       }
@@ -2074,9 +2089,17 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   int pipe_done = -1;
   if (pipe) {
     c->S.stop_on_tags = (flags & SZ_NO_STOP) ? 0 : 1;
-    int rcp = step_batch_pipelined(c, nsteps, tstep0, dt, coupling_dt, flags, periodic, gi, h, &pipe_done);
+    bool rest = false;
+    int rcp = step_batch_pipelined(c, nsteps, tstep0, dt, coupling_dt, flags, periodic, gi, h, &pipe_done, &rest);
     c->S.stop_on_tags = (flags & SZ_NO_STOP) ? 0 : 1;
     if (rcp) { leave(); return rcp; }
+    if (rest) {          // the lists outgrew the pipelined launches in step pipe_done: the rest of the batch as a batch of its own (not eligible now)
+      leave();
+      int more = 0;
+      const int rc = sz_step(c, nsteps - pipe_done, tstep0 + pipe_done, dt, coupling_dt, flags, &more);
+      if (steps_done) *steps_done = pipe_done + more;
+      return rc;
+    }
   }
   const int callid0 = c->callid; if (!pipe) c->callid += nsteps;          // (step s of this batch is collision call callid0 + s + 1, also when it is run again)
   for (int s0 = 0, mid = 0; !pipe;) {

@@ -175,7 +175,9 @@ __device__ __forceinline__ void vel_body(State S, const Params& P, const PipeAlt
     if (st_dirty) S.status[i] = st_new;
     if (frc_rm || st_new != SZ_ACTIVE) {
       if (frc_rm) { S.status[i] = SZ_REMOVE; st_new = SZ_REMOVE; }
-      if (step > 0 && S.stop_on_tags) S.cnt[C_STOP] = step;          // (request_stop for THIS step: the State carries the search's number)
+      // (request_stop for THIS step: the State carries the search's number.  A batch that runs through restarts on a removal by the forcings
+      // too -- their C_FRCSTOP hint has already made the search of step t + 1 in this launch return, so the host must start that step afresh)
+      if (step > 0 && (S.stop_on_tags || (frc_rm && S.restart_on_tags))) S.cnt[C_STOP] = step;
     }
     {          // calc_stress! / _update_stress_accum! (update_floe.jl:392-414, stress_calculators.jl:118-122)
       const double l = P.lambda;

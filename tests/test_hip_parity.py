@@ -666,6 +666,24 @@ def _tag_scenario(w, kind):
     return w
 
 
+def _offgrid_scenario(w):
+    """open boundaries on all four sides and an ocean / atmosphere grid over the western 60 % of the domain: floe 0 drifts east with the
+    ocean until none of its sub-floe points is on the grid (still well inside the domain) and the forcings tag it remove (coupling.jl:1507-1508,
+    at step 3 with coupling every step); floes 1-5 stay on the grid in two clusters that are in contact all along"""
+    from subzero_jl_amd import fields
+    sq = lambda x0, y0, s=4e3: np.array([[x0, y0], [x0, y0 + s], [x0 + s, y0 + s], [x0 + s, y0], [x0, y0]])
+    w.set_consts(E=1e3); w.set_settings()
+    w.set_domain([0, 0, 0, 0], 0.0, 1e5, 0.0, 1e5)
+    w.set_grid_fields(6, 10, 0.0, 6e4, 0.0, 1e5, 20.0, 0.0, 0.0, 0.0, 0.0)
+    rings = [sq(5.95e4, 5e4), sq(1.0e4, 2.0e4), sq(1.38e4, 2.05e4), sq(1.0e4, 2.38e4), sq(3e4, 7e4), sq(3.38e4, 7.1e4)]
+    for i, r in enumerate(rings):
+        w.add_floe(r, 0.5)
+        c = r[:4].mean(0)
+        w.set_subpoints(i, *fields.subgrid_points(r, c[0], c[1], 1e3))
+    w.set("u", np.full(len(rings), 20.0))
+    return w
+
+
 def _ab_worlds(build, env_off):
     """two contexts on the same input: the default engine and the one with the switches of env_off in the environment (read at sz_create)"""
     import os
@@ -691,7 +709,8 @@ def _assert_worlds_bit_equal(a, b, fields=None):
     assert np.array_equal(pa[0], pb[0]) and np.array_equal(pa[1], pb[1])
 
 
-@pytest.mark.parametrize("scenario", ["dense", "fast-through", "fast-stops", "fuse-stop", "retry-pause", "tagged-before", "walls", "open-stop"])
+@pytest.mark.parametrize("scenario", ["dense", "fast-through", "fast-stops", "fuse-stop", "retry-pause", "tagged-before", "walls", "open-stop",
+                                      "frc-offgrid-through", "frc-offgrid-stop", "coupling-every-10"])
 def test_pipelined_steps_equal_the_three_launch_steps(scenario):
     """Pipelined resident steps (csrc/sz_pipeline.hpp: narrow phase | next geometry, then update | next neighbour search -- two launches per
     timestep) against the three-launch steps (SZ_PIPELINE=0), bit for bit: every column, the rings, floe.interactions, the pair list, the status
@@ -700,9 +719,14 @@ def test_pipelined_steps_equal_the_three_launch_steps(scenario):
     with the tag stop (the state handed back has the parents un-swapped again); fuse-stop: the reference's stop on a fuse in the middle of a
     batch; retry-pause: the pause for the largest narrow variant inside a pipelined step; tagged-before: a parent already tagged when the batch
     starts (its first step runs on its own); walls: configs[3]'s kind of field -- four collision walls and the strait's topography, the element
-    items of the next step made beside the update; open-stop: a floe drifting through an open boundary (tagged remove, collisions.jl:438)."""
+    items of the next step made beside the update; open-stop: a floe drifting through an open boundary (tagged remove, collisions.jl:438);
+    frc-offgrid-through / -stop: a floe that drifts off a forcing grid that covers part of the domain is tagged remove by the forcings
+    (coupling.jl:1507-1508) while other floes are in contact -- in batches that run through (the step behind the tag must still search its
+    neighbours, also while the tagged floe stays off the grid; the state is also held to the oracle) and with the tag stop; coupling-every-10:
+    the dense field coupled every tenth step (the reference's default) in batches that start off that phase and cross coupling steps."""
     from subzero_jl_amd import fields
-    if scenario in ("dense", "fast-through", "fast-stops", "tagged-before"):
+    t = 0; cdt = 1
+    if scenario in ("dense", "fast-through", "fast-stops", "tagged-before", "coupling-every-10"):
         cfg = fields.make_config(n_floes=1500, seed=77, concentration=0.8)
         def build(w):
             fields.build_world(w, cfg)
@@ -714,7 +738,14 @@ def test_pipelined_steps_equal_the_three_launch_steps(scenario):
                 w.set_status(st)
             return w
         dt = cfg["dt"]
-        plan = {"dense": [(25, True), (6, True)], "fast-through": [(9, False), (14, False)], "fast-stops": [(12, True)] * 6, "tagged-before": [(8, True)]}[scenario]
+        plan = {"dense": [(25, True), (6, True)], "fast-through": [(9, False), (14, False)], "fast-stops": [(12, True)] * 6, "tagged-before": [(8, True)],
+                "coupling-every-10": [(6, False), (9, False), (12, True)]}[scenario]
+        if scenario == "coupling-every-10":
+            t = 3; cdt = 10                  # steps 3-8, 9-17, 18-29: steps 10 and 20 are coupled inside batches
+    elif scenario.startswith("frc-offgrid"):
+        build = _offgrid_scenario; dt = 10
+        plan = [(10, False), (6, False)] if scenario.endswith("through") else [(12, True)]
+        ow = _offgrid_scenario(omk()) if scenario.endswith("through") else None
     elif scenario == "walls":
         cfg = fields.make_config(n_floes=900, seed=5, walls=True, topography=True, ocean="strait")
         build = lambda w: fields.build_world(w, cfg); dt = cfg["dt"]; plan = [(20, True), (7, False)]
@@ -725,14 +756,18 @@ def test_pipelined_steps_equal_the_three_launch_steps(scenario):
     else:
         build = _retry_scenario; dt = 10; plan = [(8, False), (5, False)]
     a, b = _ab_worlds(build, {"SZ_PIPELINE": "0"})
-    t = 0; ran_pipelined = False
+    ran_pipelined = False
     for n, stop in plan:
         coupling = scenario not in ("fuse-stop", "retry-pause", "open-stop")
-        da = a.run(n, t, dt, coupling_dt=1 if coupling else 10, coupling_on=coupling, stop_on_tags=stop)
-        db = b.run(n, t, dt, coupling_dt=1 if coupling else 10, coupling_on=coupling, stop_on_tags=stop)
+        da = a.run(n, t, dt, coupling_dt=cdt if coupling else 10, coupling_on=coupling, stop_on_tags=stop)
+        db = b.run(n, t, dt, coupling_dt=cdt if coupling else 10, coupling_on=coupling, stop_on_tags=stop)
         assert da == db and not b.pipelined()
         ran_pipelined |= a.pipelined()
         _assert_worlds_bit_equal(a, b)
+        if scenario == "frc-offgrid-through":          # an A/B match alone could hide an error both paths share
+            for k in range(t, t + da):
+                ow.timestep_sim(k, dt, coupling_dt=cdt)
+            parity.compare_worlds(a, ow, rtol=1e-9)
         t += da
     assert ran_pipelined, scenario
     if scenario == "fast-stops":
@@ -741,6 +776,16 @@ def test_pipelined_steps_equal_the_three_launch_steps(scenario):
         assert 2 <= t < 12
     if scenario == "retry-pause":
         assert a.stats()["n_retry"] >= 1
+    if scenario.startswith("frc-offgrid"):
+        for w in (a, b):
+            assert w.ids()[2][0] == cases.REMOVE and np.all(w.ids()[2][1:] == cases.ACTIVE)
+            assert len(w.pairs()[0]) >= 3 and len(w.interactions()[1]) > 0          # the floes on the grid are in contact after the tag
+    if scenario == "frc-offgrid-through":
+        assert t == 16
+    if scenario == "frc-offgrid-stop":
+        assert 2 <= t < 12                                        # the batch ended on the tag step
+    if scenario == "coupling-every-10":
+        assert t > 20
 
 
 @pytest.mark.parametrize("kind", ["fuse", "open"])
@@ -1042,23 +1087,27 @@ def test_c_example_links_and_runs(tmp_path):
     assert abs(float(lines[3].split(":")[1].split()[0]) - 2e8) < 1e-3 * 2e8      # the grid output adds up to the ice area
 
 
-def _size_spectrum(w, n_small, big_r):
-    """one large floe with n_small small ones around its rim, each overlapping it a little (a Voronoi field with a size
-    spectrum in miniature): the large floe has n_small neighbours, every broad-phase cell holds dozens of floes"""
+def _size_spectrum(w, n_small, big_r, big_n=24, late=(), late_gap=900.0, late_speed=40.0):
+    """one large floe (a ring of big_n vertices) with n_small small ones around its rim, each overlapping it a little (a Voronoi
+    field with a size spectrum in miniature): the large floe has n_small neighbours, every broad-phase cell holds dozens of floes.
+    The small floes whose indices are in `late` start late_gap beyond touching distance of the large floe's bounding circle instead
+    and drift in at late_speed: they become its neighbours a few steps in."""
     w.set_consts(E=1e5); w.set_settings()
     w.set_domain([0, 0, 0, 0], -4e5, 4e5, -4e5, 4e5)
     w.set_grid_fields(8, 8, -4e5, 4e5, -4e5, 4e5, 0.0, 0.0, 0.0, 0.0, 0.0)
-    th = -np.arange(24) * (2 * np.pi / 24)
+    th = -np.arange(big_n) * (2 * np.pi / big_n)
     w.add_floe(cases.closed(np.stack([big_r * np.cos(th), big_r * np.sin(th)], 1)), 0.5)
     small_r = 0.9 * np.pi * big_r / n_small
     t6 = -np.arange(6) * (2 * np.pi / 6)
     for k in range(n_small):
         a = 2 * np.pi * k / n_small
-        c = (big_r + 0.6 * small_r) * np.array([np.cos(a), np.sin(a)])
+        d = big_r + small_r + late_gap if k in late else big_r + 0.6 * small_r
+        c = d * np.array([np.cos(a), np.sin(a)])
         w.add_floe(cases.closed(c + small_r * np.stack([np.cos(t6 + a), np.sin(t6 + a)], 1)), 0.3)
     u = np.zeros(n_small + 1); v = np.zeros(n_small + 1)
     ang = 2 * np.pi * np.arange(n_small) / n_small
-    u[1:] = -0.2 * np.cos(ang); v[1:] = -0.2 * np.sin(ang)            # the small floes press inward
+    speed = np.array([late_speed if k in late else 0.2 for k in range(n_small)])
+    u[1:] = -speed * np.cos(ang); v[1:] = -speed * np.sin(ang)            # the small floes press inward
     w.set("u", u); w.set("v", v)
     return w
 
@@ -1126,6 +1175,82 @@ def test_lists_grow_when_a_step_outgrows_them(monkeypatch, n_small, start, rowca
     [ow.timestep_sim(t, 10, coupling_dt=10, coupling_on=False) for t in range(5)]
     parity.compare_worlds(hw, ow, rtol=1e-9)
     assert np.array_equal(hw.warn_counts(), ow.warn_counts())
+
+
+def test_pipelined_batch_grows_its_lists(monkeypatch, capfd):
+    """A pipelined batch (csrc/sz_pipeline.hpp) whose large floe gains neighbours inside the batch: 20 small floes on its rim at the start,
+    10 more drift in and touch it a couple of steps later -- more than the default lists hold (SZ_MAXNB=24).  The pipelined launches are
+    compiled for lists of that width: the batch pauses in the step that outgrew them, carves larger ones and finishes on the three-launch
+    steps.  The state matches the oracle and, bit for bit, a context that never pipelines (SZ_PIPELINE=0)."""
+    monkeypatch.setenv("SZ_MAXNB", "24")
+    monkeypatch.setenv("SZ_VERBOSE", "1")
+    late = set(range(2, 30, 3))
+    build = lambda w: _size_spectrum(w, 30, 3.0e4, big_n=16, late=late)          # (rings of <= 17 vertices: the batch is eligible)
+    ow = build(omk())
+    steps = 8
+    n_nb = []
+    for t in range(steps):
+        ow.timestep_sim(t, 10, coupling_dt=10, coupling_on=False)
+        pi, pj = ow.pairs()
+        n_nb.append(int(np.sum(pi == 0) + np.sum(pj == 0)))
+    assert n_nb[0] <= 24 and max(n_nb[1:]) > 24, n_nb          # the lists overflow inside the batch, not in its first step
+    capfd.readouterr()
+    hw, hb = _ab_worlds(build, {"SZ_PIPELINE": "0"})
+    assert hw.run(steps, 0, 10, coupling_on=False, stop_on_tags=False) == steps
+    err = capfd.readouterr().err
+    assert "lists grow" in err and "pipelined batch: lists outgrew" in err, err
+    assert hb.run(steps, 0, 10, coupling_on=False, stop_on_tags=False) == steps
+    parity.compare_worlds(hw, ow, rtol=1e-9)
+    _assert_worlds_bit_equal(hw, hb)
+    assert np.array_equal(hw.warn_counts(), ow.warn_counts()) and np.array_equal(hw.warn_counts(), hb.warn_counts())
+
+
+@pytest.mark.parametrize("workload,coupling_dt,t0,steps", [("configs1", 1, 0, 6), ("configs3", 1, 0, 6), ("configs1", 10, 5, 10)])
+def test_pipelined_batch_full_size_oracle_parity(workload, coupling_dt, t0, steps):
+    """The bench's fields (10 000 floes) in one PIPELINED batch that runs through (stop_on_tags=False, as the bench's runner steps them) against
+    the oracle: pair list equal, state to 1e-9, interaction rows of the last step to 1e-10 per element, guard counters equal.  coupling_dt=10:
+    the batch runs steps 5-14 of the uploaded field, so that it starts off the coupling phase and step 10 is coupled inside it.  (It starts
+    from the upload rather than behind steps 0-4: over 16 steps the contacts amplify the round-off by which any two evaluations of the
+    same step differ -- xi 1e-14 at step 5, 4e-8 at step 13, the three-launch steps and every coupling interval alike -- beyond what a
+    1e-9 comparison can hold.)  test_full_size_oracle_parity holds the three-launch steps."""
+    cfg = _bench_cfg(workload)
+    hw, ow = _pair(cfg); ow.set_threads(_cores())
+    assert hw.run(steps, t0, cfg["dt"], coupling_dt=coupling_dt, stop_on_tags=False) == steps
+    assert hw.pipelined()
+    for t in range(t0, t0 + steps):
+        ow.timestep_sim(t, cfg["dt"], coupling_dt=coupling_dt)
+    parity.compare_pairs(hw, ow)
+    parity.compare_worlds(hw, ow, rtol=1e-9, check_inter=False)
+    parity.compare_interactions(hw, ow, 1e-10)
+    assert np.array_equal(hw.warn_counts(), ow.warn_counts())
+
+
+def test_lean_forcings_per_element_configs1():
+    """The one-way forcings of the pipelined 10 000-floe step ride in its first launch (sz_k_narrow<..., 1, 1>: forcing_body ->
+    forcing_lean_body, FMAs and v_rsq_f64 + Newton square roots).  Their contract is 1e-10 relative to the reference PER FLOE.
+    One coupled step (coupling_dt=2 from step 0: the second step of the batch is not coupled and leaves the columns alone) from the uploaded
+    state, against the oracle's first step.  Each component is compared on the scale of what it sums: fxOA / fyOA on the magnitude of the
+    floe's force vector (a component of a force along the other axis is a near-cancelling residue of per-point terms of that magnitude),
+    trqOA on max(|trqOA|, rmax |F|) (the torque of a nearly uniform stress about the centroid cancels down to round-off of terms lever x
+    force, the lever bounded by rmax)."""
+    import os
+    cfg = _bench_cfg("configs1")
+    os.environ["SZ_PIPE_MIN_STEPS"] = "2"
+    try:
+        hw = _pair(cfg)[0]
+    finally:
+        del os.environ["SZ_PIPE_MIN_STEPS"]
+    from subzero_jl_amd import fields
+    ow = fields.build_world(omk(), cfg); ow.set_threads(_cores())
+    assert hw.run(2, 0, cfg["dt"], coupling_dt=2, stop_on_tags=False) == 2
+    assert hw.pipelined() and hw.forcing_launch() == 2 and hw.narrow_kernel_name().endswith(",1,1>"), hw.narrow_kernel_name()
+    ow.timestep_sim(0, cfg["dt"], coupling_dt=2)
+    fx, fy, trq = ow.get("fxOA"), ow.get("fyOA"), ow.get("trqOA")
+    assert np.all(np.hypot(fx, fy) > 0)
+    F = np.hypot(fx, fy)
+    parity.assert_elementwise("fxOA", hw.get("fxOA"), fx, 1e-10, 0.0, scale=F)
+    parity.assert_elementwise("fyOA", hw.get("fyOA"), fy, 1e-10, 0.0, scale=F)
+    parity.assert_elementwise("trqOA", hw.get("trqOA"), trq, 1e-10, 0.0, scale=np.maximum(np.abs(trq), ow.get("rmax") * F))
 
 
 # ---------------------------------------------------------------- mixed precision (BASELINE configs[4])
