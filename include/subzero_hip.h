@@ -236,6 +236,32 @@ int sz_calc_strain(sz_ctx *ctx);
 int sz_step(sz_ctx *ctx, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt,
             int32_t flags, int32_t *steps_done);
 
+/* ---- fracture criteria on the device: determine_fractures (src/physical_processes/fractures.jl:269-280) on the resident state.
+   fracture_floes! (fractures.jl:461) splits floes on the host -- topology-changing serial work -- but only on fracture steps where
+   determine_fractures returns a floe; the device evaluates that predicate and a resident batch ends where it does.
+   FractureSettings + the criterion + FloeSettings.min_floe_area + DecayAreaScaledCalculator.α:
+     SZ_FRAC_HIBLER   HiblerYieldCurve(pstar, c): the 100-point polygon of _calculate_hibler (:83-94) rebuilt from the parents' mean
+                      height on every fracture step (update_criteria!, :234-251); px / py unused
+     SZ_FRAC_POLYGON  a fixed closed ring of npts <= 128 points in principal-stress space (MohrsCone.poly, or any criterion that does not
+                      update); pstar / c unused
+   dt = FractureSettings.Δt (> 0).  A floe is a candidate when area >= min_floe_area and the point (λmin, λmax) of its stress_accum, times
+   (area / min_floe_area)^alpha when alpha != 0, is not covered by the polygon (inside or on the boundary counts as covered).
+   sz_step with a criterion set (kind != SZ_FRAC_OFF): after every step with tstep % dt == 0 the criterion is evaluated on the device, and a
+   candidate ends the batch after that step exactly as a tag does (*steps_done counts the step; the state is the reference's just before
+   fracture_floes!; the launches of the later steps return at once; no host synchronisation per step).  SZ_NO_STOP runs through.
+   Batches with a criterion set run the three-launch steps, never the pipelined ones (csrc/sz_pipeline.hpp): the mean height is a
+   grid-wide dependency between a step's update and the next step's neighbour search, which the pipelined launches overlap.
+   Tiled runs (sz_tile_run, sz_tile_step) with a criterion set return SZ_E_STATE (the mean would need an all-reduce over the ranks).
+   SZ_FRAC_OFF (the default) adds nothing to a step, not even a launch. */
+enum { SZ_FRAC_OFF = 0, SZ_FRAC_HIBLER = 1, SZ_FRAC_POLYGON = 2 };
+int sz_set_fracture(sz_ctx *ctx, int32_t kind, int32_t dt, double pstar, double c, int32_t npts,
+                    const double *px, const double *py, double alpha, double min_floe_area);
+/* determine_fractures on the resident state as it is now: *n candidates, idx (may be NULL; room for N) = their 0-based parent indices,
+   ascending.  Needs a criterion set. */
+int sz_fracture_candidates(sz_ctx *ctx, int32_t *n, int32_t *idx);
+/* test hook: the mean parent height and (Hibler) the polygon's p of the last evaluation (sz_fracture_candidates or a batch's fracture step) */
+int sz_debug_fracture_mean(sz_ctx *ctx, double *mean_h, double *p);
+
 /* ---- measurement: HIP-event time per kernel class, accumulated since the last reset, on the
    stream the kernels are launched on; launches = number of timed launches of that class.
    on = 0: off; 1: every class; otherwise a mask, bit (k+1) = class k (e.g. 2 << SZ_K_NARROW: only

@@ -186,6 +186,9 @@ end
 const SZ_COLLISIONS_ON = Int32(1)
 const SZ_COUPLING_ON = Int32(2)
 const SZ_NO_STOP = Int32(4)
+const SZ_FRAC_OFF = Int32(0)
+const SZ_FRAC_HIBLER = Int32(1)
+const SZ_FRAC_POLYGON = Int32(2)
 boundary_kind(::OpenBoundary) = Int32(0)
 boundary_kind(::PeriodicBoundary) = Int32(1)
 boundary_kind(::CollisionBoundary) = Int32(2)
@@ -523,19 +526,69 @@ function unpack_geometry!(floes, P::Packed)
     return
 end
 
+# ------------------------------------------------------------------------------------------------ fracture criteria
+"""
+    set_fracture!(eng, sim)
+
+The simulation's fracture criterion on the device (`sz_set_fracture`): `FractureSettings.Δt`, a `HiblerYieldCurve` (rebuilt from the
+mean floe height on every fracture step, `update_criteria!`) or a `MohrsCone` (its fixed polygon), `FloeSettings.min_floe_area` and
+`DecayAreaScaledCalculator.α`.  Fractures off: `SZ_FRAC_OFF`.
+"""
+function set_fracture!(eng::HIPEngine, sim)
+    fs = sim.fracture_settings
+    if !fs.fractures_on
+        check(eng, @ccall lib.sz_set_fracture(eng.ctx::Ptr{Cvoid}, SZ_FRAC_OFF::Int32, Int32(1)::Int32, 0.0::Float64, 0.0::Float64,
+                                              Int32(0)::Int32, C_NULL::Ptr{Float64}, C_NULL::Ptr{Float64}, 0.0::Float64, 1.0::Float64)::Cint)
+        return
+    end
+    sc = sim.floe_settings.stress_calculator
+    sc isa Subzero.DecayAreaScaledCalculator ||
+        error("run_resident!: fractures need a DecayAreaScaledCalculator stress calculator (got $(typeof(sc)))")
+    α, amin, crit = Float64(sc.α), Float64(sim.floe_settings.min_floe_area), fs.criteria
+    if crit isa Subzero.HiblerYieldCurve
+        check(eng, @ccall lib.sz_set_fracture(eng.ctx::Ptr{Cvoid}, SZ_FRAC_HIBLER::Int32, Int32(fs.Δt)::Int32, Float64(crit.pstar)::Float64,
+                                              Float64(crit.c)::Float64, Int32(0)::Int32, C_NULL::Ptr{Float64}, C_NULL::Ptr{Float64},
+                                              α::Float64, amin::Float64)::Cint)
+    elseif crit isa Subzero.MohrsCone
+        ring = Subzero.find_poly_coords(crit.poly)[1]
+        px, py = Float64[Float64(q[1]) for q in ring], Float64[Float64(q[2]) for q in ring]
+        check(eng, @ccall lib.sz_set_fracture(eng.ctx::Ptr{Cvoid}, SZ_FRAC_POLYGON::Int32, Int32(fs.Δt)::Int32, 0.0::Float64, 0.0::Float64,
+                                              Int32(length(px))::Int32, px::Ptr{Float64}, py::Ptr{Float64}, α::Float64, amin::Float64)::Cint)
+    else
+        error("run_resident!: fracture criterion $(typeof(crit)) has no device form (HiblerYieldCurve, MohrsCone)")
+    end
+    return
+end
+
+# determine_fractures on the resident state: how many floes would fracture now
+function fracture_candidates(eng::HIPEngine)
+    n = Ref{Int32}(0)
+    check(eng, @ccall lib.sz_fracture_candidates(eng.ctx::Ptr{Cvoid}, n::Ptr{Int32}, C_NULL::Ptr{Int32})::Cint)
+    return Int(n[])
+end
+
 # ------------------------------------------------------------------------------------------------ resident mode
 """
     run_resident!(sim, eng; start_tstep = 0, batch = 500)
 
-`run!(sim)` for simulations in which only the hot path touches the floes between output steps (fractures, ridging /
+`run!(sim)` for simulations in which only the hot path and fracture touch the floes between output steps (ridging /
 rafting and welding off: the defaults).  Whole batches of `timestep_sim!` run on the device with the state resident in
 HBM (`sz_step`); a batch never crosses an output step of a writer, and it ends after the first step that leaves a floe
 tagged `remove` / `fuse`, so `simplify_floes!` (simulation.jl:205-214) runs exactly where the reference runs it.
 `sz_simplify_check` covers its other two triggers (rings over `max_vertices`, floes under the minimum area / height).
+
+Fractures (`FractureSettings.fractures_on` with a `HiblerYieldCurve` or `MohrsCone` criterion and a `DecayAreaScaledCalculator`):
+the device evaluates `determine_fractures` after every fracture step (`mod(tstep, Δt) == 0`) and a batch also ends after the
+first fracture step on which a floe would fracture.  The state is then pulled, `fracture_floes!` runs on the host exactly as
+`timestep_sim!` calls it (simulation.jl:172-183), then `simplify_floes!`, and the batch resumes from the uploaded state.  On
+fracture steps without a candidate `fracture_floes!` would change nothing and is skipped: `determine_fractures` draws no random
+numbers, so `sim.rng` stays exactly where the reference leaves it.
 """
 function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Integer = 500)
-    (sim.fracture_settings.fractures_on || sim.ridgeraft_settings.ridge_raft_on || sim.weld_settings.weld_on) &&
-        error("run_resident!: fracture / ridging / welding need the floes on the host every step: use run!(sim)")
+    (sim.ridgeraft_settings.ridge_raft_on || sim.weld_settings.weld_on) &&
+        error("run_resident!: ridging / welding need the floes on the host every step: use run!(sim)")
+    set_fracture!(eng, sim)
+    fractures = sim.fracture_settings.fractures_on
     Subzero.startup_sim(sim, nothing, 1)
     floes = sim.model.floes
     flags = (sim.collision_settings.collisions_on ? SZ_COLLISIONS_ON : Int32(0)) |
@@ -557,11 +610,17 @@ function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Int
         check(eng, @ccall lib.sz_step(eng.ctx::Ptr{Cvoid}, n::Int32, tstep::Int32, sim.Δt::Int32,
                                       sim.coupling_settings.Δt::Int32, flags::Int32, done::Ptr{Int32})::Cint)
         tstep += done[]; dirty = true
-        todo = Vector{Int64}(undef, 4)
-        check(eng, @ccall lib.sz_simplify_check(eng.ctx::Ptr{Cvoid}, eng.max_vertices::Int32, eng.min_floe_area::Float64,
-                                                eng.min_floe_height::Float64, todo::Ptr{Int64})::Cint)
-        if any(!iszero, todo)                        # simplify_floes! has work: it runs on the host, on the full state
+        # the batch's last step was a fracture step on which a floe fractures: fracture_floes! on the host, before simplify_floes!
+        fracture_now = fractures && done[] > 0 && mod(tstep - 1, sim.fracture_settings.Δt) == 0 && fracture_candidates(eng) > 0
+        if fracture_now
             pull_state!(eng, floes, P)
+            max_floe_id = Subzero.fracture_floes!(floes, max_floe_id, sim.rng, sim.fracture_settings, sim.floe_settings, sim.Δt)
+        end
+        todo = Vector{Int64}(undef, 4)
+        fracture_now || check(eng, @ccall lib.sz_simplify_check(eng.ctx::Ptr{Cvoid}, eng.max_vertices::Int32, eng.min_floe_area::Float64,
+                                                                eng.min_floe_height::Float64, todo::Ptr{Int64})::Cint)
+        if fracture_now || any(!iszero, todo)        # simplify_floes! has work: it runs on the host, on the full state
+            fracture_now || pull_state!(eng, floes, P)
             max_floe_id = Subzero.simplify_floes!(sim.model, max_floe_id, sim.simp_settings, sim.collision_settings,
                                                   sim.floe_settings, sim.Δt, sim.rng)
             P = upload!(eng, floes, length(floes)); upload_interactions!(eng, floes)

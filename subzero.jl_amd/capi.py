@@ -18,6 +18,7 @@ OPEN, PERIODIC, COLLISION, MOVING = 0, 1, 2, 3
 NORTH, SOUTH, EAST, WEST = 0, 1, 2, 3
 ACTIVE, REMOVE, FUSE = 1, 2, 3
 COLLISIONS_ON, COUPLING_ON, NO_STOP = 1, 2, 4
+FRAC_OFF, FRAC_HIBLER, FRAC_POLYGON = 0, 1, 2
 K_GHOSTS, K_BROAD, K_NARROW, K_REDUCE, K_FORCING, K_INTEGRATE, K_NARROW_LARGE = range(7)
 KERNEL_CLASS_NAMES = ["ghosts", "broad", "narrow", "reduce", "forcing", "integrate", "narrow_large", "exchange"]
 
@@ -82,6 +83,7 @@ EXPORTS = [
     "sz_tile_enable", "sz_owned_box", "sz_halo_record_doubles", "sz_halo_record_doubles_ctx", "sz_halo_set_boxes", "sz_halo_pack", "sz_halo_counts", "sz_tile_forcing", "sz_tile_step", "sz_sync", "sz_set_stream", "sz_debug_stamps", "sz_debug_crec_mismatches", "sz_upload_floes_f32", "sz_download_floes_f32", "sz_set_fields_f32", "sz_download_interactions_f32",
     "sz_get_boundary_rects", "sz_debug_match_vertices", "sz_debug_sample_fields", "sz_debug_pipelined",
     "sz_comm_available", "sz_comm_unique_id", "sz_comm_init", "sz_comm_init_host", "sz_comm_destroy", "sz_comm_selftest", "sz_comm_allreduce", "sz_tile_setup", "sz_tile_set_center", "sz_tile_run", "sz_tile_migrate", "sz_tile_owned_gidx", "sz_debug_migrate_path", "sz_debug_find_key", "sz_debug_pairs_of_ids", "sz_download_subpoints",
+    "sz_set_fracture", "sz_fracture_candidates", "sz_debug_fracture_mean",
 ]
 
 EUL_PARTIAL = 17      # SZ_EUL_PARTIAL: per-cell partial fields of sz_eulerian_partial
@@ -187,6 +189,9 @@ def load(build_if_missing=True):
     L.sz_debug_match_vertices.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, _ip, _ip]
     L.sz_debug_sample_fields.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp]
     L.sz_debug_pipelined.argtypes = [C.c_void_p]
+    L.sz_set_fracture.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _dp, _dp, C.c_double, C.c_double]
+    L.sz_fracture_candidates.argtypes = [C.c_void_p, _ip, _ip]
+    L.sz_debug_fracture_mean.argtypes = [C.c_void_p, _dp, _dp]
     for n in EXPORTS:
         if n not in ("sz_create", "sz_destroy", "sz_last_error", "sz_version"):
             getattr(L, n).restype = C.c_int

@@ -19,6 +19,7 @@
 #include "sz_twoway.hpp"
 #include "sz_output.hpp"
 #include "sz_migrate.hpp"
+#include "sz_fracture.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 
 using namespace sz;
@@ -166,6 +167,10 @@ struct sz_ctx {
   bool crec_current = false;        // the collision records of set gpar hold the parents as they lie (a pipelined batch left them so; any call that moves or
                                     // re-uploads floes outside such a batch clears it) and the twin set has the static quads: the next batch seeds neither
   bool no_reduce_free = false;      // SZ_REDUCE_FREE=0: keep the (rows-only) reduce launch inside every step (A/B)
+  // fracture criterion (sz_set_fracture; sz_fracture.hpp): kind SZ_FRAC_*, FractureSettings.Δt, the device block and the per-parent buffers
+  int frac_kind = 0, frac_dt = 0, frac_npts = 0, frac_cap = 0;
+  double frac_pstar = 0, frac_c = 0, frac_alpha = 0, frac_min_area = 0;
+  FracDev* frac_d = nullptr; unsigned char* frac_flag = nullptr; int* frac_idx = nullptr;
   bool maybe_tagged = false;        // a parent may be non-active on the device (an upload said so, a batch ended on a tag, a process-mode call ran):
                                     // the next batch then runs its first step on its own (see sz_step)
   int last_err_bits = 0;   // device error bits the last sync_and_check found (tiled runs agree on them between the ranks)
@@ -928,6 +933,7 @@ void sz_destroy(sz_ctx* c) {
   (void)sz_comm_destroy(c);
   for (auto& e : c->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   (void)hipFree(c->d_stats); (void)hipFree(c->S.acc);
+  (void)hipFree(c->frac_d); (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
   (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2);
   (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join);
@@ -1748,7 +1754,7 @@ void pipe_adopt(sz_ctx* c, int q) {
   c->crec_buf = T.crec; c->gpar = q;
 }
 bool pipeline_eligible(const sz_ctx* c, int nsteps, bool coll, bool sg, bool gi, bool periodic, bool cr, bool rfree, int flags) {
-  return rfree && !c->no_pipeline && coll && sg && (gi || !periodic) && cr && nsteps >= c->pipe_min_steps && c->hostN <= c->pipe_max_floes && c->precision == 0 && !c->two_way &&
+  return rfree && !c->no_pipeline && c->frac_kind == SZ_FRAC_OFF && coll && sg && (gi || !periodic) && cr && nsteps >= c->pipe_min_steps && c->hostN <= c->pipe_max_floes && c->precision == 0 && !c->two_way &&
          (!c->S.any_domain_work || (!periodic && !c->any_moving)) && c->S.maxnb <= MAXNB && !larger_rings(c) && c->pb[1].vxy && c->pb[1].work &&
          (c->S.capM - c->hostN) / 2 > 64 && !(c->dbg & 8) && (flags & SZ_COLLISIONS_ON);
 }
@@ -2008,6 +2014,96 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
 }
 }  // namespace
 
+
+// ---------------------------------------------------------------- fracture criteria (sz_fracture.hpp)
+int sz_set_fracture(sz_ctx* c, int32_t kind, int32_t dt, double pstar, double cc, int32_t npts, const double* px, const double* py,
+                    double alpha, double min_floe_area) {
+  if (!c) return SZ_E_ARG;
+  if (kind != SZ_FRAC_OFF && kind != SZ_FRAC_HIBLER && kind != SZ_FRAC_POLYGON) { c->err = "sz_set_fracture: kind is not an SZ_FRAC_* value"; return SZ_E_ARG; }
+  if (kind == SZ_FRAC_OFF) { c->frac_kind = SZ_FRAC_OFF; return SZ_OK; }
+  if (dt <= 0) { c->err = "sz_set_fracture: dt (FractureSettings.Δt) must be positive"; return SZ_E_ARG; }
+  if (kind == SZ_FRAC_POLYGON && (npts < 4 || npts > FRAC_MAXPTS || !px || !py)) {
+    c->err = "sz_set_fracture: a criterion polygon is a closed ring of 4 to 128 points"; return SZ_E_ARG;
+  }
+  if (!(min_floe_area > 0.0)) { c->err = "sz_set_fracture: min_floe_area must be positive"; return SZ_E_ARG; }
+  (void)hipSetDevice(c->device);
+  if (!c->frac_d) HIPCHK(c, hipMalloc(&c->frac_d, sizeof(FracDev)));
+  FracDev h{};
+  if (kind == SZ_FRAC_HIBLER) {
+    // the points of range(0, 2π, length = 100): k (2π) / 99 rounded once (extended precision here; Julia's range computes them in
+    // twice-precision arithmetic), and ring_coords[end] = ring_coords[1]
+    const long double two_pi = (long double)(2.0 * M_PI);
+    for (int k = 0; k < FRAC_HIBLER_PTS; k++) {
+      const double a = k == FRAC_HIBLER_PTS - 1 ? 0.0 : (double)(two_pi * k / (long double)(FRAC_HIBLER_PTS - 1));
+      h.ct[k] = cos(a); h.st[k] = sin(a);
+    }
+    npts = FRAC_HIBLER_PTS;
+  } else {
+    for (int k = 0; k < npts; k++) { h.px[k] = px[k]; h.py[k] = py[k]; }
+  }
+  HIPCHK(c, hipMemcpyAsync(c->frac_d, &h, sizeof(FracDev), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->frac_kind = kind; c->frac_dt = dt; c->frac_npts = npts;
+  c->frac_pstar = pstar; c->frac_c = cc; c->frac_alpha = alpha; c->frac_min_area = min_floe_area;
+  return SZ_OK;
+}
+// the per-parent buffers for the field as it is (hostN parents)
+static int frac_ensure(sz_ctx* c) {
+  if (c->frac_cap >= c->hostN && c->frac_flag) return SZ_OK;
+  (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx); c->frac_flag = nullptr; c->frac_idx = nullptr; c->frac_cap = 0;
+  const int cap = std::max(c->hostN, 1);
+  HIPCHK(c, hipMalloc(&c->frac_flag, (size_t)cap));
+  HIPCHK(c, hipMalloc(&c->frac_idx, (size_t)cap * sizeof(int)));
+  c->frac_cap = cap;
+  return SZ_OK;
+}
+static FracArgs frac_args(const sz_ctx* c) {
+  FracArgs F;
+  F.d = c->frac_d; F.flag = c->frac_flag; F.idx = c->frac_idx;
+  F.kind = c->frac_kind; F.npts = c->frac_npts; F.n = c->hostN;
+  F.pstar = c->frac_pstar; F.c = c->frac_c; F.alpha = c->frac_alpha; F.min_area = c->frac_min_area;
+  F.rc = cos(M_PI / 4); F.rs = sin(M_PI / 4);
+  return F;
+}
+// ASYNC: one evaluation of the criterion on the parents; T.step = the batch-relative step it ends (a candidate stops the batch there)
+static void frac_launch(sz_ctx* c, const State& T) {
+  const FracArgs F = frac_args(c);
+  hipLaunchKernelGGL(sz_k_frac_criterion, dim3(1), dim3(FRAC_TPB), 0, c->stream, T, F);
+  hipLaunchKernelGGL(sz_k_frac_test, dim3(grid_for(std::max(c->hostN, 1), 256, 2048)), dim3(256), 0, c->stream, T, F);
+}
+int sz_fracture_candidates(sz_ctx* c, int32_t* n, int32_t* idx) {
+  if (n) *n = 0;
+  if (!c || !n) return SZ_E_ARG;
+  if (!c->have_floes) { c->err = "sz_fracture_candidates: no floes uploaded"; return SZ_E_STATE; }
+  if (c->frac_kind == SZ_FRAC_OFF) { c->err = "sz_fracture_candidates: no fracture criterion set (sz_set_fracture)"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  if (int rc = frac_ensure(c)) return rc;
+  State T = c->S; T.step = 0;
+  frac_launch(c, T);
+  hipLaunchKernelGGL(sz_k_frac_compact, dim3(1), dim3(FRAC_TPB), 0, c->stream, frac_args(c));
+  int cnt = 0;
+  HIPCHK(c, hipMemcpyAsync(&cnt, &c->frac_d->count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  int rc = sync_and_check(c);
+  if (rc) return rc;
+  if (cnt < 0 || cnt > c->hostN) { c->err = "sz_fracture_candidates: bad candidate count"; return SZ_E_HIP; }
+  if (idx && cnt > 0) {
+    HIPCHK(c, hipMemcpyAsync(idx, c->frac_idx, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  *n = cnt;
+  return SZ_OK;
+}
+int sz_debug_fracture_mean(sz_ctx* c, double* mean_h, double* p) {
+  if (!c || !c->frac_d) return SZ_E_STATE;
+  (void)hipSetDevice(c->device);
+  double h2[2];
+  HIPCHK(c, hipMemcpyAsync(h2, &c->frac_d->mean_h, sizeof(h2), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (mean_h) *mean_h = h2[0];
+  if (p) *p = h2[1];
+  return SZ_OK;
+}
+
 int sz_debug_pipelined(sz_ctx* c) { return c ? c->last_pipelined : 0; }
 
 int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
@@ -2084,6 +2180,9 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   // a parent that is already tagged ends the batch after its first step, and the integrator only finds out while it runs (the tags of a
   // step itself are raised by its narrow phase / forcings, a launch earlier): that first step is then enqueued on its own, as a last step
   int s_end = rfree && c->maybe_tagged && c->S.stop_on_tags && nsteps > 1 ? 1 : nsteps;
+  // fracture criterion (sz_set_fracture): evaluated after every fracture step of a batch that stops -- one that runs through has no use for it
+  const bool frac = c->frac_kind != SZ_FRAC_OFF && c->S.stop_on_tags && !pipe;
+  if (frac) { if (int rc = frac_ensure(c)) return rc; }
   auto leave = [&]() { c->S.retry_stop = 0; c->S.body_rings = 0; c->S.ginline = 0; c->S.famrec = 0; c->S.step = 0; c->S.crec = nullptr; c->S.facc = nullptr; c->acc_mode = 0; c->reduce_mode = 0; };
   int h[C_COUNT];
   int pipe_done = -1;
@@ -2135,9 +2234,23 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
       if (coll) collisions_step(c, c->hostN, dt, periodic && !sg, sg, resume ? 0 : fmode, lean, resume);
       if (overlap && !resume) stage_forcing_join(c);
       // (inline ghosts: the last step of the batch makes none -- there is no step to make them for, and the cell lists stay the parents')
-      c->acc_mode = !facc_on ? 0 : 1 | (rfree ? 4 | (s + 1 == s_end ? 2 : 0) : 0);
-      stage_integrate(c, dt, !coll, coupling, sg, gl && !gi ? 1 - c->gl_cur : -1, gi && s + 1 < s_end ? 1 - (s & 1) : -1);
+      // a fracture step (fracture_floes!, simulation.jl:172-183) ends the batch when the criterion finds a candidate -- known only after the
+      // update: the step runs as a batch's last one (its ghosts stay, none are made for a next step), and the next step is started behind
+      // the test by launches that return at once when it has stopped the batch (sz_fracture.hpp)
+      const bool fstep = frac && (tstep % c->frac_dt) == 0;
+      const bool fcut = fstep && s + 1 < s_end;
+      c->acc_mode = !facc_on ? 0 : 1 | (rfree ? 4 | (s + 1 == s_end || fcut ? 2 : 0) : 0);
+      stage_integrate(c, dt, !coll, coupling, sg, gl && !gi ? 1 - c->gl_cur : -1, gi && s + 1 < s_end && !fcut ? 1 - (s & 1) : -1);
       if (gl && !gi) c->gl_cur ^= 1;
+      if (fstep) {
+        frac_launch(c, c->S);
+        if (fcut && gi) {
+          State T = c->S; T.step = s + 2;
+          if (coll && periodic) hipLaunchKernelGGL(sz_k_frac_resume_remove, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, T);
+          (void)hipMemsetAsync(c->S.galloc + ((s + 1) & 1) * 16, 0, 2 * sizeof(unsigned long long), c->stream);
+          hipLaunchKernelGGL(sz_k_frac_resume_seed, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, T, (s + 1) & 1, c->hostN);
+        }
+      }
     }
     c->S.step = 0;
     // floe.interactions of the step that ended the batch (reduce-free steps): one launch for the whole batch
@@ -2399,6 +2512,7 @@ int tile_forcing(sz_ctx* c) {
 int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int32_t tstep, int32_t dt, int32_t coupling_dt,
                  int32_t flags) {
   if (!c || !c->have_floes) return SZ_E_STATE;
+  if (c->frac_kind != SZ_FRAC_OFF) { c->err = "tiled runs do not evaluate fracture criteria (the mean height needs an all-reduce over the ranks): sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
   State& S = c->S;
   const bool coll = (flags & SZ_COLLISIONS_ON) != 0;
@@ -3440,6 +3554,7 @@ int sz_tile_set_center(sz_ctx* c, double x, double y) {
 // nsteps x timestep_sim! of a tiled run, collectively on every rank (same arguments everywhere)
 int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
   if (steps_done) *steps_done = 0;
+  if (c && c->frac_kind != SZ_FRAC_OFF) { c->err = "tiled runs do not evaluate fracture criteria (the mean height needs an all-reduce over the ranks): sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
   if (!c || !c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0) {
     if (c) c->err = "sz_tile_run needs sz_tile_enable and sz_tile_setup after the last sz_upload_floes";
     return SZ_E_STATE;

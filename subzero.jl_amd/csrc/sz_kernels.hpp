@@ -888,7 +888,7 @@ __device__ __forceinline__ void ghost_inline_make(State& S, const GridGeo& geo, 
   }
 }
 // start of a resident batch: the ghosts of its first step, from the parents as they lie (thread per parent)
-__global__ void __launch_bounds__(256) sz_k_ghost_inline_seed(State S, int slot, int nh) {
+__device__ __forceinline__ void ghost_inline_seed(State& S, int slot, int nh) {
   const GridGeo geo = grid_geo(S);
   const int N = nh >= 0 ? nh : S.cnt[C_N];
   const int NV0 = S.voff[N];
@@ -904,6 +904,7 @@ __global__ void __launch_bounds__(256) sz_k_ghost_inline_seed(State S, int slot,
     }
   }
 }
+__global__ void __launch_bounds__(256) sz_k_ghost_inline_seed(State S, int slot, int nh) { ghost_inline_seed(S, slot, nh); }
 
 // mixed precision: the rings of the parents into their body frame (offsets from the centroid at alpha = 0, fp32) ...
 __global__ void sz_k_body_rings(State S) {
@@ -989,7 +990,7 @@ __global__ void sz_k_ghost_commit(State S) {
 }
 // simulation.jl:138-144
 // drop_halo: tiled runs also forget the halo parents (N := owned)
-__global__ void sz_k_remove_ghosts(State S, int drop_halo) {
+__device__ __forceinline__ void remove_ghosts(const State& S, int drop_halo) {
   if (S.retry_stop && S.cnt[C_RETRYSTOP] != 0) return;       // the batch is paused inside a step: its ghosts are still needed
   int N = drop_halo ? S.cnt[C_NOWN] : S.cnt[C_N];
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
@@ -1000,6 +1001,7 @@ __global__ void sz_k_remove_ghosts(State S, int drop_halo) {
     S.cnt[C_M] = N; S.cnt[C_N] = N; S.cnt[C_NV] = S.voff[N];        // C_NGHOSTS keeps the last step's count
   }
 }
+__global__ void sz_k_remove_ghosts(State S, int drop_halo) { remove_ghosts(S, drop_halo); }
 
 // ============================================================================ broad phase (A2, A3)
 // Single block.  Prologue: commit the ghosts planned by the ghost kernels (C_M, C_NV).  Then the

@@ -549,7 +549,8 @@ class World:
     def run(self, nsteps, tstep0, dt, coupling_dt=10, collisions_on=True, coupling_on=True, stop_on_tags=True):
         """nsteps x timestep_sim! with the state resident in HBM.  Returns the number of steps run: the batch ends
         after the first step that tags a floe remove / fuse (the reference runs simplify_floes! after every step,
-        simulation.jl:205-214); stop_on_tags=False runs on regardless (measurement / soak runs)."""
+        simulation.jl:205-214), or -- with a criterion set (set_fracture) -- after the first fracture step on which a floe would
+        fracture (fracture_floes! is the host's); stop_on_tags=False runs on regardless (measurement / soak runs)."""
         self._push()
         flags = (capi.COLLISIONS_ON if collisions_on else 0) | (capi.COUPLING_ON if coupling_on else 0)
         if not stop_on_tags:
@@ -558,6 +559,36 @@ class World:
         self._chk(self.L.sz_step(self.h, int(nsteps), int(tstep0), int(dt), int(coupling_dt), flags, C.byref(done)))
         self._host_stale = True
         return int(done.value)
+
+    def set_fracture(self, kind, dt=75, pstar=2.25e5, c=20.0, poly=None, alpha=0.0, min_floe_area=1e6):
+        """FractureSettings(fractures_on, criteria, Δt = dt) with FloeSettings.min_floe_area and DecayAreaScaledCalculator.α:
+        kind capi.FRAC_HIBLER (HiblerYieldCurve(pstar, c), rebuilt from the mean height on every fracture step), capi.FRAC_POLYGON
+        (poly = (px, py), a fixed closed ring, e.g. MohrsCone's) or capi.FRAC_OFF.  run() then ends a batch after the first fracture step
+        (tstep % dt == 0) on which determine_fractures finds a floe, as it ends one on a tag (stop_on_tags)."""
+        px = py = None
+        npts = 0
+        if poly is not None:
+            px = np.ascontiguousarray(poly[0], np.float64); py = np.ascontiguousarray(poly[1], np.float64)
+            npts = len(px)
+            if len(py) != npts:
+                raise SzError("poly: x and y differ in length")
+        self._chk(self.L.sz_set_fracture(self.h, int(kind), int(dt), float(pstar), float(c), int(npts), capi.ptr(px), capi.ptr(py),
+                                         float(alpha), float(min_floe_area)))
+
+    def fracture_candidates(self):
+        """determine_fractures (fractures.jl:269-280) on the state as it is: 0-based indices of the parents that would fracture"""
+        self._push()
+        n = C.c_int32(0)
+        self._chk(self.L.sz_fracture_candidates(self.h, C.byref(n), None))
+        idx = np.zeros(max(self.N, 1), _I32)
+        self._chk(self.L.sz_fracture_candidates(self.h, C.byref(n), capi.ptr(idx, capi._ip)))
+        return idx[:n.value].copy()
+
+    def fracture_mean(self):
+        """(mean parent height, Hibler p) of the last evaluation of the criterion"""
+        m, p = C.c_double(0), C.c_double(0)
+        self._chk(self.L.sz_debug_fracture_mean(self.h, C.byref(m), C.byref(p)))
+        return m.value, p.value
 
     def timestep_sim(self, tstep, dt, coupling_dt=10, collisions_on=True, coupling_on=True):
         self.run(1, tstep, dt, coupling_dt, collisions_on, coupling_on)
