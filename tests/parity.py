@@ -19,6 +19,9 @@ State columns (positions, velocities, stresses ...) are sums and differences of 
 are compared on that scale (max-norm): a velocity that passes through zero has no meaningful relative error.
 Every helper returns / reports the worst element so that a failure names the floe and row.
 """
+import functools
+import os
+
 import numpy as np
 
 EPS = np.finfo(float).eps
@@ -54,10 +57,12 @@ def worst_element(a, b, rtol, atol, scale=None):
     return float(ratio[k]), k
 
 
-def assert_elementwise(name, a, b, rtol, atol, scale=None):
+def assert_elementwise(name, a, b, rtol, atol, scale=None, owner=None):
+    """owner: the floe of each element (interaction rows), named in the failure message"""
     r, k = worst_element(a, b, rtol, atol, scale)
     a = np.asarray(a, float).ravel(); b = np.asarray(b, float).ravel()
-    assert r <= 1.0, (f"{name}: element {k}: got {a[k]!r}, oracle {b[k]!r}, |diff| {abs(a[k] - b[k]):.3e} is {r:.2f}x the "
+    of = f" (floe {int(owner[k])})" if owner is not None and k >= 0 else ""
+    assert r <= 1.0, (f"{name}: element {k}{of}: got {a[k]!r}, oracle {b[k]!r}, |diff| {abs(a[k] - b[k]):.3e} is {r:.2f}x the "
                       f"tolerance (rtol {rtol:g}, atol {np.max(atol) if np.ndim(atol) else atol:.3e})")
     return r
 
@@ -91,14 +96,15 @@ def compare_interactions(hw, ow, rtol, report=None):
     hrows, orows = hrows[:m], orows[:m]
     assert np.array_equal(hrows[:, 0], orows[:, 0]), "partner indices differ"
     fl = force_floors(orows, np.max(ow.get("rmax")) if m else 1.0)
+    own = np.repeat(np.arange(n - 1), np.diff(ooff[:n]))
     errs = {}
-    errs["xforce"] = assert_elementwise("xforce", hrows[:, 1], orows[:, 1], rtol, fl["force"])
-    errs["yforce"] = assert_elementwise("yforce", hrows[:, 2], orows[:, 2], rtol, fl["force"])
-    errs["torque"] = assert_elementwise("torque", hrows[:, 5], orows[:, 5], rtol, fl["torque"])
-    errs["overlap"] = assert_elementwise("overlap", hrows[:, 6], orows[:, 6], rtol, fl["area"])
+    errs["xforce"] = assert_elementwise("xforce", hrows[:, 1], orows[:, 1], rtol, fl["force"], owner=own)
+    errs["yforce"] = assert_elementwise("yforce", hrows[:, 2], orows[:, 2], rtol, fl["force"], owner=own)
+    errs["torque"] = assert_elementwise("torque", hrows[:, 5], orows[:, 5], rtol, fl["torque"], owner=own)
+    errs["overlap"] = assert_elementwise("overlap", hrows[:, 6], orows[:, 6], rtol, fl["area"], owner=own)
     # force points are coordinates: relative to the coordinate magnitude of the contact
-    errs["point"] = max(assert_elementwise("xpoint", hrows[:, 3], orows[:, 3], rtol, rtol * fl["Lc"]),
-                        assert_elementwise("ypoint", hrows[:, 4], orows[:, 4], rtol, rtol * fl["Lc"]))
+    errs["point"] = max(assert_elementwise("xpoint", hrows[:, 3], orows[:, 3], rtol, rtol * fl["Lc"], owner=own),
+                        assert_elementwise("ypoint", hrows[:, 4], orows[:, 4], rtol, rtol * fl["Lc"], owner=own))
     if report is not None:
         report.update(floors=fl, worst=errs)
     return errs
@@ -140,19 +146,72 @@ def compare_worlds(hw, ow, rtol=1e-10, fields=SCALARS, check_pairs=True, check_i
             # the oracle in the reference's serial order -- where a component cancels analytically (two stars meeting head-on: s22) one leaves
             # 0, the other 1e-29 of round-off beside components of 60
             scale = max(max(np.abs(ow.get(f[:2] + c)).max() for c in ("11", "12", "21", "22")), 1e-300)
-            e = float(np.max(np.abs(a - b)) / scale)
         elif f in ("e12", "e21"):
             # the shear strain of a rigid rotation cancels analytically (update_floe.jl:436-446):
             # what is stored is round-off, so compare it on the scale of the normal components
             scale = max(np.abs(ow.get("e11")).max(), np.abs(ow.get("e22")).max(), 1e-300)
-            e = float(np.max(np.abs(a - b)) / scale)
         else:
-            e = relerr(a, b)
-        assert e <= rtol, (f, e)
+            scale = max(np.max(np.abs(b)), 1e-300) if len(b) else 1.0
+        d = np.abs(a - b)
+        e = float(np.max(d) / scale) if len(d) else 0.0
+        assert e <= rtol, (f, e, f"floe {int(np.argmax(d))}")
         out[f] = e
     ho, hx, hy = hw.rings(); oo, ox, oy = ow.rings()
     assert np.array_equal(ho, oo)
-    e = max(relerr(hx, ox), relerr(hy, oy))
-    assert e <= rtol, ("vertices", e)
-    out["vertices"] = e
+    for c, h, o in (("x", hx, ox), ("y", hy, oy)):
+        e = relerr(h, o)
+        assert e <= rtol, (f"vertices {c}", e, f"floe {int(np.searchsorted(ho, np.argmax(np.abs(h - o)), 'right')) - 1}")
+        out["vertices"] = max(out.get("vertices", 0.0), e)
     return out
+
+
+# ---------------------------------------------------------------- the bench's fields, the oracle's threads, an oracle restarted from any state
+@functools.lru_cache(maxsize=2)
+def bench_cfg(workload):
+    """the very fields bench.py times (same generator arguments as its workload table)"""
+    from subzero_jl_amd import fields
+    wl = {"configs1": dict(n_floes=10000, seed=12345), "configs3": dict(n_floes=10000, seed=12345, walls=True, topography=True, ocean="strait"),
+          "configs2": dict(n_floes=100000, seed=12346, ocean="converge_diverge")}[workload]
+    return fields.make_config(**wl)
+
+
+def cores():
+    n = len(os.sched_getaffinity(0))
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()
+        if quota != "max":
+            n = max(1, min(n, int(quota) // int(period)))
+    except Exception:
+        pass
+    return n
+
+
+def oracle_from(w, cfg):
+    """A fresh oracle holding the state of `w` (a subzero_jl_amd.World or another oracle, between steps: no ghosts) in the setting of `cfg`
+    (fields.build_world's consts, settings, domain, topography and grid fields).  The rings go in through add_floe, then every column of
+    orc.FIELDS overwrites what add_floe derived, then ids and status: the state timestep_sim reads, so that the next step of the two is the
+    same computation (test_shadow_cpu holds an oracle's clone to its original bit for bit)."""
+    from oracle import orc
+    from subzero_jl_amd import fields
+    assert "moving" not in cfg["kinds"], "oracle_from: the boundary positions of a moving domain are not carried over"
+    none = np.zeros(0)
+    ow = fields.build_world(orc.World(), dict(cfg, n_floes=0, u=none, v=none, xi=none))
+    ids, gids, status = w.ids()
+    M = w.M
+    assert len(ids) == M == cfg["n_floes"] and not np.any(gids) and not any(w.ghosts()), "oracle_from: the world holds ghosts"
+    off, x, y = w.rings()
+    h = w.get("height")
+    for i in range(M):
+        ow.add_floe(np.stack([x[off[i]:off[i + 1]], y[off[i]:off[i + 1]]], 1), h[i])
+    so, sx, sy = cfg["sub_off"], cfg["sx"], cfg["sy"]
+    if hasattr(w, "subpoints"):
+        wo, wx, wy = w.subpoints()
+        assert np.array_equal(wo, so) and np.array_equal(wx, sx) and np.array_equal(wy, sy), "oracle_from: sub-floe points differ from cfg's"
+    for i in range(M):
+        ow.set_subpoints(i, sx[so[i]:so[i + 1]], sy[so[i]:so[i + 1]])
+    for f in orc.FIELDS:
+        ow.set(f, w.get(f))
+    ow.set_ids(ids)
+    ow.set_status(status)
+    assert ow.M == M
+    return ow

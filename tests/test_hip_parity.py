@@ -487,28 +487,7 @@ def test_full_size_properties():
 
 
 # ---------------------------------------------------------------- the oracle at the sizes the metric is quoted on
-import functools
-import os
-
-
-@functools.lru_cache(maxsize=2)
-def _bench_cfg(workload):
-    """the very fields bench.py times (same generator arguments as its workload table)"""
-    from subzero_jl_amd import fields
-    wl = {"configs1": dict(n_floes=10000, seed=12345), "configs3": dict(n_floes=10000, seed=12345, walls=True, topography=True, ocean="strait"),
-          "configs2": dict(n_floes=100000, seed=12346, ocean="converge_diverge")}[workload]
-    return fields.make_config(**wl)
-
-
-def _cores():
-    n = len(os.sched_getaffinity(0))
-    try:
-        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()
-        if quota != "max":
-            n = max(1, min(n, int(quota) // int(period)))
-    except Exception:
-        pass
-    return n
+_bench_cfg, _cores = parity.bench_cfg, parity.cores
 
 
 @pytest.mark.parametrize("workload", ["configs1", "configs3"])
