@@ -13,8 +13,15 @@ ghost-floe halo traded every step (subzero_jl_amd.tiles) -- the job size is fixe
 scaling; `--floes K` runs N x K floes of the configs[1] field instead (weak scaling).
 
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (the narrow phase) with
-the algorithmic byte count of SURVEY.md §8(d) against HBM peak; `cpu_baseline` is the CPU oracle
-(a C/OpenMP port of the reference's algorithm) timed on the host cores of the same box.
+the algorithmic byte count of SURVEY.md §8(d) against HBM peak, from the launches of the timed
+steps themselves.
+
+A plain run sets up, relaxes, warms up, times, writes --dump-outputs and prints the line.  `--full`
+adds everything else the line can carry, each in runs of its own: the oracle's parity on the timed
+field and `cpu_baseline` (the CPU oracle, a C/OpenMP port of the reference's algorithm, timed on the
+host cores of the same box), the reference's default coupling interval and configs[2] on one GPU
+beside an N = 1 line, per-class kernel times, the measured copy ceiling, and for tiled runs the
+single-context parity and the one-GPU reference of the same field.
 """
 import argparse
 import json
@@ -497,17 +504,20 @@ def main():
     ap.add_argument("--coupling-dt", type=int, default=1, help="couple every k-th step (reference default: 10)")
     ap.add_argument("--relax-steps", type=int, default=50, help="untimed steps before the warm-up: the fields are generated on a jittered lattice "
                     "with overlapping neighbours and then relaxed, as SURVEY.md §8(d) specifies for the synthetic configurations (50 steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (cpu_baseline and the oracle parity of the timed field)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need (see the module "
+                    "docstring): the CPU legs, the secondary legs, per-class kernel times, the copy ceiling, the tiled parity and one-GPU reference")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU legs (cpu_baseline and the oracle parity of the timed field)")
     ap.add_argument("--rehearse-shared-gpu", action="store_true", help="N > 1 ranks that all use GPU 0, with gloo between them and the library's exchange "
                     "over the host channel (sz_comm_init_host): runs the whole multi-rank flow of this script on a one-GPU box; the "
                     "line it prints says so and is NOT a measurement")
     ap.add_argument("--force-tiled", action="store_true", help="run the halo/RCCL path even with one rank")
     ap.add_argument("--watchdog", type=float, default=300.0, help="self-launched N > 1 runs: seconds without a line from ANY rank after which the "
                     "parent kills the ranks and exits non-zero")
-    ap.add_argument("--no-strong-reference", action="store_true", help="N = 1: skip the extra leg that times the multi-GPU workload (configs[2], 100 000 floes) "
-                    "in one context on this GPU -- the denominator of the strong-scaling curve, which the N > 1 lines are measured on")
+    ap.add_argument("--no-strong-reference", action="store_true", help="--full, N = 1: skip the extra legs that time the multi-GPU workload (configs[2], 100 000 floes) "
+                    "in one context on this GPU -- the denominator of the strong-scaling curve, which the N > 1 lines are measured on -- and the reference's "
+                    "default coupling interval")
     ap.add_argument("--parity-steps", type=int, default=3, help="tiled runs: steps after which the owned columns of all ranks are compared with a "
-                    "single-context run of the same field on rank 0 (tiled_parity in the line); 0: skip")
+                    "single-context run of the same field on rank 0 (tiled_parity in the line, --full); 0: skip")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path computed in its last "
                     "step (floe state columns, ids / status, rings; with --two-way the ocean stress grids) as DIR/<name>.npy, float64, at most "
                     "64 MB in all (a fixed seeded sample of the floes above that); the inputs are fixed by the arguments")
@@ -627,37 +637,39 @@ def main():
             hw.set_precision("mixed")
         runner = lambda n, t0: tw.run(n, t0, cfg["dt"], coupling_dt=coupling_dt)
         log(f"tile set up: {len(tw.gidx)} owned floes, exchange = {backend}")
-        # ---- tiled result against the single context, at config scale: k steps of the timed field, owned columns of every rank
-        # gathered on rank 0 and compared bit for bit with ONE context stepping the whole field there
+        # ---- tiled result against the single context, at config scale (--full): k steps of the timed field, owned columns of every
+        # rank gathered on rank 0 and compared bit for bit with ONE context stepping the whole field there.  The k steps are a batch of
+        # their own in every run, so that the timed steps start from the same state with and without --full.
         k = max(0, min(args.parity_steps, args.relax_steps if args.relax_steps > 0 else args.parity_steps))
         if k > 0 and dist is not None:
             runner(k, 0); steps_run = k
-            mine = {"gidx": tw.gidx.copy()}
-            for f in PARITY_COLS:
-                mine[f] = hw.get(f)[:len(tw.gidx)]
-            parts = [None] * world if rank == 0 else None
-            dist.gather_object(mine, parts, dst=0)
-            if rank == 0:
-                tiled_parity = {"steps": k, "ranks": world, "columns": len(PARITY_COLS)}
-                try:
-                    ref = fields.build_world(subzero_jl_amd.World(local), cfg)
-                    ref.set_precision(args.precision)
-                    ref.run(k, 0, cfg["dt"], coupling_dt=coupling_dt, stop_on_tags=False); ref_steps = k
-                    g = np.concatenate([p_["gidx"] for p_ in parts])
-                    bad = {}
-                    worst = 0.0
-                    for f in PARITY_COLS:
-                        a = np.concatenate([p_[f] for p_ in parts]); b = ref.get(f)[g]
-                        if not np.array_equal(a, b):
-                            sc = max(float(np.max(np.abs(b))), 1e-300)
-                            bad[f] = float(np.max(np.abs(a - b)) / sc); worst = max(worst, bad[f])
-                    tiled_parity.update(floes_compared=int(len(g)), all_floes_covered=bool(len(g) == cfg["n_floes"] and len(np.unique(g)) == len(g)),
-                                        bit_equal=not bad, columns_differing=bad, max_rel_diff=worst,
-                                        ok=bool(not bad and len(g) == cfg["n_floes"]))
-                except Exception as e:      # noqa: BLE001
-                    tiled_parity.update(ok=False, error=str(e)[:300])
-                log(f"tiled parity after {k} steps: {tiled_parity}")
-            del mine, parts
+            if args.full:
+                mine = {"gidx": tw.gidx.copy()}
+                for f in PARITY_COLS:
+                    mine[f] = hw.get(f)[:len(tw.gidx)]
+                parts = [None] * world if rank == 0 else None
+                dist.gather_object(mine, parts, dst=0)
+                if rank == 0:
+                    tiled_parity = {"steps": k, "ranks": world, "columns": len(PARITY_COLS)}
+                    try:
+                        ref = fields.build_world(subzero_jl_amd.World(local), cfg)
+                        ref.set_precision(args.precision)
+                        ref.run(k, 0, cfg["dt"], coupling_dt=coupling_dt, stop_on_tags=False); ref_steps = k
+                        g = np.concatenate([p_["gidx"] for p_ in parts])
+                        bad = {}
+                        worst = 0.0
+                        for f in PARITY_COLS:
+                            a = np.concatenate([p_[f] for p_ in parts]); b = ref.get(f)[g]
+                            if not np.array_equal(a, b):
+                                sc = max(float(np.max(np.abs(b))), 1e-300)
+                                bad[f] = float(np.max(np.abs(a - b)) / sc); worst = max(worst, bad[f])
+                        tiled_parity.update(floes_compared=int(len(g)), all_floes_covered=bool(len(g) == cfg["n_floes"] and len(np.unique(g)) == len(g)),
+                                            bit_equal=not bad, columns_differing=bad, max_rel_diff=worst,
+                                            ok=bool(not bad and len(g) == cfg["n_floes"]))
+                    except Exception as e:      # noqa: BLE001
+                        tiled_parity.update(ok=False, error=str(e)[:300])
+                    log(f"tiled parity after {k} steps: {tiled_parity}")
+                del mine, parts
 
     def barrier():
         torch.cuda.synchronize()
@@ -665,9 +677,9 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # ---- the oracle's word on the very field this run times (N = 1): before the timing, on fresh contexts
+    # ---- the oracle's word on the very field this run times (N = 1, --full): before the timing, on fresh contexts
     parity_line = None
-    if not tiled and not args.no_cpu_baseline and rank == 0 and not args.two_way and args.precision == "f64":
+    if args.full and not tiled and not args.no_cpu_baseline and rank == 0 and not args.two_way and args.precision == "f64":
         parity_line = oracle_parity(cfg, local, steps=2, coupling_dt=coupling_dt)
         log(f"oracle parity: {parity_line}")
 
@@ -729,19 +741,21 @@ def main():
         kt = hw.kernel_times(); st_ev = hw.stats(); forcing_where = hw.forcing_launch()
     st = hw.stats()                           # counts of the last step (st_ev: the cumulative work counters of the event-timed block)
     kernel_name = hw.narrow_kernel_name()
-    ceiling = measured_hbm_ceiling(torch, torch.device("cuda", local)) if rank == 0 else 0.0
-    # per-class breakdown from a second, untimed pass with every class event-timed
-    nb = max(1, min(args.steps, 50))
-    hw.profile(True)
-    runner(nb, tstep)
-    torch.cuda.synchronize()
-    kt_all = hw.kernel_times()
-    hw.profile(False)
-    # strong scaling: the same workload on ONE GPU (rank 0, the context of the parity check beside its tile) through the SAME regime --
-    # the same relaxation and warm-up, the same step window, blocks of the same length, median -- so that the line carries its own
-    # reference point; the other ranks wait at the barrier
+    ceiling = kt_all = None
+    if args.full:
+        ceiling = measured_hbm_ceiling(torch, torch.device("cuda", local)) if rank == 0 else 0.0
+        # per-class breakdown from a second, untimed pass with every class event-timed
+        nb = max(1, min(args.steps, 50))
+        hw.profile(True)
+        runner(nb, tstep)
+        torch.cuda.synchronize()
+        kt_all = hw.kernel_times()
+        hw.profile(False)
+    # strong scaling (--full): the same workload on ONE GPU (rank 0, the context of the parity check beside its tile) through the SAME
+    # regime -- the same relaxation and warm-up, the same step window, blocks of the same length, median -- so that the line carries its
+    # own reference point; the other ranks wait at the barrier
     one_gpu = None
-    if tiled and world > 1:
+    if args.full and tiled and world > 1:
         if rank == 0:
             try:
                 if ref is None:
@@ -812,15 +826,15 @@ def main():
                          "pipelined_steps": pipelined,
                          "launches_per_step": 2 if pipelined else 3,
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "measured_copy_ceiling": ceiling, "frac_of_measured_ceiling": achieved / ceiling if ceiling > 0 else None,
+                         **({"measured_copy_ceiling": ceiling, "frac_of_measured_ceiling": achieved / ceiling if ceiling > 0 else None} if ceiling is not None else {}),
                          "kernel_ms": narrow_ms, "kernel_launches_timed": n_launch, "algorithmic_bytes_per_launch": b_launch,
                          "algorithmic_bytes_narrow_only": b_narrow, "algorithmic_bytes_geo": b_geo,
                          "counts_per_launch": win, "direction_checks": dirchk, "counts_note": "device counters accumulated over the launches the event time averages (the middle timed block)",
                          "step_algorithmic_bytes": step_bytes,
                          "step_frac": step_bytes / (el / args.steps) / 1e9 / HBM_PEAK_GBS,
                          "step_traffic": step_traffic(workload, cfg["n_floes"], kernel_name) if not tiled else None},
-            "kernel_ms_per_step": {k: (v[0] / nb) for k, v in kt_all.items()},
-            "kernel_ms_per_step_note": f"separate untimed pass of {nb} steps with all kernel classes event-timed",
+            **({"kernel_ms_per_step": {k: (v[0] / nb) for k, v in kt_all.items()},
+                "kernel_ms_per_step_note": f"separate untimed pass of {nb} steps with all kernel classes event-timed"} if kt_all is not None else {}),
             "counts": {k: st[k] for k in ("M", "N", "n_ghosts", "n_pairs", "n_pairs_clipped", "n_pair_rows", "n_elem_rows",
                                            "n_inter_rows", "n_ring_points", "n_sub_points", "n_trace_fail", "n_retry")},
             "tags_at_end_of_timed_window": {"n_status_remove": st["n_status_remove"], "n_status_fuse": st["n_status_fuse"],
@@ -848,12 +862,13 @@ def main():
             out["primary_exchange_failed"] = int(os.environ["SZ_BENCH_PRIMARY_RC"])
             out["primary_exchange_stderr"] = "gpurun_out/bench_failed_attempt_stderr.txt"
         if tiled:
-            out["exchange"] = {"backend": backend, "headers": "neighbouring tiles only (SZ_TILE_HEADERS=neighbours: measurement arm, no tag stop)" if os.environ.get("SZ_TILE_HEADERS") == "neighbours" else "every ordered pair of ranks (stop / pause words)",
-                               "ms_per_step_event_timed": (kt_all.get("exchange", (0.0, 0))[0] / nb) if "exchange" in kt_all else None,
-                               "note": "HIP events around the grouped send / receive on the library's communication stream, in the separate pass that event-times every class"}
+            out["exchange"] = {"backend": backend, "headers": "neighbouring tiles only (SZ_TILE_HEADERS=neighbours: measurement arm, no tag stop)" if os.environ.get("SZ_TILE_HEADERS") == "neighbours" else "every ordered pair of ranks (stop / pause words)"}
+            if kt_all is not None:
+                out["exchange"].update(ms_per_step_event_timed=(kt_all.get("exchange", (0.0, 0))[0] / nb) if "exchange" in kt_all else None,
+                                       note="HIP events around the grouped send / receive on the library's communication stream, in the separate pass that event-times every class")
         if args.rehearse_shared_gpu:
             out["data"] = "REHEARSAL: all ranks share GPU 0, transfers over gloo through the host -- not a measurement"
-        if world == 1 and not tiled and workload == "configs1" and coupling_dt == 1 and not args.two_way and not args.no_strong_reference:
+        if args.full and world == 1 and not tiled and workload == "configs1" and coupling_dt == 1 and not args.two_way and not args.no_strong_reference:
             # The line's `value` couples the floes to ocean and atmosphere in EVERY step (coupling_dt 1: the heaviest setting, and what rounds 1-3
             # timed).  The reference's own default is CouplingSettings(Δt = 10) (process_settings.jl:134-135): the same field, the same steps, with
             # the forcings evaluated every tenth step -- what a user who switches over with default settings would see.  Reported beside `value`,
@@ -876,7 +891,7 @@ def main():
                 del w10
             except Exception as e:      # noqa: BLE001
                 out["reference_default_coupling_interval"] = {"error": str(e)[:200]}
-        if world == 1 and not tiled and workload == "configs1" and args.floes == 0 and args.total_floes == 0 and not args.no_strong_reference:
+        if args.full and world == 1 and not tiled and workload == "configs1" and args.floes == 0 and args.total_floes == 0 and not args.no_strong_reference:
             # the N > 1 lines of this script time configs[2] (100 000 floes, strong scaling): the same field in ONE context on this GPU, through
             # the same regime, is the N = 1 point of THAT curve (this line's `value` is the metric's one-GPU configuration, configs[1])
             try:
@@ -900,7 +915,7 @@ def main():
                 del w2, cfg2
             except Exception as e:      # noqa: BLE001
                 out["strong_scaling_workload_on_one_gpu"] = {"error": str(e)[:200]}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             log("cpu baseline ...")
             out["cpu_baseline"] = cpu_baseline(cfg, relax_steps=args.relax_steps, device=local)
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
