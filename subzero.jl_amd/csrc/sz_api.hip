@@ -95,34 +95,26 @@ struct sz_ctx {
   bool blk_pts_ok = false, no_block_points = false; Pool blk_pt_allocs; int pts_N = 0;      // State::sxy (ensure_block_points); pts_N: floes whose soff entries are set (upload, migration)
   // mixed precision, geometry: fp32 broad-phase records and body-frame rings (sz_state.hpp); rings_stale: resident steps ran on the
   // body rings, the world rings vx / vy are behind (rebuilt by world_rings() before anything else looks at them)
-  bool mixed_geom_ok = false, rings_stale = false, no_body_rings = false; Pool mixed_geom_allocs;
+  bool mixed_geom_ok = false, rings_stale = false; Pool mixed_geom_allocs;
   // two-way coupling (off by default, like CouplingSettings())
-  bool tw_general_clip = false;   // SZ_TW_GENERAL_CLIP=1: floe-in-cell areas by the general clipper (8 lanes per entry) instead of the rectangle pipeline
   bool two_way = false; int tw_dt = 10; int tw_capM = 0; size_t tw_ncell = 0; bool temps_set = false;
   Pool tw_allocs, tw_field_allocs;
   // static broad-phase grid of the resident steps (fixed by the host: no bounds reduction per step)
   // inline ghosts (sz_kernels.hpp ghost_inline_make): the resident steps make a step's ghosts in the kernel that places their parents,
   // in allocation order; the reference's ghost numbers are recovered from the order keys of the last step that ran
-  bool ghost_inline = true;         // SZ_GHOST_INLINE=0: the candidate-list launch instead
   bool gi_valid = false;            // the interaction rows / pair lists on the device carry order keys of inline ghosts
   std::vector<long long> gi_keys;   // order key of the ghost at storage offset k (floe N + k) in the last step that ran
   bool gi_pending = false; int gi_pending_n = 0, gi_pending_slot = 0;      // ... still to be fetched from the device (gi_fetch)
   std::vector<int> gi_ref;          // ... and its number among the ghosts in the reference's order (ghost N + gi_ref[k])
   bool retry_seen = false;          // an item has needed the largest narrow variant: sz_step enqueues it in every step from now on
-  bool no_elems_ride = false;       // SZ_ELEMS_RIDE=0: the element items always get their own launch
   bool no_lean_narrow = false;      // SZ_LEAN_NARROW=0: always enqueue it
-  bool no_crec = false;             // SZ_CREC=0: no collision records (State::crec) in the resident steps
   double* frc_alt[4] = { nullptr, nullptr, nullptr, nullptr };      // second set of the forcing outputs fxOA, fyOA, trqOA, hflx (tiled steps with peers, see sz_tile_run)
-  bool tile_forcing_in_tail = false;      // SZ_TILE_FORCING_TAIL=1: tiled steps with peers keep the forcings in the narrow launch's tail (A/B switch)
   double2* crec_buf = nullptr;      // the records' memory (State::crec points at it only inside the batches that keep it current)
   bool crec_was_live = false;       // the last resident batch ran on records (sz_debug_crec_mismatches)
   int forcing_where = -1;           // sz_forcing_launch
   int fuse_forcing_mode = 0;        // ... 1: in the neighbour launch, 2: in the narrow launch (its tail), 0: by size -- the narrow launch while the narrow phase is one
                                     // round with a long tail (measured better up to 20 k floes, even at 40 k, worse at 65 k); SZ_FUSE_FORCING=1|2 forces one
   bool fuse_forcing = true;         // forcings inside the neighbour launch (sz_k_neighbors_forcing); SZ_FUSE_FORCING=0: own launch
-  bool fused_move = true;           // integrate + move/strain in one thread-per-floe launch when rings are small (-2 us at 10k); SZ_FUSED_MOVE=0: two launches
-  bool no_queue = false;            // SZ_NARROW_QUEUE=0: static split of the narrow items over the workgroups
-  bool no_static_grid = false;      // SZ_STATIC_GRID=0: fit the grid to the centroids every step (sz_k_bounds), as process mode does
   double rmax_max = 0.0, rmax_hint = 0.0; bool grid_ok = false, grid_live = false; double h_grid[8] = { 0 };
   unsigned scan_epoch = 0;      // launch counter of the look-back scans (their flags carry it: no reset pass)
   // ghost-candidate lists of the resident steps (sz_k_ghost_list): gl_cur = the list the next step consumes, gl_valid = it is
@@ -146,7 +138,6 @@ struct sz_ctx {
   std::vector<long long> tile_gidx; // global index of every owned floe (sz_tile_enable): status.fuse_idx of a tiled context is reported in global numbers
   bool tile_hdr_neighbours = false; // SZ_TILE_HEADERS=neighbours (measurement only, batches that run through): the inline steps trade with the neighbouring tiles only --
                                     // no header record to the others, hence no tag stop and no pause agreement in that arm (the largest narrow variant stays in)
-  bool tile_inline_off = false;     // SZ_TILE_INLINE=0: the tiled steps of sz_tile_run keep the list-based ghost pass, their own forcing launch and the one-workgroup unpack (A/B)
   double tile_box_ctr[2] = { 0, 0 }; bool tile_box_valid = false;   // centre of this rank's owned box at the last gather (sz_k_owned_box: periodic images)
   int tile_forcing_tstep = -1;      // timestep whose forcings sz_tile_forcing has already enqueued
   bool tile_dirty = false;      // ghosts / halo floes of the last sz_tile_step still appended
@@ -161,12 +152,10 @@ struct sz_ctx {
   int gpar = 0;
   bool no_pipeline = false;         // SZ_PIPELINE=0: the three-launch steps (A/B)
   int pipe_min_steps = 4;           // batches shorter than this take the three-launch steps (a pipelined batch has a prologue and an epilogue)
-  int frc_first = 0;                // SZ_FRC_FIRST=n: the forcing tail of the narrow launch as n persistent workgroups in FRONT of the narrow ones (0: behind them)
   int pipe_max_floes = 60000;       // larger fields keep the three-launch steps: they are throughput-bound, nothing idles beside the narrow phase (measured at 100 k: 0.486 against 0.476 ms; SZ_PIPE_MAX_FLOES)
   int last_pipelined = 0;           // the last sz_step batch ran pipelined (sz_debug_pipelined)
   bool crec_current = false;        // the collision records of set gpar hold the parents as they lie (a pipelined batch left them so; any call that moves or
                                     // re-uploads floes outside such a batch clears it) and the twin set has the static quads: the next batch seeds neither
-  bool no_reduce_free = false;      // SZ_REDUCE_FREE=0: keep the (rows-only) reduce launch inside every step (A/B)
   // fracture criterion (sz_set_fracture; sz_fracture.hpp): kind SZ_FRAC_*, FractureSettings.Δt, the device block and the per-parent buffers
   int frac_kind = 0, frac_dt = 0, frac_npts = 0, frac_cap = 0;
   double frac_pstar = 0, frac_c = 0, frac_alpha = 0, frac_min_area = 0;
@@ -174,7 +163,7 @@ struct sz_ctx {
   bool maybe_tagged = false;        // a parent may be non-active on the device (an upload said so, a batch ended on a tag, a process-mode call ran):
                                     // the next batch then runs its first step on its own (see sz_step)
   int last_err_bits = 0;   // device error bits the last sync_and_check found (tiled runs agree on them between the ranks)
-  int dbg = 0;   // SZ_DEBUG bits: timing experiments only (1 skip contact rows, 2 skip direction check, 4 skip clip)
+  int dbg = 0;   // SZ_DEBUG: read by the narrow kernel of a -DSZ_STAMPS build only (dbg >> 8: the workgroup it stamps, bit 16: its first round twice)
 };
 
 namespace {
@@ -562,8 +551,6 @@ bool larger_rings(const sz_ctx* c) {
 // rings that need it exist (sz_step's retry_stop mode), 2 only the larger variants (the rest of a paused step)
 void stage_narrow(sz_ctx* c, int dt, double ffmo, double fdmo, bool housekept = false, int frc = 0, int parts = 0) {
   State& S = c->S;
-  // dynamic rounds (see sz_k_narrow) where the queue heads were just cleared (static-grid steps); SZ_NARROW_QUEUE=0: off
-  const int queue = c->no_queue ? 0 : 1;      // (the reduce kernel resets the queue heads after every narrow phase)
   (void)housekept;
   long long capItems = (long long)S.capPairs + S.capElem;
   // Rings never change size inside the hot path, so the host knows whether any item can need a
@@ -585,14 +572,10 @@ void stage_narrow(sz_ctx* c, int dt, double ffmo, double fdmo, bool housekept = 
       if (getenv("SZ_VERBOSE")) fprintf(stderr, "[subzero-hip] narrow: %d workgroups per CU x %d CUs\n", per_cu, cus);
     }
     const int nbn = grid_for(capItems, TPB / G, grid);
-    int nbf = frc ? grid_for(S.capM, TPB / FRC_PLAIN, 32768) : 0;
-    const int nbfg = c->frc_first > 0 && nbf > 0 ? std::min(c->frc_first, nbf) : nbf;      // (workgroups in the grid)
-    if (c->frc_first > 0 && nbf > 0) nbf = -nbfg;
-    if (frc == 1) hipLaunchKernelGGL((sz_k_narrow<G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 1>), dim3(nbn + nbfg), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, queue, nbf, PipeAlt{}, 0, 0);
-    else if (frc == 2) hipLaunchKernelGGL((sz_k_narrow<G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 2>), dim3(nbn + nbfg), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, queue, nbf, PipeAlt{}, 0, 0);
-    else hipLaunchKernelGGL(kern, dim3(nbn), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, queue, 0, PipeAlt{}, 0, 0);
-    if (c->dbg & 8)       // timing experiment: the same launch again (same results) -- how much of a launch is a cold instruction cache?
-      hipLaunchKernelGGL(kern, dim3(nbn), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, queue, 0, PipeAlt{}, 0, 0);
+    const int nbf = frc ? grid_for(S.capM, TPB / FRC_PLAIN, 32768) : 0;
+    if (frc == 1) hipLaunchKernelGGL((sz_k_narrow<G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 1>), dim3(nbn + nbf), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, nbf, PipeAlt{}, 0, 0);
+    else if (frc == 2) hipLaunchKernelGGL((sz_k_narrow<G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 2>), dim3(nbn + nbf), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, nbf, PipeAlt{}, 0, 0);
+    else hipLaunchKernelGGL(kern, dim3(nbn), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
     t.end();
   }
   {
@@ -602,9 +585,9 @@ void stage_narrow(sz_ctx* c, int dt, double ffmo, double fdmo, bool housekept = 
     if (parts == 1 && !larger) { t.end(); return; }
     if (larger)
       hipLaunchKernelGGL((sz_k_narrow<16, NARROW_CAP1, 16, 80, 6, 64, NARROW_CAP0, 1>), dim3(grid_for(capItems, 4, 2048)), dim3(64), 0,
-                         c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, queue, 0, PipeAlt{}, 0, 0);
+                         c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
     hipLaunchKernelGGL((sz_k_narrow<64, NARROW_CAP2, NARROW_KC2, NARROW_RC2, 16, 64, NARROW_CAP1, 2>), dim3(grid_for(capItems, 1, larger ? 2048 : 256)), dim3(64), 0,
-                       c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, queue, 0, PipeAlt{}, 0, 0);
+                       c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
     t.end();
   }
 }
@@ -627,7 +610,7 @@ void collisions_step(sz_ctx* c, int n_init, int dt, bool commit_ghosts, bool sta
   if (!resume) {
     // resident steps of a field between walls: the element items are made in the tail of the neighbour search's launch
     const bool ride = static_grid && fuse_forcing != 1 && c->S.any_domain_work && !c->S.any_periodic_ew && !c->S.any_periodic_ns &&
-                      c->S.maxnb <= MAXNB && !c->no_elems_ride && !c->S.tiled;      // (a tile's neighbour launch commits the halo rows' count: the scan
+                      c->S.maxnb <= MAXNB && !c->S.tiled;      // (a tile's neighbour launch commits the halo rows' count: the scan
                                                                                         //  would read it while it changes)
     stage_broad(c, commit_ghosts, static_grid, fuse_forcing == 1, ride);
     if (!ride) stage_elems(c, true);
@@ -749,8 +732,7 @@ void stage_forcing(sz_ctx* c, int dt = -1) {      // in-order variant (process m
     scan(c, S.cl_cnt, S.cl_off, ncell, -1, ncell, C_NENT);
     hipLaunchKernelGGL(sz_k_tw_fill, dim3(ge), dim3(256), 0, c->stream, S);
     hipLaunchKernelGGL(sz_k_tw_sort, dim3(grid_for(ncell, 256)), dim3(256), 0, c->stream, S, ncell);
-    if (c->tw_general_clip) hipLaunchKernelGGL(sz_k_tw_area, dim3(grid_for((long long)S.capM * FC_CAP, 64 / TW_G, 4096)), dim3(64), 0, c->stream, S);
-    else hipLaunchKernelGGL(sz_k_tw_area_rect, dim3(grid_for((long long)S.capM * 16, 256, 8192)), dim3(256), 0, c->stream, S);
+    hipLaunchKernelGGL(sz_k_tw_area_rect, dim3(grid_for((long long)S.capM * 16, 256, 8192)), dim3(256), 0, c->stream, S);
     // tiled runs finish the cells after the partial sums of all ranks have been added up (sz_two_way_partial / _finish)
     if (!S.tiled) hipLaunchKernelGGL(sz_k_tw_reduce, dim3(grid_for(ncell, 256)), dim3(256), 0, c->stream, S, c->P, ncell, dt >= 0 ? dt : c->tw_dt);
   }
@@ -764,7 +746,7 @@ void stage_integrate(sz_ctx* c, int dt, bool reset_guards, bool apply_frc, bool 
   if (reset_guards) (void)hipMemsetAsync(c->S.warn, 0, (size_t)WARN_SLOTS * 32 * sizeof(int), c->stream);
   Timed t(c, SZ_K_INTEGRATE);
   // resident steps with small rings: one launch (thread per floe) integrates, moves the ring and bins the floe
-  if (bin && c->max_ring <= MV_RING && c->fused_move) {
+  if (bin && c->max_ring <= MV_RING) {
     // (tiled steps: the same thread also writes the floe's halo records for the next step -- sz_k_integrate<true, true>)
     if (pack) hipLaunchKernelGGL((sz_k_integrate<true, true>), dim3(grid_for(c->S.capM, 128)), dim3(128), 0, c->stream, c->S, c->P, dt, apply_frc ? 1 : 0, 1, nh, gl_fill, ginl, *pack, c->acc_mode);
     else hipLaunchKernelGGL(sz_k_integrate<true>, dim3(grid_for(c->S.capM, 128)), dim3(128), 0, c->stream, c->S, c->P, dt, apply_frc ? 1 : 0, 1, nh, gl_fill, ginl, PackInl{}, c->acc_mode);
@@ -884,28 +866,13 @@ sz_ctx* sz_create(int device_id) {
   c->device = device_id;
   if (const char* e = getenv("SZ_DEBUG")) c->dbg = atoi(e);
   if (const char* e = getenv("SZ_OVERLAP")) c->overlap_forcing = atoi(e) != 0 ? 1 : 0;
-  if (const char* e = getenv("SZ_NARROW_QUEUE")) c->no_queue = atoi(e) == 0;
-  if (const char* e = getenv("SZ_FUSED_MOVE")) c->fused_move = atoi(e) != 0;
-  if (const char* e = getenv("SZ_TW_GENERAL_CLIP")) c->tw_general_clip = atoi(e) != 0;
   if (const char* e = getenv("SZ_LEAN_NARROW")) c->no_lean_narrow = atoi(e) == 0;
-  if (const char* e = getenv("SZ_CREC")) c->no_crec = atoi(e) == 0;
-  if (const char* e = getenv("SZ_REDUCE_FREE")) c->no_reduce_free = atoi(e) == 0;
   if (const char* e = getenv("SZ_PIPELINE")) c->no_pipeline = atoi(e) == 0;
   if (const char* e = getenv("SZ_TILE_HEADERS")) c->tile_hdr_neighbours = strcmp(e, "neighbours") == 0;
   if (const char* e = getenv("SZ_PIPE_MIN_STEPS")) c->pipe_min_steps = std::max(2, atoi(e));
   if (const char* e = getenv("SZ_PIPE_MAX_FLOES")) c->pipe_max_floes = atoi(e);
-  if (const char* e = getenv("SZ_FRC_FIRST")) c->frc_first = std::max(0, atoi(e));
   if (const char* e = getenv("SZ_BLOCK_POINTS")) c->no_block_points = atoi(e) == 0;
-  if (const char* e = getenv("SZ_TILE_FORCING_TAIL")) c->tile_forcing_in_tail = atoi(e) != 0;
-  if (const char* e = getenv("SZ_GHOST_INLINE")) c->ghost_inline = atoi(e) != 0;
-  if (const char* e = getenv("SZ_TILE_INLINE")) c->tile_inline_off = atoi(e) == 0;
-  if (const char* e = getenv("SZ_ELEMS_RIDE")) c->no_elems_ride = atoi(e) == 0;
   if (const char* e = getenv("SZ_FUSE_FORCING")) { c->fuse_forcing = atoi(e) != 0; if (atoi(e) > 0) c->fuse_forcing_mode = atoi(e) >= 2 ? 2 : 1; }
-  if (const char* e = getenv("SZ_STATIC_GRID")) c->no_static_grid = atoi(e) == 0;
-  if (const char* e = getenv("SZ_BODY_RINGS")) c->no_body_rings = atoi(e) == 0;
-  if (const char* e = getenv("SZ_XCD")) c->S.xcd_neigh = atoi(e) != 0 ? 1 : 0;
-  c->S.xcd_forcing = 0;          // measured: no change at 10 k floes, 159 -> 203 us at 100 k
-  if (const char* e = getenv("SZ_XCD_FORCING")) c->S.xcd_forcing = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("SZ_GHOST_LIST")) { c->no_ghost_list = atoi(e) == 0; if (atoi(e) > 1) c->gl_max = atoi(e); }
   int prio_lo = 0, prio_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);     // lo = least urgent, hi = most urgent
@@ -1756,7 +1723,7 @@ void pipe_adopt(sz_ctx* c, int q) {
 bool pipeline_eligible(const sz_ctx* c, int nsteps, bool coll, bool sg, bool gi, bool periodic, bool cr, bool rfree, int flags) {
   return rfree && !c->no_pipeline && c->frac_kind == SZ_FRAC_OFF && coll && sg && (gi || !periodic) && cr && nsteps >= c->pipe_min_steps && c->hostN <= c->pipe_max_floes && c->precision == 0 && !c->two_way &&
          (!c->S.any_domain_work || (!periodic && !c->any_moving)) && c->S.maxnb <= MAXNB && !larger_rings(c) && c->pb[1].vxy && c->pb[1].work &&
-         (c->S.capM - c->hostN) / 2 > 64 && !(c->dbg & 8) && (flags & SZ_COLLISIONS_ON);
+         (c->S.capM - c->hostN) / 2 > 64 && (flags & SZ_COLLISIONS_ON);
 }
 
 // A batch of pipelined steps: L1(s) = narrow(s) | GEO(s) | forcings(s), L2(s) = VEL(s) | search(s + 1).  Same contract as the loop of sz_step
@@ -1823,26 +1790,23 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
   }
   const long long capItems = (long long)S0.capPairs + S0.capElem;
   const int nbn = grid_for(capItems, TPB / NARROW_G, c->narrow_grid0), nbg = grid_for(N, TPB, 1 << 20);
-  const int queue = c->no_queue ? 0 : 1;
   auto launch_L1 = [&](int s, bool make_ghosts) {
     State T = pipe_state(c, par(s)); T.step = s + 1; T.callid = callid0 + s + 1; T.retry_stop = lean ? 1 : 0;
     const PipeAlt A = pipe_alt(c, par(s + 1), make_ghosts ? 1 : 0);
     const bool coupling = coupling_at(s);
     const bool overlap = coupling && (c->overlap_forcing >= 0 ? c->overlap_forcing != 0 : N > 65536);
     if (overlap) stage_forcing_fork(c, &T);
-    int nbf = coupling && !overlap ? grid_for(S0.capM, TPB / FRC_PLAIN, 32768) : 0;
-    const int nbfg = c->frc_first > 0 && nbf > 0 ? std::min(c->frc_first, nbf) : nbf;
-    if (c->frc_first > 0 && nbf > 0) nbf = -nbfg;
+    const int nbf = coupling && !overlap ? grid_for(S0.capM, TPB / FRC_PLAIN, 32768) : 0;
     if (coupling) c->forcing_where = overlap ? 0 : 2;
     Timed tm(c, SZ_K_NARROW);          // (event-timed classes of a pipelined step: "narrow" = L1, "integrate" = L2)
-    if (nbf) hipLaunchKernelGGL((sz_k_narrow<NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 1, 1>), dim3(nbn + nbg + nbfg), dim3(TPB), 0, c->stream,
-                                T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, queue, nbf, A, nbg, N);
+    if (nbf) hipLaunchKernelGGL((sz_k_narrow<NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 1, 1>), dim3(nbn + nbg + nbf), dim3(TPB), 0, c->stream,
+                                T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, nbf, A, nbg, N);
     else hipLaunchKernelGGL((sz_k_narrow<NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 0, 1>), dim3(nbn + nbg), dim3(TPB), 0, c->stream,
-                            T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, queue, 0, A, nbg, N);
+                            T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, 0, A, nbg, N);
     tm.end();
     if (!lean) {          // the largest variant takes what the small one hands on (see stage_narrow)
       hipLaunchKernelGGL((sz_k_narrow<64, NARROW_CAP2, NARROW_KC2, NARROW_RC2, 16, 64, NARROW_CAP1, 2>), dim3(grid_for(capItems, 1, 256)), dim3(64), 0,
-                         c->stream, T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, queue, 0, PipeAlt{}, 0, 0);
+                         c->stream, T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, 0, PipeAlt{}, 0, 0);
     }
     return overlap;
   };
@@ -1930,7 +1894,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
       (void)hipMemsetAsync(S0.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream); (void)hipMemsetAsync(S0.cnt + C_PAUSED, 0, sizeof(int), c->stream);
       State T = pipe_state(c, par(sr)); T.step = sr + 1; T.callid = callid0 + sr + 1; T.retry_stop = 0;
       hipLaunchKernelGGL((sz_k_narrow<64, NARROW_CAP2, NARROW_KC2, NARROW_RC2, 16, 64, NARROW_CAP1, 2>), dim3(grid_for(capItems, 1, 256)), dim3(64), 0,
-                         c->stream, T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, queue, 0, PipeAlt{}, 0, 0);
+                         c->stream, T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, 0, PipeAlt{}, 0, 0);
       const bool host_last = sr + 1 == s_end;
       S0.retry_stop = 0;
       launch_L2(sr, !host_last, host_last, false);
@@ -2126,13 +2090,13 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   HIPCHK(c, hipMemsetAsync(c->S.cnt + C_STOP, 0, sizeof(int), c->stream));
   HIPCHK(c, hipMemsetAsync(c->S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream));
   bool last_coupled = false;
-  const bool sg = coll && c->grid_ok && !c->no_static_grid;
+  const bool sg = coll && c->grid_ok;
   if (sg) use_static_grid(c);
   const bool gl = ghost_list_wanted(c, sg);
   // (ghosts a process-mode sz_add_ghosts left attached are dropped first: the list pass only visits the parents that get new ones)
   if (gl && periodic && c->hostM != c->hostN) hipLaunchKernelGGL(sz_k_remove_ghosts, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, 0);
   // inline ghosts: no ghost launch in the steps at all (the integrator makes the next step's ghosts; needs the one-launch integrator)
-  const bool gi = gl && c->ghost_inline && !c->S.tiled && c->fused_move && c->max_ring <= MV_RING;
+  const bool gi = gl && !c->S.tiled && c->max_ring <= MV_RING;
   if (gl && !gi) use_ghost_list(c); else c->gl_valid = false;
   const int gl0 = c->gl_cur;
   c->S.ginline = gi ? 1 : 0;
@@ -2145,17 +2109,22 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   if (c->precision == 0 && !c->two_way && c->have_fields) { int rc = ensure_block_points(c); if (rc) return rc; }
   // mixed precision: the steps run on body-frame rings (the integrator moves poses, not rings) when nothing else in the batch
   // needs world rings -- single context, the list path for the ghosts, rings small enough for the fused integrator
-  const bool body = mixed && coll && sg && (gl || !periodic) && !c->S.tiled && c->fused_move && c->max_ring <= MV_RING && !c->no_body_rings;
+  const bool body = mixed && coll && sg && (gl || !periodic) && !c->S.tiled && c->max_ring <= MV_RING;
   if (!body) world_rings(c);
   c->S.body_rings = body ? 1 : 0;
   // collision records (State::crec): in batches whose kernels keep them current -- the one-launch integrator, and for periodic walls the
   // inline ghost maker; seeded here from the columns (before the ghost seed: the maker updates the records of the parents it visits)
-  const bool cr = coll && sg && !c->no_crec && c->crec_buf && c->fused_move && c->max_ring <= MV_RING && (gi || !periodic) && nsteps > 0;
+  const bool cr = coll && sg && c->crec_buf && c->max_ring <= MV_RING && (gi || !periodic) && nsteps > 0;
   c->S.crec = cr ? c->crec_buf : nullptr; c->crec_was_live = cr;
+  // Fixed-point totals (State::facc; sz_geom.hpp): the narrow phase adds every row to both floes' totals, the integrator reads them -- no reduce
+  // launch inside the steps.  floe.interactions of the step that ended the batch is assembled once, behind the batch (stage_reduce(.., behind)):
+  // that needs the ghosts of that step still in their rows, i.e. the one-launch integrator with inline ghosts (or no periodic wall), which
+  // knows when it runs a batch's last step (sz_k_integrate: last_step).  The other paths keep the launch inside the step, rows only.
+  const bool facc_on = coll && c->facc_buf != nullptr;
+  const bool rfree = facc_on && sg && (gi || !periodic) && c->max_ring <= MV_RING && !c->any_moving;
   // pipelined batches (sz_pipeline.hpp: two launches per step) run their own prologue -- records, first ghosts, first neighbour search
   c->last_pipelined = 0;
-  const bool pipe = pipeline_eligible(c, nsteps, coll, sg, gi, periodic, cr,
-                                      coll && c->facc_buf != nullptr && !c->no_reduce_free && sg && (gi || !periodic) && c->fused_move && c->max_ring <= MV_RING && !c->any_moving, flags);
+  const bool pipe = pipeline_eligible(c, nsteps, coll, sg, gi, periodic, cr, rfree, flags);
   if (!pipe) c->crec_current = false;          // (the three-launch steps seed the records they use; they may not keep the twin set's)
   if (cr && !pipe) hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(c->hostN, 256)), dim3(256), 0, c->stream, c->S, c->hostN);
   if (gi && !pipe) {               // the ghosts of the first step, from the parents as they lie (after the rings are in the batch's form)
@@ -2165,12 +2134,6 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   // the largest narrow variant only takes items the small one hands on (none in most fields): it is left out of the steps until one
   // shows up -- the batch then pauses inside that step (stopped_late()) and is finished below
   bool lean = coll && !c->retry_seen && !c->no_lean_narrow && !c->S.tiled && !larger_rings(c);
-  // Fixed-point totals (State::facc; sz_geom.hpp): the narrow phase adds every row to both floes' totals, the integrator reads them -- no reduce
-  // launch inside the steps.  floe.interactions of the step that ended the batch is assembled once, behind the batch (stage_reduce(.., behind)):
-  // that needs the ghosts of that step still in their rows, i.e. the one-launch integrator with inline ghosts (or no periodic wall), which
-  // knows when it runs a batch's last step (sz_k_integrate: last_step).  The other paths keep the launch inside the step, rows only.
-  const bool facc_on = coll && c->facc_buf != nullptr;
-  const bool rfree = facc_on && !c->no_reduce_free && sg && (gi || !periodic) && c->fused_move && c->max_ring <= MV_RING && !c->any_moving;
   c->S.facc = facc_on ? c->facc_buf : nullptr; c->S.kexp = force_scale_exp(c);
   c->reduce_mode = !facc_on ? 0 : rfree ? 2 : 1;
   if (facc_on && !pipe) {          // (a pipelined batch clears them with the rest of its prologue: one launch)
@@ -2229,7 +2192,7 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
       }
       c->S.gslot = s & 1;
       // (the totals of the rows the inline makers allocated for this step are cleared by its neighbour search when it runs on collision records;
-      //  without them -- SZ_CREC=0 -- here)
+      //  without them -- lists wider than MAXNB -- here)
       if (facc_on && gi && !(cr && c->S.maxnb <= MAXNB) && !resume) (void)hipMemsetAsync(c->facc_buf + (size_t)FX_WORDS * c->hostN, 0, (size_t)FX_WORDS * (c->S.capM - c->hostN) * sizeof(long long), c->stream);
       if (coll) collisions_step(c, c->hostN, dt, periodic && !sg, sg, resume ? 0 : fmode, lean, resume);
       if (overlap && !resume) stage_forcing_join(c);
@@ -2516,7 +2479,7 @@ int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int
   (void)hipSetDevice(c->device);
   State& S = c->S;
   const bool coll = (flags & SZ_COLLISIONS_ON) != 0;
-  const bool sg = coll && c->grid_ok && !c->no_static_grid;
+  const bool sg = coll && c->grid_ok;
   if (sg) use_static_grid(c);
   const bool gl = ghost_list_wanted(c, sg);
   if (gl) use_ghost_list(c); else c->gl_valid = false;
@@ -3566,10 +3529,10 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   const bool coll = (flags & SZ_COLLISIONS_ON) != 0;
   // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
   // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
-  // Needs what the inline ghost maker needs (rings that fit the one-launch integrator, the static grid).  Otherwise (and with
-  // SZ_TILE_INLINE=0): the list-based steps of sz_tile_step.
+  // Needs what the inline ghost maker needs (rings that fit the one-launch integrator, the static grid).  Otherwise: the list-based steps
+  // of sz_tile_step.
   S.crec = nullptr;
-  const bool inl = coll && !c->tile_inline_off && c->ghost_inline && c->fused_move && c->grid_ok && !c->no_static_grid && !c->two_way &&
+  const bool inl = coll && c->grid_ok && !c->two_way &&
                    std::max(c->max_ring, c->max_ring_tiled) <= MV_RING && ((flags & SZ_COUPLING_ON) == 0 || c->have_fields);
   if (!inl) {
     // The tag stop of these steps (one-way coupling): the pack kernel's header records carry every rank's stop word to EVERY rank, the unpack
@@ -3636,7 +3599,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   HIPCHK(c, hipMemsetAsync(S.galloc, 0, 32 * sizeof(unsigned long long), c->stream));
   // the periodic ghosts of the owned floes for the first step (and the swap of parents that lie outside the domain), BEFORE the first pack
   // collision records of the owned floes (the halo floes get theirs from the unpack kernel, ghosts from their maker; see sz_step)
-  S.crec = (!c->no_crec && c->crec_buf && nsteps > 0) ? c->crec_buf : nullptr; c->crec_was_live = S.crec != nullptr;
+  S.crec = (c->crec_buf && nsteps > 0) ? c->crec_buf : nullptr; c->crec_was_live = S.crec != nullptr;
   if (S.crec) hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(c->hostN, 256)), dim3(256), 0, c->stream, S, c->hostN);
   // (the periodic ghosts of the owned floes for the first step, and the swap of parents that lie outside the domain: in the loop, BEHIND the
   //  first pack -- see there)
@@ -3644,7 +3607,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   // in the unpack of the NEXT one -- after its integrator has made that step's ghosts over the rows of this one -- so the rows are then
   // assembled inside every step (rows only); alone, or in batches that run through (SZ_NO_STOP), once behind the batch.
   const bool facc_on = c->facc_buf != nullptr;
-  const int rmode = !facc_on ? 0 : (c->no_reduce_free || (n > 1 && S.stop_on_tags)) ? 1 : 2;
+  const int rmode = !facc_on ? 0 : n > 1 && S.stop_on_tags ? 1 : 2;
   S.facc = facc_on ? c->facc_buf : nullptr; S.kexp = force_scale_exp(c); c->reduce_mode = rmode;
   if (facc_on) {
     HIPCHK(c, hipMemsetAsync(c->facc_buf, 0, (size_t)FX_WORDS * S.capM * sizeof(long long), c->stream));
@@ -3705,7 +3668,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
     // With peers the forcings of the owned floes (they need nothing from the halo) run BESIDE the exchange -- on the main stream while the
     // communication stream trades the regions, before the host's channel blocks -- and the narrow launch carries no forcing tail; without
     // peers there is nothing to hide them behind and they ride in the narrow launch's tail as in sz_step.
-    const bool beside = coupling && n > 1 && !(c->pmask >> SZ_K_FORCING & 1u) && !c->tile_forcing_in_tail;
+    const bool beside = coupling && n > 1 && !(c->pmask >> SZ_K_FORCING & 1u);
     // (these forcings run before this rank knows whether a peer has asked for the batch to end at the previous step -- the unpack kernel
     //  below finds out.  They therefore write a SECOND set of the four output columns, alternating step by step, and the set the last
     //  step that really ran has written is made the context's at the end of the call: a batch that ends early leaves fxOA .. hflx of the

@@ -660,7 +660,7 @@ enum { KIN_I = 0, KIN_J = 7, KIN_AREA_I = 5, KIN_H_I = 6, KIN_AREA_J = 12, KIN_H
 
 struct ItemCtx {
   int mode;            // ITEM_PAIR: floe-floe; ITEM_OPEN: open boundary; ITEM_SOLID: collision/moving boundary, topography
-  double E, nu, mu; int dt; int dbg;
+  double E, nu, mu; int dt;
   double max_overlap;  // floe_floe_max_overlap (pairs) or floe_domain_max_overlap (elements)
   int elem_dir;        // -1 floe-floe / topography; else SZ_NORTH.. for _normal_direction_correct!
   double elem_val;
@@ -717,7 +717,6 @@ SZ_DEV void contact_post(MEM& m, int gl, int na, int nb, const ItemCtx& cx_, int
       if (amax / area_i > cx_.max_overlap) { flags |= IT_REMOVE; break; }
       force_factor = cx_.E * h_i / sqrt(area_i);
     }
-    if (cx_.dbg & 1) break;
     STAMP(st, 12);
     // unique crossing points (GO.intersection_points): first occurrences in canonical order
     const int K = m.nx;
@@ -778,12 +777,12 @@ SZ_DEV void contact_post(MEM& m, int gl, int na, int nb, const ItemCtx& cx_, int
         }
       }
       // the direction check runs for a region with area and a contact length (collisions.jl:58)
-      const bool check = m.rarea[0][rr] != 0 && ddl > 0.1 && !(cx_.dbg & 2);
+      const bool check = m.rarea[0][rr] != 0 && ddl > 0.1;
       // a region with exactly two crossings on its boundary is a lens: its check can be certified from the crossing detection of the
       // translated polygon alone (certified_check below)
       int ncr = 0;
       for (int k = 0; k < K; k++) ncr += m.creg[k] == rr;
-      if (gl == 0) { m.dlv[w] = ddl; m.dxv[w] = ddx; m.dyv[w] = ddy; if (check) { m.chk[nchk] = (int8_t)w; m.chkc[nchk] = (ncr == 2 && !(cx_.dbg & 64)) ? 1 : 0; } }
+      if (gl == 0) { m.dlv[w] = ddl; m.dxv[w] = ddx; m.dyv[w] = ddy; if (check) { m.chk[nchk] = (int8_t)w; m.chkc[nchk] = ncr == 2 ? 1 : 0; } }
       if (check) nchk++;
     }
     STAMP(st, 8);

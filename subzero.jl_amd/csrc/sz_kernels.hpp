@@ -1198,22 +1198,6 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int nblk, int nact) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
 }
 
-// the same for workgroups [first, first + nblk) of a launch (horizontal fusion: the forcing workgroups come after the neighbour
-// search's): the XCD label is that of the PHYSICAL workgroup id, the rank counts the workgroups of the range on that XCD
-__device__ __forceinline__ int xcd_contiguous_from(int phys, int first, int nblk, int nact) {
-  const int x = phys % 8;
-  const int f0 = first + ((x - first % 8) + 8) % 8;            // first workgroup of the range on XCD x
-  const int idx = (phys - f0) / 8;
-  // workgroups of the range per XCD: labels in the range's own order are (x - first) mod 8
-  const int lx = ((x - first % 8) + 8) % 8;
-  if (nact <= nblk) {
-    const int q = nact / 8, r = nact % 8;
-    const int cnt = q + (lx < r ? 1 : 0), start = lx < r ? lx * (q + 1) : r * (q + 1) + (lx - r) * q;
-    return idx < cnt ? start + idx : -1;
-  }
-  const int q = nblk / 8, r = nblk % 8;
-  return (lx < r ? lx * (q + 1) : r * (q + 1) + (lx - r) * q) + idx;
-}
 
 // Work list of the narrow phase: NSEG segments of capPairs / NSEG pair items, filled by the neighbour search (segment =
 // workgroup index modulo NSEG, one tail counter per segment a cache line apart: same-address atomics serialise chip-wide).
@@ -1298,13 +1282,11 @@ __device__ __forceinline__ void neighbors_body(State& S, int bid, int nblk) {
   const int ncx = g.ncx, ncy = g.ncy;
   const int seg = bid % NSEG, segcap = seg_cap(S);
   // (measured: contiguous ranges per XCD pay in the reduce kernel -- 12.9 -> 11.3 us at 10 k floes, 51 -> 44 at 100 k -- but cost
-  //  the neighbour search and, through the uneven segments of the work list, the narrow phase 20 % at 100 k floes: plain order
-  //  here unless SZ_XCD=1)
-  const int vb0 = S.xcd_neigh ? xcd_contiguous(bid, nblk, (M + GPB - 1) / GPB) : bid;
+  //  the neighbour search and, through the uneven segments of the work list, the narrow phase 20 % at 100 k floes: plain order here)
   // (the floe's own row is asked for before the count of floes is looked at -- rows up to capM exist, one past the end is read and
   //  ignored: the launch's first two round trips, counter block and row, become one)
   static_assert(16 % GPB == 0 || GPB % 16 == 0, "blocks of rows must not straddle nsplit");
-  for (int kb = vb0 < 0 ? S.capM : vb0 * GPB; kb < S.capM; kb += nblk * GPB) {
+  for (int kb = bid * GPB; kb < S.capM; kb += nblk * GPB) {
     const bool hi = REC && kb >= nsplit;                        // (uniform)
     const int k = (hi ? kb + kshift : kb) + gi;
     const bool act = k < (hi ? lim1 : lim0);
@@ -1329,7 +1311,7 @@ __device__ __forceinline__ void neighbors_body(State& S, int bid, int nblk) {
     }
     loads_issued();
     if (stop_test(S, stop) || kb >= M) break;
-    if (bid == 0 && threadIdx.x == 0 && kb == vb0 * GPB) { S.cnt[C_ITEMCLASS] = 0; S.cnt[C_NFUSE] = 0; }     // per-step counters the narrow phase raises
+    if (bid == 0 && threadIdx.x == 0 && kb == bid * GPB) { S.cnt[C_ITEMCLASS] = 0; S.cnt[C_NFUSE] = 0; }     // per-step counters the narrow phase raises
     if constexpr (REC) { if (act && k >= nfix) S.facc[(size_t)k * FX_WORDS + gl] = 0; }         // (NB_G = FX_WORDS lanes: one line)
     __syncthreads();
     if (gl == 0) { cnts[gi][0] = 0; cnts[gi][1] = 0; npool[gi] = 0; if constexpr (MW == 1) wmask[gi] = (mask_t)0; }
@@ -1559,12 +1541,10 @@ __device__ __forceinline__ void neighbors_body(State& S, int bid, int nblk) {
 // NBC = 256 (a floe with more than 64 neighbours in one direction: a large floe among many small ones): a quarter of the lane groups per
 // workgroup (48 KB of LDS for four floes) -- the capacity that keeps such a field running, not a fast path
 template <int NBC> constexpr int nb_tpb() { return NBC > 64 ? 64 : NB_TPB; }
-#ifndef SZ_NB_LEAN_WPE
-#define SZ_NB_LEAN_WPE 1      // (measured: the lean instantiation on records compiled for five wavefronts per SIMD -- 96 registers, 32 B of scratch -- is slower,
-                              //  79.2 -> 84.8 us at 100 k floes, even at 40 k: profiles/r03_runs/r3_h_*)
-#endif
+// (measured: the lean instantiation on records compiled for five wavefronts per SIMD -- 96 registers, 32 B of scratch -- is slower,
+//  79.2 -> 84.8 us at 100 k floes, even at 40 k: profiles/r03_runs/r3_h_*)
 template <bool FAM, int NBC = MAXNB, bool REC = false>
-__global__ void __launch_bounds__(nb_tpb<NBC>(), (NBC > 64 ? 1 : NBC > MAXNB ? (FAM ? 3 : 4) : (REC && !FAM ? SZ_NB_LEAN_WPE : 1))) sz_k_neighbors(State S) { neighbors_body<nb_tpb<NBC>(), FAM, NBC, REC>(S, blockIdx.x, gridDim.x); }
+__global__ void __launch_bounds__(nb_tpb<NBC>(), (NBC > 64 ? 1 : NBC > MAXNB ? (FAM ? 3 : 4) : 1)) sz_k_neighbors(State S) { neighbors_body<nb_tpb<NBC>(), FAM, NBC, REC>(S, blockIdx.x, gridDim.x); }
 
 // The compact pair list in the reference's serial order (i asc, j asc) -- out_off, pair_i, pair_j -- is only made when
 // the host asks for it (sz_download_pairs): fill after a scan of n_out.
@@ -1663,32 +1643,24 @@ __global__ void __launch_bounds__(NB_TPB) sz_k_neighbors_elem(State S, unsigned 
 // narrow phase of a small field is ONE round whose length is set by its slowest wavefront (~47 us at 10 k floes, most
 // wavefronts are done after 20): the forcings (22 us as a launch of their own) run in that tail instead of beside the neighbour search.
 template <bool TW>
-__device__ __forceinline__ void forcing_body(State& S, const Params& P, int bid, int nblk, int pmax, int first);
-__device__ __forceinline__ void forcing_mixed_body(State& S, const Params& P, int bid, int nblk, int first);
+__device__ __forceinline__ void forcing_body(State& S, const Params& P, int bid, int nblk, int pmax);
+__device__ __forceinline__ void forcing_mixed_body(State& S, const Params& P, int bid, int nblk);
 // GEO / PA / nbg / nn (pipelined steps, sz_pipeline.hpp): nbg more workgroups, straight behind the narrow ones, make the geometry of the NEXT step
 // (thread per parent, nn parents) into the other parity's buffers
 __device__ __forceinline__ void geo_body(State S, const PipeAlt& A, int dt, int bid, int nblk, int N);
 template <int G, int CAP, int KC, int RC, int RM, int TPB, int LO, int CLS, int WPE = 1, int FRC = 0, int GEO = 0>
-__global__ void __launch_bounds__(TPB, WPE) sz_k_narrow(State S, Params P, int dt, double ff_max_overlap, double fd_max_overlap, int dbg, int queue, int nbf,
+__global__ void __launch_bounds__(TPB, WPE) sz_k_narrow(State S, Params P, int dt, double ff_max_overlap, double fd_max_overlap, int dbg, int nbf,
                                                        PipeAlt PA, int nbg, int nn) {
   constexpr int GPB = TPB / G;
-  // nbf < 0: -nbf forcing workgroups IN FRONT of the narrow ones (a few persistent wavefronts per CU that walk all floes, in the wave slots the
-  // narrow workgroups -- which fill the LDS -- leave free) instead of behind them
-  const int nf = nbf < 0 ? -nbf : nbf;
-  const int nblk = (int)gridDim.x - (FRC != 0 ? nf : 0) - (GEO != 0 ? nbg : 0);       // the narrow workgroups
+  const int nblk = (int)gridDim.x - (FRC != 0 ? nbf : 0) - (GEO != 0 ? nbg : 0);       // the narrow workgroups
   // (the GEO workgroups come FIRST: a few wavefronts per CU that fit beside the narrow ones -- those fill the LDS, not the wave slots -- and
   //  are done long before the narrow round is; behind the narrow workgroups they would only start when those finish)
   if (GEO != 0 && (int)blockIdx.x < nbg) { geo_body(S, PA, dt, (int)blockIdx.x, nbg, nn); return; }
-  int bidx = (int)blockIdx.x - (GEO != 0 ? nbg : 0);        // this workgroup's number among the narrow ones
-  if (FRC != 0) {
-    int fb = -1, first = 0;
-    if (nbf < 0) { if (bidx < nf) { fb = bidx; first = GEO != 0 ? nbg : 0; } else bidx -= nf; }
-    else if (bidx >= nblk) { fb = bidx - nblk; first = nblk + (GEO != 0 ? nbg : 0); }
-    if (fb >= 0) {
-      if (FRC == 1) forcing_body<false>(S, P, fb, nf, 0, first);
-      else forcing_mixed_body(S, P, fb, nf, first);
-      return;
-    }
+  const int bidx = (int)blockIdx.x - (GEO != 0 ? nbg : 0);        // this workgroup's number among the narrow ones
+  if (FRC != 0 && bidx >= nblk) {
+    if (FRC == 1) forcing_body<false>(S, P, bidx - nblk, nbf, 0);
+    else forcing_mixed_body(S, P, bidx - nblk, nbf);
+    return;
   }
   static_assert(4 * KC <= 2 * RC, "raw crossing slots alias reg[1]");
   Stamps st; STAMP_INIT(st);
@@ -1737,7 +1709,7 @@ __global__ void __launch_bounds__(TPB, WPE) sz_k_narrow(State S, Params P, int d
   // items at a time and the wavefront then works the flagged ones off one by one.
   constexpr bool SCAN = (G == 64 && TPB == 64);
   constexpr int STRIDE = SCAN ? 64 : GPB;
-  const bool useq = CLS == 0 && !SCAN && queue != 0;       // (the larger variants look at every item of their segment: static rounds)
+  const bool useq = CLS == 0 && !SCAN;       // (the larger variants look at every item of their segment: static rounds)
   const int rb = bidx / NSEG, nbq = (nblk + NSEG - 1 - qk) / NSEG;    // this workgroup's rank in its segment, workgroups per segment
   const int limit = nitems;
   // (measured and dropped: spreading the only round of a small field over ALL resident workgroups -- 6 to 7 items per wavefront
@@ -1796,7 +1768,7 @@ __global__ void __launch_bounds__(TPB, WPE) sz_k_narrow(State S, Params P, int d
     }
     STAMP(st, 23);
     ItemCtx ic;
-    ic.E = P.E; ic.nu = P.nu; ic.mu = P.mu; ic.dt = dt; ic.dbg = dbg;
+    ic.E = P.E; ic.nu = P.nu; ic.mu = P.mu; ic.dt = dt;
     ic.mode = ITEM_PAIR; ic.max_overlap = ff_max_overlap; ic.elem_dir = -1; ic.elem_val = 0.0; ic.rigid_j = 0;
     int flags = 0;
     int pna = 0, pnb = 0, poa = 1, pob = 1; Box pba{ 0, 0, 0, 0 }, pbb{ 0, 0, 0, 0 };      // operands of the pass's clip
@@ -1936,7 +1908,7 @@ __global__ void __launch_bounds__(TPB, WPE) sz_k_narrow(State S, Params P, int d
 #endif
       for (int pass = 0; pass == 0 || (pass - 1) * GPB < total; pass++) {
         bool run = false, cert = false; int g = gi, q = 0, buf = 0; double ox = 0.0, oy = 0.0;
-        if (pass == 0) run = have && !(dbg & 4);
+        if (pass == 0) run = have;
         else {
           const int idx = (pass - 1) * GPB + gi;
           if (idx < total) {
@@ -2085,7 +2057,7 @@ __global__ void __launch_bounds__(TPB, WPE) sz_k_narrow(State S, Params P, int d
     // one set of atomics per wavefront, spread over ACC_SLOTS lines (same-address atomics serialise chip-wide)
     unsigned v[7];
     for (int k = 0; k < 7; k++) { v[k] = gl != 0 ? 0u : k == 0 ? m.acc16[0] : k == 1 ? m.acc[0] : k == 2 ? m.acc[1] : k == 3 ? m.acc16[1] : k == 4 ? m.acc16[2] : k == 5 ? m.acc16[3] : m.acc16[4]; for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d); }
-    if ((threadIdx.x & 63) == 0 && !(dbg & 32)) {          // (SZ_DEBUG=32: without the work counters -- a timing experiment)
+    if ((threadIdx.x & 63) == 0) {
       unsigned long long* a = S.acc + (size_t)((bidx * (TPB / 64) + (threadIdx.x >> 6)) % ACC_SLOTS) * 8;
       for (int k = 0; k < 7; k++) if (v[k]) atomicAdd(a + 1 + k, (unsigned long long)v[k]);
       if (CLS == 0 && bidx == 0 && threadIdx.x == 0) atomicAdd(a, 1ull);
@@ -2469,12 +2441,9 @@ __device__ __forceinline__ void forcing_wrap(const State& S, int i, double& cx, 
   if (S.any_periodic_ns) { const double maxv = S.eval[0], minv = S.eval[1], L = maxv - minv; if (cy < minv) cy = cy + L; else if (maxv < cy) cy = cy + (-L); }
 }
 constexpr int FRC_G = 32;      // lanes per floe of the two-way variant
-#ifndef FRC_PLAIN_LANES
-#define FRC_PLAIN_LANES 16
-#endif
-constexpr int FRC_PLAIN = FRC_PLAIN_LANES;   // lanes per floe of the one-way kernels.  Round 4, lean loop (tools/probe/r4_frc_lanes.sh; ms/step at 10 k | 100 k floes):
-                                             // 64 lanes 0.0846 | 0.5173, 32 lanes 0.0772 | 0.4894, 16 lanes 0.0765 | 0.4773, 8 lanes 0.0774 | 0.5038 -- a floe's ~100 points
-                                             // fill 7 trips of 16 lanes to 90 %, 4 trips of 32 to 78 %; with 8 lanes the floes' scalar loads take over
+constexpr int FRC_PLAIN = 16;   // lanes per floe of the one-way kernels.  Round 4, lean loop (tools/probe/r4_frc_lanes.sh; ms/step at 10 k | 100 k floes):
+                                // 64 lanes 0.0846 | 0.5173, 32 lanes 0.0772 | 0.4894, 16 lanes 0.0765 | 0.4773, 8 lanes 0.0774 | 0.5038 -- a floe's ~100 points
+                                // fill 7 trips of 16 lanes to 90 %, 4 trips of 32 to 78 %; with 8 lanes the floes' scalar loads take over
 // Two-way coupling (TW): the kernel also fills the floe's part of grid.floe_locations / ocean.scells
 // (floe_to_grid_info!, coupling.jl:1417-1454): per distinct centre cell its sub-floe points fall into, the
 // periodic shift of the first such point, the sum of minus the ocean stress over the points IN POINT ORDER, and
@@ -2485,10 +2454,9 @@ constexpr int TW_PMAX = 512;    // sub-floe points per floe with two-way couplin
 constexpr int TW_FPB = 4;       // floes per workgroup of the two-way variant (128 threads)
 // pmax (two-way only): sub-floe points per floe the launch provides LDS for (dynamic: 21 bytes per point and floe;
 // the host sizes it from the largest floe, so that as many floes as possible are in flight per CU)
-// bid / nblk: rank and number of the forcing workgroups; first: physical id of the first of them in the launch.  The floes of one
-// XCD's workgroups are a contiguous index range (= a region in space): a lattice node is then fetched by one or two XCDs' L2
-// instead of all eight
-// ---- the one-way forcings with lean per-point arithmetic (round 4; SZ_FRC_LEAN=0 compiles the plain loop back in for A/B).
+// bid / nblk: rank and number of the forcing workgroups (measured and dropped: the floes of one XCD's workgroups as a contiguous index
+// range -- no change at 10 k floes, 159 -> 203 us at 100 k)
+// ---- the one-way forcings with lean per-point arithmetic (round 4; two-way coupling keeps the plain per-point loop of forcing_body).
 // The contract on fxOA / fyOA / trqOA / hflx is a tolerance against the reference (1e-10 relative; the reference's own tests hold them to
 // 1e-3), not bit-equality with the straightforward evaluation -- and the kernel is bound by the fp64 instructions it issues (L1 launch at
 // 10 k floes: 63 % of all issue cycles busy, a third of its vector instructions are this loop).  What stays EXACTLY as before: the
@@ -2498,9 +2466,6 @@ constexpr int TW_FPB = 4;       // floes per workgroup of the two-way variant (1
 //     relative speeds: zero or far above the denormal range),
 //   * the stress sums contracted into fused multiply-adds,
 //   * the next point's body coordinates are asked for before the current point is worked on.
-#ifndef SZ_FRC_LEAN
-#define SZ_FRC_LEAN 1
-#endif
 __device__ __forceinline__ double sqrt_fast(double s) {
   const double y = __builtin_amdgcn_rsq(s);
   double g = s * y, h = 0.5 * y;
@@ -2511,11 +2476,11 @@ __device__ __forceinline__ double sqrt_fast(double s) {
   return s > 0.0 ? g : 0.0;
 }
 template <int FG>
-__device__ __forceinline__ void forcing_lean_body(State& S, const Params& P, int bid, int nblk, int first);
+__device__ __forceinline__ void forcing_lean_body(State& S, const Params& P, int bid, int nblk);
 
 template <bool TW>
-__device__ __forceinline__ void forcing_body(State& S, const Params& P, int bid, int nblk, int pmax, int first) {
-  if constexpr (!TW && SZ_FRC_LEAN != 0) { forcing_lean_body<FRC_PLAIN>(S, P, bid, nblk, first); return; }
+__device__ __forceinline__ void forcing_body(State& S, const Params& P, int bid, int nblk, int pmax) {
+  if constexpr (!TW) { forcing_lean_body<FRC_PLAIN>(S, P, bid, nblk); return; }
   extern __shared__ double tw_lds[];
   constexpr int FG = TW ? FRC_G : FRC_PLAIN;      // lanes per floe
   int lane = threadIdx.x % FG, wpb = blockDim.x / FG, wid = threadIdx.x / FG;
@@ -2530,8 +2495,7 @@ __device__ __forceinline__ void forcing_body(State& S, const Params& P, int bid,
   int N = S.cnt[C_NOWN];
   int per_x = S.ekind[2] == 1, per_y = S.ekind[0] == 1;
   double cturn = cos(P.turn), sturn = sin(P.turn);
-  const int vb0 = S.xcd_forcing ? xcd_contiguous_from(first + bid, first, nblk, (N + wpb - 1) / wpb) : bid;
-  for (int i = vb0 < 0 ? N : vb0 * wpb + wid; i < N; i += nblk * wpb) {
+  for (int i = bid * wpb + wid; i < N; i += nblk * wpb) {
     double cxf = S.cx[i], cyf = S.cy[i], u = S.u[i], v = S.v[i], xi = S.xi[i];
     forcing_wrap(S, i, cxf, cyf);
     double ca = S.trig[2 * i], sa = S.trig[2 * i + 1];   // cos(alpha), sin(alpha)
@@ -2728,13 +2692,12 @@ __device__ __forceinline__ void forcing_lean_floe(const State& S, const Params& 
   }
 }
 template <int FG>
-__device__ __forceinline__ void forcing_lean_body(State& S, const Params& P, int bid, int nblk, int first) {
+__device__ __forceinline__ void forcing_lean_body(State& S, const Params& P, int bid, int nblk) {
   const int lane = threadIdx.x % FG, wpb = blockDim.x / FG, wid = threadIdx.x / FG;
   if (stopped(S)) return;
   const int N = S.cnt[C_NOWN];
   const FrcConsts C = frc_consts(S, P);
-  const int vb0 = S.xcd_forcing ? xcd_contiguous_from(first + bid, first, nblk, (N + wpb - 1) / wpb) : bid;
-  for (int i = vb0 < 0 ? N : vb0 * wpb + wid; i < N; i += nblk * wpb) {
+  for (int i = bid * wpb + wid; i < N; i += nblk * wpb) {
     int npt; double fx, fy, trq, hf;
     forcing_lean_floe<FG>(S, P, C, i, lane, npt, fx, fy, trq, hf);
     if (lane == 0) {
@@ -2747,7 +2710,7 @@ __device__ __forceinline__ void forcing_lean_body(State& S, const Params& P, int
 }
 
 template <bool TW>
-__global__ void __launch_bounds__(256) sz_k_forcing(State S, Params P, int pmax) { forcing_body<TW>(S, P, blockIdx.x, gridDim.x, pmax, 0); }
+__global__ void __launch_bounds__(256) sz_k_forcing(State S, Params P, int pmax) { forcing_body<TW>(S, P, blockIdx.x, gridDim.x, pmax); }
 
 // dynamic LDS of sz_k_forcing<true> for pmax points per floe
 inline size_t tw_forcing_lds(int pmax) { return (size_t)TW_FPB * ((size_t)2 * pmax * sizeof(double) + (size_t)(pmax + FC_CAP) * (sizeof(int) + 1)); }
@@ -2802,15 +2765,14 @@ __device__ __forceinline__ float sample_field32(const float* nodes, int f, const
   float c1 = (1.0f - ty) * nodes[(size_t)c.o10 * 8 + f] + ty * nodes[(size_t)c.o11 * 8 + f];
   return (1.0f - tx) * c0 + tx * c1;
 }
-__device__ __forceinline__ void forcing_mixed_body(State& S, const Params& P, int bid, int nblk, int first) {
+__device__ __forceinline__ void forcing_mixed_body(State& S, const Params& P, int bid, int nblk) {
   if (stopped(S)) return;
   int N = S.cnt[C_NOWN];
   int lane = threadIdx.x % FRC_PLAIN, wpb = blockDim.x / FRC_PLAIN, wid = threadIdx.x / FRC_PLAIN;
   int per_x = S.ekind[2] == 1, per_y = S.ekind[0] == 1;
   const float cturn = (float)cos(P.turn), sturn = (float)sin(P.turn);
   const float ka = (float)(P.rho_a * P.Cd_ia), ko = (float)(P.rho_o * P.Cd_io);
-  const int vb0 = S.xcd_forcing ? xcd_contiguous_from(first + bid, first, nblk, (N + wpb - 1) / wpb) : bid;
-  for (int i = vb0 < 0 ? N : vb0 * wpb + wid; i < N; i += nblk * wpb) {
+  for (int i = bid * wpb + wid; i < N; i += nblk * wpb) {
     double cxf = S.cx[i], cyf = S.cy[i]; const double u = S.u[i], v = S.v[i];
     forcing_wrap(S, i, cxf, cyf);
     const float uf = (float)u, vf = (float)v, xif = (float)S.xi[i];
@@ -2862,7 +2824,7 @@ __device__ __forceinline__ void forcing_mixed_body(State& S, const Params& P, in
   }
 }
 
-__global__ void __launch_bounds__(256, 6) sz_k_forcing_mixed(State S, Params P) { forcing_mixed_body(S, P, blockIdx.x, gridDim.x, 0); }
+__global__ void __launch_bounds__(256, 6) sz_k_forcing_mixed(State S, Params P) { forcing_mixed_body(S, P, blockIdx.x, gridDim.x); }
 
 // Horizontal fusion: the neighbour search and the forcings are independent of each other (the forcings only need
 // the state the previous step left) and both are latency-bound per-floe kernels of ~20 us that leave most of the
@@ -2871,8 +2833,8 @@ __global__ void __launch_bounds__(256, 6) sz_k_forcing_mixed(State S, Params P) 
 template <int FRC, bool REC = false>
 __global__ void __launch_bounds__(256) sz_k_neighbors_forcing(State S, Params P, int nb_neigh) {
   if ((int)blockIdx.x < nb_neigh) neighbors_body<256, false, MAXNB, REC>(S, blockIdx.x, nb_neigh);      // (fields of 30 k floes and more: the lean instantiation)
-  else if (FRC == 1) forcing_body<false>(S, P, (int)blockIdx.x - nb_neigh, (int)gridDim.x - nb_neigh, 0, nb_neigh);
-  else forcing_mixed_body(S, P, (int)blockIdx.x - nb_neigh, (int)gridDim.x - nb_neigh, nb_neigh);
+  else if (FRC == 1) forcing_body<false>(S, P, (int)blockIdx.x - nb_neigh, (int)gridDim.x - nb_neigh, 0);
+  else forcing_mixed_body(S, P, (int)blockIdx.x - nb_neigh, (int)gridDim.x - nb_neigh);
 }
 
 // ============================================================================ rigid-body update (A12)

@@ -82,8 +82,6 @@ struct State {
   int pipe;                  // this launch belongs to a pipelined step (the ghost maker leaves the parent's COLUMNS alone and marks a swapped parent)
   int restart_on_tags;       // pipelined batches that run through (SZ_NO_STOP): a NEW tag still ends the enqueued steps -- the host starts the rest again,
                              // so that the next step's ghosts are made knowing the tag (the steps' ghosts are made one launch ahead of the tags)
-  int xcd_forcing;           // SZ_XCD_FORCING=1: XCD-contiguous floe ranges in the forcing kernels (A/B switch; default off: slower at 100 k)
-  int xcd_neigh;             // SZ_XCD=1: XCD-contiguous floe ranges in the neighbour search too (A/B switch; default off)
   // ---- counters
   int* cnt;
   int* warn;                 // guard counters of timestep_floe_properties!: WARN_SLOTS slots of 32 ints (one 128-byte line each; words 0..3 =

@@ -2,9 +2,9 @@
 // The forcing kernel (sz_k_forcing<true>) has left, per floe, the centre cells its sub-floe points fell into
 // with the summed ocean stress (floe_to_grid_info!).  Here: the per-cell lists (a counting sort over the
 // (Nx+1) x (Ny+1) centre cells, entries ordered by floe index = the order the serial reference pushes them),
-// the area of floe ∩ cell for every entry (the same group-cooperative clip as the contact path, the cell
-// rectangle as ring a, the translated floe ring as ring b: intersect_polys(cell_poly, floe_poly)), and the
-// per-cell reduction incl. the atmosphere-on-ocean stress and the heat-flux factor.
+// the area of floe ∩ cell for every entry (intersect_polys(cell_poly, floe_poly): the translated floe ring
+// clipped to the cell rectangle, sz_k_tw_area_rect), and the per-cell reduction incl. the atmosphere-on-ocean
+// stress and the heat-flux factor.
 #pragma once
 #include "sz_kernels.hpp"
 
@@ -57,51 +57,7 @@ __device__ __forceinline__ void center_cell(const State& S, int ix0, int iy0, in
     ymax = ymax > S.gyf ? S.gyf : (ymax < S.gy0 ? S.gy0 : ymax);
   }
 }
-// floe_area_in_cell of every (floe, cell) entry: G lanes per entry
-constexpr int TW_G = 8, TW_CAP = 32, TW_KC = 16, TW_RC = 64, TW_RM = 6;
-__global__ void __launch_bounds__(64) sz_k_tw_area(State S) {
-  if (stopped(S)) return;          // (a step behind the one that ended the batch: its launches are enqueued and return at once, like the forcing kernel's)
-  if (stopped(S)) return;
-  constexpr int GPB = 64 / TW_G;
-  __shared__ GroupMem<TW_CAP, TW_KC, TW_RC, TW_RM> mem[GPB];
-  const int gl = threadIdx.x % TW_G, gi = threadIdx.x / TW_G;
-  auto& m = mem[gi];
-  const int nent = S.cnt[C_NENT];
-  const int per_x = S.ekind[2] == 1, per_y = S.ekind[0] == 1;
-  if (gl == 0) { m.err = 0; m.ntracefail = 0; }
-  Stamps st; STAMP_INIT(st);
-  for (int t0 = blockIdx.x * GPB; t0 < nent; t0 += gridDim.x * GPB) {
-    const int t = t0 + gi;
-    if (t >= nent) continue;
-    const int ent = S.cl_ent[t];
-    const int i = ent / FC_CAP, q = S.fc_key[ent], code = S.fc_code[ent];
-    const int ix0 = q / (S.Ny + 1), iy0 = q % (S.Ny + 1);
-    // (shifted_idx - idx) * grid.Δ, coupling.jl:1432-1433: the shift is one grid length or none
-    const double dx = (double)((code % 3 - 1) * S.Nx) * S.gdx, dy = (double)((code / 3 - 1) * S.Ny) * S.gdy;
-    double xmin, xmax, ymin, ymax;
-    center_cell(S, ix0, iy0, per_x, per_y, xmin, xmax, ymin, ymax);
-    const int bo = S.voff[i], nb = S.voff[i + 1] - bo;
-    gsync();
-    if (nb > TW_CAP) { if (gl == 0) { atomicOr(&S.cnt[C_ERR], ERR_CAP_RING); S.fc_area[ent] = 0.0; } continue; }
-    // _make_bounding_box_polygon: (xmin,ymin) (xmin,ymax) (xmax,ymax) (xmax,ymin) (xmin,ymin)
-    if (gl < 5) { m.ax[gl] = (gl == 2 || gl == 3) ? xmax : xmin; m.ay[gl] = (gl == 1 || gl == 2) ? ymax : ymin; }
-    for (int k = gl; k < nb; k += TW_G) { const double2 p = S.vxy[bo + k]; m.bx[k] = p.x + dx; m.by[k] = p.y + dy; }   // _translate_poly
-    gsync();
-    const Box ba{ xmin, xmax, ymin, ymax };
-    const Box bb{ S.bbx0[i] + dx, S.bbx1[i] + dx, S.bby0[i] + dy, S.bby1[i] + dy };
-    const int oa = ring_signed_area(m.ax, m.ay, 5) >= 0.0 ? 1 : -1;   // as sz_k_osign does for floe rings (listed clockwise: -1)
-    clip<TW_G>(m, gl, 0.0, 0.0, 5, oa, nb, (int)S.osign[i], 0, ba, bb, st);
-    gsync();
-    double a = 0.0;
-    const int nreg = m.nreg[0];
-    for (int r = 0; r < nreg; r++) a += m.rarea[0][r];
-    if (gl == 0) S.fc_area[ent] = a;
-  }
-  gsync();
-  if (gl == 0 && (m.err & (ERR_CAP_XING | ERR_CAP_REGION))) atomicOr(&S.cnt[C_ERR], m.err);
-  if (gl == 0 && m.ntracefail) atomicAdd(&S.cnt[C_TRACE_FAIL], m.ntracefail);
-}
-// ---- the same areas, one thread per entry.  The clip window is an axis-parallel rectangle, so the intersection
+// ---- floe_area_in_cell of every (floe, cell) entry, one thread per entry.  The clip window is an axis-parallel rectangle, so the intersection
 // is what the re-entrant Sutherland-Hodgman pipeline produces: every ring vertex is pushed through the four
 // half-plane stages (left, right, bottom, top), each stage remembers its first and previous point only, and what
 // leaves the last stage is summed into the shoelace area on the fly -- no polygon is stored, no LDS, no lane sits
@@ -109,7 +65,8 @@ __global__ void __launch_bounds__(64) sz_k_tw_area(State S) {
 // emits one ring whose connecting edges run along the window's boundary back and forth and cancel in the area,
 // so the sum equals the total of the pieces (what the reference adds up over intersect_polys' regions).
 // Coordinates are taken relative to the window's corner: the result carries less round-off than the general
-// clipper's (differences of a few 1e-11 relative at 2000 km; the tests state 1e-9).
+// clipper of the contact path (differences of a few 1e-11 relative at 2000 km; the tests state 1e-9), and the
+// rings have no size cap.
 struct RectClip {
   double w, h;                  // window [0, w] x [0, h]
   double fx[4], fy[4], px[4], py[4];

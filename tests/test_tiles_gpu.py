@@ -971,7 +971,7 @@ def migration_case(world, n, seed, steps, every, verbose=True, shape="star", fas
     cfg = _field(n, seed, fast=fast, shape=shape)
     hw = fields.build_world(subzero_jl_amd.World(0), cfg)
     if os.environ.get("SZ_FUZZ_PRECISION") == "mixed":
-        hw.set_precision("mixed")          # (with SZ_BODY_RINGS=0 in the environment: a tile keeps its rings in world coordinates, fp64)
+        hw.set_precision("mixed")          # (a tile keeps its rings in world coordinates, fp64; this single context runs on body-frame rings)
     ran = hw.run(steps, 0, cfg["dt"], coupling_dt=1, stop_on_tags=stop)
     seen = np.zeros(n, bool); moved = 0
     for rank, gidx, out, mv, cost in res:

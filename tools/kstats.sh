@@ -1,6 +1,6 @@
 #!/bin/bash
 # per-kernel averages (rocprofv3 --kernel-trace --stats) of the default bench under an environment setting:
-#   tools/kstats.sh SZ_STATIC_GRID=0
+#   tools/kstats.sh SZ_OVERLAP=1
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for kv in "$@"; do export "$kv"; done
 cd /tmp && export TMPDIR=/tmp

@@ -1,5 +1,5 @@
 #!/bin/bash
-# kernel durations at 100 k floes, every kernel alone on the chip (SZ_OVERLAP=0), under extra environment settings:  r4_kstats_100k_env.sh SZ_REDUCE_FREE=0
+# kernel durations at 100 k floes, every kernel alone on the chip (SZ_OVERLAP=0), under extra environment settings:  r4_kstats_100k_env.sh SZ_PIPELINE=0
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for kv in "$@"; do export "$kv"; done
 cd /tmp && export TMPDIR=/tmp; rm -rf $R/gpurun_out/prof_ka
