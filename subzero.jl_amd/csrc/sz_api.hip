@@ -220,6 +220,8 @@ inline int grid_for(long long n, int tpb, int maxb = 4096) {
   if (b > maxb) b = maxb;
   return (int)b;
 }
+// timestep tstep computes the forcings (a coupling step)
+inline bool coupling_at(int flags, int coupling_dt, int tstep) { return (flags & SZ_COUPLING_ON) && coupling_dt > 0 && (tstep % coupling_dt) == 0; }
 
 struct Timed {   // RAII-free helper: begin/end a timed kernel class
   sz_ctx* c; int k; size_t idx = (size_t)-1; hipStream_t st;
@@ -339,6 +341,23 @@ int grow_lists(sz_ctx* c, int bits) {
   c->inter_lost = false;             // (the call that is run again provides the rows)
   return rc;
 }
+// The rows of a batch's last step, assembled behind the batch, outgrew the stride (ERR_CAP_INTER alone; the device word is clear): only the
+// rows' memory grows (collisions.jl:290-296) and that launch runs again, on the State `rows` builds -- after the carve, which moves inter_cnt /
+// inter_rows.  h: the counter block of the last try.
+template <typename RowsState>
+int regrow_rows(sz_ctx* c, int* h, RowsState rows) {
+  for (int tries = 0; tries < 6; tries++) {
+    c->S.rowcap *= 4;
+    if (c->S.rowcap > 8192) { c->err = "a floe has more than 8192 interaction rows"; return SZ_E_CAPACITY; }
+    if (int rc = carve_interactions(c)) return rc;
+    c->inter_lost = false;
+    const State R = rows();
+    hipLaunchKernelGGL(sz_k_inter_fill, dim3(grid_for(R.capM, 128 / IF_G, 16384)), dim3(128), 0, c->stream, R, 1, c->hostN, 0, 1, 1);
+    const int rc = sync_and_check(c, h);
+    if (!(rc == SZ_E_CAPACITY && c->last_err_bits == ERR_CAP_INTER)) return rc;
+  }
+  return SZ_E_CAPACITY;
+}
 
 // ---------------------------------------------------------------- element table upload
 int upload_elements(sz_ctx* c) {
@@ -447,6 +466,22 @@ void world_rings(sz_ctx* c) {
 }
 // every call outside the resident steps: the candidate list they keep goes stale, the world rings must be current
 void leave_resident(sz_ctx* c) { c->gl_valid = false; c->S.famrec = 0; c->crec_current = false; world_rings(c); }
+// The per-batch modes of State and sz_ctx (what a resident batch's kernels are told about the batch they run in) for the life of one batch
+// driver, sz_step or sz_tile_run: the batch starts from their process-mode values, and every way out of it -- early returns and HIPCHK
+// included -- puts them back.  What is meant to outlive a batch (candidate lists, records, pending ghost keys, tags) is no mode.
+struct BatchModes {
+  sz_ctx* c;
+  explicit BatchModes(sz_ctx* c_) : c(c_) { clear(); }
+  ~BatchModes() { clear(); }
+  BatchModes(const BatchModes&) = delete;
+  BatchModes& operator=(const BatchModes&) = delete;
+  void clear() {
+    State& S = c->S;
+    S.step = 0; S.retry_stop = 0; S.stop_on_tags = 0; S.restart_on_tags = 0; S.ginline = 0; S.famrec = 0; S.body_rings = 0;
+    S.crec = nullptr; S.facc = nullptr; S.goff = 0; S.gcap = 0; S.pipe = 0;
+    c->acc_mode = 0; c->reduce_mode = 0;
+  }
+};
 
 // the candidate list of the coming step, seeded from the parents as they lie
 void use_ghost_list(sz_ctx* c) {
@@ -455,6 +490,13 @@ void use_ghost_list(sz_ctx* c) {
   c->gl_cur = 0;
   hipLaunchKernelGGL(sz_k_ghost_seed, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, 0);
   c->gl_valid = true;
+}
+// inline ghosts: those of the step that starts a batch (or starts it again) from the parents as they lie, in allocator `slot`
+int reseed_inline_ghosts(sz_ctx* c, int slot) {
+  HIPCHK(c, hipMemsetAsync(c->S.galloc, 0, 32 * sizeof(unsigned long long), c->stream));
+  c->S.gslot = slot;
+  hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, slot, c->hostN);
+  return SZ_OK;
 }
 bool ghost_list_wanted(const sz_ctx* c, bool sg) {
   // (the list pass gives a parent one wavefront lane per ring point: rings of up to 64 points)
@@ -547,6 +589,20 @@ void stage_elems(sz_ctx* c, bool enabled) {
 bool larger_rings(const sz_ctx* c) {
   return std::max(std::max(c->max_ring, c->max_elem_ring), c->S.tiled ? c->max_ring_tiled : 0) > NARROW_CAP0;
 }
+// grid of the first narrow variant: as many workgroups as the chip holds at once, so that every one of them runs the same number of rounds
+int narrow_grid(sz_ctx* c) {
+  int& grid = c->narrow_grid0;
+  if (grid == 0) {
+    int per_cu = 0, cus = 0;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sz_k_narrow<NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, 64, 0, 0, 3, 0>, 64, 0);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+    grid = per_cu > 0 && cus > 0 ? per_cu * cus : 2048;
+    if (const char* e = getenv("SZ_NARROW_GRID")) { int v = atoi(e); if (v > 0) grid = v; }
+    if (getenv("SZ_VERBOSE")) fprintf(stderr, "[subzero-hip] narrow: %d workgroups per CU x %d CUs\n", per_cu, cus);
+  }
+  return grid;
+}
+void narrow_largest(sz_ctx* c, const State& T, int dt, double ffmo, double fdmo, int maxb);
 // parts: 0 everything (the largest variant is always enqueued: it takes the items the others hand on), 1 without the largest variant unless
 // rings that need it exist (sz_step's retry_stop mode), 2 only the larger variants (the rest of a paused step)
 void stage_narrow(sz_ctx* c, int dt, double ffmo, double fdmo, bool housekept = false, int frc = 0, int parts = 0) {
@@ -562,16 +618,7 @@ void stage_narrow(sz_ctx* c, int dt, double ffmo, double fdmo, bool housekept = 
     constexpr int G = NARROW_G, TPB = 64;
     // 160 VGPRs (3 wavefronts per SIMD) and 16 KB of LDS per workgroup: 10 workgroups = 80 items in flight per CU
     auto kern = sz_k_narrow<G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 0>;
-    int& grid = c->narrow_grid0;
-    if (grid == 0) {       // as many workgroups as the chip holds at once, so that every one of them runs the same number of rounds
-      int per_cu = 0, cus = 0;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, TPB, 0);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-      grid = per_cu > 0 && cus > 0 ? per_cu * cus : 2048;
-      if (const char* e = getenv("SZ_NARROW_GRID")) { int v = atoi(e); if (v > 0) grid = v; }
-      if (getenv("SZ_VERBOSE")) fprintf(stderr, "[subzero-hip] narrow: %d workgroups per CU x %d CUs\n", per_cu, cus);
-    }
-    const int nbn = grid_for(capItems, TPB / G, grid);
+    const int nbn = grid_for(capItems, TPB / G, narrow_grid(c));
     const int nbf = frc ? grid_for(S.capM, TPB / FRC_PLAIN, 32768) : 0;
     if (frc == 1) hipLaunchKernelGGL((sz_k_narrow<G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 1>), dim3(nbn + nbf), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, nbf, PipeAlt{}, 0, 0);
     else if (frc == 2) hipLaunchKernelGGL((sz_k_narrow<G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 2>), dim3(nbn + nbf), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, nbf, PipeAlt{}, 0, 0);
@@ -586,15 +633,25 @@ void stage_narrow(sz_ctx* c, int dt, double ffmo, double fdmo, bool housekept = 
     if (larger)
       hipLaunchKernelGGL((sz_k_narrow<16, NARROW_CAP1, 16, 80, 6, 64, NARROW_CAP0, 1>), dim3(grid_for(capItems, 4, 2048)), dim3(64), 0,
                          c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
-    hipLaunchKernelGGL((sz_k_narrow<64, NARROW_CAP2, NARROW_KC2, NARROW_RC2, 16, 64, NARROW_CAP1, 2>), dim3(grid_for(capItems, 1, larger ? 2048 : 256)), dim3(64), 0,
-                       c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
+    narrow_largest(c, S, dt, ffmo, fdmo, larger ? 2048 : 256);
     t.end();
   }
+}
+// the largest narrow variant, on the items the smaller ones hand on; maxb caps its grid (256, or 2048 where larger rings exist)
+void narrow_largest(sz_ctx* c, const State& T, int dt, double ffmo, double fdmo, int maxb) {
+  hipLaunchKernelGGL((sz_k_narrow<64, NARROW_CAP2, NARROW_KC2, NARROW_RC2, 16, 64, NARROW_CAP1, 2>), dim3(grid_for((long long)T.capPairs + T.capElem, 1, maxb)), dim3(64), 0,
+                     c->stream, T, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
 }
 
 // m_hint: see sz_k_inter_fill (resident steps: the parents + the ghosts the last look at the device showed, and some)
 // the force scale of the fixed-point totals (sz_geom.hpp fx_force_exp): |row force| <= (1 + mu) E h sqrt(area)
 int force_scale_exp(const sz_ctx* c) { const double b = (1.0 + std::max(c->P.mu, 0.0)) * c->P.E; return (b > 0.0 && b < 1e300 ? std::ilogb(b) : 0) + 1; }
+// the fixed-point totals and the forcings' stop hint from zero: a batch's start, and a step that is run again (its narrow phase adds its rows again)
+int clear_totals(sz_ctx* c) {
+  HIPCHK(c, hipMemsetAsync(c->facc_buf, 0, (size_t)FX_WORDS * c->S.capM * sizeof(long long), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->S.cnt + C_FRCSTOP, 0, sizeof(int), c->stream));
+  return SZ_OK;
+}
 // behind: the launch that assembles the rows of a reduce-free batch's last step (parents' centroids of that step from `mot`)
 void stage_reduce(sz_ctx* c, int mirror, int n_init, int dt, int m_hint = 0, bool behind = false) {
   State& S = c->S;
@@ -605,6 +662,14 @@ void stage_reduce(sz_ctx* c, int mirror, int n_init, int dt, int m_hint = 0, boo
   t.end();
 }
 
+// where a coupling step's forcings ride when nothing else rules it out (`fuse`): 0 nowhere (a launch of their own), 1 in the neighbour search's
+// launch, 2 in the narrow launch's tail -- by size unless SZ_FUSE_FORCING says.  (Riding in the neighbour launch pays while both kernels leave
+// the chip idle: measured better up to 40 k floes, neutral at 100 k dense, worse at 100 k sparse -- there the forcings get their own launch.)
+int forcing_fuse_mode(const sz_ctx* c, bool fuse) {
+  if (!fuse || (c->pmask >> SZ_K_FORCING & 1u) || !c->fuse_forcing || c->hostN > 65536) return 0;
+  const int m = c->fuse_forcing_mode ? c->fuse_forcing_mode : (c->hostN <= 30000 ? 2 : 1);
+  return m == 1 && c->S.maxnb > MAXNB ? 2 : m;      // (the neighbour + forcing launch exists for the default neighbour capacity only)
+}
 // a step of sz_step: `resume` = the rest of a step that paused after its narrow launch (see stopped_late())
 void collisions_step(sz_ctx* c, int n_init, int dt, bool commit_ghosts, bool static_grid, int fuse_forcing, bool lean, bool resume) {
   if (!resume) {
@@ -1731,6 +1796,7 @@ bool pipeline_eligible(const sz_ctx* c, int nsteps, bool coll, bool sg, bool gi,
 // the last step assembled, strain evaluated, ghosts detached).
 // *rest_out: the lists grew past what the pipelined launches are compiled for (MAXNB); the batch handed back the state at step *done_out and the
 // caller runs the rest on the three-launch steps.
+// It runs inside sz_step's BatchModes scope (the modes sz_step has set are the batch's) and opens none of its own.
 int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling_dt, int flags, bool periodic, bool gi, int* h, int* done_out, bool* rest_out) {
   State& S0 = c->S;
   const int N = c->hostN;
@@ -1740,17 +1806,16 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
   const int q0 = c->gpar;
   auto par = [&](int s) { return (q0 + s) & 1; };
   S0.stop_on_tags = user_stop ? 1 : 0; S0.restart_on_tags = user_stop ? 0 : 1;
-  S0.ginline = gi ? 1 : 0; S0.famrec = gi ? 1 : 0; S0.pipe = 0;
+  S0.ginline = gi ? 1 : 0; S0.famrec = gi ? 1 : 0;
   S0.facc = c->facc_buf; S0.kexp = force_scale_exp(c);
   bool lean = !c->retry_seen && !c->no_lean_narrow;
-  auto leave = [&](int rc) { S0.retry_stop = 0; S0.ginline = 0; S0.famrec = 0; S0.step = 0; S0.crec = nullptr; S0.facc = nullptr; S0.goff = 0; S0.gcap = 0; S0.pipe = 0; S0.restart_on_tags = 0; c->acc_mode = 0; c->reduce_mode = 0; return rc; };
   Clears clr(c);          // (the batch's clears go out with the first prologue's, in one launch)
   clr.add(c->facc_buf, (size_t)FX_WORDS * S0.capM * sizeof(long long));
   clr.add(S0.cnt + C_FRCSTOP, sizeof(int));
   const int callid0 = c->callid; c->callid += nsteps;
   // ---- the prologue of a (sub-)batch that starts at step s: cells, records, ghosts and the neighbour search of that step, from the floes as they lie
   bool first_start = true;
-  auto prologue = [&](int s) -> int {
+  auto prologue = [&](int s) {
     const int q = par(s);
     pipe_adopt(c, q);                                   // (the geometry of step s is in set q: the context's own from here on)
     S0.step = 0; S0.goff = 0; S0.gcap = 0;
@@ -1776,24 +1841,13 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
       hipLaunchKernelGGL((sz_k_neighbors_elem<false, true>), dim3(gr.x + nbe0), bl, 0, c->stream, T, next_epoch(c), (int)gr.x);
     } else if (fam) hipLaunchKernelGGL((sz_k_neighbors<true, MAXNB, true>), gr, bl, 0, c->stream, T);
     else hipLaunchKernelGGL((sz_k_neighbors<false, MAXNB, true>), gr, bl, 0, c->stream, T);
-    return SZ_OK;
   };
-  auto coupling_at = [&](int s) { return (flags & SZ_COUPLING_ON) && coupling_dt > 0 && ((tstep0 + s) % coupling_dt) == 0; };
-  // grid of the narrow launch (as stage_narrow)
   constexpr int TPB = 64;
-  if (c->narrow_grid0 == 0) {
-    int per_cu = 0, cus = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sz_k_narrow<NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 0>, TPB, 0);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-    c->narrow_grid0 = per_cu > 0 && cus > 0 ? per_cu * cus : 2048;
-    if (const char* e = getenv("SZ_NARROW_GRID")) { int v = atoi(e); if (v > 0) c->narrow_grid0 = v; }
-  }
-  const long long capItems = (long long)S0.capPairs + S0.capElem;
-  const int nbn = grid_for(capItems, TPB / NARROW_G, c->narrow_grid0), nbg = grid_for(N, TPB, 1 << 20);
+  const int nbn = grid_for((long long)S0.capPairs + S0.capElem, TPB / NARROW_G, narrow_grid(c)), nbg = grid_for(N, TPB, 1 << 20);
   auto launch_L1 = [&](int s, bool make_ghosts) {
     State T = pipe_state(c, par(s)); T.step = s + 1; T.callid = callid0 + s + 1; T.retry_stop = lean ? 1 : 0;
     const PipeAlt A = pipe_alt(c, par(s + 1), make_ghosts ? 1 : 0);
-    const bool coupling = coupling_at(s);
+    const bool coupling = coupling_at(flags, coupling_dt, tstep0 + s);
     const bool overlap = coupling && (c->overlap_forcing >= 0 ? c->overlap_forcing != 0 : N > 65536);
     if (overlap) stage_forcing_fork(c, &T);
     const int nbf = coupling && !overlap ? grid_for(S0.capM, TPB / FRC_PLAIN, 32768) : 0;
@@ -1804,10 +1858,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     else hipLaunchKernelGGL((sz_k_narrow<NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 0, 1>), dim3(nbn + nbg), dim3(TPB), 0, c->stream,
                             T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, 0, A, nbg, N);
     tm.end();
-    if (!lean) {          // the largest variant takes what the small one hands on (see stage_narrow)
-      hipLaunchKernelGGL((sz_k_narrow<64, NARROW_CAP2, NARROW_KC2, NARROW_RC2, 16, 64, NARROW_CAP1, 2>), dim3(grid_for(capItems, 1, 256)), dim3(64), 0,
-                         c->stream, T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, 0, PipeAlt{}, 0, 0);
-    }
+    if (!lean) narrow_largest(c, T, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, 256);          // (it takes what the small one hands on)
     return overlap;
   };
   auto launch_L2 = [&](int s, bool with_search, bool host_last, bool joined) {
@@ -1819,12 +1870,12 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     const unsigned ep = nbe ? next_epoch(c) : 0u;
     const int am = 1 | 4 | (host_last ? 2 : 0);
     Timed tm(c, SZ_K_INTEGRATE);
-    if (fam) hipLaunchKernelGGL((sz_k_vel_search<true>), dim3(nbv + nbs + nbe), dim3(NB_TPB), 0, c->stream, T, c->P, A, dt, coupling_at(s) ? 1 : 0, nbv, N, am, nbe, ep);
-    else hipLaunchKernelGGL((sz_k_vel_search<false>), dim3(nbv + nbs + nbe), dim3(NB_TPB), 0, c->stream, T, c->P, A, dt, coupling_at(s) ? 1 : 0, nbv, N, am, nbe, ep);
+    if (fam) hipLaunchKernelGGL((sz_k_vel_search<true>), dim3(nbv + nbs + nbe), dim3(NB_TPB), 0, c->stream, T, c->P, A, dt, coupling_at(flags, coupling_dt, tstep0 + s) ? 1 : 0, nbv, N, am, nbe, ep);
+    else hipLaunchKernelGGL((sz_k_vel_search<false>), dim3(nbv + nbs + nbe), dim3(NB_TPB), 0, c->stream, T, c->P, A, dt, coupling_at(flags, coupling_dt, tstep0 + s) ? 1 : 0, nbv, N, am, nbe, ep);
     tm.end();
   };
   // what lies behind the last step `last` (0-based) of the batch: parents un-swapped after a tag stop, strain, the step's rows, rows home, ghosts off
-  auto epilogue = [&](int last, bool after_device_stop) -> int {
+  auto epilogue = [&](int last, bool after_device_stop) {
     const int q = par(last + 1);                          // the geometry of the state that is handed back
     pipe_adopt(c, q);
     if (after_device_stop) {
@@ -1837,13 +1888,12 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     // the rows of step `last`: its links and row region are parity par(last)'s; the parents' centroids of that step are in mot
     State R = pipe_state(c, par(last)); R.step = 0; R.vxy = T.vxy;
     hipLaunchKernelGGL(sz_k_inter_fill, dim3(grid_for(S0.capM, 128 / IF_G, 16384)), dim3(128), 0, c->stream, R, 1, N, 0, 1, 2 + last);      // (2 + last: behind, for 1-based step last + 1)
-    return SZ_OK;
   };
   int s_end = c->maybe_tagged && user_stop && nsteps > 1 ? 1 : nsteps;
   int s0 = 0, done = 0; bool need_prologue = true;
   for (;;) {
     S0.retry_stop = lean ? 1 : 0;
-    if (need_prologue) { int rc = prologue(s0); if (rc) return leave(rc); need_prologue = false; }
+    if (need_prologue) { prologue(s0); need_prologue = false; }
     for (int s = s0; s < s_end; s++) {
       const bool host_last = s + 1 == s_end;
       const bool joined = launch_L1(s, !host_last);
@@ -1852,7 +1902,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     // the epilogue of the case "all steps ran" goes out with the steps: its launches look at the counters and return when the batch ended early
     // (sz_k_inter_fill: behind-mode guard; the strain launch is harmless either way and is repeated below)
     S0.step = 0;
-    { int rc = epilogue(s_end - 1, false); if (rc) return leave(rc); }
+    epilogue(s_end - 1, false);
     HIPCHK(c, hipMemcpyAsync(h, S0.cnt, C_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream2));
     if (h[C_ERR] & ~ERR_CAP_INTER) {          // (the rows' stride, ERR_CAP_INTER, is dealt with behind the loop: the bit stays up until then)
@@ -1863,10 +1913,9 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
         int z = 0; (void)hipMemcpy(S0.cnt + C_ERR, &z, sizeof(int), hipMemcpyHostToDevice);
         const int sr = h[C_RETRYSTOP] - 1;
         pipe_adopt(c, par(sr));
-        int rc = grow_lists(c, bits & (ERR_CAP_NEIGH | ERR_CAP_PAIRS)); if (rc) return leave(rc);
+        int rc = grow_lists(c, bits & (ERR_CAP_NEIGH | ERR_CAP_PAIRS)); if (rc) return rc;
         (void)hipMemsetAsync(S0.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream); (void)hipMemsetAsync(S0.cnt + C_STOP, 0, sizeof(int), c->stream);
-        (void)hipMemsetAsync(S0.cnt + C_FRCSTOP, 0, sizeof(int), c->stream);
-        (void)hipMemsetAsync(c->facc_buf, 0, (size_t)FX_WORDS * S0.capM * sizeof(long long), c->stream);
+        if ((rc = clear_totals(c))) return rc;
         if (S0.maxnb > MAXNB) {
           // the prologue's and the L2 launch's neighbour search are instantiated for MAXNB-wide rows (neighbors_body's row stride): with the
           // wider lists the steps from sr on are the three-launch ones.  The state of step sr is set par(sr)'s (adopted above); the ghost links
@@ -1878,13 +1927,13 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
           if (getenv("SZ_VERBOSE")) fprintf(stderr, "[subzero-hip] pipelined batch: lists outgrew its neighbour capacity in step %d of %d, the rest on the three-launch steps\n", sr + 1, nsteps);
           c->grid_live = false; c->crec_current = false; c->callid = callid0 + sr;
           *done_out = sr; *rest_out = true;
-          return leave(SZ_OK);
+          return SZ_OK;
         }
         s0 = sr; need_prologue = true;
         continue;
       }
       (void)sync_and_check(c, h);          // (sets the error text, clears the word)
-      return leave(SZ_E_CAPACITY);
+      return SZ_E_CAPACITY;
     }
     if (lean && h[C_RETRYSTOP] > 0) {
       // paused inside step sr: an item for the largest narrow variant.  That variant on the step's own State, the step's second launch again, on
@@ -1893,18 +1942,17 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
       c->retry_seen = true; lean = false;
       (void)hipMemsetAsync(S0.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream); (void)hipMemsetAsync(S0.cnt + C_PAUSED, 0, sizeof(int), c->stream);
       State T = pipe_state(c, par(sr)); T.step = sr + 1; T.callid = callid0 + sr + 1; T.retry_stop = 0;
-      hipLaunchKernelGGL((sz_k_narrow<64, NARROW_CAP2, NARROW_KC2, NARROW_RC2, 16, 64, NARROW_CAP1, 2>), dim3(grid_for(capItems, 1, 256)), dim3(64), 0,
-                         c->stream, T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, 0, PipeAlt{}, 0, 0);
+      narrow_largest(c, T, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, 256);
       const bool host_last = sr + 1 == s_end;
       S0.retry_stop = 0;
       launch_L2(sr, !host_last, host_last, false);
       s0 = sr + 1;
       if (s0 >= s_end) {          // it was the last step: only the epilogue is left
         S0.step = 0;
-        { int rc = epilogue(s_end - 1, false); if (rc) return leave(rc); }
+        epilogue(s_end - 1, false);
         HIPCHK(c, hipMemcpyAsync(h, S0.cnt, C_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (h[C_ERR] & ~ERR_CAP_INTER) { (void)sync_and_check(c, h); return leave(SZ_E_CAPACITY); }
+        if (h[C_ERR] & ~ERR_CAP_INTER) { (void)sync_and_check(c, h); return SZ_E_CAPACITY; }
         done = s_end;
         break;
       }
@@ -1914,7 +1962,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
       // a tag ended the enqueued steps after step k: the state behind it (GEO(k) has run ahead: parents un-swapped), then either the end of
       // the batch (the caller's stop) or -- a batch that runs through -- the rest of it, started like a batch (the ghosts know the tag now)
       const int k = h[C_STOP] - 1;
-      if (user_stop) { int rc = epilogue(k, true); if (rc) return leave(rc); done = k + 1; HIPCHK(c, hipMemcpyAsync(h, S0.cnt, C_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); break; }
+      if (user_stop) { epilogue(k, true); done = k + 1; HIPCHK(c, hipMemcpyAsync(h, S0.cnt, C_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); break; }
       pipe_adopt(c, par(k + 1));
       { State T = pipe_state(c, par(k + 1)); T.step = 0; hipLaunchKernelGGL(sz_k_unswap, dim3(grid_for(N, 128)), dim3(128), 0, c->stream, T, pipe_alt(c, par(k), 0), N); }
       (void)hipMemsetAsync(S0.cnt + C_STOP, 0, sizeof(int), c->stream); (void)hipMemsetAsync(S0.cnt + C_FRCSTOP, 0, sizeof(int), c->stream);
@@ -1930,21 +1978,9 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
   }
   // ---- the batch is over: state in set par(done); rows of step done - 1 assembled (region par(done - 1))
   const int qlast = par(done - 1);
-  if (h[C_ERR] & ERR_CAP_INTER) {          // a floe of the last step has more rows than the stride holds: more room, the launch again (sz_step does the same)
+  if (h[C_ERR] & ERR_CAP_INTER) {          // a floe of the last step has more rows than the stride holds
     int z = 0; (void)hipMemcpy(S0.cnt + C_ERR, &z, sizeof(int), hipMemcpyHostToDevice);
-    for (int tries = 0; tries < 6; tries++) {
-      S0.rowcap *= 4;
-      if (S0.rowcap > 8192) { c->err = "a floe has more than 8192 interaction rows"; return leave(SZ_E_CAPACITY); }
-      int rc = carve_interactions(c); if (rc) return leave(rc);
-      c->inter_lost = false;
-      State R = pipe_state(c, qlast); R.step = 0; R.vxy = S0.vxy;
-      hipLaunchKernelGGL(sz_k_inter_fill, dim3(grid_for(S0.capM, 128 / IF_G, 16384)), dim3(128), 0, c->stream, R, 1, N, 0, 1, 1);
-      HIPCHK(c, hipMemcpyAsync(h, S0.cnt, C_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      if (!(h[C_ERR] & ERR_CAP_INTER)) break;
-      (void)hipMemcpy(S0.cnt + C_ERR, &z, sizeof(int), hipMemcpyHostToDevice);
-    }
-    if (h[C_ERR]) { (void)sync_and_check(c, h); return leave(SZ_E_CAPACITY); }
+    if (int rc = regrow_rows(c, h, [&] { State R = pipe_state(c, qlast); R.step = 0; R.vxy = S0.vxy; return R; })) return rc;
   }
   {          // the per-row results of the last step to the rows straight behind the parents; its links become the context's; ghosts off
     const State R = pipe_state(c, qlast);
@@ -1966,7 +2002,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     const int keepG = h[C_NGHOSTS];
     int rc = sync_and_check(c, h);
     h[C_NGHOSTS] = keepG;
-    if (rc) return leave(rc);
+    if (rc) return rc;
   }
   if (done < nsteps) c->grid_live = false;
   *done_out = done;
@@ -1974,7 +2010,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
   c->crec_current = done == nsteps;          // (the records of the adopted set follow the columns; after a tag stop the un-swap rewrote a few: seeded again next time)
   // (h[C_STOP]: the caller's view -- a batch that ran through ended at nsteps)
   if (!user_stop) h[C_STOP] = 0;
-  return leave(SZ_OK);
+  return SZ_OK;
 }
 }  // namespace
 
@@ -2084,12 +2120,12 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
     int rc = ensure_two_way(c); if (rc) return rc;
   }
   if (!coll) { if (int rc = need_interactions(c)) return rc; }
+  BatchModes modes(c);
   // the batch ends after the first step that leaves a parent tagged remove / fuse (simplify_floes!, simulation.jl:205-214,
   // is the host's): the launches of the later steps are enqueued all the same and return at once (stopped())
   c->S.stop_on_tags = (flags & SZ_NO_STOP) ? 0 : 1;
   HIPCHK(c, hipMemsetAsync(c->S.cnt + C_STOP, 0, sizeof(int), c->stream));
   HIPCHK(c, hipMemsetAsync(c->S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream));
-  bool last_coupled = false;
   const bool sg = coll && c->grid_ok;
   if (sg) use_static_grid(c);
   const bool gl = ghost_list_wanted(c, sg);
@@ -2127,36 +2163,27 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   const bool pipe = pipeline_eligible(c, nsteps, coll, sg, gi, periodic, cr, rfree, flags);
   if (!pipe) c->crec_current = false;          // (the three-launch steps seed the records they use; they may not keep the twin set's)
   if (cr && !pipe) hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(c->hostN, 256)), dim3(256), 0, c->stream, c->S, c->hostN);
-  if (gi && !pipe) {               // the ghosts of the first step, from the parents as they lie (after the rings are in the batch's form)
-    HIPCHK(c, hipMemsetAsync(c->S.galloc, 0, 32 * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, 0, c->hostN);
-  }
+  // the ghosts of the first step, from the parents as they lie (after the rings are in the batch's form)
+  if (gi && !pipe) { if (int rc = reseed_inline_ghosts(c, 0)) return rc; }
   // the largest narrow variant only takes items the small one hands on (none in most fields): it is left out of the steps until one
   // shows up -- the batch then pauses inside that step (stopped_late()) and is finished below
   bool lean = coll && !c->retry_seen && !c->no_lean_narrow && !c->S.tiled && !larger_rings(c);
   c->S.facc = facc_on ? c->facc_buf : nullptr; c->S.kexp = force_scale_exp(c);
   c->reduce_mode = !facc_on ? 0 : rfree ? 2 : 1;
-  if (facc_on && !pipe) {          // (a pipelined batch clears them with the rest of its prologue: one launch)
-    HIPCHK(c, hipMemsetAsync(c->facc_buf, 0, (size_t)FX_WORDS * c->S.capM * sizeof(long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->S.cnt + C_FRCSTOP, 0, sizeof(int), c->stream));
-  }
+  if (facc_on && !pipe) { if (int rc = clear_totals(c)) return rc; }          // (a pipelined batch clears them with the rest of its prologue: one launch)
   // a parent that is already tagged ends the batch after its first step, and the integrator only finds out while it runs (the tags of a
   // step itself are raised by its narrow phase / forcings, a launch earlier): that first step is then enqueued on its own, as a last step
   int s_end = rfree && c->maybe_tagged && c->S.stop_on_tags && nsteps > 1 ? 1 : nsteps;
   // fracture criterion (sz_set_fracture): evaluated after every fracture step of a batch that stops -- one that runs through has no use for it
   const bool frac = c->frac_kind != SZ_FRAC_OFF && c->S.stop_on_tags && !pipe;
   if (frac) { if (int rc = frac_ensure(c)) return rc; }
-  auto leave = [&]() { c->S.retry_stop = 0; c->S.body_rings = 0; c->S.ginline = 0; c->S.famrec = 0; c->S.step = 0; c->S.crec = nullptr; c->S.facc = nullptr; c->acc_mode = 0; c->reduce_mode = 0; };
   int h[C_COUNT];
   int pipe_done = -1;
   if (pipe) {
-    c->S.stop_on_tags = (flags & SZ_NO_STOP) ? 0 : 1;
     bool rest = false;
-    int rcp = step_batch_pipelined(c, nsteps, tstep0, dt, coupling_dt, flags, periodic, gi, h, &pipe_done, &rest);
-    c->S.stop_on_tags = (flags & SZ_NO_STOP) ? 0 : 1;
-    if (rcp) { leave(); return rcp; }
-    if (rest) {          // the lists outgrew the pipelined launches in step pipe_done: the rest of the batch as a batch of its own (not eligible now)
-      leave();
+    if (int rc = step_batch_pipelined(c, nsteps, tstep0, dt, coupling_dt, flags, periodic, gi, h, &pipe_done, &rest)) return rc;
+    if (rest) {          // the lists outgrew the pipelined launches in step pipe_done: the rest of the batch as a batch of its own (not eligible now;
+                         //  its scope starts from the process-mode values)
       int more = 0;
       const int rc = sz_step(c, nsteps - pipe_done, tstep0 + pipe_done, dt, coupling_dt, flags, &more);
       if (steps_done) *steps_done = pipe_done + more;
@@ -2170,23 +2197,19 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
       int tstep = tstep0 + s;
       c->S.step = s + 1; c->S.callid = callid0 + s + 1;
       const bool resume = mid && s == s0;
-      const bool coupling = (flags & SZ_COUPLING_ON) && coupling_dt > 0 && (tstep % coupling_dt) == 0;
+      const bool coupling = coupling_at(flags, coupling_dt, tstep);
       const bool overlap = coupling && !c->two_way && (c->overlap_forcing >= 0 ? c->overlap_forcing != 0 : (c->hostN > 65536 && c->precision == 0 && coll));
       // with collisions on, the ghosts of step s are detached by the ghost kernels of step s+1 (nothing
       // in between looks past the parents) and committed by the bounds kernel: two launches less
       // The forcings only read the floes' state at the start of the step (after the ghost pass has wrapped the parents that left the
       // domain) and write columns nothing reads before the update: they can run beside the collision kernels (second stream, fork
       // after the ghost pass) or inside one of their launches.
-      // (riding in the neighbour launch pays while both kernels leave the chip idle: measured better up to 40 k floes,
-      // neutral at 100 k dense, worse at 100 k sparse -- there the forcings get their own launch)
-      const bool fuse = coupling && !overlap && coll && !c->two_way && !(c->pmask >> SZ_K_FORCING & 1u) && c->fuse_forcing && c->hostN <= 65536;
-      int fmode = !fuse ? 0 : c->fuse_forcing_mode ? c->fuse_forcing_mode : (c->hostN <= 30000 ? 2 : 1);
-      if (fmode == 1 && c->S.maxnb > MAXNB) fmode = 2;      // (the neighbour + forcing launch exists for the default neighbour capacity only)
+      const int fmode = forcing_fuse_mode(c, coupling && !overlap && coll && !c->two_way);
       if (!resume) {          // (a paused step has all of this behind it)
         if (coll && !gi) stage_ghosts(c, true, sg, gl);
         // (after the ghost pass, like the reference's timestep_coupling!: a parent that has just swapped with its ghost is sampled where it
         //  now lies -- the same lattice values as at its image, but the interpolation weights come from other coordinates)
-        if (coupling && !overlap && !fuse) stage_forcing(c, dt);
+        if (coupling && !overlap && !fmode) stage_forcing(c, dt);
         if (overlap) stage_forcing_fork(c);
         if (coupling) c->forcing_where = fmode;
       }
@@ -2221,52 +2244,32 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
     if (coll && periodic) hipLaunchKernelGGL(sz_k_remove_ghosts, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, 0);
     int rc = sync_and_check(c, h);
     if (rfree && rc == SZ_E_CAPACITY && c->last_err_bits == ERR_CAP_INTER && h[C_RETRYSTOP] == 0) {
-      // a floe of that last step has more rows than the stride holds: only the rows' memory grows (collisions.jl:290-296), and the launch runs
-      // again on the parents with the ghost links sz_k_remove_ghosts has put aside
-      rc = SZ_OK;
-      for (int tries = 0; tries < 6; tries++) {
-        c->S.rowcap *= 4;
-        if (c->S.rowcap > 8192) { c->err = "a floe has more than 8192 interaction rows"; leave(); return SZ_E_CAPACITY; }
-        if ((rc = carve_interactions(c))) { leave(); return rc; }
-        c->inter_lost = false;
-        State S2 = c->S; S2.ngh = c->S.ngh_save; S2.gh = c->S.gh_save;
-        hipLaunchKernelGGL(sz_k_inter_fill, dim3(grid_for(S2.capM, 128 / IF_G, 16384)), dim3(128), 0, c->stream, S2, 1, c->hostN, 0, 1, 1);
-        int h2[C_COUNT];
-        rc = sync_and_check(c, h2);
-        if (!(rc == SZ_E_CAPACITY && c->last_err_bits == ERR_CAP_INTER)) break;
-      }
+      // a floe of that last step has more rows than the stride holds: the launch runs again on the parents with the ghost links
+      // sz_k_remove_ghosts has put aside
+      int h2[C_COUNT];
+      rc = regrow_rows(c, h2, [&] { State R = c->S; R.ngh = c->S.ngh_save; R.gh = c->S.gh_save; return R; });
     }
     if (rc == SZ_E_CAPACITY && growable(c->last_err_bits) && h[C_RETRYSTOP] > 0 && coll) {
       // A list outgrown inside step h[C_RETRYSTOP] (neighbours per floe, pair items, rows per floe): the batch paused there before anything
       // of the floes' state changed (capacity_stop()).  Larger lists, then that step and the rest of the batch again, from the parents as
       // they lie -- exactly as a batch that starts at that step would (cells, the step's ghosts): the reference's lists grow (collisions.jl:290-296).
-      if ((rc = grow_lists(c, c->last_err_bits))) { leave(); return rc; }
+      if ((rc = grow_lists(c, c->last_err_bits))) return rc;
       s0 = h[C_RETRYSTOP] - 1; mid = 0;
       (void)hipMemsetAsync(c->S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream);
       (void)hipMemsetAsync(c->S.cnt + C_STOP, 0, sizeof(int), c->stream);
-      if (facc_on) {          // (the narrow phase of the step that is run again adds its rows again)
-        (void)hipMemsetAsync(c->facc_buf, 0, (size_t)FX_WORDS * c->S.capM * sizeof(long long), c->stream);
-        (void)hipMemsetAsync(c->S.cnt + C_FRCSTOP, 0, sizeof(int), c->stream);
-      }
+      if (facc_on && (rc = clear_totals(c))) return rc;
       c->grid_live = false; use_static_grid(c);
       if (cr) hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(c->hostN, 256)), dim3(256), 0, c->stream, c->S, c->hostN);
-      if (gi) {
-        (void)hipMemsetAsync(c->S.galloc, 0, 32 * sizeof(unsigned long long), c->stream);
-        c->S.gslot = s0 & 1;
-        hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, s0 & 1, c->hostN);
-      } else if (gl) { c->gl_valid = false; use_ghost_list(c); }
+      if (gi) { if ((rc = reseed_inline_ghosts(c, s0 & 1))) return rc; }
+      else if (gl) { c->gl_valid = false; use_ghost_list(c); }
       continue;
     }
-    if (rc) { leave(); return rc; }
+    if (rc) return rc;
     if ((!lean || h[C_RETRYSTOP] == 0) && s_end < nsteps && h[C_STOP] == 0) {
       // the first step ran on its own (a parent might have been tagged already) and nothing ended the batch: the rest of it, from the floes
       // as they lie -- the cells hold the parents (the step made no ghosts), the ghosts of the next step are seeded as at a batch's start
       s0 = s_end; s_end = nsteps; mid = 0;
-      if (gi) {
-        (void)hipMemsetAsync(c->S.galloc, 0, 32 * sizeof(unsigned long long), c->stream);
-        c->S.gslot = s0 & 1;
-        hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, s0 & 1, c->hostN);
-      }
+      if (gi && (rc = reseed_inline_ghosts(c, s0 & 1))) return rc;
       continue;
     }
     if (!lean || h[C_RETRYSTOP] == 0) break;
@@ -2276,11 +2279,8 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
     if (gl && !gi) c->gl_cur = (gl0 + s0) & 1;
     (void)hipMemsetAsync(c->S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream);
   }
-  c->S.retry_stop = 0;
-  c->S.ginline = 0; c->S.famrec = 0; c->S.crec = nullptr; c->S.facc = nullptr; c->acc_mode = 0; c->reduce_mode = 0;
   if (coll && (h[C_STOP] > 0 || (flags & SZ_NO_STOP))) c->maybe_tagged = true;
   if (body && nsteps > 0) c->rings_stale = true;
-  c->S.body_rings = 0;
   if (coll) { c->inter_any = true; c->inter_lost = false; }
   int rc = SZ_OK;
   const int done = pipe ? pipe_done : h[C_STOP] > 0 ? std::min(h[C_STOP], (int)nsteps) : nsteps;
@@ -2300,7 +2300,7 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   // sz_timestep_collisions does (only that step can have produced fuse pairs: the batch stops on the first tag)
   if (coll && done > 0) {
     const int tlast = tstep0 + done - 1;
-    last_coupled = (flags & SZ_COUPLING_ON) && coupling_dt > 0 && (tlast % coupling_dt) == 0;
+    const bool last_coupled = coupling_at(flags, coupling_dt, tlast);
     if (h[C_STOP] > 0 || (flags & SZ_NO_STOP)) {
       rc = host_fuse_fixup(c, h, true, true, last_coupled);
       c->fuse_lists.resize(c->hostM);
@@ -2487,7 +2487,7 @@ int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int
     // halo floes join the candidate list of THIS step (the owned floes were appended by the last integrator)
     hipLaunchKernelGGL(sz_k_halo_unpack, dim3(1), dim3(1024), 0, c->stream, S, (const double*)d_recv, nranks, cap, sg ? 1 : 0, gl ? c->gl_cur : -1);
   }
-  const bool coupling = (flags & SZ_COUPLING_ON) && coupling_dt > 0 && (tstep % coupling_dt) == 0;
+  const bool coupling = coupling_at(flags, coupling_dt, tstep);
   const bool periodic = S.any_periodic_ew || S.any_periodic_ns;
   // the forcings of this step: already enqueued by sz_tile_forcing (beside the exchange), else now -- in either
   // case before the ghost pass, like sz_step
@@ -2652,7 +2652,7 @@ int sz_simplify_check(sz_ctx* c, int32_t max_vertices, double min_floe_area, dou
 int sz_tile_forcing(sz_ctx* c, int32_t tstep, int32_t coupling_dt, int32_t flags) {
   if (!c || !c->have_floes) return SZ_E_STATE;
   (void)hipSetDevice(c->device);
-  const bool coupling = (flags & SZ_COUPLING_ON) && coupling_dt > 0 && (tstep % coupling_dt) == 0;
+  const bool coupling = coupling_at(flags, coupling_dt, tstep);
   if (!coupling) return SZ_OK;
   int rc = tile_forcing(c); if (rc) return rc;
   c->tile_forcing_tstep = tstep;
@@ -3527,11 +3527,11 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   State& S = c->S;
   const int n = c->comm_n, me = c->comm_rank;
   const bool coll = (flags & SZ_COLLISIONS_ON) != 0;
+  BatchModes modes(c);
   // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
   // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
   // Needs what the inline ghost maker needs (rings that fit the one-launch integrator, the static grid).  Otherwise: the list-based steps
   // of sz_tile_step.
-  S.crec = nullptr;
   const bool inl = coll && c->grid_ok && !c->two_way &&
                    std::max(c->max_ring, c->max_ring_tiled) <= MV_RING && ((flags & SZ_COUPLING_ON) == 0 || c->have_fields);
   if (!inl) {
@@ -3542,33 +3542,30 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
     // once; their all-reduces of the per-cell sums still run on every rank (collectives must), on the sums of the step that ended the
     // batch, and sz_two_way_finish writes the ocean fields of that step once more: the same values.
     const bool stopping = !(flags & SZ_NO_STOP);
-    S.stop_on_tags = stopping ? 1 : 0; S.retry_stop = 0;
+    S.stop_on_tags = stopping ? 1 : 0;
     HIPCHK(c, hipMemsetAsync(S.cnt + C_STOP, 0, sizeof(int), c->stream));
     HIPCHK(c, hipMemsetAsync(S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream));
-    // (every way out of the loop leaves the context as a batch that has ended: no step number in the State, or the next process-mode call's
-    //  kernels would take themselves for launches behind a stop)
-    auto out = [&](int rc) { S.step = 0; S.stop_on_tags = 0; return rc; };
     for (int s = 0; s < nsteps; s++) {
       const int tstep = tstep0 + s;
       c->tile_dt = dt;
       S.step = stopping ? s + 1 : 0;
-      if (c->tile_since_box < 0 || c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return out(rc); }
+      if (c->tile_since_box < 0 || c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }
       c->tile_since_box++;
-      const bool coupling = (flags & SZ_COUPLING_ON) && coupling_dt > 0 && (tstep % coupling_dt) == 0;
+      const bool coupling = coupling_at(flags, coupling_dt, tstep);
       tile_pack(c);
       // (the host's channel blocks: the forcings go to the device first and run while the host trades the regions)
-      if (coupling && !stopping && n > 1 && c->host_transport) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return out(rc); }
-      { int rc = tile_exchange(c, stopping); if (rc) return out(rc); }
+      if (coupling && !stopping && n > 1 && c->host_transport) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return rc; }
+      { int rc = tile_exchange(c, stopping); if (rc) return rc; }
       // the forcings of the owned floes need nothing from the halo: they run beside the exchange
-      if (coupling && !stopping && !(n > 1 && c->host_transport)) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return out(rc); }
-      if (n > 1 && hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return out(SZ_E_HIP); }
+      if (coupling && !stopping && !(n > 1 && c->host_transport)) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return rc; }
+      if (n > 1 && hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return SZ_E_HIP; }
       int rc = sz_tile_step(c, c->d_recv, n, c->halo_cap, tstep, dt, coupling_dt, flags);
-      if (rc) return out(rc);
+      if (rc) return rc;
       if (c->two_way && coupling) {       // ice-on-ocean stress: per-cell partial sums, summed over the ranks, finished on every rank
         const size_t nc = 3 * c->tw_ncell;
         if (!c->d_tw_partial) { int r2 = dalloc(c, &c->d_tw_partial, nc, c->tw_part_allocs); if (r2) return r2; }
         if ((rc = sz_two_way_partial(c, c->d_tw_partial)) || (rc = sz_comm_allreduce(c, c->d_tw_partial, (int64_t)nc)) ||
-            (rc = sz_two_way_finish(c, c->d_tw_partial, dt))) return out(rc);
+            (rc = sz_two_way_finish(c, c->d_tw_partial, dt))) return rc;
       }
     }
     // (the ranks agree on the error word: a rank with a device error and a clean one return the same code)
@@ -3595,7 +3592,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   use_static_grid(c);
   if (c->precision == 1) { int rc = ensure_mixed(c); if (rc) return rc; }
   else if (!c->two_way && c->have_fields) { int rc = ensure_block_points(c); if (rc) return rc; }
-  S.ginline = 1; S.famrec = 1; S.retry_stop = 0; S.body_rings = 0;
+  S.ginline = 1; S.famrec = 1;
   HIPCHK(c, hipMemsetAsync(S.galloc, 0, 32 * sizeof(unsigned long long), c->stream));
   // the periodic ghosts of the owned floes for the first step (and the swap of parents that lie outside the domain), BEFORE the first pack
   // collision records of the owned floes (the halo floes get theirs from the unpack kernel, ghosts from their maker; see sz_step)
@@ -3609,14 +3606,14 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   const bool facc_on = c->facc_buf != nullptr;
   const int rmode = !facc_on ? 0 : n > 1 && S.stop_on_tags ? 1 : 2;
   S.facc = facc_on ? c->facc_buf : nullptr; S.kexp = force_scale_exp(c); c->reduce_mode = rmode;
-  if (facc_on) {
-    HIPCHK(c, hipMemsetAsync(c->facc_buf, 0, (size_t)FX_WORDS * S.capM * sizeof(long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(S.cnt + C_FRCSTOP, 0, sizeof(int), c->stream));
-  }
+  if (facc_on) { if (int rc = clear_totals(c)) return rc; }
   auto accm = [&](bool last) { return !facc_on ? 0 : 1 | (rmode == 2 ? 4 | (last ? 2 : 0) : 0); };
-  int cur_set = 0;          // (the forcing output set in use: see `beside` below)
-  auto swap_frc = [&]() { std::swap(S.fxOA, c->frc_alt[0]); std::swap(S.fyOA, c->frc_alt[1]); std::swap(S.trqOA, c->frc_alt[2]); std::swap(S.hflx, c->frc_alt[3]); cur_set ^= 1; };
-  auto fail = [&](int rc) { if (cur_set) swap_frc(); S.ginline = 0; S.famrec = 0; S.step = 0; S.crec = nullptr; S.retry_stop = 0; S.facc = nullptr; c->acc_mode = 0; c->reduce_mode = 0; return rc; };
+  // the forcing output set in use (see `beside` below): a way out before the end of the batch takes the columns back to set 0, as at entry
+  struct FrcSets {
+    sz_ctx* c; int cur; bool keep;
+    void use(int set) { if (set != cur) { std::swap(c->S.fxOA, c->frc_alt[0]); std::swap(c->S.fyOA, c->frc_alt[1]); std::swap(c->S.trqOA, c->frc_alt[2]); std::swap(c->S.hflx, c->frc_alt[3]); cur = set; } }
+    ~FrcSets() { if (!keep) use(0); }
+  } frc{ c, 0, false };
   // SZ_SYNC_DEBUG=1 (diagnosis of a faulting kernel): wait after every stage of every step and say so on stderr -- the last line names the stage
   const bool dbgsync = getenv("SZ_SYNC_DEBUG") != nullptr;
   auto stage_done = [&](int s, const char* what) {
@@ -3628,6 +3625,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   };
   stage_done(-1, "seed");
   std::vector<signed char> fset((size_t)std::max(nsteps, 1), (signed char)-1);      // the output set the forcings of step s wrote (-1: none of this kind)
+  auto last_set = [&](int upto) { int set = 0; for (int s2 = 0; s2 < upto; s2++) if (fset[s2] >= 0) set = fset[s2]; return set; };      // (of steps [0, upto); 0: as at entry)
   // The largest narrow variant is left out of the steps until an item needs it, as in sz_step (-4 us and a launch boundary per step).  A
   // rank whose narrow phase meets such an item pauses inside that step (C_RETRYSTOP); its pause rides in the header records of the next
   // exchange (sz_k_halo_pack hdr[2]), whose unpack kernel stops every other rank before that step has touched anything.  After the sync
@@ -3655,7 +3653,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
     S.step = s + 1; S.gslot = s & 1;
     c->tile_dt = dt;
     if (s == s_begin && s_begin == 0) {
-      if (c->tile_since_box < 0 || c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return fail(rc); }
+      if (c->tile_since_box < 0 || c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }
       stage_done(s, "rebox");
     }
     if (s == s_begin && fresh) {
@@ -3663,7 +3661,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
       if (periodic) hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(S.capM, 256)), dim3(256), 0, c->stream, S, s & 1, c->hostN);
     }
     c->tile_since_box++;
-    const bool coupling = (flags & SZ_COUPLING_ON) && coupling_dt > 0 && (tstep % coupling_dt) == 0;
+    const bool coupling = coupling_at(flags, coupling_dt, tstep);
     stage_done(s, "pack");
     // With peers the forcings of the owned floes (they need nothing from the halo) run BESIDE the exchange -- on the main stream while the
     // communication stream trades the regions, before the host's channel blocks -- and the narrow launch carries no forcing tail; without
@@ -3673,22 +3671,20 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
     //  below finds out.  They therefore write a SECOND set of the four output columns, alternating step by step, and the set the last
     //  step that really ran has written is made the context's at the end of the call: a batch that ends early leaves fxOA .. hflx of the
     //  step it ended with, as sz_step does.)
-    if (beside) { swap_frc(); fset[s] = (signed char)cur_set; }
+    if (beside) { frc.use(frc.cur ^ 1); fset[s] = (signed char)frc.cur; }
     if (beside && c->host_transport) stage_forcing(c, dt);
-    { int rc = tile_exchange(c, hdr_all); if (rc) return fail(rc); }
+    { int rc = tile_exchange(c, hdr_all); if (rc) return rc; }
     if (beside && !c->host_transport) stage_forcing(c, dt);
     if (n > 1) {
-      if (hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return fail(SZ_E_HIP); }
+      if (hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return SZ_E_HIP; }
       const long long slots = (long long)n * c->halo_cap;
       hipLaunchKernelGGL(sz_k_halo_unpack_inline, dim3(grid_for(slots, UNPACK_TPB, 1 << 20)), dim3(UNPACK_TPB), 0, c->stream, S, (const double*)c->d_recv, n, me, c->halo_cap,
                          S.gslot, c->hostN);
     }
     stage_done(s, "exchange + unpack");
-    // the forcings: where sz_step puts them (the tail of the narrow launch for tiles of up to 30 k owned floes, the neighbour launch up to 65 k)
-    const bool fuse = coupling && !beside && !(c->pmask >> SZ_K_FORCING & 1u) && c->fuse_forcing && c->hostN <= 65536;
-    int fmode = !fuse ? 0 : c->fuse_forcing_mode ? c->fuse_forcing_mode : (c->hostN <= 30000 ? 2 : 1);
-    if (fmode == 1 && S.maxnb > MAXNB) fmode = 2;
-    if (coupling && !fuse && !beside) stage_forcing(c, dt);
+    // the forcings that did not run beside the exchange: where sz_step puts them (forcing_fuse_mode)
+    const int fmode = forcing_fuse_mode(c, coupling && !beside);
+    if (coupling && !fmode && !beside) stage_forcing(c, dt);
     if (coupling) c->forcing_where = fmode;
     S.callid = ++c->callid; callid_of[s] = S.callid;
     if (facc_on && !(S.crec && S.maxnb <= MAXNB)) (void)hipMemsetAsync(c->facc_buf + (size_t)FX_WORDS * c->hostN, 0, (size_t)FX_WORDS * (S.capM - c->hostN) * sizeof(long long), c->stream);      // (see sz_step)
@@ -3699,7 +3695,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
       stage_reduce(c, 1, -1, dt, 0); stage_done(s, "reduce");
     } else collisions_step(c, -1, dt, false, true, fmode, lean, false);
     const bool pack_next = s + 1 < nsteps;
-    if (pack_next && c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return fail(rc); }      // (synchronises: once per gather interval)
+    if (pack_next && c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }      // (synchronises: once per gather interval)
     const PackInl pk = tile_pack_args(c);
     c->acc_mode = accm(s + 1 == nsteps);
     stage_integrate(c, dt, false, coupling, true, -1, periodic && s + 1 < nsteps ? 1 - (s & 1) : -1, pack_next ? &pk : nullptr);
@@ -3709,29 +3705,27 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   if (rmode == 2 && nsteps > 0) stage_reduce(c, 1, -1, dt, 0, true);          // floe.interactions of the step that ended the batch
   c->tile_dirty = nsteps > 0;
   rc = sync_and_check(c, h);                     // (drops the halo floes and ghosts of the last step: tile_cleanup -- unless a step is paused)
-  if (rc == SZ_E_HIP) return fail(rc);
+  if (rc == SZ_E_HIP) return rc;
   {          // (the ranks agree on the error word BEFORE anybody decides to run steps again: a rank leaving on its own would hang the others)
     int all = 0;
     const int rc2 = comm_agree_bits(c, rc ? (c->last_err_bits ? c->last_err_bits : 1) : 0, &all);
-    if (rc2) return fail(rc2);
-    if (all) return fail(SZ_E_CAPACITY);
+    if (rc2) return rc2;
+    if (all) return SZ_E_CAPACITY;
   }
   // the step that was paused (here or on a peer) and the step a tag ended the batch at, as every rank sees them (comm_agree_steps)
   int sp = h[C_RETRYSTOP], st_all = h[C_STOP];
-  { const int rc3 = comm_agree_steps(c, h[C_STOP], h[C_RETRYSTOP], &st_all, &sp); if (rc3) return fail(rc3); }
+  { const int rc3 = comm_agree_steps(c, h[C_STOP], h[C_RETRYSTOP], &st_all, &sp); if (rc3) return rc3; }
   if (st_all > 0) h[C_STOP] = st_all;
   if (!lean || sp <= 0 || (st_all > 0 && st_all < sp)) break;
   // ---- a pause for the largest narrow variant in step sp
   const int tsp = tstep0 + sp - 1;
-  const bool coupling_sp = (flags & SZ_COUPLING_ON) && coupling_dt > 0 && (tsp % coupling_dt) == 0;
+  const bool coupling_sp = coupling_at(flags, coupling_dt, tsp);
   HIPCHK(c, hipMemsetAsync(S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream));
   HIPCHK(c, hipMemsetAsync(S.cnt + C_PAUSED, 0, sizeof(int), c->stream));
   S.retry_stop = 0; c->retry_seen = true; lean = false;
   {          // the forcing outputs as of step sp (the steps after it are run again).  BEFORE that step is finished: its integrator reads them, and
              // the steps enqueued behind it have gone on alternating the sets on the host while their forcing kernels returned at once
-    int want = 0;
-    for (int s2 = 0; s2 < sp; s2++) if (fset[s2] >= 0) want = fset[s2];
-    if (want != cur_set) swap_frc();
+    frc.use(last_set(sp));
     for (int s2 = sp; s2 < nsteps; s2++) fset[s2] = -1;
   }
   if (h[C_PAUSED] == sp) {          // this rank's step: the variant, then what the pause held back
@@ -3746,7 +3740,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   c->tile_dirty = true;
   if (sp >= nsteps || (st_all > 0 && st_all <= sp)) {               // (the last step of the batch -- or a peer tagged a floe in this very step: the batch ends with it -- nothing is run again)
     rc = sync_and_check(c, h);
-    if (rc == SZ_E_HIP) return fail(rc);
+    if (rc == SZ_E_HIP) return rc;
     if (st_all > 0) h[C_STOP] = h[C_STOP] > 0 ? std::min(h[C_STOP], st_all) : st_all;
     break;
   }
@@ -3766,7 +3760,6 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   }
   s_begin = sp;          // (the ghosts of that step: behind its pack, at the top of the loop)
   }
-  S.step = 0; S.ginline = 0; S.famrec = 0; S.crec = nullptr; S.retry_stop = 0; S.facc = nullptr; c->acc_mode = 0; c->reduce_mode = 0;
   {
     int all = 0;
     const int rc2 = comm_agree_bits(c, rc ? (c->last_err_bits ? c->last_err_bits : 1) : 0, &all);
@@ -3775,17 +3768,13 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   }
   const int done = h[C_STOP] > 0 ? std::min(h[C_STOP], (int)nsteps) : nsteps;
   if (steps_done) *steps_done = done;
-  {          // the forcing outputs of the last step that ran (see `beside` above)
-    int want = 0;                                                        // (set 0: the columns as they were at entry)
-    for (int s2 = 0; s2 < done; s2++) if (fset[s2] >= 0) want = fset[s2];
-    if (want != cur_set) swap_frc();
-  }
+  frc.use(last_set(done)); frc.keep = true;          // the forcing outputs of the last step that ran (see `beside` above)
   if (done < nsteps) c->grid_live = false;          // stopped early: cells hold floes of a step that did not come
   c->inter_any = true; c->inter_lost = false;
   // status.fuse_idx of the step that ended the batch (as sz_step: only that step can have produced fuse pairs)
   if (done > 0 && (h[C_STOP] > 0 || (flags & SZ_NO_STOP))) {
     const int tlast = tstep0 + done - 1;
-    const bool last_coupled = (flags & SZ_COUPLING_ON) && coupling_dt > 0 && (tlast % coupling_dt) == 0;
+    const bool last_coupled = coupling_at(flags, coupling_dt, tlast);
     c->gi_pending_n = h[C_NGHOSTS]; c->gi_pending_slot = (done - 1) & 1; c->gi_pending = true;
     rc = tile_fuse_replay(c, h, last_coupled);
     c->gi_pending = false;
