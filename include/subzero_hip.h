@@ -262,6 +262,34 @@ int sz_fracture_candidates(sz_ctx *ctx, int32_t *n, int32_t *idx);
 /* test hook: the mean parent height and (Hibler) the polygon's p of the last evaluation (sz_fracture_candidates or a batch's fracture step) */
 int sz_debug_fracture_mean(sz_ctx *ctx, double *mean_h, double *p);
 
+/* ---- welding overlaps on the device: the geometry of timestep_welding! (src/physical_processes/welding.jl:91-182) on the resident state.
+   The reference clips every pair of floes that share a welding bin (bin_floe_centroids, :23-55), pass potential_interaction (:128-131; parents
+   only, no periodic images) and are active and under max_weld_area (:116-127), and welds on inter_area (:134), a random draw and an area
+   window (:140-145); the fuse itself (fuse_two_floes!, :161-168) is topology-changing serial host work.  The device computes the OVERLAP TABLE:
+   every such pair i < j with inter_area > 0, ordered as the reference visits them -- bins in eachindex order (k = (yidx - 1) Nx + xidx - 1), then i,
+   then j ascending -- with inter_area = the sum of GO.area over all regions of intersect_polys.  The loop only ever asks for pairs whose two floes
+   are still as they were when the call began, so the table of the state at the start serves the whole call; an empty table means
+   the call changes nothing and draws no random number.
+   sz_set_welding: WeldSettings (process_settings.jl:526-533).  n = 0 turns it off (the default: nothing changes, not even a launch).  dts / nxs / nys
+   in the order the reference keeps them (sorted by Δt, largest first); the set of a step is the FIRST k with tstep % dts[k] == 0
+   (simulation.jl:186-189).
+   sz_step with welding set, in batches that stop: the batch ends after the first welding step whose table (for that step's Nx, Ny) is not empty;
+   *steps_done counts that step, the state is the reference's just before timestep_welding!, and sz_weld_overlaps then gives the same table, bit
+   for bit.  A tag or a fracture candidate on the same step ends the batch first (fracture_floes! runs before the welding).  The table of the batch's
+   own last step is left to the caller.  The steps between two welding steps run as ordinary batches (pipelined where those are); one host
+   synchronisation per welding step.  SZ_NO_STOP runs through and evaluates nothing.
+   Tiled runs (sz_tile_run, sz_tile_step) with welding set return SZ_E_STATE (the bins span ranks).
+   Limits: Nx * Ny * N^2 < 9e18 (the 64-bit pair key); rings of up to 254 vertices (the largest clip working set; beyond it SZ_E_CAPACITY). */
+int sz_set_welding(sz_ctx *ctx, int32_t n, const int32_t *dts, const int32_t *nxs, const int32_t *nys, double max_weld_area);
+/* the table of the state as it is now: *n entries; idx_i / idx_j (0-based parents) / inter_area have room for cap entries, or are all NULL to
+   ask for *n only.  Needs the domain and the grid extents (sz_set_domain, sz_set_fields); two calls on the same state give the same bits. */
+int sz_weld_overlaps(sz_ctx *ctx, int32_t nx, int32_t ny, double max_weld_area,
+                     int32_t *n, int32_t cap, int32_t *idx_i, int32_t *idx_j, double *inter_area);
+/* test hooks: per parent (room for N) the 0-based bin number of bin_floe_centroids or -1 (not binned: at or behind the first floe whose centroid
+   is out of bounds, welding.jl:38 breaks there); the candidate pairs (before the clip) of the last table pass */
+int sz_debug_weld_bins(sz_ctx *ctx, int32_t nx, int32_t ny, int32_t *bin);
+int sz_debug_weld_npairs(sz_ctx *ctx, int32_t *n);
+
 /* ---- measurement: HIP-event time per kernel class, accumulated since the last reset, on the
    stream the kernels are launched on; launches = number of timed launches of that class.
    on = 0: off; 1: every class; otherwise a mask, bit (k+1) = class k (e.g. 2 << SZ_K_NARROW: only

@@ -567,12 +567,100 @@ function fracture_candidates(eng::HIPEngine)
     return Int(n[])
 end
 
+# ------------------------------------------------------------------------------------------------ welding
+"""
+    set_welding!(eng, sim)
+
+The simulation's `WeldSettings` on the device (`sz_set_welding`): `Δts`, `Nxs`, `Nys` in the order the settings keep them (sorted by `Δt`,
+largest first) and `max_weld_area`.  Welding off: no sets.
+"""
+function set_welding!(eng::HIPEngine, sim)
+    ws = sim.weld_settings
+    if !ws.weld_on
+        check(eng, @ccall lib.sz_set_welding(eng.ctx::Ptr{Cvoid}, Int32(0)::Int32, C_NULL::Ptr{Int32}, C_NULL::Ptr{Int32}, C_NULL::Ptr{Int32},
+                                             1.0::Float64)::Cint)
+        return
+    end
+    dts, nxs, nys = Int32.(ws.Δts), Int32.(ws.Nxs), Int32.(ws.Nys)
+    check(eng, @ccall lib.sz_set_welding(eng.ctx::Ptr{Cvoid}, Int32(length(dts))::Int32, dts::Ptr{Int32}, nxs::Ptr{Int32}, nys::Ptr{Int32},
+                                         Float64(ws.max_weld_area)::Float64)::Cint)
+    return
+end
+
+"""
+    weld_overlaps(eng, nx, ny, max_weld_area) -> (i, j, inter_area)
+
+The welding overlap table of the resident state (`sz_weld_overlaps`): the pairs `i < j` (1-based) `timestep_welding!` would clip for an
+`nx` x `ny` welding grid and find overlapping, with their intersection areas, in the order its loops visit them (bin, then `i`, then `j`).
+"""
+function weld_overlaps(eng::HIPEngine, nx::Integer, ny::Integer, max_weld_area::Real)
+    n = Ref{Int32}(0)
+    check(eng, @ccall lib.sz_weld_overlaps(eng.ctx::Ptr{Cvoid}, Int32(nx)::Int32, Int32(ny)::Int32, Float64(max_weld_area)::Float64, n::Ptr{Int32},
+                                           Int32(0)::Int32, C_NULL::Ptr{Int32}, C_NULL::Ptr{Int32}, C_NULL::Ptr{Float64})::Cint)
+    cap = max(Int(n[]), 1)
+    ti, tj, ta = Vector{Int32}(undef, cap), Vector{Int32}(undef, cap), Vector{Float64}(undef, cap)
+    check(eng, @ccall lib.sz_weld_overlaps(eng.ctx::Ptr{Cvoid}, Int32(nx)::Int32, Int32(ny)::Int32, Float64(max_weld_area)::Float64, n::Ptr{Int32},
+                                           Int32(cap)::Int32, ti::Ptr{Int32}, tj::Ptr{Int32}, ta::Ptr{Float64})::Cint)
+    m = Int(n[])
+    return (i = Int.(ti[1:m]) .+ 1, j = Int.(tj[1:m]) .+ 1, inter_area = ta[1:m])
+end
+
+"""
+    timestep_welding!(floes, max_floe_id, table, weld_settings, floe_settings, weld_idx, Δt, rng)
+
+`Subzero.timestep_welding!` (welding.jl:91-182) with the clip of every candidate pair replaced by a lookup in the device's overlap `table`
+(`weld_overlaps` for the `Nxs[weld_idx]` x `Nys[weld_idx]` grid, taken from the state the call starts from).  The table lists exactly the pairs
+with `inter_area > 0` in the order the reference's loops reach them, grouped by bin and by `i`; a pair that is not listed has `inter_area = 0`,
+for which the reference draws no random number and welds nothing.  Every entry is looked at when its turn comes: both floes still active and
+under `max_weld_area`, one draw per entry, the union-area window; the partners of one `i` are then fused largest overlap first until the welded
+floe would exceed `max_weld_area`.  The areas in the table stay valid through the call: floe `i` changes shape only after its own entries have been
+read, and a `j` that was fused away earlier is tagged `remove` and skipped.
+"""
+function timestep_welding!(floes, max_floe_id, table, weld_settings, floe_settings, weld_idx, Δt, rng = Subzero.Xoshiro())
+    ws = weld_settings
+    nent = length(table.i)
+    e = 1
+    while e <= nent
+        i = table.i[e]
+        stop = e
+        while stop < nent && table.i[stop+1] == i
+            stop += 1
+        end
+        partners = Tuple{Int, Float64}[]
+        if floes.status[i].tag == Subzero.active && floes.area[i] < ws.max_weld_area
+            for q in e:stop
+                j, a = table.j[q], table.inter_area[q]
+                (floes.status[j].tag == Subzero.active && floes.area[j] < ws.max_weld_area) || continue
+                prob = ws.welding_coeff * (a / floes.area[i])
+                union_area = floes.area[i] + floes.area[j] - a
+                if a > 0 && prob > rand(rng) && ws.min_weld_area < union_area && ws.max_weld_area > union_area
+                    push!(partners, (j, a))
+                end
+            end
+        end
+        sort!(partners, by = last, rev = true)
+        for (j, a) in partners
+            floes.area[i] + floes.area[j] - a > ws.max_weld_area && break
+            Subzero.fuse_two_floes!(Subzero.get_floe(floes, i), Subzero.get_floe(floes, j), Δt, floe_settings, max_floe_id, rng)
+            floes.id[i] = -1          # numbered below, in index order, as the reference does
+        end
+        e = stop + 1
+    end
+    for i in eachindex(floes.id)
+        if floes.id[i] == -1
+            max_floe_id += 1
+            floes.id[i] = max_floe_id
+        end
+    end
+    return max_floe_id
+end
+
 # ------------------------------------------------------------------------------------------------ resident mode
 """
     run_resident!(sim, eng; start_tstep = 0, batch = 500)
 
-`run!(sim)` for simulations in which only the hot path and fracture touch the floes between output steps (ridging /
-rafting and welding off: the defaults).  Whole batches of `timestep_sim!` run on the device with the state resident in
+`run!(sim)` for simulations in which only the hot path, fracture and welding touch the floes between output steps (ridging /
+rafting off: the default).  Whole batches of `timestep_sim!` run on the device with the state resident in
 HBM (`sz_step`); a batch never crosses an output step of a writer, and it ends after the first step that leaves a floe
 tagged `remove` / `fuse`, so `simplify_floes!` (simulation.jl:205-214) runs exactly where the reference runs it.
 `sz_simplify_check` covers its other two triggers (rings over `max_vertices`, floes under the minimum area / height).
@@ -583,12 +671,20 @@ first fracture step on which a floe would fracture.  The state is then pulled, `
 `timestep_sim!` calls it (simulation.jl:172-183), then `simplify_floes!`, and the batch resumes from the uploaded state.  On
 fracture steps without a candidate `fracture_floes!` would change nothing and is skipped: `determine_fractures` draws no random
 numbers, so `sim.rng` stays exactly where the reference leaves it.
+
+Welding (`WeldSettings.weld_on`): on a welding step (`findfirst(x -> mod(tstep, x) == 0, Δts)`, simulation.jl:184-202) the device computes the
+overlap table of the pairs `timestep_welding!` would clip, and a batch also ends after the first welding step whose table is not empty.  The
+state is then pulled and `timestep_welding!(floes, max_floe_id, table, ...)` of this module welds from the table, then `simplify_floes!` as in
+the reference.  With an empty table the reference's call changes nothing and draws no random number; it is skipped.  The reference hands
+`timestep_welding!` no `rng` (a fresh `Xoshiro()` per call), and so does this loop.
 """
 function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Integer = 500)
-    (sim.ridgeraft_settings.ridge_raft_on || sim.weld_settings.weld_on) &&
-        error("run_resident!: ridging / welding need the floes on the host every step: use run!(sim)")
+    sim.ridgeraft_settings.ridge_raft_on &&
+        error("run_resident!: ridging / rafting needs the floes on the host every step: use run!(sim)")
     set_fracture!(eng, sim)
+    set_welding!(eng, sim)
     fractures = sim.fracture_settings.fractures_on
+    ws = sim.weld_settings
     Subzero.startup_sim(sim, nothing, 1)
     floes = sim.model.floes
     flags = (sim.collision_settings.collisions_on ? SZ_COLLISIONS_ON : Int32(0)) |
@@ -616,11 +712,26 @@ function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Int
             pull_state!(eng, floes, P)
             max_floe_id = Subzero.fracture_floes!(floes, max_floe_id, sim.rng, sim.fracture_settings, sim.floe_settings, sim.Δt)
         end
+        # ... and a welding step: the table of the floes as they are now (behind fracture_floes!, as in timestep_sim!), welded on the host
+        weld_idx = sim.weld_settings.weld_on && done[] > 0 ? findfirst(x -> mod(tstep - 1, x) == 0, ws.Δts) : nothing
+        weld_now = false
+        if !isnothing(weld_idx)
+            if fracture_now          # the device still holds the floes from before fracture_floes!
+                P = upload!(eng, floes, length(floes)); upload_interactions!(eng, floes)
+            end
+            table = weld_overlaps(eng, ws.Nxs[weld_idx], ws.Nys[weld_idx], ws.max_weld_area)
+            if !isempty(table.i)
+                fracture_now || pull_state!(eng, floes, P)
+                max_floe_id = timestep_welding!(floes, max_floe_id, table, ws, sim.floe_settings, weld_idx, sim.Δt)
+                weld_now = true
+            end
+        end
+        host_ahead = fracture_now || weld_now
         todo = Vector{Int64}(undef, 4)
-        fracture_now || check(eng, @ccall lib.sz_simplify_check(eng.ctx::Ptr{Cvoid}, eng.max_vertices::Int32, eng.min_floe_area::Float64,
-                                                                eng.min_floe_height::Float64, todo::Ptr{Int64})::Cint)
-        if fracture_now || any(!iszero, todo)        # simplify_floes! has work: it runs on the host, on the full state
-            fracture_now || pull_state!(eng, floes, P)
+        host_ahead || check(eng, @ccall lib.sz_simplify_check(eng.ctx::Ptr{Cvoid}, eng.max_vertices::Int32, eng.min_floe_area::Float64,
+                                                              eng.min_floe_height::Float64, todo::Ptr{Int64})::Cint)
+        if host_ahead || any(!iszero, todo)        # simplify_floes! has work: it runs on the host, on the full state
+            host_ahead || pull_state!(eng, floes, P)
             max_floe_id = Subzero.simplify_floes!(sim.model, max_floe_id, sim.simp_settings, sim.collision_settings,
                                                   sim.floe_settings, sim.Δt, sim.rng)
             P = upload!(eng, floes, length(floes)); upload_interactions!(eng, floes)

@@ -20,6 +20,7 @@
 #include "sz_output.hpp"
 #include "sz_migrate.hpp"
 #include "sz_fracture.hpp"
+#include "sz_weld.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 
 using namespace sz;
@@ -160,6 +161,14 @@ struct sz_ctx {
   int frac_kind = 0, frac_dt = 0, frac_npts = 0, frac_cap = 0;
   double frac_pstar = 0, frac_c = 0, frac_alpha = 0, frac_min_area = 0;
   FracDev* frac_d = nullptr; unsigned char* frac_flag = nullptr; int* frac_idx = nullptr;
+  // welding (sz_set_welding; sz_weld.hpp): WeldSettings' Δts / Nxs / Nys in the reference's order and max_weld_area; the buffers of the overlap-table
+  // pass (its own search cells, bins, pair keys, areas, table), carved for weld_capN parents, weld_cells cells and weld_cap pairs
+  std::vector<int> weld_dts, weld_nxs, weld_nys; double weld_max_area = 0;
+  Pool weld_allocs; int weld_capN = 0, weld_cells = 0, weld_cap = 0; void* weld_tmp = nullptr; size_t weld_tmp_bytes = 0;
+  WeldArgs weld{}; int *weld_cell_cnt = nullptr, *weld_cell_slots = nullptr, *weld_cell_ovf = nullptr, *weld_cell_items = nullptr; double* weld_bounds = nullptr;
+  WeldDev weld_h{}; double weld_h_grid[8] = { 0 };          // host sides of the two small uploads of a pass
+  int weld_npairs = 0;              // candidate pairs of the last pass (sz_debug_weld_npairs)
+  bool last_stopped = false;        // the last batch of resident steps ended on a stop request (tag, fracture candidate), not at its last step
   bool maybe_tagged = false;        // a parent may be non-active on the device (an upload said so, a batch ended on a tag, a process-mode call ran):
                                     // the next batch then runs its first step on its own (see sz_step)
   int last_err_bits = 0;   // device error bits the last sync_and_check found (tiled runs agree on them between the ranks)
@@ -966,6 +975,7 @@ void sz_destroy(sz_ctx* c) {
   for (auto& e : c->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   (void)hipFree(c->d_stats); (void)hipFree(c->S.acc);
   (void)hipFree(c->frac_d); (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx);
+  free_pool(c->weld_allocs); (void)hipFree(c->weld_tmp);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
   (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2);
   (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join);
@@ -2106,7 +2116,8 @@ int sz_debug_fracture_mean(sz_ctx* c, double* mean_h, double* p) {
 
 int sz_debug_pipelined(sz_ctx* c) { return c ? c->last_pipelined : 0; }
 
-int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
+// One batch of resident steps (sz_step without welding, or one of the segments sz_step cuts a batch with welding into)
+static int step_segment(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
   if (steps_done) *steps_done = 0;
   if (!c || !c->have_floes) return SZ_E_STATE;
   if (nsteps < 0) return SZ_E_ARG;
@@ -2185,7 +2196,7 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
     if (rest) {          // the lists outgrew the pipelined launches in step pipe_done: the rest of the batch as a batch of its own (not eligible now;
                          //  its scope starts from the process-mode values)
       int more = 0;
-      const int rc = sz_step(c, nsteps - pipe_done, tstep0 + pipe_done, dt, coupling_dt, flags, &more);
+      const int rc = step_segment(c, nsteps - pipe_done, tstep0 + pipe_done, dt, coupling_dt, flags, &more);
       if (steps_done) *steps_done = pipe_done + more;
       return rc;
     }
@@ -2280,6 +2291,7 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
     (void)hipMemsetAsync(c->S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream);
   }
   if (coll && (h[C_STOP] > 0 || (flags & SZ_NO_STOP))) c->maybe_tagged = true;
+  c->last_stopped = h[C_STOP] > 0;
   if (body && nsteps > 0) c->rings_stale = true;
   if (coll) { c->inter_any = true; c->inter_lost = false; }
   int rc = SZ_OK;
@@ -2309,6 +2321,188 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   }
   return rc;
 }
+
+// ---------------------------------------------------------------- welding overlap table (sz_weld.hpp)
+int sz_set_welding(sz_ctx* c, int32_t n, const int32_t* dts, const int32_t* nxs, const int32_t* nys, double max_weld_area) {
+  if (!c) return SZ_E_ARG;
+  if (n == 0) { c->weld_dts.clear(); c->weld_nxs.clear(); c->weld_nys.clear(); return SZ_OK; }
+  if (n < 0 || !dts || !nxs || !nys) { c->err = "sz_set_welding: n sets need dts, nxs and nys"; return SZ_E_ARG; }
+  for (int k = 0; k < n; k++) {
+    if (dts[k] <= 0) { c->err = "sz_set_welding: every dt (WeldSettings.Δts) must be positive"; return SZ_E_ARG; }
+    if (nxs[k] < 1 || nys[k] < 1) { c->err = "sz_set_welding: every Nx, Ny must be at least 1 (bin_floe_centroids asserts it)"; return SZ_E_ARG; }
+  }
+  if (!(max_weld_area > 0.0)) { c->err = "sz_set_welding: max_weld_area must be positive"; return SZ_E_ARG; }
+  c->weld_dts.assign(dts, dts + n); c->weld_nxs.assign(nxs, nxs + n); c->weld_nys.assign(nys, nys + n);
+  c->weld_max_area = max_weld_area;
+  return SZ_OK;
+}
+
+namespace {
+// the welding set of timestep tstep: the FIRST k with tstep % dts[k] == 0 (findfirst, simulation.jl:186-189), or -1
+int weld_set_at(const sz_ctx* c, int tstep) {
+  for (size_t k = 0; k < c->weld_dts.size(); k++) if (tstep % c->weld_dts[k] == 0) return (int)k;
+  return -1;
+}
+// the pass's buffers for the parents as they are, `need` pairs and `cells` search cells
+int weld_ensure(sz_ctx* c, int need, int cells) {
+  const int N = std::max(c->hostN, 1);
+  if (c->weld.d && N <= c->weld_capN && cells <= c->weld_cells && need <= c->weld_cap) return SZ_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  free_pool(c->weld_allocs);
+  c->weld = WeldArgs{}; c->weld_capN = c->weld_cells = c->weld_cap = 0;
+  const size_t cap = (size_t)std::max((long long)need, 8LL * N + 1024);
+  if (cap > (size_t)1 << 30) { c->err = "welding: candidate pair count overflow"; return SZ_E_CAPACITY; }
+  Pool& P = c->weld_allocs; WeldArgs& W = c->weld; int rc;
+  if ((rc = dalloc(c, &W.d, 1, P)) || (rc = dalloc(c, &W.bin, N, P)) || (rc = dalloc(c, &c->weld_bounds, 8, P)) ||
+      (rc = dalloc(c, &c->weld_cell_cnt, (size_t)cells + 1, P)) || (rc = dalloc(c, &c->weld_cell_ovf, (size_t)cells + 1, P)) ||
+      (rc = dalloc(c, &c->weld_cell_slots, (size_t)cells * CELL_K, P)) || (rc = dalloc(c, &c->weld_cell_items, N, P)) ||
+      (rc = dalloc(c, &W.keys_in, cap, P)) || (rc = dalloc(c, &W.keys, cap, P)) || (rc = dalloc(c, &W.area, cap, P)) || (rc = dalloc(c, &W.retry, cap, P)) ||
+      (rc = dalloc(c, &W.ti, cap, P)) || (rc = dalloc(c, &W.tj, cap, P)) || (rc = dalloc(c, &W.ta, cap, P))) { W.d = nullptr; return rc; }
+  c->weld_capN = N; c->weld_cells = cells; c->weld_cap = (int)cap; W.cap = (int)cap;
+  return SZ_OK;
+}
+// The overlap table of the parents as they lie, for nx x ny bins: *ntable entries in c->weld.ti / tj / ta.  Synchronous; reads the floes' columns and
+// rings, writes nothing but its own buffers (a batch that goes on behind it finds the state as the steps left it).
+int weld_pass(sz_ctx* c, int nx, int ny, double max_area, int* ntable) {
+  *ntable = 0;
+  State& S = c->S;
+  const int N = c->hostN;
+  if (N <= 0) { c->err = "welding: no floes"; return SZ_E_STATE; }
+  // (k n + i) n + j must fit an unsigned 64-bit key
+  if ((long double)nx * (long double)ny * (long double)N * (long double)N >= 9.0e18L) { c->err = "welding: Nx * Ny * N^2 does not fit the 64-bit pair key"; return SZ_E_ARG; }
+  const double rm = std::max(c->rmax_max, c->rmax_hint);
+  if (!(rm > 0.0) || !(S.gxf > S.gx0) || !(S.gyf > S.gy0)) { c->err = "welding: needs the floes' rmax and the grid extents (sz_set_fields)"; return SZ_E_STATE; }
+  // search cells over the grid's box, at least 2 max(rmax) wide (setup_grid's rule), indices clamped: no periodic wrap in this search
+  const double cmin = 2.0 * rm * (1.0 + 1e-9);
+  long long ncx = std::max(1LL, (long long)std::floor(std::min((S.gxf - S.gx0) / cmin, 1e6)));
+  long long ncy = std::max(1LL, (long long)std::floor(std::min((S.gyf - S.gy0) / cmin, 1e6)));
+  const long long cell_max = std::max(4LL * N, 1024LL);
+  while (ncx * ncy > cell_max) { ncx = std::max(1LL, ncx / 2); ncy = std::max(1LL, ncy / 2); }
+  const int cells = (int)(ncx * ncy);
+  double* g = c->weld_h_grid;
+  g[0] = S.gx0; g[1] = S.gy0; g[2] = (S.gxf - S.gx0) / (double)ncx; g[3] = (S.gyf - S.gy0) / (double)ncy; g[4] = (double)ncx; g[5] = (double)ncy; g[6] = 0.0; g[7] = 0.0;
+  world_rings(c);
+  int need = 0;
+  for (int round = 0;; round++) {
+    if (int rc = weld_ensure(c, need, cells)) return rc;
+    WeldArgs& W = c->weld;
+    W.n = N; W.nx = nx; W.ny = ny; W.max_area = max_area;
+    State T = S; T.step = 0;
+    T.bounds = c->weld_bounds; T.cell_cnt = c->weld_cell_cnt; T.cell_slots = c->weld_cell_slots; T.cell_ovf = c->weld_cell_ovf; T.cell_items = c->weld_cell_items;
+    c->weld_h = WeldDev{ N, 0, 0, 0 };
+    HIPCHK(c, hipMemcpyAsync(W.d, &c->weld_h, sizeof(WeldDev), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->weld_bounds, g, 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->weld_cell_cnt, 0, ((size_t)cells + 1) * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->weld_cell_ovf, 0, ((size_t)cells + 1) * sizeof(int), c->stream));
+    const int nb = grid_for(N, 256, 2048);
+    hipLaunchKernelGGL(sz_k_weld_oob, dim3(nb), dim3(256), 0, c->stream, T, W);
+    hipLaunchKernelGGL(sz_k_weld_bins, dim3(nb), dim3(256), 0, c->stream, T, W);
+    hipLaunchKernelGGL(sz_k_weld_pairs, dim3(nb), dim3(256), 0, c->stream, T, W);
+    HIPCHK(c, hipMemcpyAsync(&c->weld_h, W.d, sizeof(WeldDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int P = c->weld_h.npairs;
+    if (P < 0) { c->err = "welding: candidate pair count overflow"; return SZ_E_CAPACITY; }
+    if (P > W.cap) {          // the pair arrays grow like the other lists; nothing is truncated
+      if (round > 0) { c->err = "welding: the pair arrays did not grow enough"; return SZ_E_CAPACITY; }
+      need = P + P / 4;
+      continue;
+    }
+    c->weld_npairs = P;
+    if (P > 0) {
+      const unsigned long long top = (unsigned long long)nx * ny * (unsigned long long)N * (unsigned long long)N;
+      unsigned bits = 1; while (bits < 64 && (top >> bits)) bits++;
+      size_t tmp_bytes = 0;
+      HIPCHK(c, rocprim::radix_sort_keys(nullptr, tmp_bytes, W.keys_in, W.keys, (size_t)P, 0u, bits, c->stream));
+      if (tmp_bytes > c->weld_tmp_bytes) {
+        (void)hipFree(c->weld_tmp); c->weld_tmp = nullptr; c->weld_tmp_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->weld_tmp, tmp_bytes + tmp_bytes / 2));
+        c->weld_tmp_bytes = tmp_bytes + tmp_bytes / 2;
+      }
+      HIPCHK(c, rocprim::radix_sort_keys(c->weld_tmp, tmp_bytes, W.keys_in, W.keys, (size_t)P, 0u, bits, c->stream));
+      hipLaunchKernelGGL((sz_k_weld_area<WELD_G0, WELD_CAP0, WELD_KC0, WELD_RC0, WELD_RM0, 0>), dim3(grid_for(P, 64 / WELD_G0, 1 << 16)), dim3(64), 0, c->stream, S, W, P);
+      // (what the small working set handed on; its count lives on the device: a fixed grid, most of it returns at once)
+      hipLaunchKernelGGL((sz_k_weld_area<WELD_G1, WELD_CAP1, WELD_KC1, WELD_RC1, WELD_RM1, 1>), dim3(grid_for(P, 1, 512)), dim3(64), 0, c->stream, S, W, P);
+      hipLaunchKernelGGL(sz_k_weld_table, dim3(1), dim3(WELD_TPB), 0, c->stream, W, P);
+      HIPCHK(c, hipMemcpyAsync(&c->weld_h, W.d, sizeof(WeldDev), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (int rc = sync_and_check(c)) return rc;
+    if (c->weld_h.ntable < 0 || c->weld_h.ntable > P) { c->err = "welding: bad table count"; return SZ_E_HIP; }
+    *ntable = c->weld_h.ntable;
+    return SZ_OK;
+  }
+}
+int weld_query_checks(sz_ctx* c, const char* who, int32_t nx, int32_t ny) {
+  if (!c) return SZ_E_ARG;
+  if (nx < 1 || ny < 1) { c->err = std::string(who) + ": Nx and Ny must be at least 1"; return SZ_E_ARG; }
+  if (!c->have_floes) { c->err = std::string(who) + ": no floes uploaded"; return SZ_E_STATE; }
+  if (!c->have_domain || !c->have_fields) { c->err = std::string(who) + ": the bins need the domain's boundary kinds and the grid extents (sz_set_domain, sz_set_fields)"; return SZ_E_STATE; }
+  if (c->S.tiled) { c->err = std::string(who) + ": tiled contexts do not compute welding overlaps (the bins span ranks)"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  return sync_and_check(c);          // hostN current, nothing pending
+}
+}  // namespace
+
+int sz_weld_overlaps(sz_ctx* c, int32_t nx, int32_t ny, double max_weld_area, int32_t* n, int32_t cap, int32_t* idx_i, int32_t* idx_j, double* inter_area) {
+  if (n) *n = 0;
+  if (!c || !n) return SZ_E_ARG;
+  if (!(max_weld_area > 0.0)) { c->err = "sz_weld_overlaps: max_weld_area must be positive"; return SZ_E_ARG; }
+  if (int rc = weld_query_checks(c, "sz_weld_overlaps", nx, ny)) return rc;
+  int nt = 0;
+  if (int rc = weld_pass(c, nx, ny, max_weld_area, &nt)) return rc;
+  *n = nt;
+  if (!idx_i && !idx_j && !inter_area) return SZ_OK;
+  if (cap < nt) { c->err = "sz_weld_overlaps: cap is smaller than the table (*n)"; return SZ_E_ARG; }
+  if (nt > 0) {
+    if (idx_i) HIPCHK(c, hipMemcpyAsync(idx_i, c->weld.ti, (size_t)nt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (idx_j) HIPCHK(c, hipMemcpyAsync(idx_j, c->weld.tj, (size_t)nt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (inter_area) HIPCHK(c, hipMemcpyAsync(inter_area, c->weld.ta, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return SZ_OK;
+}
+int sz_debug_weld_bins(sz_ctx* c, int32_t nx, int32_t ny, int32_t* bin) {
+  if (!c || !bin) return SZ_E_ARG;
+  if (int rc = weld_query_checks(c, "sz_debug_weld_bins", nx, ny)) return rc;
+  int nt = 0;
+  if (int rc = weld_pass(c, nx, ny, INFINITY, &nt)) return rc;
+  HIPCHK(c, hipMemcpy(bin, c->weld.bin, (size_t)c->hostN * sizeof(int), hipMemcpyDeviceToHost));
+  return SZ_OK;
+}
+int sz_debug_weld_npairs(sz_ctx* c, int32_t* n) {
+  if (!c || !n) return SZ_E_ARG;
+  *n = c->weld_npairs;
+  return SZ_OK;
+}
+
+// sz_step with welding set (sz_set_welding), in batches that stop: the batch is cut into segments that END on a welding step (tstep % dts[k] == 0,
+// timestep_welding! runs behind timestep_floe_properties!, simulation.jl:184-202).  A segment is an ordinary batch through the drivers above -- its
+// last step keeps its ghosts, the rows come home behind it, segments of pipe_min_steps or more stay pipelined -- then the overlap table of that
+// step's (Nx, Ny): empty = the reference's call would change nothing and draw no random number, and the next segment starts; not empty = the batch
+// ends there (steps_done counts the welding step; sz_weld_overlaps gives the caller the same table again).  A tag or a fracture candidate ends the
+// segment and the batch first, as fracture_floes! runs before the welding.  The batch's own last step is not looked at: the caller sees that the
+// batch ended on a welding step and asks.  Batches that run through (SZ_NO_STOP) and contexts without welding take the driver as it is.
+int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
+  if (!c || c->weld_dts.empty() || (flags & SZ_NO_STOP) || nsteps <= 0) return step_segment(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done);
+  if (steps_done) *steps_done = 0;
+  if (!c->have_floes) return SZ_E_STATE;
+  if (c->S.tiled) { c->err = "tiled contexts do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
+  if (!c->have_domain || !c->have_fields) { c->err = "sz_step with welding set: the bins need the grid extents (sz_set_fields)"; return SZ_E_STATE; }
+  int done = 0;
+  while (done < nsteps) {
+    int len = nsteps - done, set = -1;
+    for (int s = 0; s < nsteps - done; s++) { const int k = weld_set_at(c, tstep0 + done + s); if (k >= 0) { len = s + 1; set = k; break; } }
+    int more = 0;
+    const int rc = step_segment(c, len, tstep0 + done, dt, coupling_dt, flags, &more);
+    done += more;
+    if (steps_done) *steps_done = done;
+    if (rc || more < len || c->last_stopped || set < 0 || done == nsteps) return rc;
+    int nt = 0;
+    if (int rc2 = weld_pass(c, c->weld_nxs[set], c->weld_nys[set], c->weld_max_area, &nt)) return rc2;
+    if (nt > 0) break;
+  }
+  return SZ_OK;
+}
+
 
 int sz_profile_enable(sz_ctx* c, int32_t on) {
   if (!c) return SZ_E_ARG;
@@ -2476,6 +2670,7 @@ int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int
                  int32_t flags) {
   if (!c || !c->have_floes) return SZ_E_STATE;
   if (c->frac_kind != SZ_FRAC_OFF) { c->err = "tiled runs do not evaluate fracture criteria (the mean height needs an all-reduce over the ranks): sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
+  if (!c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
   State& S = c->S;
   const bool coll = (flags & SZ_COLLISIONS_ON) != 0;
@@ -3518,6 +3713,7 @@ int sz_tile_set_center(sz_ctx* c, double x, double y) {
 int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
   if (steps_done) *steps_done = 0;
   if (c && c->frac_kind != SZ_FRAC_OFF) { c->err = "tiled runs do not evaluate fracture criteria (the mean height needs an all-reduce over the ranks): sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
+  if (c && !c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
   if (!c || !c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0) {
     if (c) c->err = "sz_tile_run needs sz_tile_enable and sz_tile_setup after the last sz_upload_floes";
     return SZ_E_STATE;

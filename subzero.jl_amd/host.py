@@ -550,7 +550,9 @@ class World:
         """nsteps x timestep_sim! with the state resident in HBM.  Returns the number of steps run: the batch ends
         after the first step that tags a floe remove / fuse (the reference runs simplify_floes! after every step,
         simulation.jl:205-214), or -- with a criterion set (set_fracture) -- after the first fracture step on which a floe would
-        fracture (fracture_floes! is the host's); stop_on_tags=False runs on regardless (measurement / soak runs)."""
+        fracture (fracture_floes! is the host's), or -- with welding set (set_welding) -- after the first welding step on which two floes that
+        could weld overlap (weld_overlaps() then gives the table timestep_welding! works from; the fuse is the host's);
+        stop_on_tags=False runs on regardless (measurement / soak runs)."""
         self._push()
         flags = (capi.COLLISIONS_ON if collisions_on else 0) | (capi.COUPLING_ON if coupling_on else 0)
         if not stop_on_tags:
@@ -589,6 +591,41 @@ class World:
         m, p = C.c_double(0), C.c_double(0)
         self._chk(self.L.sz_debug_fracture_mean(self.h, C.byref(m), C.byref(p)))
         return m.value, p.value
+
+    def set_welding(self, dts, nxs, nys, max_weld_area=2e9):
+        """WeldSettings(weld_on, Δts = dts, Nxs = nxs, Nys = nys, max_weld_area) in the reference's order (sorted by Δt, largest first; the set of a
+        step is the first with tstep % dt == 0); empty lists turn it off.  run() then ends a batch after the first welding step whose overlap
+        table is not empty."""
+        d, x, y = (np.ascontiguousarray(a, _I32).ravel() for a in (dts, nxs, nys))
+        if not (len(d) == len(x) == len(y)):
+            raise SzError("set_welding: dts, nxs and nys differ in length")
+        self._chk(self.L.sz_set_welding(self.h, len(d), capi.ptr(d, capi._ip), capi.ptr(x, capi._ip), capi.ptr(y, capi._ip), float(max_weld_area)))
+
+    def weld_overlaps(self, nx, ny, max_weld_area=2e9):
+        """the welding overlap table of the state as it is (welding.jl:91-152): (i, j, inter_area), 0-based parents i < j that share a bin of the
+        nx x ny welding grid, are active and under max_weld_area, pass potential_interaction and overlap; in the reference's visiting order"""
+        self._push()
+        n = C.c_int32(0)
+        self._chk(self.L.sz_weld_overlaps(self.h, int(nx), int(ny), float(max_weld_area), C.byref(n), 0, None, None, None))
+        cap = max(int(n.value), 1)
+        i = np.zeros(cap, _I32); j = np.zeros(cap, _I32); a = np.zeros(cap)
+        self._chk(self.L.sz_weld_overlaps(self.h, int(nx), int(ny), float(max_weld_area), C.byref(n), cap, capi.ptr(i, capi._ip), capi.ptr(j, capi._ip),
+                                          capi.ptr(a)))
+        return i[:n.value].copy(), j[:n.value].copy(), a[:n.value].copy()
+
+    def weld_bins(self, nx, ny):
+        """bin_floe_centroids (welding.jl:23-55): per parent the 0-based bin number (yidx - 1) * nx + (xidx - 1), or -1 for the floes at and behind
+        the first centroid that is out of bounds"""
+        self._push()
+        b = np.zeros(max(self.N, 1), _I32)
+        self._chk(self.L.sz_debug_weld_bins(self.h, int(nx), int(ny), capi.ptr(b, capi._ip)))
+        return b[:self.N].copy()
+
+    def weld_candidate_pairs(self):
+        """pairs the last table pass clipped (the reference's candidates before intersect_polys)"""
+        n = C.c_int32(0)
+        self._chk(self.L.sz_debug_weld_npairs(self.h, C.byref(n)))
+        return int(n.value)
 
     def timestep_sim(self, tstep, dt, coupling_dt=10, collisions_on=True, coupling_on=True):
         self.run(1, tstep, dt, coupling_dt, collisions_on, coupling_on)
