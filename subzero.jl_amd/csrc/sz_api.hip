@@ -29,14 +29,6 @@ namespace {
 
 constexpr int NK = SZ_K_COUNT + 2;   // + large narrow variant, + the halo exchange of a tiled step (events on the communication stream)
 constexpr int K_NARROW_LARGE = SZ_K_COUNT, K_EXCHANGE = SZ_K_COUNT + 1;
-#ifndef NARROW_G
-#define NARROW_G 8
-#endif
-#ifndef NARROW_KC0          // working set of the first narrow variant: crossings, region points
-#define NARROW_KC0 8
-#define NARROW_RC0 16
-#endif
-
 struct EvPair { int k; hipEvent_t a, b; };
 
 // Device allocations of one lifetime.  The ~130 columns and work arrays are carved out of a few large chunks
@@ -147,9 +139,9 @@ struct sz_ctx {
   // the step, 2 it is left out of the steps and runs once behind the batch (the reduce-free steps)
   long long* facc_buf = nullptr; int acc_mode = 0, reduce_mode = 0;
   // pipelined resident steps (sz_pipeline.hpp): the second set of what is double-buffered by step parity.  pb[0] is what the upload carved
-  // (State::vxy, crec_buf, the cell lists, the work list, the ghost links), pb[1] its twin; gpar: the set that holds the context's state.
-  struct PipeBuf { double2 *vxy = nullptr, *crec = nullptr; int *cell_cnt = nullptr, *cell_slots = nullptr, *cell_ovf = nullptr, *cell_items = nullptr;
-                   int4* work = nullptr; int* wq = nullptr; int *gh = nullptr, *ngh = nullptr; } pb[2];
+  // (State::vxy, crec_buf, the cell lists, the work list, the ghost links), pb[1] its twin; gpar: the set that holds the context's state -- c->S
+  // points at pb[gpar]'s buffers, the records apart: State::crec is a batch mode, the set's records are crec_buf (own_set_carved, pipe_adopt).
+  StepSet pb[2] = {};
   int gpar = 0;
   bool no_pipeline = false;         // SZ_PIPELINE=0: the three-launch steps (A/B)
   int pipe_min_steps = 4;           // batches shorter than this take the three-launch steps (a pipelined batch has a prologue and an epilogue)
@@ -306,21 +298,24 @@ int carve_interactions(sz_ctx* c) {
   }
   return SZ_OK;
 }
+// members of the parity set were carved into c->S: the context's own set follows (c->S is set gpar's; the set's records are crec_buf)
+void own_set_carved(sz_ctx* c) { StepSet& B = c->pb[c->gpar]; step_set_copy(B, c->S); B.crec = c->crec_buf; }
 // neighbour lists (stride State::maxnb), the narrow phase's work list and the rows of its items (State::capPairs)
 int carve_lists(sz_ctx* c) {
   State& S = c->S;
+  StepSet& twin = c->pb[1 - c->gpar];
   reset_pool(c->list_allocs);
   int rc;
 #define DL(field, n) if ((rc = dalloc(c, &S.field, (size_t)(n), c->list_allocs))) return rc
   DL(nb_out, (size_t)S.capM * S.maxnb); DL(nb_in, (size_t)S.capM * S.maxnb);
   DL(work, 2 * ((size_t)S.capPairs + NSEG)); DL(wq, NSEG * 32); DL(pair_i, S.capPairs); DL(pair_j, S.capPairs);
-  if ((rc = dalloc(c, &c->pb[1].work, 2 * ((size_t)S.capPairs + NSEG), c->list_allocs)) || (rc = dalloc(c, &c->pb[1].wq, (size_t)NSEG * 32, c->list_allocs))) return rc;
-  c->pb[0].work = S.work; c->pb[0].wq = S.wq;
+  if ((rc = dalloc(c, &twin.work, 2 * ((size_t)S.capPairs + NSEG), c->list_allocs)) || (rc = dalloc(c, &twin.wq, (size_t)NSEG * 32, c->list_allocs))) return rc;
+  own_set_carved(c);
   DL(it_rows, ((size_t)S.capPairs + S.capElem) * ROWS_PER_ITEM * 5); DL(it_info, (size_t)S.capM * S.maxnb + S.capElem + 1);
 #undef DL
   trim_pool(c->list_allocs);
   HIPCHK(c, hipMemsetAsync(S.wq, 0, NSEG * 32 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->pb[1].wq, 0, NSEG * 32 * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(twin.wq, 0, NSEG * 32 * sizeof(int), c->stream));
   return SZ_OK;
 }
 // The reference's lists grow as needed (collisions.jl:290-296: vcat; the Dict of the pair loop).  A call / step that outgrew a list has
@@ -538,42 +533,43 @@ void stage_ghosts(sz_ctx* c, bool in_step = false, bool commit = false, bool use
   t.end();
 }
 
+// workgroups of the neighbour search, on its own or as a part of a launch (sz_k_neighbors_elem, sz_k_vel_search)
+int search_grid(const State& T) { return grid_for(T.capM, NB_TPB / NB_G, 8192); }
+// The neighbour search of the step State T stands for; it appends the pair items to the narrow phase's work list itself (no scan, no pair-list
+// launch).  The instantiation follows from T: the ones that read the collision records where T.crec says they are current in this batch (the
+// default stride only), the Dict rule's family records where ghosts can exist (fam), the row stride class from T.maxnb.
+// elems: the floe-element items ride in the launch's tail (fields between walls: the lean instantiation -- no ghosts, no Dict rule)
+// forcing: the step's forcings ride in it (sz_k_neighbors_forcing)
+void launch_search(sz_ctx* c, const State& T, bool elems = false, bool forcing = false) {
+  const bool rec = T.crec != nullptr;
+  if (forcing) {
+    const int nbn = grid_for(T.capM, 256 / NB_G, 8192), nbf = grid_for(T.capM, 256 / FRC_PLAIN, 8192);
+    const auto kern = c->precision == 1 ? (rec ? sz_k_neighbors_forcing<2, true> : sz_k_neighbors_forcing<2, false>)
+                                        : (rec ? sz_k_neighbors_forcing<1, true> : sz_k_neighbors_forcing<1, false>);
+    hipLaunchKernelGGL(kern, dim3(nbn + nbf), dim3(256), 0, c->stream, T, c->P, nbn);
+  } else if (elems) {
+    const int nbn = search_grid(T), nbe = grid_for(T.capM, NB_TPB, 1 << 20);
+    const auto kern = rec ? sz_k_neighbors_elem<false, true> : sz_k_neighbors_elem<false, false>;
+    hipLaunchKernelGGL(kern, dim3(nbn + nbe), dim3(NB_TPB), 0, c->stream, T, next_epoch(c), nbn);
+  } else {
+    const bool fam = c->hostN <= 40000 && (T.any_periodic_ew || T.any_periodic_ns);      // (no periodic wall: no ghosts, no Dict rule)
+    const bool wide = T.maxnb > 64;          // (a floe with more than 64 neighbours: the capacity that keeps such a field running, 64 threads per workgroup)
+    const auto kern = T.maxnb <= MAXNB ? (fam ? (rec ? sz_k_neighbors<true, MAXNB, true> : sz_k_neighbors<true, MAXNB>) : (rec ? sz_k_neighbors<false, MAXNB, true> : sz_k_neighbors<false, MAXNB>))
+                      : !wide ? (fam ? sz_k_neighbors<true, 64> : sz_k_neighbors<false, 64>) : sz_k_neighbors<false, 256>;
+    hipLaunchKernelGGL(kern, dim3(wide ? grid_for(T.capM, 64 / NB_G, 16384) : search_grid(T)), dim3(wide ? 64 : NB_TPB), 0, c->stream, T);
+  }
+}
 // static_grid: the geometry in S.bounds is the host's (use_static_grid), no bounds kernel; the pair kernel does
 // the housekeeping the bounds kernel would have done
 void stage_broad(sz_ctx* c, bool commit_ghosts = false, bool static_grid = false, bool fuse_forcing = false, bool with_elems = false) {
   State& S = c->S;
   Timed t(c, SZ_K_BROAD);
-  int gM = grid_for(S.capM, 256);
   if (!static_grid) {          // with the static grid the cells are already current (see sz_k_cell_build)
     hipLaunchKernelGGL(sz_k_bounds, dim3(1), dim3(1024), 0, c->stream, S, commit_ghosts ? 1 : 0);
-    hipLaunchKernelGGL(sz_k_cell_build, dim3(gM), dim3(256), 0, c->stream, S, 0);
+    hipLaunchKernelGGL(sz_k_cell_build, dim3(grid_for(S.capM, 256)), dim3(256), 0, c->stream, S, 0);
     c->grid_live = false;
   }
-  // the neighbour search appends the pair items to the narrow phase's work list itself: no scan, no pair-list launch
-  const bool rec = S.crec != nullptr;      // collision records are current in this batch: the instantiations that read them
-  if (fuse_forcing) {          // the step's forcings ride in the neighbour launch (sz_k_neighbors_forcing)
-    const int nbn = grid_for(S.capM, 256 / NB_G, 8192), nbf = grid_for(S.capM, 256 / FRC_PLAIN, 8192);
-    if (c->precision == 1) { if (rec) hipLaunchKernelGGL((sz_k_neighbors_forcing<2, true>), dim3(nbn + nbf), dim3(256), 0, c->stream, S, c->P, nbn); else hipLaunchKernelGGL((sz_k_neighbors_forcing<2, false>), dim3(nbn + nbf), dim3(256), 0, c->stream, S, c->P, nbn); }
-    else { if (rec) hipLaunchKernelGGL((sz_k_neighbors_forcing<1, true>), dim3(nbn + nbf), dim3(256), 0, c->stream, S, c->P, nbn); else hipLaunchKernelGGL((sz_k_neighbors_forcing<1, false>), dim3(nbn + nbf), dim3(256), 0, c->stream, S, c->P, nbn); }
-  } else
-  {
-    const dim3 gr(grid_for(S.capM, NB_TPB / NB_G, 8192)), bl(NB_TPB);
-    const bool fam = c->hostN <= 40000 && (S.any_periodic_ew || S.any_periodic_ns);      // (no periodic wall: no ghosts, no Dict rule)
-    if (with_elems) {          // the element items in the launch's tail (elems_ride)
-      // (no periodic wall, no ghosts, no Dict rule: the search's lean instantiation)
-      const int nbn = (int)gr.x, nbe = grid_for(S.capM, NB_TPB, 1 << 20);
-      if (rec) hipLaunchKernelGGL((sz_k_neighbors_elem<false, true>), dim3(nbn + nbe), bl, 0, c->stream, S, next_epoch(c), nbn);
-      else hipLaunchKernelGGL((sz_k_neighbors_elem<false, false>), dim3(nbn + nbe), bl, 0, c->stream, S, next_epoch(c), nbn);
-    } else if (S.maxnb <= MAXNB) {
-      if (fam) { if (rec) hipLaunchKernelGGL((sz_k_neighbors<true, MAXNB, true>), gr, bl, 0, c->stream, S); else hipLaunchKernelGGL((sz_k_neighbors<true, MAXNB>), gr, bl, 0, c->stream, S); }
-      else { if (rec) hipLaunchKernelGGL((sz_k_neighbors<false, MAXNB, true>), gr, bl, 0, c->stream, S); else hipLaunchKernelGGL((sz_k_neighbors<false, MAXNB>), gr, bl, 0, c->stream, S); }
-    } else if (S.maxnb <= 64) {
-      if (fam) hipLaunchKernelGGL((sz_k_neighbors<true, 64>), gr, bl, 0, c->stream, S);
-      else hipLaunchKernelGGL((sz_k_neighbors<false, 64>), gr, bl, 0, c->stream, S);
-    } else {          // (a floe with more than 64 neighbours: the capacity that keeps such a field running)
-      hipLaunchKernelGGL((sz_k_neighbors<false, 256>), dim3(grid_for(S.capM, 64 / NB_G, 16384)), dim3(64), 0, c->stream, S);
-    }
-  }
+  launch_search(c, S, with_elems, fuse_forcing);
   t.end();
 }
 
@@ -592,6 +588,23 @@ void stage_elems(sz_ctx* c, bool enabled) {
   t.end();
 }
 
+#ifndef NARROW_G
+#define NARROW_G 8
+#endif
+#ifndef NARROW_KC0          // working set of the first narrow variant: crossings, region points
+#define NARROW_KC0 8
+#define NARROW_RC0 16
+#endif
+// The three narrow variants, by ring capacity (NARROW_CAP0 / 1 / 2, sz_kernels.hpp): every launch, the occupancy query and sz_narrow_kernel_name
+// name them through these.  The first one's leading template arguments -- G, CAP, KC, RC, RM, TPB, LO, CLS, WPE -- are followed by FRC (the
+// step's forcings ride in the launch: 1 fp64, 2 mixed precision) and GEO (a pipelined step: the next step's geometry rides in it).
+constexpr int NARROW_TPB = 64;
+#define NARROW_FIRST_ARGS NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, NARROW_TPB, 0, 0, 3
+template <int FRC = 0, int GEO = 0> constexpr auto narrow_first = sz_k_narrow<NARROW_FIRST_ARGS, FRC, GEO>;
+constexpr decltype(narrow_first<>) narrow_first_frc[3] = { narrow_first<0>, narrow_first<1>, narrow_first<2> };          // the three-launch steps' flavours, by FRC
+constexpr auto narrow_larger = sz_k_narrow<16, NARROW_CAP1, 16, 80, 6, NARROW_TPB, NARROW_CAP0, 1>;
+constexpr auto narrow_last = sz_k_narrow<64, NARROW_CAP2, NARROW_KC2, NARROW_RC2, 16, NARROW_TPB, NARROW_CAP1, 2>;
+
 // frc: the step's forcings ride in the launch of the first variant (0: no, 1: fp64, 2: mixed precision)
 // rings above the first narrow variant's capacity exist (rings never change size inside the hot path, so the host knows; halo floes of a
 // tiled run arrive unseen: their bound counts)
@@ -603,7 +616,9 @@ int narrow_grid(sz_ctx* c) {
   int& grid = c->narrow_grid0;
   if (grid == 0) {
     int per_cu = 0, cus = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sz_k_narrow<NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, 64, 0, 0, 3, 0>, 64, 0);
+    // (asked of the plain flavour for all of them: the FRC / GEO flavours are held to the same 168 registers and 16 KB of LDS per workgroup --
+    //  test_hot_kernels_keep_their_register_budgets -- so a CU holds as many of their narrow workgroups)
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, narrow_first<>, NARROW_TPB, 0);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
     grid = per_cu > 0 && cus > 0 ? per_cu * cus : 2048;
     if (const char* e = getenv("SZ_NARROW_GRID")) { int v = atoi(e); if (v > 0) grid = v; }
@@ -611,45 +626,41 @@ int narrow_grid(sz_ctx* c) {
   }
   return grid;
 }
-void narrow_largest(sz_ctx* c, const State& T, int dt, double ffmo, double fdmo, int maxb);
+// A launch of the first narrow variant on the step State T stands for (event-timed as the class "narrow"): 168 VGPRs (3 wavefronts per SIMD) and
+// 16 KB of LDS per workgroup -- 10 workgroups = 80 items in flight per CU.  kern: the flavour; frc: it has the step's forcings in its tail.
+// A (a GEO flavour; pipelined steps, sz_pipeline.hpp): the geometry of the next step, for N parents, into the parity A names -- in front
+void launch_narrow_first(sz_ctx* c, decltype(narrow_first<>) kern, const State& T, int dt, double ffmo, double fdmo, bool frc, const PipeAlt* A = nullptr, int N = 0) {
+  const int nbn = grid_for((long long)T.capPairs + T.capElem, NARROW_TPB / NARROW_G, narrow_grid(c));
+  const int nbf = frc ? grid_for(T.capM, NARROW_TPB / FRC_PLAIN, 32768) : 0, nbg = A ? grid_for(N, NARROW_TPB, 1 << 20) : 0;
+  Timed t(c, SZ_K_NARROW);
+  hipLaunchKernelGGL(kern, dim3(nbn + nbg + nbf), dim3(NARROW_TPB), 0, c->stream, T, c->P, dt, ffmo, fdmo, c->dbg, nbf, A ? *A : PipeAlt{}, nbg, N);
+  t.end();
+}
+// the largest narrow variant, on the items the smaller ones hand on; maxb caps its grid (256, or 2048 where larger rings exist)
+void narrow_largest(sz_ctx* c, const State& T, int dt, double ffmo, double fdmo, int maxb) {
+  hipLaunchKernelGGL(narrow_last, dim3(grid_for((long long)T.capPairs + T.capElem, 1, maxb)), dim3(NARROW_TPB), 0,
+                     c->stream, T, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
+}
 // parts: 0 everything (the largest variant is always enqueued: it takes the items the others hand on), 1 without the largest variant unless
 // rings that need it exist (sz_step's retry_stop mode), 2 only the larger variants (the rest of a paused step)
-void stage_narrow(sz_ctx* c, int dt, double ffmo, double fdmo, bool housekept = false, int frc = 0, int parts = 0) {
+void stage_narrow(sz_ctx* c, int dt, double ffmo, double fdmo, int frc = 0, int parts = 0) {
   State& S = c->S;
-  (void)housekept;
   long long capItems = (long long)S.capPairs + S.capElem;
   // Rings never change size inside the hot path, so the host knows whether any item can need a
   // larger variant (halo floes of a tiled run arrive unseen: then always check on the device).
   const bool larger = larger_rings(c);
   if (larger && parts != 2) hipLaunchKernelGGL(sz_k_items_clear, dim3(grid_for(capItems, 256)), dim3(256), 0, c->stream, S);
-  if (parts != 2) {
-    Timed t(c, SZ_K_NARROW);
-    constexpr int G = NARROW_G, TPB = 64;
-    // 160 VGPRs (3 wavefronts per SIMD) and 16 KB of LDS per workgroup: 10 workgroups = 80 items in flight per CU
-    auto kern = sz_k_narrow<G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 0>;
-    const int nbn = grid_for(capItems, TPB / G, narrow_grid(c));
-    const int nbf = frc ? grid_for(S.capM, TPB / FRC_PLAIN, 32768) : 0;
-    if (frc == 1) hipLaunchKernelGGL((sz_k_narrow<G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 1>), dim3(nbn + nbf), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, nbf, PipeAlt{}, 0, 0);
-    else if (frc == 2) hipLaunchKernelGGL((sz_k_narrow<G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 2>), dim3(nbn + nbf), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, nbf, PipeAlt{}, 0, 0);
-    else hipLaunchKernelGGL(kern, dim3(nbn), dim3(TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
-    t.end();
-  }
+  if (parts != 2) launch_narrow_first(c, narrow_first_frc[frc], S, dt, ffmo, fdmo, frc != 0);
   {
     // larger working sets: items with larger rings (only if such rings can exist) and items the
     // smaller variant handed on; both kernels return at once when the step has no such item
     Timed t(c, K_NARROW_LARGE);
     if (parts == 1 && !larger) { t.end(); return; }
     if (larger)
-      hipLaunchKernelGGL((sz_k_narrow<16, NARROW_CAP1, 16, 80, 6, 64, NARROW_CAP0, 1>), dim3(grid_for(capItems, 4, 2048)), dim3(64), 0,
-                         c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
+      hipLaunchKernelGGL(narrow_larger, dim3(grid_for(capItems, 4, 2048)), dim3(NARROW_TPB), 0, c->stream, S, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
     narrow_largest(c, S, dt, ffmo, fdmo, larger ? 2048 : 256);
     t.end();
   }
-}
-// the largest narrow variant, on the items the smaller ones hand on; maxb caps its grid (256, or 2048 where larger rings exist)
-void narrow_largest(sz_ctx* c, const State& T, int dt, double ffmo, double fdmo, int maxb) {
-  hipLaunchKernelGGL((sz_k_narrow<64, NARROW_CAP2, NARROW_KC2, NARROW_RC2, 16, 64, NARROW_CAP1, 2>), dim3(grid_for((long long)T.capPairs + T.capElem, 1, maxb)), dim3(64), 0,
-                     c->stream, T, c->P, dt, ffmo, fdmo, c->dbg, 0, PipeAlt{}, 0, 0);
 }
 
 // m_hint: see sz_k_inter_fill (resident steps: the parents + the ghosts the last look at the device showed, and some)
@@ -689,7 +700,7 @@ void collisions_step(sz_ctx* c, int n_init, int dt, bool commit_ghosts, bool sta
     stage_broad(c, commit_ghosts, static_grid, fuse_forcing == 1, ride);
     if (!ride) stage_elems(c, true);
   }
-  stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, static_grid, fuse_forcing == 2 ? (c->precision == 1 ? 2 : 1) : 0, resume ? 2 : lean ? 1 : 0);
+  stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, fuse_forcing == 2 ? (c->precision == 1 ? 2 : 1) : 0, resume ? 2 : lean ? 1 : 0);
   // (rows the step can hold at most, for the reduce's first batch of loads: a tile's halo floes are bounded by the slots of its receive regions,
   //  and any of them may bring up to three ghosts)
   int halo = 0;
@@ -700,7 +711,7 @@ void collisions_step(sz_ctx* c, int n_init, int dt, bool commit_ghosts, bool sta
 void collisions(sz_ctx* c, int n_init, int dt, bool commit_ghosts = false, bool static_grid = false, int fuse_forcing = 0) {
   stage_broad(c, commit_ghosts, static_grid, fuse_forcing == 1);
   stage_elems(c, true);
-  stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, static_grid, fuse_forcing == 2 ? (c->precision == 1 ? 2 : 1) : 0);
+  stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, fuse_forcing == 2 ? (c->precision == 1 ? 2 : 1) : 0);
   stage_reduce(c, 1, n_init, dt);
 }
 
@@ -1104,6 +1115,36 @@ int host_max_neighbours(const sz_ctx* c, const sz_floe_columns* f, int M, int* w
   }
   return best;
 }
+// A field has just been placed in the context's columns -- an upload's copies, a migration's gathered rows: N parents with G ghosts behind them,
+// V ring points, sub-floe offsets set for pts_N floes.  The counter block; the per-floe counts a kernel may read before a collision call has
+// written them (a re-upload carves the chunks of the previous one again: sz_k_stats walks n_out -- they must not hold what some other array
+// left there); ring signs, boxes and trig; then the host's knowledge of the old field goes.  gl_est: how long the ghost-candidate list will
+// be (an upper bound); rmax_max / rmax_hint: largest rmax of this field, and of all ranks' (0: unknown) -- the static grid is made from them.
+int field_placed(sz_ctx* c, int N, int G, int V, int pts_N, int gl_est, double rmax_max, double rmax_hint) {
+  State& S = c->S;
+  int h[C_COUNT + 64 + 72] = { 0 };
+  h[C_M] = N + G; h[C_N] = N; h[C_NV] = V; h[C_NGHOSTS] = G; h[C_NOWN] = N;
+  H2D(S.cnt, h, C_COUNT + 64 + 72, int);
+  HIPCHK(c, hipMemsetAsync(S.over_stamp, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(S.n_out, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(S.n_in, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(S.el_off, 0, ((size_t)S.capM + 2) * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(S.warn, 0, (size_t)WARN_SLOTS * 32 * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(S.lb_flag, 0, ((size_t)S.capM / 128 + 8) * sizeof(unsigned), c->stream)); c->scan_epoch = 0;      // (the look-back scans' epochs start over)
+  hipLaunchKernelGGL(sz_k_osign, dim3(grid_for(S.capM, 256)), dim3(256), 0, c->stream, S, 0);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // a new field: whatever sz_tile_enable / sz_tile_setup established belongs to the old one (exchange buffers sized for its capM, the
+  // drift reference, the gather interval): sz_tile_run refuses to run until both have been called again
+  S.tiled = 0; S.famrec = 0;
+  c->tile_margin = 0.0; c->tile_since_box = -1; c->halo_cap = 0; c->d_send = c->d_recv = c->d_ref = nullptr; c->d_dcap = nullptr;
+  c->hostM = N + G; c->hostN = N; c->have_floes = true; c->tile_dirty = false; c->mixed_pts_ok = false; c->blk_pts_ok = false; S.sxy = nullptr; c->pts_N = pts_N;
+  c->gl_valid = false; c->gl_est = gl_est; c->crec_current = false;
+  c->mixed_geom_ok = false; c->rings_stale = false; S.rec32 = nullptr; S.ring32 = nullptr; S.body_rings = 0;
+  c->rmax_max = rmax_max; c->rmax_hint = rmax_hint;
+  setup_grid(c);
+  c->fuse_lists.assign(N + G, {});
+  return SZ_OK;
+}
 }  // namespace
 
 int sz_upload_floes(sz_ctx* c, int64_t M64, int64_t N64, const sz_floe_columns* f) {
@@ -1183,24 +1224,24 @@ int sz_upload_floes(sz_ctx* c, int64_t M64, int64_t N64, const sz_floe_columns* 
   c->max_sub = 0;
   if (f->sub_off) for (int i = 0; i < N; i++) c->max_sub = std::max(c->max_sub, f->sub_off[i + 1] - f->sub_off[i]);
   DA(gplan, S.capM + 1); DA(gscan4, S.capM + 1); DA(gtot4, 4);
-  DA(lb_agg, S.capM / 128 + 8); DA(lb_inc, S.capM / 128 + 8); DA(lb_flag, S.capM / 128 + 8); c->scan_epoch = 0;      // (tiles of 128 .. SCAN_B elements)
+  DA(lb_agg, S.capM / 128 + 8); DA(lb_inc, S.capM / 128 + 8); DA(lb_flag, S.capM / 128 + 8);      // (tiles of 128 .. SCAN_B elements)
   DA(gflag, S.capM + 1); DA(gvscan, S.capM + 2); DA(gcand, (size_t)2 * S.capM); DA(galloc, 32); DA(gkeys, (size_t)2 * S.capM); DA(fam, S.capM);
   DA(crec, (size_t)8 * S.capM); c->crec_buf = S.crec; S.crec = nullptr;
   {          // the twin set of the pipelined steps' double buffers (sz_pipeline.hpp)
-    sz_ctx::PipeBuf& B = c->pb[1];
+    StepSet& B = c->pb[1];
     if ((rc = dalloc(c, &B.vxy, (size_t)S.capV, c->allocs)) || (rc = dalloc(c, &B.crec, (size_t)8 * S.capM, c->allocs)) ||
         (rc = dalloc(c, &B.gh, (size_t)MAX_GHOSTS * S.capM, c->allocs)) || (rc = dalloc(c, &B.ngh, (size_t)S.capM, c->allocs))) return rc;
     HIPCHK(c, hipMemsetAsync(B.gh, 0xff, (size_t)MAX_GHOSTS * S.capM * sizeof(int), c->stream));
     c->gpar = 0;
   }
   DA(facc, (size_t)FX_WORDS * S.capM); c->facc_buf = S.facc; S.facc = nullptr;
-  c->maybe_tagged = false; c->crec_current = false;
+  c->maybe_tagged = false;          // (what the host's status column says: a migration's floes keep what the context knew)
   if (f->status) for (int i = 0; i < N; i++) if (f->status[i] != SZ_ACTIVE) { c->maybe_tagged = true; break; }
   for (int k = 0; k < 4; k++) if ((rc = dalloc(c, &c->frc_alt[k], (size_t)S.capM, c->allocs))) return rc;
   DA(bounds, 16 + 64 * 4); DA(cell_cnt, S.capCells + 1); DA(cell_ovf, S.capCells + 1); DA(cell_slots, (size_t)S.capCells * CELL_K + 8);
   DA(cell_items, S.capM);
   {
-    sz_ctx::PipeBuf& B = c->pb[1];
+    StepSet& B = c->pb[1];
     if ((rc = dalloc(c, &B.cell_cnt, (size_t)S.capCells + 1, c->allocs)) || (rc = dalloc(c, &B.cell_ovf, (size_t)S.capCells + 1, c->allocs)) ||
         (rc = dalloc(c, &B.cell_slots, (size_t)S.capCells * CELL_K + 8, c->allocs)) || (rc = dalloc(c, &B.cell_items, (size_t)S.capM, c->allocs))) return rc;
   }
@@ -1208,14 +1249,6 @@ int sz_upload_floes(sz_ctx* c, int64_t M64, int64_t N64, const sz_floe_columns* 
   DA(out_off, S.capM + 2);
   DA(el_off, S.capM + 2); DA(el_floe, S.capElem); DA(el_elem, S.capElem);
   DA(inter_off, S.capM + 2);
-  HIPCHK(c, hipMemsetAsync(S.over_stamp, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
-  // (a re-upload carves the chunks of the previous one again: per-floe COUNTS that a kernel may read before a collision call has written them
-  //  -- sz_k_stats walks n_out -- must not hold what some other array left there)
-  HIPCHK(c, hipMemsetAsync(S.n_out, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.n_in, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.el_off, 0, ((size_t)S.capM + 2) * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.warn, 0, (size_t)WARN_SLOTS * 32 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.lb_flag, 0, ((size_t)S.capM / 128 + 8) * sizeof(unsigned), c->stream));      // (the look-back scans' epochs start over with scan_epoch = 0)
   if (!f->sub_off) HIPCHK(c, hipMemsetAsync(S.soff, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
   // neighbour lists, pair items and their rows: in a pool of their own, carved again (larger) when a step outgrows them
   if ((rc = carve_lists(c))) return rc;
@@ -1225,37 +1258,28 @@ int sz_upload_floes(sz_ctx* c, int64_t M64, int64_t N64, const sz_floe_columns* 
   // sz_upload_interactions or a collision call provides them again
   if ((rc = carve_interactions(c))) return rc;
   DA(blk, std::max(S.capCells, std::max(S.capM, 1024)) / SCAN_B + 1024);
-  { sz_ctx::PipeBuf& B = c->pb[0]; B.vxy = S.vxy; B.crec = c->crec_buf; B.cell_cnt = S.cell_cnt; B.cell_slots = S.cell_slots; B.cell_ovf = S.cell_ovf; B.cell_items = S.cell_items; B.gh = S.gh; B.ngh = S.ngh; }
+  own_set_carved(c);          // (set 0 -- gpar above -- is what this upload carved)
   DA(tagA, S.capM + 1);
   if (!tag0.empty()) { H2D(S.tagA, tag0.data(), M, int); HIPCHK(c, hipStreamSynchronize(c->stream)); }
   DA(stamps, 512 + 8 * 8000);
   trim_pool(c->allocs);
-  int h[C_COUNT + 64 + 72] = { 0 };
-  h[C_M] = M; h[C_N] = N; h[C_NV] = V; h[C_NGHOSTS] = M - N; h[C_NOWN] = N;
-  S.tiled = 0; S.famrec = 0;
-  // a new field: whatever sz_tile_enable / sz_tile_setup established belongs to the old one (exchange buffers sized for its capM, the
-  // drift reference, the gather interval): sz_tile_run refuses to run until both have been called again
-  c->tile_margin = 0.0; c->tile_since_box = -1; c->halo_cap = 0; c->d_send = c->d_recv = c->d_ref = nullptr; c->d_dcap = nullptr;
-  free_pool(c->comm_allocs);
-  H2D(S.cnt, h, C_COUNT + 64 + 72, int);
-  hipLaunchKernelGGL(sz_k_osign, dim3(grid_for(S.capM, 256)), dim3(256), 0, c->stream, S, 0);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->hostM = M; c->hostN = N; c->have_floes = true; c->tile_dirty = false; c->mixed_pts_ok = false; c->blk_pts_ok = false; S.sxy = nullptr; c->pts_N = f->sub_off ? N : 0; c->upload_M = M; c->upload_V = V;
-  c->gl_valid = false; c->gl_est = 0;
-  c->mixed_geom_ok = false; c->rings_stale = false; S.rec32 = nullptr; S.ring32 = nullptr; S.body_rings = 0;
-  if (f->rmax) {          // parents near a periodic wall: how long the ghost-candidate list will be (a superset of it)
+  free_pool(c->comm_allocs);          // (sized for the old field's capM; a migration keeps its capacities and these chunks with them)
+  int gl_est = N;          // parents near a periodic wall: how long the ghost-candidate list will be (a superset of it)
+  double rmax_max = 0.0;
+  if (f->rmax) {
     const double x0 = c->h_vals[3], xf = c->h_vals[2], y0 = c->h_vals[1], yf = c->h_vals[0];
     const bool pew = c->h_kinds[SZ_EAST] == SZ_PERIODIC && c->h_kinds[SZ_WEST] == SZ_PERIODIC;
     const bool pns = c->h_kinds[SZ_NORTH] == SZ_PERIODIC && c->h_kinds[SZ_SOUTH] == SZ_PERIODIC;
+    gl_est = 0;
     for (int i = 0; i < N; i++) {
       const double r = f->rmax[i];
-      if ((pew && (f->cx[i] - r < x0 || f->cx[i] + r > xf)) || (pns && (f->cy[i] - r < y0 || f->cy[i] + r > yf))) c->gl_est++;
+      if ((pew && (f->cx[i] - r < x0 || f->cx[i] + r > xf)) || (pns && (f->cy[i] - r < y0 || f->cy[i] + r > yf))) gl_est++;
     }
-  } else c->gl_est = N;
-  c->rmax_max = 0.0; c->rmax_hint = 0.0;
-  if (f->rmax) for (int i = 0; i < M; i++) c->rmax_max = std::max(c->rmax_max, f->rmax[i]);
-  setup_grid(c);
-  c->fuse_lists.assign(M, {});
+    for (int i = 0; i < M; i++) rmax_max = std::max(rmax_max, f->rmax[i]);
+  }
+  // (an upload may bring ghosts, and floes without sub-floe points; its largest rmax is the host's, and no other rank's is known: no hint)
+  if ((rc = field_placed(c, N, M - N, V, f->sub_off ? N : 0, gl_est, rmax_max, 0.0))) return rc;
+  c->upload_M = M; c->upload_V = V;
   return SZ_OK;
 }
 
@@ -1772,9 +1796,7 @@ struct Clears {
 // the State of step parity q: everything that is double-buffered points at set q; rows of the step's makers at region q
 State pipe_state(sz_ctx* c, int q) {
   State S = c->S;
-  const sz_ctx::PipeBuf& B = c->pb[q];
-  S.vxy = B.vxy; S.crec = B.crec; S.cell_cnt = B.cell_cnt; S.cell_slots = B.cell_slots; S.cell_ovf = B.cell_ovf; S.cell_items = B.cell_items;
-  S.work = B.work; S.wq = B.wq; S.gh = B.gh; S.ngh = B.ngh;
+  step_set_copy(S, c->pb[q]);
   // rows of a step's makers: set 0 straight behind the parents (as everywhere else), set 1 from a multiple of 16 half way through the spare rows
   const int nr1 = (c->hostN + (S.capM - c->hostN) / 2 + 15) & ~15;
   S.goff = q ? nr1 - c->hostN : 0; S.gcap = q ? S.capM - nr1 : nr1 - c->hostN; S.gslot = q;
@@ -1783,17 +1805,15 @@ State pipe_state(sz_ctx* c, int q) {
 PipeAlt pipe_alt(sz_ctx* c, int q, int make_ghosts) {
   const State T = pipe_state(c, q);
   PipeAlt A;
-  A.crec = T.crec; A.vxy = T.vxy; A.cell_cnt = T.cell_cnt; A.cell_slots = T.cell_slots; A.cell_ovf = T.cell_ovf; A.cell_items = T.cell_items;
-  A.work = T.work; A.wq = T.wq; A.gh = T.gh; A.ngh = T.ngh; A.goff = T.goff; A.gslot = T.gslot; A.make_ghosts = make_ghosts;
+  step_set_copy(A, T); A.goff = T.goff; A.gslot = T.gslot; A.make_ghosts = make_ghosts;
   return A;
 }
-// make set q the context's own (c->S, crec_buf): where the state lies after a pipelined batch
+// make set q the context's own (c->S, crec_buf): where the state lies after a pipelined batch.  State::crec of c->S is a batch mode -- null, or
+// the records the batch started on -- and stays what it is: the set's records become crec_buf
 void pipe_adopt(sz_ctx* c, int q) {
-  const State T = pipe_state(c, q);
-  State& S = c->S;
-  S.vxy = T.vxy; S.cell_cnt = T.cell_cnt; S.cell_slots = T.cell_slots; S.cell_ovf = T.cell_ovf; S.cell_items = T.cell_items;
-  S.work = T.work; S.wq = T.wq; S.gh = T.gh; S.ngh = T.ngh;
-  c->crec_buf = T.crec; c->gpar = q;
+  double2* const mode = c->S.crec;
+  step_set_copy(c->S, c->pb[q]);
+  c->crec_buf = c->S.crec; c->S.crec = mode; c->gpar = q;
 }
 bool pipeline_eligible(const sz_ctx* c, int nsteps, bool coll, bool sg, bool gi, bool periodic, bool cr, bool rfree, int flags) {
   return rfree && !c->no_pipeline && c->frac_kind == SZ_FRAC_OFF && coll && sg && (gi || !periodic) && cr && nsteps >= c->pipe_min_steps && c->hostN <= c->pipe_max_floes && c->precision == 0 && !c->two_way &&
@@ -1831,7 +1851,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     S0.step = 0; S0.goff = 0; S0.gcap = 0;
     if (!first_start) c->grid_live = false;             // (a restart: the cells hold ghosts of a step that is started afresh)
     use_static_grid(c);                                 // cells[q] <- the parents (unless they are: the last batch's update binned them)
-    const sz_ctx::PipeBuf& O = c->pb[1 - q];
+    const StepSet& O = c->pb[1 - q];
     clr.add(O.cell_cnt, ((size_t)S0.capCells + 1) * sizeof(int));
     clr.add(O.cell_ovf, ((size_t)S0.capCells + 1) * sizeof(int));
     clr.add(c->pb[0].wq, NSEG * 32 * sizeof(int)); clr.add(c->pb[1].wq, NSEG * 32 * sizeof(int));
@@ -1845,29 +1865,18 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     first_start = false;
     State T = pipe_state(c, q); T.step = s + 1; T.callid = callid0 + s + 1; T.retry_stop = lean ? 1 : 0;
     if (gi) hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(S0.capM, 256)), dim3(256), 0, c->stream, T, q, N);
-    const dim3 gr(grid_for(S0.capM, NB_TPB / NB_G, 8192)), bl(NB_TPB);
-    if (elems) {          // (between walls: the element items of the step in the tail of its search, as the three-launch steps do)
-      const int nbe0 = grid_for(S0.capM, NB_TPB, 1 << 20);
-      hipLaunchKernelGGL((sz_k_neighbors_elem<false, true>), dim3(gr.x + nbe0), bl, 0, c->stream, T, next_epoch(c), (int)gr.x);
-    } else if (fam) hipLaunchKernelGGL((sz_k_neighbors<true, MAXNB, true>), gr, bl, 0, c->stream, T);
-    else hipLaunchKernelGGL((sz_k_neighbors<false, MAXNB, true>), gr, bl, 0, c->stream, T);
+    launch_search(c, T, elems);          // (between walls: the element items of the step in the tail of its search, as the three-launch steps do)
   };
-  constexpr int TPB = 64;
-  const int nbn = grid_for((long long)S0.capPairs + S0.capElem, TPB / NARROW_G, narrow_grid(c)), nbg = grid_for(N, TPB, 1 << 20);
   auto launch_L1 = [&](int s, bool make_ghosts) {
     State T = pipe_state(c, par(s)); T.step = s + 1; T.callid = callid0 + s + 1; T.retry_stop = lean ? 1 : 0;
     const PipeAlt A = pipe_alt(c, par(s + 1), make_ghosts ? 1 : 0);
     const bool coupling = coupling_at(flags, coupling_dt, tstep0 + s);
     const bool overlap = coupling && (c->overlap_forcing >= 0 ? c->overlap_forcing != 0 : N > 65536);
     if (overlap) stage_forcing_fork(c, &T);
-    const int nbf = coupling && !overlap ? grid_for(S0.capM, TPB / FRC_PLAIN, 32768) : 0;
     if (coupling) c->forcing_where = overlap ? 0 : 2;
-    Timed tm(c, SZ_K_NARROW);          // (event-timed classes of a pipelined step: "narrow" = L1, "integrate" = L2)
-    if (nbf) hipLaunchKernelGGL((sz_k_narrow<NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 1, 1>), dim3(nbn + nbg + nbf), dim3(TPB), 0, c->stream,
-                                T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, nbf, A, nbg, N);
-    else hipLaunchKernelGGL((sz_k_narrow<NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, 4, TPB, 0, 0, 3, 0, 1>), dim3(nbn + nbg), dim3(TPB), 0, c->stream,
-                            T, c->P, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, c->dbg, 0, A, nbg, N);
-    tm.end();
+    // (event-timed classes of a pipelined step: "narrow" = L1, "integrate" = L2)
+    const bool frc = coupling && !overlap;          // (pipelined batches are fp64: pipeline_eligible)
+    launch_narrow_first(c, frc ? narrow_first<1, 1> : narrow_first<0, 1>, T, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, frc, &A, N);
     if (!lean) narrow_largest(c, T, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, 256);          // (it takes what the small one hands on)
     return overlap;
   };
@@ -1875,7 +1884,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     if (joined) stage_forcing_join(c);
     State T = pipe_state(c, par(s + 1)); T.step = s + 2; T.callid = callid0 + s + 2; T.retry_stop = lean ? 1 : 0;
     const PipeAlt A = pipe_alt(c, par(s), 0);
-    const int nbv = grid_for(N, NB_TPB, 1 << 20), nbs = with_search ? grid_for(S0.capM, NB_TPB / NB_G, 8192) : 0;
+    const int nbv = grid_for(N, NB_TPB, 1 << 20), nbs = with_search ? search_grid(T) : 0;
     const int nbe = with_search && elems ? grid_for(N, NB_TPB, 1 << 20) : 0;
     const unsigned ep = nbe ? next_epoch(c) : 0u;
     const int am = 1 | 4 | (host_last ? 2 : 0);
@@ -2514,7 +2523,11 @@ int sz_profile_enable(sz_ctx* c, int32_t on) {
 int sz_narrow_kernel_name(sz_ctx* c, char* buf, int32_t n) {
   if (!c || !buf || n < 8) return SZ_E_ARG;
   const int frc = c->forcing_where == 2 ? (c->precision == 1 ? 2 : 1) : 0;
-  snprintf(buf, (size_t)n, "sz_k_narrow<%d,%d,%d,%d,4,64,0,0,3,%d,%d>", NARROW_G, NARROW_CAP0, NARROW_KC0, NARROW_RC0, frc, c->last_pipelined ? 1 : 0);
+  const int args[] = { NARROW_FIRST_ARGS, frc, c->last_pipelined ? 1 : 0 };          // narrow_first<FRC, GEO>, argument by argument
+  std::string name = "sz_k_narrow<";
+  for (int a : args) name += std::to_string(a) + ",";
+  name.back() = '>';
+  snprintf(buf, (size_t)n, "%s", name.c_str());
   return SZ_OK;
 }
 int sz_forcing_launch(sz_ctx* c, int32_t* where) {
@@ -3203,14 +3216,25 @@ int sz_tile_setup(sz_ctx* c, double Lx, double Ly, int32_t per_x, int32_t per_y,
 // the tile; the in-reference analogue is the parent / ghost swap of collisions.jl:942-950.  floe.interactions of the last collision call do
 // not travel (the next step's collision call rebuilds them before anything reads them).
 namespace {
-// variable-size all-to-all of doubles between the ranks: sendv[d] to rank d, recvv[s] (sized here) from rank s
-int comm_alltoallv(sz_ctx* c, const std::vector<std::vector<double>>& sendv, std::vector<std::vector<double>>& recvv) {
-  const int n = c->comm_n, me = c->comm_rank;
-  recvv.assign(n, {});
-  if (n == 1) return SZ_OK;
-  // sizes first: every rank's row of the size matrix
-  std::vector<int> mine(n), all((size_t)n * n);
-  for (int d = 0; d < n; d++) mine[d] = (int)sendv[d].size();
+// One trade over the host's transport: per peer what goes out and what comes in (pointer and bytes each; a site names a peer with neither, or
+// leaves it out, as the transport's pairing of the calls on both sides needs).  The five parallel arrays sz_host_transport::sendrecv takes.
+struct HostTrade {
+  std::vector<int32_t> peer; std::vector<const void*> sp; std::vector<void*> rp; std::vector<int64_t> sb, rb;
+  void add(int d, const void* s, size_t s_bytes, void* r, size_t r_bytes) {
+    peer.push_back(d);
+    sp.push_back(s); sb.push_back((int64_t)s_bytes);
+    rp.push_back(r); rb.push_back((int64_t)r_bytes);
+  }
+  int run(sz_ctx* c) {
+    HOSTCHK(c, c->host_tr.sendrecv(c->host_tr.user, (int32_t)peer.size(), peer.data(), sp.data(), sb.data(), rp.data(), rb.data()), "sendrecv");
+    return SZ_OK;
+  }
+};
+// sizes of a variable-size all-to-all: mine[d] doubles go to rank d; all[s * n + d] = what rank s sends to rank d
+int comm_sizes(sz_ctx* c, const std::vector<int>& mine, std::vector<int>& all) {
+  const int n = c->comm_n;
+  all.assign((size_t)n * n, 0);
+  if (n == 1) { all[0] = mine[0]; return SZ_OK; }
   int* d_row = (int*)(c->d_gather + 8 + 8 * 64);          // (the count-matrix area of the box gather: free between gathers)
   HIPCHK(c, hipMemcpyAsync(d_row, mine.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
   int* d_all = d_row + 64;
@@ -3218,16 +3242,23 @@ int comm_alltoallv(sz_ctx* c, const std::vector<std::vector<double>>& sendv, std
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(all.data(), d_all, all.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SZ_OK;
+}
+// variable-size all-to-all of doubles between the ranks: sendv[d] to rank d, recvv[s] (sized here) from rank s
+int comm_alltoallv(sz_ctx* c, const std::vector<std::vector<double>>& sendv, std::vector<std::vector<double>>& recvv) {
+  const int n = c->comm_n, me = c->comm_rank;
+  recvv.assign(n, {});
+  if (n == 1) return SZ_OK;
+  // sizes first: every rank's row of the size matrix
+  std::vector<int> mine(n), all;
+  for (int d = 0; d < n; d++) mine[d] = (int)sendv[d].size();
+  int rc = comm_sizes(c, mine, all);
+  if (rc) return rc;
   for (int s2 = 0; s2 < n; s2++) if (s2 != me) recvv[s2].assign((size_t)all[(size_t)s2 * n + me], 0.0);
   if (c->host_transport) {
-    std::vector<int32_t> peer; std::vector<const void*> sp; std::vector<void*> rp; std::vector<int64_t> sb, rb;
-    for (int d = 0; d < n; d++) {
-      if (d == me) continue;
-      peer.push_back(d); sp.push_back(sendv[d].data()); sb.push_back((int64_t)(sendv[d].size() * sizeof(double)));
-      rp.push_back(recvv[d].data()); rb.push_back((int64_t)(recvv[d].size() * sizeof(double)));
-    }
-    HOSTCHK(c, c->host_tr.sendrecv(c->host_tr.user, (int32_t)peer.size(), peer.data(), sp.data(), sb.data(), rp.data(), rb.data()), "sendrecv");
-    return SZ_OK;
+    HostTrade tr;
+    for (int d = 0; d < n; d++) if (d != me) tr.add(d, sendv[d].data(), sendv[d].size() * sizeof(double), recvv[d].data(), recvv[d].size() * sizeof(double));
+    return tr.run(c);
   }
   // RCCL: device staging buffers, one grouped send / receive
   size_t ts = 0, tr = 0;
@@ -3249,21 +3280,23 @@ int comm_alltoallv(sz_ctx* c, const std::vector<std::vector<double>>& sendv, std
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SZ_OK;
 }
-// sizes of a variable-size all-to-all: mine[d] doubles go to rank d; all[s * n + d] = what rank s sends to rank d
-int comm_sizes(sz_ctx* c, const std::vector<int>& mine, std::vector<int>& all) {
-  const int n = c->comm_n;
-  all.assign((size_t)n * n, 0);
-  if (n == 1) { all[0] = mine[0]; return SZ_OK; }
-  int* d_row = (int*)(c->d_gather + 8 + 8 * 64);          // (the count-matrix area of the box gather: free between gathers)
-  HIPCHK(c, hipMemcpyAsync(d_row, mine.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  int* d_all = d_row + 64;
-  int rc = comm_allgather(c, d_row, d_all, (size_t)n, NCCL_INT32, sizeof(int));
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(all.data(), d_all, all.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SZ_OK;
-}
-
+// The tiling of a context, taken before a migration replaces its field (the new field forgets it, as after any upload) and established again
+// behind it with the same parameters: collective.  px > 0: the tiles are the px x py boxes of the domain, and the owned box of the first gather
+// takes its centroids at the image nearest to this rank's box centre (sz_tile_set_center).
+struct Retile {
+  double Lx, Ly, margin, ring_hint, rmax_hint; int per_x, per_y, rebox, precision;
+  explicit Retile(const sz_ctx* c) : Lx(c->tile_Lx), Ly(c->tile_Ly), margin(c->tile_margin), ring_hint((double)c->max_ring_tiled), rmax_hint(c->rmax_hint), per_x(c->tile_per_x),
+                                     per_y(c->tile_per_y), rebox(c->tile_rebox_fixed ? -c->tile_rebox_every : c->tile_rebox_every), precision(c->precision) {}
+  int again(sz_ctx* c, const long long* gidx, int px, int py) const {
+    if (int rc = sz_tile_enable(c, (const int64_t*)gidx, ring_hint, rmax_hint)) return rc;
+    if (int rc = sz_tile_setup(c, Lx, Ly, per_x, per_y, margin, rebox)) return rc;
+    const double x0 = c->h_vals[3], y0 = c->h_vals[1], DLx = c->h_vals[2] - c->h_vals[3], DLy = c->h_vals[0] - c->h_vals[1];
+    const int me = c->comm_rank;
+    if (px > 0) (void)sz_tile_set_center(c, x0 + ((me % px) + 0.5) * DLx / px, y0 + ((me / px) + 0.5) * DLy / py);
+    c->precision = precision;
+    return SZ_OK;
+  }
+};
 // sz_tile_migrate with the movers packed on the device (sz_migrate.hpp): owners, pack, exchange device to device, merge of the directories, the
 // rows gathered into the new order, then what sz_upload_floes does behind its copies (counters, ring signs and boxes, cleared per-floe counts).
 // The capacities the context was carved with stay; *fell_back = 1 (and nothing has changed) when some rank's new tile would crowd them --
@@ -3333,13 +3366,9 @@ int tile_migrate_device(sz_ctx* c, int px, int py, const int32_t* owner_override
     std::vector<double> hs(std::max<size_t>(ts, 1)), hr(std::max<size_t>(tr, 1));
     if (ts) HIPCHK(c, hipMemcpyAsync(hs.data(), d_sendb, ts * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<int32_t> peer; std::vector<const void*> sp; std::vector<void*> rp; std::vector<int64_t> sb, rb;
-    for (int d = 0; d < n; d++) {
-      if (d == me) continue;
-      peer.push_back(d); sp.push_back(hs.data() + base[d]); sb.push_back((int64_t)mine[d] * (int64_t)sizeof(double));
-      rp.push_back(hr.data() + rbase[d]); rb.push_back((int64_t)rsize[d] * (int64_t)sizeof(double));
-    }
-    HOSTCHK(c, c->host_tr.sendrecv(c->host_tr.user, (int32_t)peer.size(), peer.data(), sp.data(), sb.data(), rp.data(), rb.data()), "sendrecv");
+    HostTrade trade;
+    for (int d = 0; d < n; d++) if (d != me) trade.add(d, hs.data() + base[d], (size_t)mine[d] * sizeof(double), hr.data() + rbase[d], (size_t)rsize[d] * sizeof(double));
+    if ((rc = trade.run(c))) return rc;
     if (tr) HIPCHK(c, hipMemcpyAsync(d_recvb, hr.data(), tr * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   } else if (n > 1) {
@@ -3419,37 +3448,16 @@ int tile_migrate_device(sz_ctx* c, int px, int py, const int32_t* owner_override
     HIPCHK(c, hipMemcpyAsync(S.sy, d_tsy, (size_t)NSn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   }
   HIPCHK(c, hipMemcpyAsync(S.soff, d_nsoff, ((size_t)Nn + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-  // ---- as behind the copies of sz_upload_floes: counters, per-floe counts a kernel may read before a collision call writes them, ring signs / boxes / trig
-  int h[C_COUNT + 64 + 72] = { 0 };
-  h[C_M] = Nn; h[C_N] = Nn; h[C_NV] = Vn; h[C_NGHOSTS] = 0; h[C_NOWN] = Nn;
-  HIPCHK(c, hipMemcpyAsync(S.cnt, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(S.over_stamp, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.n_out, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.n_in, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.el_off, 0, ((size_t)S.capM + 2) * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.warn, 0, (size_t)WARN_SLOTS * 32 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.lb_flag, 0, ((size_t)S.capM / 128 + 8) * sizeof(unsigned), c->stream)); c->scan_epoch = 0;
-  HIPCHK(c, hipMemsetAsync(S.inter_cnt, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));          // (no rows until the next collision call)
-  hipLaunchKernelGGL(sz_k_osign, dim3(grid_for(S.capM, 256)), dim3(256), 0, c->stream, S, 0);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // ---- the field is placed: as behind the copies of sz_upload_floes (no ghosts; every floe's sub-floe offsets are set; the estimates and bounds the
+  // context held still bound the floes it kept, those of the floes that arrived come on top).  No interaction rows until the next collision call
+  // -- an upload keeps those of a field of the same size.
+  HIPCHK(c, hipMemsetAsync(S.inter_cnt, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
+  const Retile tiling(c);
+  if ((rc = field_placed(c, Nn, 0, Vn, Nn, std::min(Nn, c->gl_est + R), std::max(c->rmax_max, rmax_in), c->rmax_hint))) return rc;
   free_pool(old_sub);
-  const double Lx0 = c->tile_Lx, Ly0 = c->tile_Ly, margin = c->tile_margin; const int perx = c->tile_per_x, pery = c->tile_per_y;
-  const int rebox = c->tile_rebox_fixed ? -c->tile_rebox_every : c->tile_rebox_every;
-  const double ring_hint = (double)c->max_ring_tiled, rmax_hint = c->rmax_hint;
-  const int prec = c->precision;
-  S.tiled = 0; S.famrec = 0;
-  c->tile_margin = 0.0; c->tile_since_box = -1; c->halo_cap = 0; c->d_send = c->d_recv = c->d_ref = nullptr; c->d_dcap = nullptr;
-  c->hostM = Nn; c->hostN = Nn; c->tile_dirty = false; c->mixed_pts_ok = false; c->blk_pts_ok = false; S.sxy = nullptr; c->pts_N = Nn;
-  c->gl_valid = false; c->gl_est = std::min(Nn, c->gl_est + R);          // (the ghost-candidate estimate is an upper bound)
-  c->mixed_geom_ok = false; c->rings_stale = false; S.rec32 = nullptr; S.ring32 = nullptr; S.body_rings = 0;
-  c->max_ring = std::max(c->max_ring, ring_in); c->max_sub = std::max(c->max_sub, sub_in); c->rmax_max = std::max(c->rmax_max, rmax_in);
-  setup_grid(c);
-  c->fuse_lists.assign(Nn, {});
+  c->max_ring = std::max(c->max_ring, ring_in); c->max_sub = std::max(c->max_sub, sub_in);
   c->inter_lost = false; c->inter_any = true;
-  if ((rc = sz_tile_enable(c, (const int64_t*)ngid.data(), ring_hint, rmax_hint))) return rc;
-  if ((rc = sz_tile_setup(c, Lx0, Ly0, perx, pery, margin, rebox))) return rc;
-  if (!owner_override) (void)sz_tile_set_center(c, x0 + ((me % px) + 0.5) * Lx / px, y0 + ((me / px) + 0.5) * Ly / py);
-  c->precision = prec;
+  if ((rc = tiling.again(c, ngid.data(), owner_override ? 0 : px, py))) return rc;
   trim_pool(pool.v);
   if (n_owned) *n_owned = Nn;
   return SZ_OK;
@@ -3589,10 +3597,8 @@ int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_ov
   }
   if (nvx.empty()) { nvx.push_back(0.0); nvy.push_back(0.0); }
   if (nsx.empty()) { nsx.push_back(0.0); nsy.push_back(0.0); }
-  // ---- rebuild through the upload path, then the tile set-up again (collective, same parameters as before)
-  const double Lx0 = c->tile_Lx, Ly0 = c->tile_Ly, margin = c->tile_margin; const int perx = c->tile_per_x, pery = c->tile_per_y;
-  const int rebox = c->tile_rebox_fixed ? -c->tile_rebox_every : c->tile_rebox_every;
-  const double ring_hint = (double)c->max_ring_tiled, rmax_hint = c->rmax_hint;
+  // ---- rebuild through the upload path, then the tile set-up again
+  const Retile tiling(c);
   sz_floe_columns f; memset(&f, 0, sizeof(f));
   f.cx = ncol[0].data(); f.cy = ncol[1].data(); f.rmax = ncol[2].data(); f.area = ncol[3].data(); f.height = ncol[4].data(); f.mass = ncol[5].data(); f.moment = ncol[6].data();
   f.alpha = ncol[7].data(); f.u = ncol[8].data(); f.v = ncol[9].data(); f.xi = ncol[10].data(); f.p_dxdt = ncol[11].data(); f.p_dydt = ncol[12].data(); f.p_dalphadt = ncol[13].data();
@@ -3600,14 +3606,10 @@ int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_ov
   f.hflx_factor = ncol[20].data(); f.overarea = ncol[21].data(); f.coll_fx = ncol[22].data(); f.coll_fy = ncol[23].data(); f.coll_trq = ncol[24].data();
   f.stress_accum = nten[0].data(); f.stress_instant = nten[1].data(); f.strain = nten[2].data();
   f.id = (int64_t*)nid.data(); f.status = nstatus.data(); f.vert_off = nvoff.data(); f.vx = nvx.data(); f.vy = nvy.data(); f.sub_off = nsoff.data(); f.sx = nsx.data(); f.sy = nsy.data();
-  const int prec = c->precision;
   if ((rc = sz_upload_floes(c, Nn, Nn, &f))) return rc;
   c->inter_lost = false; c->inter_any = true;
   HIPCHK(c, hipMemsetAsync(S.inter_cnt, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));          // (no rows until the next collision call)
-  if ((rc = sz_tile_enable(c, (const int64_t*)ngid.data(), ring_hint, rmax_hint))) return rc;
-  if ((rc = sz_tile_setup(c, Lx0, Ly0, perx, pery, margin, rebox))) return rc;
-  if (!owner_override) (void)sz_tile_set_center(c, x0 + ((me % px) + 0.5) * Lx / px, y0 + ((me / px) + 0.5) * Ly / py);
-  c->precision = prec;
+  if ((rc = tiling.again(c, ngid.data(), owner_override ? 0 : px, py))) return rc;
   if (n_owned) *n_owned = Nn;
   return SZ_OK;
 }
@@ -3642,19 +3644,18 @@ int tile_exchange(sz_ctx* c, bool all_ranks) {
   if (c->host_transport) {
     Timed tx(c, K_EXCHANGE, c->comm_stream);
     c->h_send.resize((size_t)n * stride); c->h_recv.resize((size_t)n * stride);
-    std::vector<int32_t> peer; std::vector<const void*> sp; std::vector<void*> rp; std::vector<int64_t> sb, rb;
+    HostTrade tr;
     for (int d = 0; d < n; d++) {
       if (d == me || (!all_ranks && c->cap_send[d] <= 0 && c->cap_recv[d] <= 0)) continue;
       const size_t ns = (all_ranks || c->cap_send[d] > 0) ? (size_t)(c->cap_send[d] + 1) * HREC : 0;
       const size_t nr = (all_ranks || c->cap_recv[d] > 0) ? (size_t)(c->cap_recv[d] + 1) * HREC : 0;
       if (ns) HIPCHK(c, hipMemcpyAsync(c->h_send.data() + d * stride, c->d_send + d * stride, ns * sizeof(double), hipMemcpyDeviceToHost, c->comm_stream));
-      peer.push_back(d); sp.push_back(c->h_send.data() + d * stride); sb.push_back((int64_t)(ns * sizeof(double)));
-      rp.push_back(c->h_recv.data() + d * stride); rb.push_back((int64_t)(nr * sizeof(double)));
+      tr.add(d, c->h_send.data() + d * stride, ns * sizeof(double), c->h_recv.data() + d * stride, nr * sizeof(double));
     }
     HIPCHK(c, hipStreamSynchronize(c->comm_stream));
-    HOSTCHK(c, c->host_tr.sendrecv(c->host_tr.user, (int32_t)peer.size(), peer.data(), sp.data(), sb.data(), rp.data(), rb.data()), "sendrecv");
-    for (size_t k = 0; k < peer.size(); k++)
-      if (rb[k]) HIPCHK(c, hipMemcpyAsync(c->d_recv + peer[k] * stride, rp[k], (size_t)rb[k], hipMemcpyHostToDevice, c->comm_stream));
+    if (int rc = tr.run(c)) return rc;
+    for (size_t k = 0; k < tr.peer.size(); k++)
+      if (tr.rb[k]) HIPCHK(c, hipMemcpyAsync(c->d_recv + tr.peer[k] * stride, tr.rp[k], (size_t)tr.rb[k], hipMemcpyHostToDevice, c->comm_stream));
     HIPCHK(c, hipStreamSynchronize(c->comm_stream));       // (h_recv is reused by the next step)
     tx.end();
   } else {
@@ -3887,7 +3888,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
     if (dbgsync) {          // (the stages of collisions_step one by one)
       stage_broad(c, false, true, fmode == 1, false); stage_done(s, "neighbour search");
       stage_elems(c, true); stage_done(s, "element items");
-      stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, true, fmode == 2 ? (c->precision == 1 ? 2 : 1) : 0, 0); stage_done(s, "narrow phase");
+      stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, fmode == 2 ? (c->precision == 1 ? 2 : 1) : 0, 0); stage_done(s, "narrow phase");
       stage_reduce(c, 1, -1, dt, 0); stage_done(s, "reduce");
     } else collisions_step(c, -1, dt, false, true, fmode, lean, false);
     const bool pack_next = s + 1 < nsteps;
@@ -3926,7 +3927,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   }
   if (h[C_PAUSED] == sp) {          // this rank's step: the variant, then what the pause held back
     S.step = sp; S.gslot = (sp - 1) & 1; S.callid = callid_of[sp - 1];
-    stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, true, 0, 2);
+    stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, 0, 2);
     stage_reduce(c, 1, -1, dt, 0);
     c->acc_mode = accm(sp >= nsteps);
     stage_integrate(c, dt, false, coupling_sp, true, -1, -1);

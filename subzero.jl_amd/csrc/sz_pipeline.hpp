@@ -22,8 +22,7 @@ namespace sz {
 
 // the State of the other parity
 __device__ __forceinline__ State pipe_other(State S, const PipeAlt& A) {
-  S.crec = A.crec; S.vxy = A.vxy; S.cell_cnt = A.cell_cnt; S.cell_slots = A.cell_slots; S.cell_ovf = A.cell_ovf; S.cell_items = A.cell_items;
-  S.work = A.work; S.wq = A.wq; S.gh = A.gh; S.ngh = A.ngh; S.goff = A.goff; S.gslot = A.gslot;
+  step_set_copy(S, A); S.goff = A.goff; S.gslot = A.gslot;
   return S;
 }
 

@@ -200,15 +200,28 @@ struct State {
                              // steps really did, for the roofline of bench.py (sz_get_stats acc_*, cleared by sz_profile_reset)
 };
 
-// what a launch of a pipelined step (sz_pipeline.hpp) needs of the OTHER step parity -- the State it is given holds one parity's pointers
+// What the pipelined steps (sz_pipeline.hpp) double-buffer by step parity, stated once: collision records, rings, the four cell arrays, the
+// work list and its queue heads, the ghost links and their counts.  State has a member of each of these names (declared above, among its
+// own: the kernels read S.crec, S.vxy, ..); StepSet and PipeAlt are declared from the list, and step_set_copy moves a set between any
+// two of them.  A new member: one entry here, its member in State, its allocation, its use in a kernel.
+#define SZ_STEP_SET(X) \
+  X(double2*, crec) X(double2*, vxy) X(int*, cell_cnt) X(int*, cell_slots) X(int*, cell_ovf) X(int*, cell_items) \
+  X(int4*, work) X(int*, wq) X(int*, gh) X(int*, ngh)
+#define SZ_STEP_SET_MEMBER(T, name) T name;
+struct StepSet { SZ_STEP_SET(SZ_STEP_SET_MEMBER) };          // one parity's buffers (the host keeps two: sz_ctx::pb)
+// what a launch of a pipelined step needs of the OTHER step parity -- the State it is given holds one parity's pointers
 struct PipeAlt {
-  double2 *crec, *vxy;
-  int *cell_cnt, *cell_slots, *cell_ovf, *cell_items;
-  int4* work; int* wq;
-  int *gh, *ngh;
+  SZ_STEP_SET(SZ_STEP_SET_MEMBER)
   int goff, gslot;
   int make_ghosts;        // GEO: 0 in a step the host knows to be the batch's last (no ghosts, no swap: there is no step to make them for)
 };
+#undef SZ_STEP_SET_MEMBER
+template <typename To, typename From>
+__host__ __device__ __forceinline__ void step_set_copy(To& to, const From& from) {
+#define SZ_STEP_SET_COPY(T, name) to.name = from.name;
+  SZ_STEP_SET(SZ_STEP_SET_COPY)
+#undef SZ_STEP_SET_COPY
+}
 
 using szg_flags_note = int;   // IT_FUSE / IT_REMOVE are defined in sz_geom.hpp
 
