@@ -261,11 +261,25 @@ void tile_cleanup(sz_ctx* c) {
   hipLaunchKernelGGL(sz_k_remove_ghosts, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, 1);
   c->tile_dirty = false;
 }
+// the counter block as the stream leaves it: copied behind everything enqueued so far, and waited for
+int fetch_counters(sz_ctx* c, int* h) {
+  HIPCHK(c, hipMemcpyAsync(h, c->S.cnt, C_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SZ_OK;
+}
+// The words through which the kernels of a resident batch end or pause it (sz_state.hpp), cleared between (sub-)batches: one memset per word
+// of the mask, in the order of the list below
+constexpr unsigned W_STOP = 1u << C_STOP, W_RETRYSTOP = 1u << C_RETRYSTOP, W_PAUSED = 1u << C_PAUSED, W_FRCSTOP = 1u << C_FRCSTOP;
+hipError_t clear_stop_words(sz_ctx* c, unsigned mask) {
+  hipError_t e = hipSuccess;
+  for (int w : { C_STOP, C_RETRYSTOP, C_PAUSED, C_FRCSTOP }) if (e == hipSuccess && (mask >> w & 1u)) e = hipMemsetAsync(c->S.cnt + w, 0, sizeof(int), c->stream);
+  return e;
+}
+// collision records of the first n floes of T from their columns (State::crec must point at the records)
+void seed_records(sz_ctx* c, const State& T, int n) { hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, T, n); }
 int sync_and_check(sz_ctx* c, int* cnt_out = nullptr) {
   tile_cleanup(c);
   int h[C_COUNT];
-  HIPCHK(c, hipMemcpyAsync(h, c->S.cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = fetch_counters(c, h)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream2));
   if (c->pmask) resolve_events(c);
   c->hostM = h[C_M]; c->hostN = h[C_N];
@@ -277,8 +291,7 @@ int sync_and_check(sz_ctx* c, int* cnt_out = nullptr) {
              "device capacity/consistency error bits 0x%x (ring=1 crossings=2 regions=4 rows=8 trace=16 neighbours=32 "
              "pairs=64 elems=128 inter=256 floes=512 verts=1024 cells=2048 ghosts/parent=4096 scan=8192 halo-drift=16384 fixed-point-range=32768)", h[C_ERR]);
     c->err = buf;
-    int z = 0;
-    (void)hipMemcpy(c->S.cnt + C_ERR, &z, sizeof(int), hipMemcpyHostToDevice);
+    int z = 0; (void)hipMemcpy(c->S.cnt + C_ERR, &z, sizeof(int), hipMemcpyHostToDevice);
     return SZ_E_CAPACITY;
   }
   return SZ_OK;
@@ -669,7 +682,7 @@ int force_scale_exp(const sz_ctx* c) { const double b = (1.0 + std::max(c->P.mu,
 // the fixed-point totals and the forcings' stop hint from zero: a batch's start, and a step that is run again (its narrow phase adds its rows again)
 int clear_totals(sz_ctx* c) {
   HIPCHK(c, hipMemsetAsync(c->facc_buf, 0, (size_t)FX_WORDS * c->S.capM * sizeof(long long), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->S.cnt + C_FRCSTOP, 0, sizeof(int), c->stream));
+  HIPCHK(c, clear_stop_words(c, W_FRCSTOP));
   return SZ_OK;
 }
 // behind: the launch that assembles the rows of a reduce-free batch's last step (parents' centroids of that step from `mot`)
@@ -1292,8 +1305,7 @@ int sz_get_stats(sz_ctx* c, sz_stats* out) {
   hipLaunchKernelGGL(sz_k_stats, dim3(grid_for((long long)S.capPairs + S.capElem, 256, 1024)), dim3(256), 0, c->stream, S, c->d_stats);
   int h[C_COUNT]; long long st[20];
   HIPCHK(c, hipMemcpyAsync(st, c->d_stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h, S.cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = fetch_counters(c, h)) return rc;
   int soffN = 0;
   HIPCHK(c, hipMemcpy(&soffN, S.soff + h[C_N], sizeof(int), hipMemcpyDeviceToHost));
   out->M = h[C_M]; out->N = h[C_N]; out->n_ring_points = h[C_NV]; out->n_sub_points = soffN;
@@ -1436,8 +1448,7 @@ int sz_download_interactions(sz_ctx* c, int32_t* off, double* rows) {
   // rows are kept at a fixed stride on the device: compact to CSR here
   scan(c, S.inter_cnt, S.inter_off, S.capM, C_M, 0, C_NINTER);
   int h[C_COUNT];
-  HIPCHK(c, hipMemcpyAsync(h, S.cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = fetch_counters(c, h)) return rc;
   HIPCHK(c, hipMemcpy(off, S.inter_off, (size_t)(h[C_M] + 1) * sizeof(int), hipMemcpyDeviceToHost));
   int total = h[C_NINTER];
   if (rows && total > 0) {
@@ -1815,30 +1826,89 @@ void pipe_adopt(sz_ctx* c, int q) {
   step_set_copy(c->S, c->pb[q]);
   c->crec_buf = c->S.crec; c->S.crec = mode; c->gpar = q;
 }
-bool pipeline_eligible(const sz_ctx* c, int nsteps, bool coll, bool sg, bool gi, bool periodic, bool cr, bool rfree, int flags) {
-  return rfree && !c->no_pipeline && c->frac_kind == SZ_FRAC_OFF && coll && sg && (gi || !periodic) && cr && nsteps >= c->pipe_min_steps && c->hostN <= c->pipe_max_floes && c->precision == 0 && !c->two_way &&
-         (!c->S.any_domain_work || (!periodic && !c->any_moving)) && c->S.maxnb <= MAXNB && !larger_rings(c) && c->pb[1].vxy && c->pb[1].work &&
+// ---------------------------------------------------------------- what a resident batch decides (BatchPlan)
+// Everything a batch driver branches on, decided once before the batch touches anything: a function of the context as the last call left it
+// and of the arguments -- no rule reads what batch_enter sets up (the static grid, the ghost list, the ensure_* buffers, the world rings).
+struct BatchPlan {
+  // a periodic pair of walls; SZ_COLLISIONS_ON; the batch ends at the first tag (no SZ_NO_STOP)
+  bool periodic, coll, user_stop;
+  // static grid; ghosts from the candidate list; inline ghosts (made by the integrator); mixed precision; its steps run on body-frame rings
+  bool sg, gl, gi, mixed, body;
+  // collision records kept current; fixed-point totals; reduce-free steps (rows once, behind the batch); the pipelined two-launch steps; a
+  // fracture criterion is evaluated in the batch
+  bool cr, facc_on, rfree, pipe, frac;
+  // the steps start without the largest narrow variant (a driver puts it in when an item needs it); the first step is enqueued on its own, as
+  // a last step
+  bool lean, first_alone;
+  int reduce_mode;                     // sz_ctx::reduce_mode of the batch
+  void set_rfree(bool r) { rfree = r; reduce_mode = !facc_on ? 0 : r ? 2 : 1; }
+};
+// what the integrator is told (sz_ctx::acc_mode): totals on, reduce-free steps, and in those: the host knows this is the batch's last step
+static int integrator_acc_mode(bool facc_on, bool rfree, bool last) { return !facc_on ? 0 : 1 | (rfree ? 4 | (last ? 2 : 0) : 0); }
+// the largest narrow variant only takes items the small one hands on (none in most fields): it is left out of the steps until one
+// shows up -- the batch then pauses inside that step (stopped_late()) and its driver finishes it
+static bool lean_wanted(const sz_ctx* c) { return !c->retry_seen && !c->no_lean_narrow && !larger_rings(c); }
+// collision records (State::crec): in batches whose kernels keep them current -- the one-launch integrator, and for periodic walls the
+// inline ghost maker.
+// Fixed-point totals (State::facc; sz_geom.hpp): the narrow phase adds every row to both floes' totals, the integrator reads them -- no reduce
+// launch inside the steps.
+static void plan_records_totals(BatchPlan& p, const sz_ctx* c, int nsteps) {
+  p.cr = p.coll && p.sg && c->crec_buf && c->max_ring <= MV_RING && (p.gi || !p.periodic) && nsteps > 0;
+  p.facc_on = p.coll && c->facc_buf != nullptr;
+}
+bool pipeline_eligible(const sz_ctx* c, const BatchPlan& p, int nsteps, int flags) {
+  return p.rfree && !c->no_pipeline && c->frac_kind == SZ_FRAC_OFF && p.coll && p.sg && (p.gi || !p.periodic) && p.cr && nsteps >= c->pipe_min_steps && c->hostN <= c->pipe_max_floes && c->precision == 0 && !c->two_way &&
+         (!c->S.any_domain_work || (!p.periodic && !c->any_moving)) && c->S.maxnb <= MAXNB && !larger_rings(c) && c->pb[1].vxy && c->pb[1].work &&
          (c->S.capM - c->hostN) / 2 > 64 && (flags & SZ_COLLISIONS_ON);
+}
+static BatchPlan plan_batch(const sz_ctx* c, int nsteps, int flags) {
+  BatchPlan p{};
+  p.periodic = c->S.any_periodic_ew || c->S.any_periodic_ns;
+  p.coll = (flags & SZ_COLLISIONS_ON) != 0;
+  // the batch ends after the first step that leaves a parent tagged remove / fuse (simplify_floes!, simulation.jl:205-214,
+  // is the host's): the launches of the later steps are enqueued all the same and return at once (stopped())
+  p.user_stop = !(flags & SZ_NO_STOP);
+  p.sg = p.coll && c->grid_ok;
+  p.gl = ghost_list_wanted(c, p.sg);
+  // inline ghosts: no ghost launch in the steps at all (the integrator makes the next step's ghosts; needs the one-launch integrator)
+  p.gi = p.gl && !c->S.tiled && c->max_ring <= MV_RING;
+  p.mixed = c->precision == 1 && !c->two_way;
+  // mixed precision: the steps run on body-frame rings (the integrator moves poses, not rings) when nothing else in the batch
+  // needs world rings -- single context, the list path for the ghosts, rings small enough for the fused integrator
+  p.body = p.mixed && p.coll && p.sg && (p.gl || !p.periodic) && !c->S.tiled && c->max_ring <= MV_RING;
+  plan_records_totals(p, c, nsteps);
+  // floe.interactions of the step that ended the batch is assembled once, behind the batch (stage_reduce(.., behind)): that needs the ghosts
+  // of that step still in their rows, i.e. the one-launch integrator with inline ghosts (or no periodic wall), which knows when it runs a
+  // batch's last step (sz_k_integrate: last_step).  The other paths keep the launch inside the step, rows only.
+  p.set_rfree(p.facc_on && p.sg && (p.gi || !p.periodic) && c->max_ring <= MV_RING && !c->any_moving);
+  // pipelined batches (sz_pipeline.hpp: two launches per step) run their own prologue -- records, first ghosts, first neighbour search
+  p.pipe = pipeline_eligible(c, p, nsteps, flags);
+  // (a tile's three-launch steps keep the variant in; the pipelined steps do not ask whether the context is tiled -- kept as found)
+  p.lean = p.coll && lean_wanted(c) && (p.pipe || !c->S.tiled);
+  // a parent that is already tagged ends the batch after its first step, and the integrator only finds out while it runs (the tags of a
+  // step itself are raised by its narrow phase / forcings, a launch earlier): that first step is then enqueued on its own, as a last step
+  p.first_alone = p.rfree && c->maybe_tagged && p.user_stop && nsteps > 1;
+  // fracture criterion (sz_set_fracture): evaluated after every fracture step of a batch that stops -- one that runs through has no use for it
+  p.frac = c->frac_kind != SZ_FRAC_OFF && p.user_stop && !p.pipe;
+  return p;
 }
 
 // A batch of pipelined steps: L1(s) = narrow(s) | GEO(s) | forcings(s), L2(s) = VEL(s) | search(s + 1).  Same contract as the loop of sz_step
 // it replaces: h = the counter block after the batch, *done = the steps that ran; the context's state is complete when it returns (rows of
 // the last step assembled, strain evaluated, ghosts detached).
+// *slot_out: the allocator slot of the last step's inline ghosts (the parity of its set).
 // *rest_out: the lists grew past what the pipelined launches are compiled for (MAXNB); the batch handed back the state at step *done_out and the
 // caller runs the rest on the three-launch steps.
-// It runs inside sz_step's BatchModes scope (the modes sz_step has set are the batch's) and opens none of its own.
-int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling_dt, int flags, bool periodic, bool gi, int* h, int* done_out, bool* rest_out) {
+// It runs inside sz_step's BatchModes scope (the modes batch_enter has set from the plan are the batch's) and opens none of its own.
+int step_batch_pipelined(sz_ctx* c, const BatchPlan& plan, int nsteps, int tstep0, int dt, int coupling_dt, int flags, int* h, int* done_out, int* slot_out, bool* rest_out) {
   State& S0 = c->S;
   const int N = c->hostN;
-  const bool user_stop = !(flags & SZ_NO_STOP);
-  const bool fam = N <= 40000 && periodic;
+  const bool fam = N <= 40000 && plan.periodic;
   const bool elems = S0.any_domain_work != 0;          // (eligible only without a periodic pair: no ghosts, the floe count is the host's)
   const int q0 = c->gpar;
   auto par = [&](int s) { return (q0 + s) & 1; };
-  S0.stop_on_tags = user_stop ? 1 : 0; S0.restart_on_tags = user_stop ? 0 : 1;
-  S0.ginline = gi ? 1 : 0; S0.famrec = gi ? 1 : 0;
-  S0.facc = c->facc_buf; S0.kexp = force_scale_exp(c);
-  bool lean = !c->retry_seen && !c->no_lean_narrow;
+  S0.restart_on_tags = plan.user_stop ? 0 : 1;
+  bool lean = plan.lean;
   Clears clr(c);          // (the batch's clears go out with the first prologue's, in one launch)
   clr.add(c->facc_buf, (size_t)FX_WORDS * S0.capM * sizeof(long long));
   clr.add(S0.cnt + C_FRCSTOP, sizeof(int));
@@ -1861,10 +1931,10 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     clr.launch(c);
     // the records of both sets from the columns (the static quads of the twin; its geometry quads are GEO's) -- unless the last batch left them current
     if (!(first_start && c->crec_current))
-      for (int b = 0; b < 2; b++) { State T = pipe_state(c, b); T.step = 0; hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(N, 256)), dim3(256), 0, c->stream, T, N); }
+      for (int b = 0; b < 2; b++) { State T = pipe_state(c, b); T.step = 0; seed_records(c, T, N); }
     first_start = false;
     State T = pipe_state(c, q); T.step = s + 1; T.callid = callid0 + s + 1; T.retry_stop = lean ? 1 : 0;
-    if (gi) hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(S0.capM, 256)), dim3(256), 0, c->stream, T, q, N);
+    if (plan.gi) hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(S0.capM, 256)), dim3(256), 0, c->stream, T, q, N);
     launch_search(c, T, elems);          // (between walls: the element items of the step in the tail of its search, as the three-launch steps do)
   };
   auto launch_L1 = [&](int s, bool make_ghosts) {
@@ -1908,7 +1978,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     State R = pipe_state(c, par(last)); R.step = 0; R.vxy = T.vxy;
     hipLaunchKernelGGL(sz_k_inter_fill, dim3(grid_for(S0.capM, 128 / IF_G, 16384)), dim3(128), 0, c->stream, R, 1, N, 0, 1, 2 + last);      // (2 + last: behind, for 1-based step last + 1)
   };
-  int s_end = c->maybe_tagged && user_stop && nsteps > 1 ? 1 : nsteps;
+  int s_end = plan.first_alone ? 1 : nsteps;
   int s0 = 0, done = 0; bool need_prologue = true;
   for (;;) {
     S0.retry_stop = lean ? 1 : 0;
@@ -1922,8 +1992,8 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     // (sz_k_inter_fill: behind-mode guard; the strain launch is harmless either way and is repeated below)
     S0.step = 0;
     epilogue(s_end - 1, false);
-    HIPCHK(c, hipMemcpyAsync(h, S0.cnt, C_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream2));
+    if (int rc = fetch_counters(c, h)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream2));
     if (h[C_ERR] & ~ERR_CAP_INTER) {          // (the rows' stride, ERR_CAP_INTER, is dealt with behind the loop: the bit stays up until then)
       const int bits = h[C_ERR] & ~ERR_CAP_INTER;
       if (growable(bits) && h[C_RETRYSTOP] > 0) {
@@ -1933,7 +2003,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
         const int sr = h[C_RETRYSTOP] - 1;
         pipe_adopt(c, par(sr));
         int rc = grow_lists(c, bits & (ERR_CAP_NEIGH | ERR_CAP_PAIRS)); if (rc) return rc;
-        (void)hipMemsetAsync(S0.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream); (void)hipMemsetAsync(S0.cnt + C_STOP, 0, sizeof(int), c->stream);
+        (void)clear_stop_words(c, W_RETRYSTOP); (void)clear_stop_words(c, W_STOP);
         if ((rc = clear_totals(c))) return rc;
         if (S0.maxnb > MAXNB) {
           // the prologue's and the L2 launch's neighbour search are instantiated for MAXNB-wide rows (neighbors_body's row stride): with the
@@ -1959,7 +2029,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
       // with the steps behind it (the variant stays in from now on)
       const int sr = h[C_RETRYSTOP] - 1;
       c->retry_seen = true; lean = false;
-      (void)hipMemsetAsync(S0.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream); (void)hipMemsetAsync(S0.cnt + C_PAUSED, 0, sizeof(int), c->stream);
+      (void)clear_stop_words(c, W_RETRYSTOP | W_PAUSED);
       State T = pipe_state(c, par(sr)); T.step = sr + 1; T.callid = callid0 + sr + 1; T.retry_stop = 0;
       narrow_largest(c, T, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, 256);
       const bool host_last = sr + 1 == s_end;
@@ -1969,8 +2039,7 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
       if (s0 >= s_end) {          // it was the last step: only the epilogue is left
         S0.step = 0;
         epilogue(s_end - 1, false);
-        HIPCHK(c, hipMemcpyAsync(h, S0.cnt, C_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (int rc = fetch_counters(c, h)) return rc;
         if (h[C_ERR] & ~ERR_CAP_INTER) { (void)sync_and_check(c, h); return SZ_E_CAPACITY; }
         done = s_end;
         break;
@@ -1981,10 +2050,10 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
       // a tag ended the enqueued steps after step k: the state behind it (GEO(k) has run ahead: parents un-swapped), then either the end of
       // the batch (the caller's stop) or -- a batch that runs through -- the rest of it, started like a batch (the ghosts know the tag now)
       const int k = h[C_STOP] - 1;
-      if (user_stop) { epilogue(k, true); done = k + 1; HIPCHK(c, hipMemcpyAsync(h, S0.cnt, C_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); break; }
+      if (plan.user_stop) { epilogue(k, true); done = k + 1; if (int rc = fetch_counters(c, h)) return rc; break; }
       pipe_adopt(c, par(k + 1));
       { State T = pipe_state(c, par(k + 1)); T.step = 0; hipLaunchKernelGGL(sz_k_unswap, dim3(grid_for(N, 128)), dim3(128), 0, c->stream, T, pipe_alt(c, par(k), 0), N); }
-      (void)hipMemsetAsync(S0.cnt + C_STOP, 0, sizeof(int), c->stream); (void)hipMemsetAsync(S0.cnt + C_FRCSTOP, 0, sizeof(int), c->stream);
+      (void)clear_stop_words(c, W_STOP | W_FRCSTOP);
       s0 = k + 1; need_prologue = true;
       continue;
     }
@@ -2023,12 +2092,9 @@ int step_batch_pipelined(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling
     h[C_NGHOSTS] = keepG;
     if (rc) return rc;
   }
-  if (done < nsteps) c->grid_live = false;
-  *done_out = done;
-  c->last_pipelined = 1; c->gi_pending_slot = qlast;
-  c->crec_current = done == nsteps;          // (the records of the adopted set follow the columns; after a tag stop the un-swap rewrote a few: seeded again next time)
+  *done_out = done; *slot_out = qlast;
   // (h[C_STOP]: the caller's view -- a batch that ran through ended at nsteps)
-  if (!user_stop) h[C_STOP] = 0;
+  if (!plan.user_stop) h[C_STOP] = 0;
   return SZ_OK;
 }
 }  // namespace
@@ -2125,93 +2191,46 @@ int sz_debug_fracture_mean(sz_ctx* c, double* mean_h, double* p) {
 
 int sz_debug_pipelined(sz_ctx* c) { return c ? c->last_pipelined : 0; }
 
-// One batch of resident steps (sz_step without welding, or one of the segments sz_step cuts a batch with welding into)
-static int step_segment(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
-  if (steps_done) *steps_done = 0;
-  if (!c || !c->have_floes) return SZ_E_STATE;
-  if (nsteps < 0) return SZ_E_ARG;
-  if ((flags & SZ_COUPLING_ON) && !c->have_fields) { c->err = "sz_set_fields must be called before coupling"; return SZ_E_STATE; }
-  (void)hipSetDevice(c->device);
-  const bool periodic = c->S.any_periodic_ew || c->S.any_periodic_ns;
-  const bool coll = (flags & SZ_COLLISIONS_ON) != 0;
-  if (c->two_way && (flags & SZ_COUPLING_ON)) {
-    if (c->S.tiled) { c->err = "tiled contexts couple through sz_tile_step + sz_two_way_partial / sz_two_way_finish"; return SZ_E_STATE; }
-    if (!c->temps_set) { c->err = "two-way coupling needs sz_set_temps (after the sz_set_fields that fixed the lattice shape)"; return SZ_E_STATE; }
-    int rc = ensure_two_way(c); if (rc) return rc;
-  }
-  if (!coll) { if (int rc = need_interactions(c)) return rc; }
-  BatchModes modes(c);
-  // the batch ends after the first step that leaves a parent tagged remove / fuse (simplify_floes!, simulation.jl:205-214,
-  // is the host's): the launches of the later steps are enqueued all the same and return at once (stopped())
-  c->S.stop_on_tags = (flags & SZ_NO_STOP) ? 0 : 1;
-  HIPCHK(c, hipMemsetAsync(c->S.cnt + C_STOP, 0, sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream));
-  const bool sg = coll && c->grid_ok;
-  if (sg) use_static_grid(c);
-  const bool gl = ghost_list_wanted(c, sg);
+// The side effects of a batch's start, from the plan: the stop words, the cells, the ghosts' form, the buffers and rings the steps read, the
+// records and totals.  The per-batch modes it sets are put back by the caller's BatchModes scope.  *gl0: the candidate list the batch starts on.
+static int batch_enter(sz_ctx* c, const BatchPlan& p, int* gl0) {
+  c->S.stop_on_tags = p.user_stop ? 1 : 0;
+  HIPCHK(c, clear_stop_words(c, W_STOP | W_RETRYSTOP));
+  if (p.sg) use_static_grid(c);
   // (ghosts a process-mode sz_add_ghosts left attached are dropped first: the list pass only visits the parents that get new ones)
-  if (gl && periodic && c->hostM != c->hostN) hipLaunchKernelGGL(sz_k_remove_ghosts, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, 0);
-  // inline ghosts: no ghost launch in the steps at all (the integrator makes the next step's ghosts; needs the one-launch integrator)
-  const bool gi = gl && !c->S.tiled && c->max_ring <= MV_RING;
-  if (gl && !gi) use_ghost_list(c); else c->gl_valid = false;
-  const int gl0 = c->gl_cur;
-  c->S.ginline = gi ? 1 : 0;
-  if (gi) c->S.famrec = 1;
-  if (c->gi_pending && c->gi_valid && !coll) { int rc = gi_fetch(c); if (rc) return rc; }      // (the key tables are about to be reused)
-  c->gi_pending = false;
-  if (coll) c->gi_valid = false;    // (this batch's rows replace the old ones; set again below if they carry order keys of inline ghosts)
-  const bool mixed = c->precision == 1 && !c->two_way;
-  if (mixed) { int rc = ensure_mixed(c); if (rc) return rc; }
+  if (p.gl && p.periodic && c->hostM != c->hostN) hipLaunchKernelGGL(sz_k_remove_ghosts, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, 0);
+  if (p.gl && !p.gi) use_ghost_list(c); else c->gl_valid = false;
+  *gl0 = c->gl_cur;
+  c->S.ginline = p.gi ? 1 : 0; if (p.gi) c->S.famrec = 1;
+  if (c->gi_pending && c->gi_valid && !p.coll) { int rc = gi_fetch(c); if (rc) return rc; }      // (the key tables are about to be reused)
+  c->gi_pending = false; if (p.coll) c->gi_valid = false;    // (this batch's rows replace the old ones; batch_leave sets it again if they carry order keys of inline ghosts)
+  if (p.mixed) { int rc = ensure_mixed(c); if (rc) return rc; }
   if (c->precision == 0 && !c->two_way && c->have_fields) { int rc = ensure_block_points(c); if (rc) return rc; }
-  // mixed precision: the steps run on body-frame rings (the integrator moves poses, not rings) when nothing else in the batch
-  // needs world rings -- single context, the list path for the ghosts, rings small enough for the fused integrator
-  const bool body = mixed && coll && sg && (gl || !periodic) && !c->S.tiled && c->max_ring <= MV_RING;
-  if (!body) world_rings(c);
-  c->S.body_rings = body ? 1 : 0;
-  // collision records (State::crec): in batches whose kernels keep them current -- the one-launch integrator, and for periodic walls the
-  // inline ghost maker; seeded here from the columns (before the ghost seed: the maker updates the records of the parents it visits)
-  const bool cr = coll && sg && c->crec_buf && c->max_ring <= MV_RING && (gi || !periodic) && nsteps > 0;
-  c->S.crec = cr ? c->crec_buf : nullptr; c->crec_was_live = cr;
-  // Fixed-point totals (State::facc; sz_geom.hpp): the narrow phase adds every row to both floes' totals, the integrator reads them -- no reduce
-  // launch inside the steps.  floe.interactions of the step that ended the batch is assembled once, behind the batch (stage_reduce(.., behind)):
-  // that needs the ghosts of that step still in their rows, i.e. the one-launch integrator with inline ghosts (or no periodic wall), which
-  // knows when it runs a batch's last step (sz_k_integrate: last_step).  The other paths keep the launch inside the step, rows only.
-  const bool facc_on = coll && c->facc_buf != nullptr;
-  const bool rfree = facc_on && sg && (gi || !periodic) && c->max_ring <= MV_RING && !c->any_moving;
-  // pipelined batches (sz_pipeline.hpp: two launches per step) run their own prologue -- records, first ghosts, first neighbour search
+  if (!p.body) world_rings(c);
+  c->S.body_rings = p.body ? 1 : 0;
+  // the records are seeded here from the columns (before the ghost seed: the maker updates the records of the parents it visits)
+  c->S.crec = p.cr ? c->crec_buf : nullptr; c->crec_was_live = p.cr;
   c->last_pipelined = 0;
-  const bool pipe = pipeline_eligible(c, nsteps, coll, sg, gi, periodic, cr, rfree, flags);
-  if (!pipe) c->crec_current = false;          // (the three-launch steps seed the records they use; they may not keep the twin set's)
-  if (cr && !pipe) hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(c->hostN, 256)), dim3(256), 0, c->stream, c->S, c->hostN);
+  if (!p.pipe) c->crec_current = false;          // (the three-launch steps seed the records they use; they may not keep the twin set's)
+  if (p.cr && !p.pipe) seed_records(c, c->S, c->hostN);
   // the ghosts of the first step, from the parents as they lie (after the rings are in the batch's form)
-  if (gi && !pipe) { if (int rc = reseed_inline_ghosts(c, 0)) return rc; }
-  // the largest narrow variant only takes items the small one hands on (none in most fields): it is left out of the steps until one
-  // shows up -- the batch then pauses inside that step (stopped_late()) and is finished below
-  bool lean = coll && !c->retry_seen && !c->no_lean_narrow && !c->S.tiled && !larger_rings(c);
-  c->S.facc = facc_on ? c->facc_buf : nullptr; c->S.kexp = force_scale_exp(c);
-  c->reduce_mode = !facc_on ? 0 : rfree ? 2 : 1;
-  if (facc_on && !pipe) { if (int rc = clear_totals(c)) return rc; }          // (a pipelined batch clears them with the rest of its prologue: one launch)
-  // a parent that is already tagged ends the batch after its first step, and the integrator only finds out while it runs (the tags of a
-  // step itself are raised by its narrow phase / forcings, a launch earlier): that first step is then enqueued on its own, as a last step
-  int s_end = rfree && c->maybe_tagged && c->S.stop_on_tags && nsteps > 1 ? 1 : nsteps;
-  // fracture criterion (sz_set_fracture): evaluated after every fracture step of a batch that stops -- one that runs through has no use for it
-  const bool frac = c->frac_kind != SZ_FRAC_OFF && c->S.stop_on_tags && !pipe;
-  if (frac) { if (int rc = frac_ensure(c)) return rc; }
-  int h[C_COUNT];
-  int pipe_done = -1;
-  if (pipe) {
-    bool rest = false;
-    if (int rc = step_batch_pipelined(c, nsteps, tstep0, dt, coupling_dt, flags, periodic, gi, h, &pipe_done, &rest)) return rc;
-    if (rest) {          // the lists outgrew the pipelined launches in step pipe_done: the rest of the batch as a batch of its own (not eligible now;
-                         //  its scope starts from the process-mode values)
-      int more = 0;
-      const int rc = step_segment(c, nsteps - pipe_done, tstep0 + pipe_done, dt, coupling_dt, flags, &more);
-      if (steps_done) *steps_done = pipe_done + more;
-      return rc;
-    }
-  }
-  const int callid0 = c->callid; if (!pipe) c->callid += nsteps;          // (step s of this batch is collision call callid0 + s + 1, also when it is run again)
-  for (int s0 = 0, mid = 0; !pipe;) {
+  if (p.gi && !p.pipe) { if (int rc = reseed_inline_ghosts(c, 0)) return rc; }
+  c->S.facc = p.facc_on ? c->facc_buf : nullptr; c->S.kexp = force_scale_exp(c); c->reduce_mode = p.reduce_mode;
+  if (p.facc_on && !p.pipe) { if (int rc = clear_totals(c)) return rc; }          // (a pipelined batch clears them with the rest of its prologue: one launch)
+  if (p.frac) { if (int rc = frac_ensure(c)) return rc; }
+  return SZ_OK;
+}
+
+// A batch of three-launch steps (neighbour search, narrow phase, integrator).  The contract of step_batch_pipelined: h = the counter block after
+// the batch, *done = the steps that ran, *slot_out = the allocator slot of the last step's inline ghosts; the context's state is complete when
+// it returns (rows of the last step assembled, ghosts detached).  It starts again from inside: lists grown, the first step alone, a pause for
+// the largest narrow variant.
+static int step_batch_three_launch(sz_ctx* c, const BatchPlan& p, int gl0, int nsteps, int tstep0, int dt, int coupling_dt, int flags, int* h, int* done_out, int* slot_out) {
+  const bool periodic = p.periodic, coll = p.coll, sg = p.sg, gl = p.gl, gi = p.gi, cr = p.cr, facc_on = p.facc_on, rfree = p.rfree, frac = p.frac;
+  bool lean = p.lean;
+  int s_end = p.first_alone ? 1 : nsteps;
+  const int callid0 = c->callid; c->callid += nsteps;          // (step s of this batch is collision call callid0 + s + 1, also when it is run again)
+  for (int s0 = 0, mid = 0;;) {
     c->S.retry_stop = lean ? 1 : 0;
     for (int s = s0; s < s_end; s++) {
       int tstep = tstep0 + s;
@@ -2245,7 +2264,7 @@ static int step_segment(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, i
       // the test by launches that return at once when it has stopped the batch (sz_fracture.hpp)
       const bool fstep = frac && (tstep % c->frac_dt) == 0;
       const bool fcut = fstep && s + 1 < s_end;
-      c->acc_mode = !facc_on ? 0 : 1 | (rfree ? 4 | (s + 1 == s_end || fcut ? 2 : 0) : 0);
+      c->acc_mode = integrator_acc_mode(facc_on, rfree, s + 1 == s_end || fcut);
       stage_integrate(c, dt, !coll, coupling, sg, gl && !gi ? 1 - c->gl_cur : -1, gi && s + 1 < s_end && !fcut ? 1 - (s & 1) : -1);
       if (gl && !gi) c->gl_cur ^= 1;
       if (fstep) {
@@ -2275,11 +2294,10 @@ static int step_segment(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, i
       // they lie -- exactly as a batch that starts at that step would (cells, the step's ghosts): the reference's lists grow (collisions.jl:290-296).
       if ((rc = grow_lists(c, c->last_err_bits))) return rc;
       s0 = h[C_RETRYSTOP] - 1; mid = 0;
-      (void)hipMemsetAsync(c->S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream);
-      (void)hipMemsetAsync(c->S.cnt + C_STOP, 0, sizeof(int), c->stream);
+      (void)clear_stop_words(c, W_RETRYSTOP); (void)clear_stop_words(c, W_STOP);
       if (facc_on && (rc = clear_totals(c))) return rc;
       c->grid_live = false; use_static_grid(c);
-      if (cr) hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(c->hostN, 256)), dim3(256), 0, c->stream, c->S, c->hostN);
+      if (cr) seed_records(c, c->S, c->hostN);
       if (gi) { if ((rc = reseed_inline_ghosts(c, s0 & 1))) return rc; }
       else if (gl) { c->gl_valid = false; use_ghost_list(c); }
       continue;
@@ -2297,38 +2315,80 @@ static int step_segment(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, i
     c->retry_seen = true; lean = false;
     s0 = h[C_RETRYSTOP] - 1; mid = 1;
     if (gl && !gi) c->gl_cur = (gl0 + s0) & 1;
-    (void)hipMemsetAsync(c->S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream);
+    (void)clear_stop_words(c, W_RETRYSTOP);
   }
-  if (coll && (h[C_STOP] > 0 || (flags & SZ_NO_STOP))) c->maybe_tagged = true;
+  *done_out = h[C_STOP] > 0 ? std::min(h[C_STOP], nsteps) : nsteps; *slot_out = (*done_out - 1) & 1;
+  return SZ_OK;
+}
+
+// What a batch leaves behind, and who reads it:
+//   maybe_tagged      a parent may carry a tag: the next plan's first_alone
+//   last_stopped      a tag ended the batch
+//   last_pipelined    sz_debug_pipelined, sz_narrow_kernel_name
+//   crec_current      the records of both sets follow the columns: the next pipelined prologue does not seed them (every call outside the
+//                     resident steps drops it: leave_resident).  After a tag stop the un-swap rewrote a few: seeded again next time
+//   rings_stale       the world rings lag the poses: world_rings, before anything reads them
+//   inter_any / inter_lost   floe.interactions on the device is the batch's: need_interactions, the downloads
+//   gl_cur / gl_est   the candidate list the last step that RAN has filled, and how long it is: use_ghost_list, ghost_list_wanted, the list pass
+//   gi_pending, gi_pending_n, gi_pending_slot, gi_valid   the order keys of the last step's inline ghosts, not fetched yet: gi_fetch
+//   grid_live         the cells hold the parents as they lie: use_static_grid
+//   fuse_lists, gl_valid   status.fuse_idx of the step that ended the batch, replayed on the host; the replay may change tags
+static int batch_leave(sz_ctx* c, const BatchPlan& p, int gl0, const int* h, int done, int slot, int nsteps, int tstep0, int coupling_dt, int flags) {
+  if (p.coll && (h[C_STOP] > 0 || !p.user_stop)) c->maybe_tagged = true;
   c->last_stopped = h[C_STOP] > 0;
-  if (body && nsteps > 0) c->rings_stale = true;
-  if (coll) { c->inter_any = true; c->inter_lost = false; }
-  int rc = SZ_OK;
-  const int done = pipe ? pipe_done : h[C_STOP] > 0 ? std::min(h[C_STOP], (int)nsteps) : nsteps;
-  if (steps_done) *steps_done = done;
-  if (gl && !gi) {        // the list the last step that RAN has filled, and how long it is
-    c->gl_cur = (gl0 + done) & 1;
-    c->gl_est = h[C_NGCAND + c->gl_cur];
-  }
-  if (gi) {               // the order keys of the last step's ghosts are what the host needs to number them as the reference does:
+  c->last_pipelined = p.pipe; c->crec_current = p.pipe && done == nsteps;
+  if (p.body && nsteps > 0) c->rings_stale = true;
+  if (p.coll) { c->inter_any = true; c->inter_lost = false; }
+  if (p.gl && !p.gi) { c->gl_cur = (gl0 + done) & 1; c->gl_est = h[C_NGCAND + c->gl_cur]; }
+  if (p.gi) {               // the order keys of the last step's ghosts are what the host needs to number them as the reference does:
     // they are fetched when somebody asks for numbers (gi_fetch: downloads, the fuse replay) -- most batches end without
-    c->gi_pending_n = done > 0 ? h[C_NGHOSTS] : 0; if (!pipe) c->gi_pending_slot = (done - 1) & 1; c->gi_pending = true;
-    if (coll) c->gi_valid = done > 0;
-    if (done < nsteps) c->grid_live = false;       // stopped early: the step that ended the batch has binned ghosts for a step that did not come
+    c->gi_pending_n = done > 0 ? h[C_NGHOSTS] : 0; c->gi_pending_slot = slot; c->gi_pending = true;
+    if (p.coll) c->gi_valid = done > 0;
     c->gl_est = std::max(c->gl_est, c->gi_pending_n);        // (sizes the list pass should the next batch use it)
   }
+  // stopped early: the step that ended the batch has binned ghosts (inline makers, the pipelined update) for a step that did not come
+  if ((p.gi || p.pipe) && done < nsteps) c->grid_live = false;
   // status.fuse_idx of the step that ended the batch: the reference's serial propagation, replayed on the host as
   // sz_timestep_collisions does (only that step can have produced fuse pairs: the batch stops on the first tag)
-  if (coll && done > 0) {
-    const int tlast = tstep0 + done - 1;
-    const bool last_coupled = coupling_at(flags, coupling_dt, tlast);
-    if (h[C_STOP] > 0 || (flags & SZ_NO_STOP)) {
-      rc = host_fuse_fixup(c, h, true, true, last_coupled);
-      c->fuse_lists.resize(c->hostM);
-      c->gl_valid = false;          // the replay may have changed status tags
-    }
+  int rc = SZ_OK;
+  if (p.coll && done > 0 && (h[C_STOP] > 0 || !p.user_stop)) {
+    rc = host_fuse_fixup(c, h, true, true, coupling_at(flags, coupling_dt, tstep0 + done - 1));
+    c->fuse_lists.resize(c->hostM);
+    c->gl_valid = false;          // the replay may have changed status tags
   }
   return rc;
+}
+
+// One batch of resident steps (sz_step without welding, or one of the segments sz_step cuts a batch with welding into): checks, plan, enter,
+// one driver, leave
+static int step_segment(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
+  if (steps_done) *steps_done = 0;
+  if (!c || !c->have_floes) return SZ_E_STATE;
+  if (nsteps < 0) return SZ_E_ARG;
+  if ((flags & SZ_COUPLING_ON) && !c->have_fields) { c->err = "sz_set_fields must be called before coupling"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  if (c->two_way && (flags & SZ_COUPLING_ON)) {
+    if (c->S.tiled) { c->err = "tiled contexts couple through sz_tile_step + sz_two_way_partial / sz_two_way_finish"; return SZ_E_STATE; }
+    if (!c->temps_set) { c->err = "two-way coupling needs sz_set_temps (after the sz_set_fields that fixed the lattice shape)"; return SZ_E_STATE; }
+    int rc = ensure_two_way(c); if (rc) return rc;
+  }
+  if (!(flags & SZ_COLLISIONS_ON)) { if (int rc = need_interactions(c)) return rc; }
+  const BatchPlan plan = plan_batch(c, nsteps, flags);
+  BatchModes modes(c);
+  int h[C_COUNT], gl0 = 0, done = 0, slot = 0; bool rest = false;
+  if (int rc = batch_enter(c, plan, &gl0)) return rc;
+  if (plan.pipe) {
+    if (int rc = step_batch_pipelined(c, plan, nsteps, tstep0, dt, coupling_dt, flags, h, &done, &slot, &rest)) return rc;
+    if (rest) {          // the lists outgrew the pipelined launches in step `done`: the rest of the batch as a batch of its own (not eligible now;
+                         //  its scope starts from the process-mode values)
+      int more = 0;
+      const int rc = step_segment(c, nsteps - done, tstep0 + done, dt, coupling_dt, flags, &more);
+      if (steps_done) *steps_done = done + more;
+      return rc;
+    }
+  } else if (int rc = step_batch_three_launch(c, plan, gl0, nsteps, tstep0, dt, coupling_dt, flags, h, &done, &slot)) return rc;
+  if (steps_done) *steps_done = done;
+  return batch_leave(c, plan, gl0, h, done, slot, nsteps, tstep0, coupling_dt, flags);
 }
 
 // ---------------------------------------------------------------- welding overlap table (sz_weld.hpp)
@@ -2937,42 +2997,33 @@ int comm_allgather(sz_ctx* c, const void* d_src, void* d_dst, size_t count, int 
   return SZ_OK;
 }
 
-// Collective: the OR of a word over the ranks.  Device errors (capacity bits, halo drift) are per rank and sticky; a rank that returned
-// on its own while its peers went on into the next collective would leave them waiting forever (RCCL has no timeout).  Every point
-// at which sz_tile_run looks at the error word therefore agrees on it first: all ranks return the same code at the same step.
-int comm_agree_bits(sz_ctx* c, int local, int* all) {
+// one int of every rank (n <= 64), on every rank
+int comm_gather_int(sz_ctx* c, int local, int* all64) {
   const int n = c->comm_n;
-  *all = local;
+  all64[0] = local;
   if (n == 1) return SZ_OK;
   int* d = (int*)(c->d_gather + 8 + 8 * 64 + 64 * 64 / 2);       // the 64 spare doubles behind the count matrix: word | words of all ranks
   HIPCHK(c, hipMemcpyAsync(d, &local, sizeof(int), hipMemcpyHostToDevice, c->stream));
   int rc = comm_allgather(c, d, d + 32, 1, NCCL_INT32, sizeof(int));
   if (rc) return rc;
-  int h[64];
-  HIPCHK(c, hipMemcpyAsync(h, d + 32, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(all64, d + 32, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SZ_OK;
+}
+// Collective: the OR of a word over the ranks.  Device errors (capacity bits, halo drift) are per rank and sticky; a rank that returned
+// on its own while its peers went on into the next collective would leave them waiting forever (RCCL has no timeout).  Every point
+// at which sz_tile_run looks at the error word therefore agrees on it first: all ranks return the same code at the same step.
+int comm_agree_bits(sz_ctx* c, int local, int* all) {
+  int h[64];
+  if (const int rc = comm_gather_int(c, local, h)) return rc;
   int bits = 0, who = -1;
-  for (int r = 0; r < n; r++) { if (h[r] && who < 0) who = r; bits |= h[r]; }
+  for (int r = 0; r < c->comm_n; r++) { if (h[r] && who < 0) who = r; bits |= h[r]; }
   *all = bits;
   if (bits && !local) {
     char buf[200];
     snprintf(buf, sizeof(buf), "rank %d of the tiled run reported device error bits 0x%x (this rank is clean; all ranks stop together)", who, bits);
     c->err = buf;
   }
-  return SZ_OK;
-}
-// sync + sticky device errors of THIS rank + agreement: SZ_OK on every rank or the same error code on every rank
-// one int of every rank (n <= 64), on every rank
-int comm_gather_int(sz_ctx* c, int local, int* all64) {
-  const int n = c->comm_n;
-  all64[0] = local;
-  if (n == 1) return SZ_OK;
-  int* d = (int*)(c->d_gather + 8 + 8 * 64 + 64 * 64 / 2);
-  HIPCHK(c, hipMemcpyAsync(d, &local, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  int rc = comm_allgather(c, d, d + 32, 1, NCCL_INT32, sizeof(int));
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(all64, d + 32, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   return SZ_OK;
 }
 // The two words that decide how a tiled batch goes on -- the step a tag ended it at (C_STOP) and the step that paused for the largest narrow
@@ -2989,13 +3040,16 @@ int comm_agree_steps(sz_ctx* c, int stop_local, int pause_local, int* stop_all, 
   *stop_all = s; *pause_all = p;
   return SZ_OK;
 }
-int tile_sync_agree(sz_ctx* c, int* cnt_out = nullptr) {
-  int rc = sync_and_check(c, cnt_out);
-  if (rc == SZ_E_HIP) return rc;              // (the runtime itself failed: nothing to agree on)
+// the agreement on this rank's sync_and_check status rc
+static int tile_agree(sz_ctx* c, int rc) {
   int all = 0;
-  const int rc2 = comm_agree_bits(c, rc ? (c->last_err_bits ? c->last_err_bits : 1) : 0, &all);
-  if (rc2) return rc2;
+  if (const int rc2 = comm_agree_bits(c, rc ? (c->last_err_bits ? c->last_err_bits : 1) : 0, &all)) return rc2;
   return all ? SZ_E_CAPACITY : SZ_OK;
+}
+// sync + sticky device errors of THIS rank + agreement: SZ_OK on every rank or the same error code on every rank
+int tile_sync_agree(sz_ctx* c, int* cnt_out = nullptr) {
+  const int rc = sync_and_check(c, cnt_out);
+  return rc == SZ_E_HIP ? rc : tile_agree(c, rc);              // (the runtime itself failed: nothing to agree on)
 }
 
 // do the expanded box of rank d and the (margin-expanded) owned box of rank s meet, periodic images included?
@@ -3701,118 +3755,103 @@ int tile_fuse_replay(sz_ctx* c, const int* h, bool last_coupled) {
     for (int& v : c->fuse_lists[i]) { if (v < 0 || v >= (int)keys.size()) continue; long long key = keys[v]; if (key >= lim) key = (key & (lim - 1)) >> 2; v = (int)key; }
   return SZ_OK;
 }
-}  // namespace
-
-// the centre of this rank's tile (optional, after sz_tile_setup): in a periodic direction the owned box of the FIRST gather then takes every
-// centroid at its image nearest to it, as the later gathers do with the centre of the box before (sz_k_owned_box)
-int sz_tile_set_center(sz_ctx* c, double x, double y) {
-  if (!c || !c->S.tiled || c->tile_margin <= 0) { if (c) c->err = "sz_tile_set_center needs sz_tile_setup"; return SZ_E_STATE; }
-  c->tile_box_ctr[0] = x; c->tile_box_ctr[1] = y; c->tile_box_valid = true;
-  return SZ_OK;
+// The plan of a tiled batch of inline steps (sz_tile_run has checked what they need: collisions, the static grid, rings that fit the one-launch
+// integrator, no two-way coupling).  The ghosts are made by whoever places the parent (integrator: owned floes, unpack: halo floes): inline
+// ghosts without a candidate list.  Records and totals: plan_batch's rules.  A tile's own:
+//  - rfree.  With peers and the tag stop a rank learns that a step was the batch's last only in the unpack of the NEXT one -- after its
+//    integrator has made that step's ghosts over the rows of this one -- so the rows are then assembled inside every step (rows only); alone,
+//    or in batches that run through (SZ_NO_STOP), once behind the batch.  (Moving walls do not enter the rule.)
+//  - lean.  Not under SZ_SYNC_DEBUG (dbgsync: the stages run one by one), and not without the all-pairs headers (hdr_all): a pause must
+//    reach every rank.
+static BatchPlan plan_tile_batch(const sz_ctx* c, int nsteps, int flags, bool hdr_all, bool dbgsync) {
+  BatchPlan p{};
+  p.periodic = c->S.any_periodic_ew || c->S.any_periodic_ns;
+  p.coll = p.sg = p.gi = true;
+  p.user_stop = !(flags & SZ_NO_STOP);
+  p.mixed = c->precision == 1;
+  plan_records_totals(p, c, nsteps);
+  p.set_rfree(p.facc_on && !(c->comm_n > 1 && p.user_stop));
+  p.lean = lean_wanted(c) && !dbgsync && hdr_all;
+  return p;
 }
-// nsteps x timestep_sim! of a tiled run, collectively on every rank (same arguments everywhere)
-int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
-  if (steps_done) *steps_done = 0;
-  if (c && c->frac_kind != SZ_FRAC_OFF) { c->err = "tiled runs do not evaluate fracture criteria (the mean height needs an all-reduce over the ranks): sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
-  if (c && !c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
-  if (!c || !c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0) {
-    if (c) c->err = "sz_tile_run needs sz_tile_enable and sz_tile_setup after the last sz_upload_floes";
-    return SZ_E_STATE;
-  }
-  if (nsteps < 0) return SZ_E_ARG;
-  (void)hipSetDevice(c->device);
-  State& S = c->S;
-  const int n = c->comm_n, me = c->comm_rank;
-  const bool coll = (flags & SZ_COLLISIONS_ON) != 0;
-  BatchModes modes(c);
-  // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
-  // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
-  // Needs what the inline ghost maker needs (rings that fit the one-launch integrator, the static grid).  Otherwise: the list-based steps
-  // of sz_tile_step.
-  const bool inl = coll && c->grid_ok && !c->two_way &&
-                   std::max(c->max_ring, c->max_ring_tiled) <= MV_RING && ((flags & SZ_COUPLING_ON) == 0 || c->have_fields);
-  if (!inl) {
-    // The tag stop of these steps (one-way coupling): the pack kernel's header records carry every rank's stop word to EVERY rank, the unpack
-    // kernel of the next step reads them before that step has touched anything and ends the batch there (sz_k_halo_unpack), as in the inline
-    // steps.  The forcings then run behind the unpack instead of beside the exchange: a rank must not compute the forcings of a step its
-    // peers have already called off.  Two-way coupling across tiles (round 4): the same stop -- the steps behind it are enqueued and return at
-    // once; their all-reduces of the per-cell sums still run on every rank (collectives must), on the sums of the step that ended the
-    // batch, and sz_two_way_finish writes the ocean fields of that step once more: the same values.
-    const bool stopping = !(flags & SZ_NO_STOP);
-    S.stop_on_tags = stopping ? 1 : 0;
-    HIPCHK(c, hipMemsetAsync(S.cnt + C_STOP, 0, sizeof(int), c->stream));
-    HIPCHK(c, hipMemsetAsync(S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream));
-    for (int s = 0; s < nsteps; s++) {
-      const int tstep = tstep0 + s;
-      c->tile_dt = dt;
-      S.step = stopping ? s + 1 : 0;
-      if (c->tile_since_box < 0 || c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }
-      c->tile_since_box++;
-      const bool coupling = coupling_at(flags, coupling_dt, tstep);
-      tile_pack(c);
-      // (the host's channel blocks: the forcings go to the device first and run while the host trades the regions)
-      if (coupling && !stopping && n > 1 && c->host_transport) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return rc; }
-      { int rc = tile_exchange(c, stopping); if (rc) return rc; }
-      // the forcings of the owned floes need nothing from the halo: they run beside the exchange
-      if (coupling && !stopping && !(n > 1 && c->host_transport)) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return rc; }
-      if (n > 1 && hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return SZ_E_HIP; }
-      int rc = sz_tile_step(c, c->d_recv, n, c->halo_cap, tstep, dt, coupling_dt, flags);
-      if (rc) return rc;
-      if (c->two_way && coupling) {       // ice-on-ocean stress: per-cell partial sums, summed over the ranks, finished on every rank
-        const size_t nc = 3 * c->tw_ncell;
-        if (!c->d_tw_partial) { int r2 = dalloc(c, &c->d_tw_partial, nc, c->tw_part_allocs); if (r2) return r2; }
-        if ((rc = sz_two_way_partial(c, c->d_tw_partial)) || (rc = sz_comm_allreduce(c, c->d_tw_partial, (int64_t)nc)) ||
-            (rc = sz_two_way_finish(c, c->d_tw_partial, dt))) return rc;
-      }
+// sz_tile_run on the list-based steps of sz_tile_step
+static int tile_run_listed(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling_dt, int flags, int32_t* steps_done) {
+  State& S = c->S; const int n = c->comm_n;
+  // The tag stop of these steps (one-way coupling): the pack kernel's header records carry every rank's stop word to EVERY rank, the unpack
+  // kernel of the next step reads them before that step has touched anything and ends the batch there (sz_k_halo_unpack), as in the inline
+  // steps.  The forcings then run behind the unpack instead of beside the exchange: a rank must not compute the forcings of a step its
+  // peers have already called off.  Two-way coupling across tiles (round 4): the same stop -- the steps behind it are enqueued and return at
+  // once; their all-reduces of the per-cell sums still run on every rank (collectives must), on the sums of the step that ended the
+  // batch, and sz_two_way_finish writes the ocean fields of that step once more: the same values.
+  const bool stopping = !(flags & SZ_NO_STOP);
+  S.stop_on_tags = stopping ? 1 : 0;
+  HIPCHK(c, clear_stop_words(c, W_STOP | W_RETRYSTOP));
+  for (int s = 0; s < nsteps; s++) {
+    const int tstep = tstep0 + s;
+    c->tile_dt = dt;
+    S.step = stopping ? s + 1 : 0;
+    if (c->tile_since_box < 0 || c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }
+    c->tile_since_box++;
+    const bool coupling = coupling_at(flags, coupling_dt, tstep);
+    tile_pack(c);
+    // (the host's channel blocks: the forcings go to the device first and run while the host trades the regions)
+    if (coupling && !stopping && n > 1 && c->host_transport) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return rc; }
+    { int rc = tile_exchange(c, stopping); if (rc) return rc; }
+    // the forcings of the owned floes need nothing from the halo: they run beside the exchange
+    if (coupling && !stopping && !(n > 1 && c->host_transport)) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return rc; }
+    if (n > 1 && hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return SZ_E_HIP; }
+    int rc = sz_tile_step(c, c->d_recv, n, c->halo_cap, tstep, dt, coupling_dt, flags); if (rc) return rc;
+    if (c->two_way && coupling) {       // ice-on-ocean stress: per-cell partial sums, summed over the ranks, finished on every rank
+      const size_t nc = 3 * c->tw_ncell;
+      if (!c->d_tw_partial) { int r2 = dalloc(c, &c->d_tw_partial, nc, c->tw_part_allocs); if (r2) return r2; }
+      if ((rc = sz_two_way_partial(c, c->d_tw_partial)) || (rc = sz_comm_allreduce(c, c->d_tw_partial, (int64_t)nc)) ||
+          (rc = sz_two_way_finish(c, c->d_tw_partial, dt))) return rc;
     }
-    // (the ranks agree on the error word: a rank with a device error and a clean one return the same code)
-    S.step = 0;
-    int hl[C_COUNT] = { 0 };
-    const int rce = tile_sync_agree(c, hl);
-    c->fuse_lists.resize(c->hostM);
-    const int done = stopping && hl[C_STOP] > 0 ? std::min(hl[C_STOP], (int)nsteps) : nsteps;
-    if (done < nsteps) { c->grid_live = false; c->gl_valid = false; }          // stopped early: cells and ghost-candidate lists belong to steps that did not come
-    if (steps_done) *steps_done = done;
-    return rce;
   }
-  // ---------------- inline steps
-  const bool periodic = S.any_periodic_ew || S.any_periodic_ns;
+  // (the ranks agree on the error word: a rank with a device error and a clean one return the same code)
+  S.step = 0;
+  int hl[C_COUNT] = { 0 };
+  const int rce = tile_sync_agree(c, hl);
+  c->fuse_lists.resize(c->hostM);
+  const int done = stopping && hl[C_STOP] > 0 ? std::min(hl[C_STOP], (int)nsteps) : nsteps;
+  if (done < nsteps) { c->grid_live = false; c->gl_valid = false; }          // stopped early: cells and ghost-candidate lists belong to steps that did not come
+  if (steps_done) *steps_done = done;
+  return rce;
+}
+// sz_tile_run on the inline steps: the single context's (step_batch_three_launch with inline ghosts), plus the pack and unpack kernels and the
+// exchange, and the restarts the ranks agree on
+static int tile_run_inline(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling_dt, int flags, int32_t* steps_done) {
+  State& S = c->S; const int n = c->comm_n, me = c->comm_rank;
+  // SZ_SYNC_DEBUG=1 (diagnosis of a faulting kernel): wait after every stage of every step and say so on stderr -- the last line names the stage
+  const bool dbgsync = getenv("SZ_SYNC_DEBUG") != nullptr;
+  const bool hdr_all = !(c->tile_hdr_neighbours && (flags & SZ_NO_STOP));      // (the A/B arm without the all-pairs headers: see tile_hdr_neighbours)
+  const BatchPlan plan = plan_tile_batch(c, nsteps, flags, hdr_all, dbgsync);
+  const bool periodic = plan.periodic, facc_on = plan.facc_on, rfree = plan.rfree;
   tile_cleanup(c);                                  // (the halo floes / ghosts a list-based call may have left attached)
-  if (c->gi_pending) c->gi_pending = false;
-  c->gi_valid = false;
-  c->gl_valid = false;
+  c->gi_pending = false; c->gi_valid = false; c->gl_valid = false;
   world_rings(c);
-  S.stop_on_tags = (flags & SZ_NO_STOP) ? 0 : 1;
-  HIPCHK(c, hipMemsetAsync(S.cnt + C_STOP, 0, sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.cnt + C_PAUSED, 0, sizeof(int), c->stream));
+  S.stop_on_tags = plan.user_stop ? 1 : 0;
+  HIPCHK(c, clear_stop_words(c, W_STOP | W_RETRYSTOP | W_PAUSED));
   use_static_grid(c);
-  if (c->precision == 1) { int rc = ensure_mixed(c); if (rc) return rc; }
+  if (plan.mixed) { int rc = ensure_mixed(c); if (rc) return rc; }
   else if (!c->two_way && c->have_fields) { int rc = ensure_block_points(c); if (rc) return rc; }
   S.ginline = 1; S.famrec = 1;
   HIPCHK(c, hipMemsetAsync(S.galloc, 0, 32 * sizeof(unsigned long long), c->stream));
   // the periodic ghosts of the owned floes for the first step (and the swap of parents that lie outside the domain), BEFORE the first pack
   // collision records of the owned floes (the halo floes get theirs from the unpack kernel, ghosts from their maker; see sz_step)
-  S.crec = (c->crec_buf && nsteps > 0) ? c->crec_buf : nullptr; c->crec_was_live = S.crec != nullptr;
-  if (S.crec) hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(c->hostN, 256)), dim3(256), 0, c->stream, S, c->hostN);
+  S.crec = plan.cr ? c->crec_buf : nullptr; c->crec_was_live = plan.cr;
+  if (plan.cr) seed_records(c, S, c->hostN);
   // (the periodic ghosts of the owned floes for the first step, and the swap of parents that lie outside the domain: in the loop, BEHIND the
   //  first pack -- see there)
-  // fixed-point totals and reduce-free steps as in sz_step.  With peers and the tag stop a rank learns that a step was the batch's last only
-  // in the unpack of the NEXT one -- after its integrator has made that step's ghosts over the rows of this one -- so the rows are then
-  // assembled inside every step (rows only); alone, or in batches that run through (SZ_NO_STOP), once behind the batch.
-  const bool facc_on = c->facc_buf != nullptr;
-  const int rmode = !facc_on ? 0 : n > 1 && S.stop_on_tags ? 1 : 2;
-  S.facc = facc_on ? c->facc_buf : nullptr; S.kexp = force_scale_exp(c); c->reduce_mode = rmode;
+  // fixed-point totals and reduce-free steps as in sz_step (plan_tile_batch)
+  S.facc = facc_on ? c->facc_buf : nullptr; S.kexp = force_scale_exp(c); c->reduce_mode = plan.reduce_mode;
   if (facc_on) { if (int rc = clear_totals(c)) return rc; }
-  auto accm = [&](bool last) { return !facc_on ? 0 : 1 | (rmode == 2 ? 4 | (last ? 2 : 0) : 0); };
   // the forcing output set in use (see `beside` below): a way out before the end of the batch takes the columns back to set 0, as at entry
   struct FrcSets {
     sz_ctx* c; int cur; bool keep;
     void use(int set) { if (set != cur) { std::swap(c->S.fxOA, c->frc_alt[0]); std::swap(c->S.fyOA, c->frc_alt[1]); std::swap(c->S.trqOA, c->frc_alt[2]); std::swap(c->S.hflx, c->frc_alt[3]); cur = set; } }
     ~FrcSets() { if (!keep) use(0); }
   } frc{ c, 0, false };
-  // SZ_SYNC_DEBUG=1 (diagnosis of a faulting kernel): wait after every stage of every step and say so on stderr -- the last line names the stage
-  const bool dbgsync = getenv("SZ_SYNC_DEBUG") != nullptr;
   auto stage_done = [&](int s, const char* what) {
     if (!dbgsync) return;
     const hipError_t e = hipStreamSynchronize(c->stream);
@@ -3828,8 +3867,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   // exchange (sz_k_halo_pack hdr[2]), whose unpack kernel stops every other rank before that step has touched anything.  After the sync
   // all ranks know the step: the rank that paused finishes it (the variant, the reduce, the integrator), and everybody runs the rest of
   // the batch again from the step after it, as a batch that starts there (cells, ghosts, records seeded anew) with the variant in.
-  const bool hdr_all = !(c->tile_hdr_neighbours && (flags & SZ_NO_STOP));      // (the A/B arm without the all-pairs headers: see tile_hdr_neighbours)
-  bool lean = !c->retry_seen && !c->no_lean_narrow && !larger_rings(c) && !dbgsync && hdr_all;
+  bool lean = plan.lean;
   std::vector<int> callid_of((size_t)std::max(nsteps, 1), 0);
   int h[C_COUNT]; int rc = SZ_OK;
   // The halo records of step s + 1 are written by the integrator of step s: the thread that has just placed the floe holds all a record
@@ -3844,125 +3882,113 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   // collisions.jl:942-950) and packed the halo records -- and simply take up the steps where the pause stopped them.
   bool fresh = true;
   for (int s_begin = 0;;) {
-  S.retry_stop = lean ? 1 : 0;
-  for (int s = s_begin; s < nsteps; s++) {
-    const int tstep = tstep0 + s;
-    S.step = s + 1; S.gslot = s & 1;
-    c->tile_dt = dt;
-    if (s == s_begin && s_begin == 0) {
-      if (c->tile_since_box < 0 || c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }
-      stage_done(s, "rebox");
+    S.retry_stop = lean ? 1 : 0;
+    for (int s = s_begin; s < nsteps; s++) {
+      const int tstep = tstep0 + s;
+      S.step = s + 1; S.gslot = s & 1;
+      c->tile_dt = dt;
+      if (s == s_begin && s_begin == 0) {
+        if (c->tile_since_box < 0 || c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }
+        stage_done(s, "rebox");
+      }
+      if (s == s_begin && fresh) {
+        tile_pack(c);
+        if (periodic) hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(S.capM, 256)), dim3(256), 0, c->stream, S, s & 1, c->hostN);
+      }
+      c->tile_since_box++;
+      const bool coupling = coupling_at(flags, coupling_dt, tstep);
+      stage_done(s, "pack");
+      // With peers the forcings of the owned floes (they need nothing from the halo) run BESIDE the exchange -- on the main stream while the
+      // communication stream trades the regions, before the host's channel blocks -- and the narrow launch carries no forcing tail; without
+      // peers there is nothing to hide them behind and they ride in the narrow launch's tail as in sz_step.
+      const bool beside = coupling && n > 1 && !(c->pmask >> SZ_K_FORCING & 1u);
+      // (these forcings run before this rank knows whether a peer has asked for the batch to end at the previous step -- the unpack kernel
+      //  below finds out.  They therefore write a SECOND set of the four output columns, alternating step by step, and the set the last
+      //  step that really ran has written is made the context's at the end of the call: a batch that ends early leaves fxOA .. hflx of the
+      //  step it ended with, as sz_step does.)
+      if (beside) { frc.use(frc.cur ^ 1); fset[s] = (signed char)frc.cur; }
+      if (beside && c->host_transport) stage_forcing(c, dt);
+      { int rc = tile_exchange(c, hdr_all); if (rc) return rc; }
+      if (beside && !c->host_transport) stage_forcing(c, dt);
+      if (n > 1) {
+        if (hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return SZ_E_HIP; }
+        const long long slots = (long long)n * c->halo_cap;
+        hipLaunchKernelGGL(sz_k_halo_unpack_inline, dim3(grid_for(slots, UNPACK_TPB, 1 << 20)), dim3(UNPACK_TPB), 0, c->stream, S, (const double*)c->d_recv, n, me, c->halo_cap,
+                           S.gslot, c->hostN);
+      }
+      stage_done(s, "exchange + unpack");
+      // the forcings that did not run beside the exchange: where sz_step puts them (forcing_fuse_mode)
+      const int fmode = forcing_fuse_mode(c, coupling && !beside);
+      if (coupling && !fmode && !beside) stage_forcing(c, dt);
+      if (coupling) c->forcing_where = fmode;
+      S.callid = ++c->callid; callid_of[s] = S.callid;
+      if (facc_on && !(S.crec && S.maxnb <= MAXNB)) (void)hipMemsetAsync(c->facc_buf + (size_t)FX_WORDS * c->hostN, 0, (size_t)FX_WORDS * (S.capM - c->hostN) * sizeof(long long), c->stream);      // (see sz_step)
+      if (dbgsync) {          // (the stages of collisions_step one by one)
+        stage_broad(c, false, true, fmode == 1, false); stage_done(s, "neighbour search");
+        stage_elems(c, true); stage_done(s, "element items");
+        stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, fmode == 2 ? (c->precision == 1 ? 2 : 1) : 0, 0); stage_done(s, "narrow phase");
+        stage_reduce(c, 1, -1, dt, 0); stage_done(s, "reduce");
+      } else collisions_step(c, -1, dt, false, true, fmode, lean, false);
+      const bool pack_next = s + 1 < nsteps;
+      if (pack_next && c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }      // (synchronises: once per gather interval)
+      const PackInl pk = tile_pack_args(c);
+      c->acc_mode = integrator_acc_mode(facc_on, rfree, s + 1 == nsteps);
+      stage_integrate(c, dt, false, coupling, true, -1, periodic && s + 1 < nsteps ? 1 - (s & 1) : -1, pack_next ? &pk : nullptr);
+      stage_done(s, "integrate");
     }
-    if (s == s_begin && fresh) {
-      tile_pack(c);
-      if (periodic) hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(S.capM, 256)), dim3(256), 0, c->stream, S, s & 1, c->hostN);
-    }
-    c->tile_since_box++;
-    const bool coupling = coupling_at(flags, coupling_dt, tstep);
-    stage_done(s, "pack");
-    // With peers the forcings of the owned floes (they need nothing from the halo) run BESIDE the exchange -- on the main stream while the
-    // communication stream trades the regions, before the host's channel blocks -- and the narrow launch carries no forcing tail; without
-    // peers there is nothing to hide them behind and they ride in the narrow launch's tail as in sz_step.
-    const bool beside = coupling && n > 1 && !(c->pmask >> SZ_K_FORCING & 1u);
-    // (these forcings run before this rank knows whether a peer has asked for the batch to end at the previous step -- the unpack kernel
-    //  below finds out.  They therefore write a SECOND set of the four output columns, alternating step by step, and the set the last
-    //  step that really ran has written is made the context's at the end of the call: a batch that ends early leaves fxOA .. hflx of the
-    //  step it ended with, as sz_step does.)
-    if (beside) { frc.use(frc.cur ^ 1); fset[s] = (signed char)frc.cur; }
-    if (beside && c->host_transport) stage_forcing(c, dt);
-    { int rc = tile_exchange(c, hdr_all); if (rc) return rc; }
-    if (beside && !c->host_transport) stage_forcing(c, dt);
-    if (n > 1) {
-      if (hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return SZ_E_HIP; }
-      const long long slots = (long long)n * c->halo_cap;
-      hipLaunchKernelGGL(sz_k_halo_unpack_inline, dim3(grid_for(slots, UNPACK_TPB, 1 << 20)), dim3(UNPACK_TPB), 0, c->stream, S, (const double*)c->d_recv, n, me, c->halo_cap,
-                         S.gslot, c->hostN);
-    }
-    stage_done(s, "exchange + unpack");
-    // the forcings that did not run beside the exchange: where sz_step puts them (forcing_fuse_mode)
-    const int fmode = forcing_fuse_mode(c, coupling && !beside);
-    if (coupling && !fmode && !beside) stage_forcing(c, dt);
-    if (coupling) c->forcing_where = fmode;
-    S.callid = ++c->callid; callid_of[s] = S.callid;
-    if (facc_on && !(S.crec && S.maxnb <= MAXNB)) (void)hipMemsetAsync(c->facc_buf + (size_t)FX_WORDS * c->hostN, 0, (size_t)FX_WORDS * (S.capM - c->hostN) * sizeof(long long), c->stream);      // (see sz_step)
-    if (dbgsync) {          // (the stages of collisions_step one by one)
-      stage_broad(c, false, true, fmode == 1, false); stage_done(s, "neighbour search");
-      stage_elems(c, true); stage_done(s, "element items");
-      stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, fmode == 2 ? (c->precision == 1 ? 2 : 1) : 0, 0); stage_done(s, "narrow phase");
-      stage_reduce(c, 1, -1, dt, 0); stage_done(s, "reduce");
-    } else collisions_step(c, -1, dt, false, true, fmode, lean, false);
-    const bool pack_next = s + 1 < nsteps;
-    if (pack_next && c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }      // (synchronises: once per gather interval)
-    const PackInl pk = tile_pack_args(c);
-    c->acc_mode = accm(s + 1 == nsteps);
-    stage_integrate(c, dt, false, coupling, true, -1, periodic && s + 1 < nsteps ? 1 - (s & 1) : -1, pack_next ? &pk : nullptr);
-    stage_done(s, "integrate");
-  }
-  S.step = 0;
-  if (rmode == 2 && nsteps > 0) stage_reduce(c, 1, -1, dt, 0, true);          // floe.interactions of the step that ended the batch
-  c->tile_dirty = nsteps > 0;
-  rc = sync_and_check(c, h);                     // (drops the halo floes and ghosts of the last step: tile_cleanup -- unless a step is paused)
-  if (rc == SZ_E_HIP) return rc;
-  {          // (the ranks agree on the error word BEFORE anybody decides to run steps again: a rank leaving on its own would hang the others)
-    int all = 0;
-    const int rc2 = comm_agree_bits(c, rc ? (c->last_err_bits ? c->last_err_bits : 1) : 0, &all);
-    if (rc2) return rc2;
-    if (all) return SZ_E_CAPACITY;
-  }
-  // the step that was paused (here or on a peer) and the step a tag ended the batch at, as every rank sees them (comm_agree_steps)
-  int sp = h[C_RETRYSTOP], st_all = h[C_STOP];
-  { const int rc3 = comm_agree_steps(c, h[C_STOP], h[C_RETRYSTOP], &st_all, &sp); if (rc3) return rc3; }
-  if (st_all > 0) h[C_STOP] = st_all;
-  if (!lean || sp <= 0 || (st_all > 0 && st_all < sp)) break;
-  // ---- a pause for the largest narrow variant in step sp
-  const int tsp = tstep0 + sp - 1;
-  const bool coupling_sp = coupling_at(flags, coupling_dt, tsp);
-  HIPCHK(c, hipMemsetAsync(S.cnt + C_RETRYSTOP, 0, sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(S.cnt + C_PAUSED, 0, sizeof(int), c->stream));
-  S.retry_stop = 0; c->retry_seen = true; lean = false;
-  {          // the forcing outputs as of step sp (the steps after it are run again).  BEFORE that step is finished: its integrator reads them, and
-             // the steps enqueued behind it have gone on alternating the sets on the host while their forcing kernels returned at once
+    S.step = 0;
+    if (rfree && nsteps > 0) stage_reduce(c, 1, -1, dt, 0, true);          // floe.interactions of the step that ended the batch
+    c->tile_dirty = nsteps > 0;
+    rc = sync_and_check(c, h);                     // (drops the halo floes and ghosts of the last step: tile_cleanup -- unless a step is paused)
+    if (rc == SZ_E_HIP) return rc;
+    // (the ranks agree on the error word BEFORE anybody decides to run steps again: a rank leaving on its own would hang the others)
+    if (const int ra = tile_agree(c, rc)) return ra;
+    // the step that was paused (here or on a peer) and the step a tag ended the batch at, as every rank sees them (comm_agree_steps)
+    int sp = h[C_RETRYSTOP], st_all = h[C_STOP];
+    { const int rc3 = comm_agree_steps(c, h[C_STOP], h[C_RETRYSTOP], &st_all, &sp); if (rc3) return rc3; }
+    if (st_all > 0) h[C_STOP] = st_all;
+    if (!lean || sp <= 0 || (st_all > 0 && st_all < sp)) break;
+    // ---- a pause for the largest narrow variant in step sp
+    const bool coupling_sp = coupling_at(flags, coupling_dt, tstep0 + sp - 1);
+    HIPCHK(c, clear_stop_words(c, W_RETRYSTOP | W_PAUSED));
+    S.retry_stop = 0; c->retry_seen = true; lean = false;
+    // the forcing outputs as of step sp (the steps after it are run again).  BEFORE that step is finished: its integrator reads them, and
+    // the steps enqueued behind it have gone on alternating the sets on the host while their forcing kernels returned at once
     frc.use(last_set(sp));
     for (int s2 = sp; s2 < nsteps; s2++) fset[s2] = -1;
+    if (h[C_PAUSED] == sp) {          // this rank's step: the variant, then what the pause held back
+      S.step = sp; S.gslot = (sp - 1) & 1; S.callid = callid_of[sp - 1];
+      stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, 0, 2);
+      stage_reduce(c, 1, -1, dt, 0);
+      c->acc_mode = integrator_acc_mode(facc_on, rfree, sp >= nsteps);
+      stage_integrate(c, dt, false, coupling_sp, true, -1, -1);
+      S.step = 0;
+      if (rfree && sp >= nsteps) stage_reduce(c, 1, -1, dt, 0, true);
+    }
+    c->tile_dirty = true;
+    if (sp >= nsteps || (st_all > 0 && st_all <= sp)) {               // (the last step of the batch -- or a peer tagged a floe in this very step: the batch ends with it -- nothing is run again)
+      rc = sync_and_check(c, h);
+      if (rc == SZ_E_HIP) return rc;
+      if (st_all > 0) h[C_STOP] = h[C_STOP] > 0 ? std::min(h[C_STOP], st_all) : st_all;
+      break;
+    }
+    // the rest of the batch again.  The rank that paused: from its floes as they lie after step sp (sz_step's capacity restart does the same);
+    // the others: on from where the pause stopped them (see `fresh`)
+    fresh = h[C_PAUSED] == sp;
+    if (fresh) {
+      tile_cleanup(c);
+      c->grid_live = false; use_static_grid(c);
+      HIPCHK(c, hipMemsetAsync(S.galloc, 0, 32 * sizeof(unsigned long long), c->stream));
+      if (plan.cr) seed_records(c, S, c->hostN);
+    } else {
+      c->tile_dirty = false;          // (nothing to drop: the rows behind the owned floes are the NEXT step's ghosts)
+      // the header records this rank's last pack left say "paused" (the launches enqueued behind the pause wrote the word there): not any more
+      const size_t hstride = (size_t)(c->halo_cap + 1) * halo_rec(S);
+      for (int d = 0; d < n; d++) HIPCHK(c, hipMemsetAsync(c->d_send + (size_t)d * hstride + 2, 0, sizeof(double), c->stream));
+    }
+    s_begin = sp;          // (the ghosts of that step: behind its pack, at the top of the loop)
   }
-  if (h[C_PAUSED] == sp) {          // this rank's step: the variant, then what the pause held back
-    S.step = sp; S.gslot = (sp - 1) & 1; S.callid = callid_of[sp - 1];
-    stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, 0, 2);
-    stage_reduce(c, 1, -1, dt, 0);
-    c->acc_mode = accm(sp >= nsteps);
-    stage_integrate(c, dt, false, coupling_sp, true, -1, -1);
-    S.step = 0;
-    if (rmode == 2 && sp >= nsteps) stage_reduce(c, 1, -1, dt, 0, true);
-  }
-  c->tile_dirty = true;
-  if (sp >= nsteps || (st_all > 0 && st_all <= sp)) {               // (the last step of the batch -- or a peer tagged a floe in this very step: the batch ends with it -- nothing is run again)
-    rc = sync_and_check(c, h);
-    if (rc == SZ_E_HIP) return rc;
-    if (st_all > 0) h[C_STOP] = h[C_STOP] > 0 ? std::min(h[C_STOP], st_all) : st_all;
-    break;
-  }
-  // the rest of the batch again.  The rank that paused: from its floes as they lie after step sp (sz_step's capacity restart does the same);
-  // the others: on from where the pause stopped them (see `fresh`)
-  fresh = h[C_PAUSED] == sp;
-  if (fresh) {
-    tile_cleanup(c);
-    c->grid_live = false; use_static_grid(c);
-    HIPCHK(c, hipMemsetAsync(S.galloc, 0, 32 * sizeof(unsigned long long), c->stream));
-    if (S.crec) hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(c->hostN, 256)), dim3(256), 0, c->stream, S, c->hostN);
-  } else {
-    c->tile_dirty = false;          // (nothing to drop: the rows behind the owned floes are the NEXT step's ghosts)
-    // the header records this rank's last pack left say "paused" (the launches enqueued behind the pause wrote the word there): not any more
-    const size_t hstride = (size_t)(c->halo_cap + 1) * halo_rec(S);
-    for (int d = 0; d < n; d++) HIPCHK(c, hipMemsetAsync(c->d_send + (size_t)d * hstride + 2, 0, sizeof(double), c->stream));
-  }
-  s_begin = sp;          // (the ghosts of that step: behind its pack, at the top of the loop)
-  }
-  {
-    int all = 0;
-    const int rc2 = comm_agree_bits(c, rc ? (c->last_err_bits ? c->last_err_bits : 1) : 0, &all);
-    if (rc2) return rc2;
-    if (all) return SZ_E_CAPACITY;
-  }
+  if (const int ra = tile_agree(c, rc)) return ra;
   const int done = h[C_STOP] > 0 ? std::min(h[C_STOP], (int)nsteps) : nsteps;
   if (steps_done) *steps_done = done;
   frc.use(last_set(done)); frc.keep = true;          // the forcing outputs of the last step that ran (see `beside` above)
@@ -3970,14 +3996,38 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   c->inter_any = true; c->inter_lost = false;
   // status.fuse_idx of the step that ended the batch (as sz_step: only that step can have produced fuse pairs)
   if (done > 0 && (h[C_STOP] > 0 || (flags & SZ_NO_STOP))) {
-    const int tlast = tstep0 + done - 1;
-    const bool last_coupled = coupling_at(flags, coupling_dt, tlast);
     c->gi_pending_n = h[C_NGHOSTS]; c->gi_pending_slot = (done - 1) & 1; c->gi_pending = true;
-    rc = tile_fuse_replay(c, h, last_coupled);
+    rc = tile_fuse_replay(c, h, coupling_at(flags, coupling_dt, tstep0 + done - 1));
     c->gi_pending = false;
   }
   c->fuse_lists.resize(c->hostM);
   return rc;
+}
+}  // namespace
+
+// the centre of this rank's tile (optional, after sz_tile_setup): in a periodic direction the owned box of the FIRST gather then takes every
+// centroid at its image nearest to it, as the later gathers do with the centre of the box before (sz_k_owned_box)
+int sz_tile_set_center(sz_ctx* c, double x, double y) {
+  if (!c || !c->S.tiled || c->tile_margin <= 0) { if (c) c->err = "sz_tile_set_center needs sz_tile_setup"; return SZ_E_STATE; }
+  c->tile_box_ctr[0] = x; c->tile_box_ctr[1] = y; c->tile_box_valid = true;
+  return SZ_OK;
+}
+// nsteps x timestep_sim! of a tiled run, collectively on every rank (same arguments everywhere)
+int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
+  if (steps_done) *steps_done = 0;
+  if (c && c->frac_kind != SZ_FRAC_OFF) { c->err = "tiled runs do not evaluate fracture criteria (the mean height needs an all-reduce over the ranks): sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
+  if (c && !c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
+  if (!c || !c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0) { if (c) c->err = "sz_tile_run needs sz_tile_enable and sz_tile_setup after the last sz_upload_floes"; return SZ_E_STATE; }
+  if (nsteps < 0) return SZ_E_ARG;
+  (void)hipSetDevice(c->device);
+  // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
+  // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
+  // Needs what the inline ghost maker needs (rings that fit the one-launch integrator, the static grid).  Otherwise: the list-based steps
+  // of sz_tile_step.  Either driver runs under this one scope.
+  const bool inl = (flags & SZ_COLLISIONS_ON) && c->grid_ok && !c->two_way &&
+                   std::max(c->max_ring, c->max_ring_tiled) <= MV_RING && ((flags & SZ_COUPLING_ON) == 0 || c->have_fields);
+  BatchModes modes(c);
+  return inl ? tile_run_inline(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done) : tile_run_listed(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done);
 }
 
 // counts of the last sz_halo_pack per destination rank (synchronises); used to size the exchange buffers
