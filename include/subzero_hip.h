@@ -18,6 +18,8 @@
  *   sz_collide_domain             <- floe_domain_interaction!(floe, domain, consts, Δt,
  *                                    max_overlap)                           collisions.jl:594-662
  *   sz_remove_ghosts              <- ghost-row deletion in timestep_sim!    src/simulation_components/simulation.jl:138-144
+ *   sz_remove_floes               <- remove_floes!(floes, grid, domain, dissolved, floe_settings), where simplify_floes!
+ *                                    reduces to it                         src/physical_processes/simplification.jl:279-314
  *   sz_timestep_coupling          <- timestep_coupling!(model, Δt, consts, coupling_settings,
  *                                    floe_settings), one-way part           src/physical_processes/coupling.jl:1705-1738
  *   sz_timestep_floe_properties   <- timestep_floe_properties!(floes, tstep, Δt, floe_settings)
@@ -289,6 +291,35 @@ int sz_weld_overlaps(sz_ctx *ctx, int32_t nx, int32_t ny, double max_weld_area,
    is out of bounds, welding.jl:38 breaks there); the candidate pairs (before the clip) of the last table pass */
 int sz_debug_weld_bins(sz_ctx *ctx, int32_t nx, int32_t ny, int32_t *bin);
 int sz_debug_weld_npairs(sz_ctx *ctx, int32_t *n);
+
+/* ---- removal and dissolution on the device (csrc/sz_remove.hpp): remove_floes! (simplification.jl:279-314) where simplify_floes!
+   reduces to it -- no floe tagged fuse and no ring over max_vertices, so the pass needs no polygon union, no smoothing and no random number.
+   sz_remove_floes runs the pass once on the state as it is, over the parents (ghosts in the list, or a tiled context -- row numbers are global
+   there --: SZ_E_STATE): in the reference's branch order a floe that is not tagged remove and lies under min_floe_area or min_floe_height
+   dissolves, a floe tagged remove is removed (not dissolved as well), the others stay, in their order, with status active.  Every column
+   sz_upload_floes takes moves to its new row, with the rings, the sub-floe points and the per-floe interaction rows (partner numbers left as they
+   are, as the reference leaves them); everything derived is as sz_upload_floes leaves it.  *n_removed / *n_dissolved count the two kinds.
+   *done = 0: the pass is DECLINED and nothing has changed -- a floe is tagged fuse, a ring has more than max_vertices points (GI.npoint counts
+   the closing point, as sz_simplify_check), no floe would be left, or a dissolving floe's cell index leaves the matrix (below).  Not an error:
+   the host's simplify_floes! takes over.
+   The dissolved mass goes to the RUNNING ocean.dissolved lattice the context holds, (Nx + 1) (Ny + 1) doubles in the layout of
+   sz_download_ocean_stress, zero after sz_set_fields: the host uploads the matrix it has (sz_upload_dissolved) and later overwrites its own with
+   sz_download_dissolved -- deltas would change the summation order.  The dissolving floes are walked in descending row order, as
+   reverse(eachindex(floes)) does: sums into one cell agree to the bit.  dissolve_floe! (simplification.jl:18-32) indexes its matrix as
+   [yidx, xidx]; the quirk is kept (lattice element [yidx - 1][xidx - 1]).  Where that index lies outside the matrix the reference throws a
+   BoundsError (non-square grids only): the pass is declined.
+   sz_set_removal(on, SimplificationSettings.max_vertices -- INT32_MAX with smooth_vertices_on == false --, FloeSettings.min_floe_area,
+   min_floe_height): off by default.  sz_step with removal set, in batches that stop: a tag that ends a segment before the batch's last step is
+   followed by the pass; done = the batch goes on at the next step (*steps_done counts on), declined = it ends there as without removal.  On a
+   fracture step with a candidate, or a welding step of a context with welding set, the batch ends as before (simulation.jl:172-214: fracture,
+   weld, then simplify) and the caller calls sz_remove_floes itself.  The batch's own last step is not looked at.  SZ_NO_STOP batches and
+   contexts without removal set run as before: not a launch more.
+   sz_download_origin: per parent the row it had at the last sz_upload_floes (the identity after an upload, composed through the passes). */
+int sz_set_removal(sz_ctx *ctx, int32_t on, int32_t max_vertices, double min_floe_area, double min_floe_height);
+int sz_remove_floes(sz_ctx *ctx, int32_t *done, int32_t *n_removed, int32_t *n_dissolved);
+int sz_upload_dissolved(sz_ctx *ctx, const double *dissolved);
+int sz_download_dissolved(sz_ctx *ctx, double *dissolved);
+int sz_download_origin(sz_ctx *ctx, int32_t *origin);
 
 /* ---- measurement: HIP-event time per kernel class, accumulated since the last reset, on the
    stream the kernels are launched on; launches = number of timed launches of that class.

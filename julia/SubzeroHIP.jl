@@ -203,6 +203,7 @@ mutable struct HIPEngine
     max_vertices::Int32          # SimplificationSettings / FloeSettings values of the simulation the engine was made for
     min_floe_area::Float64       # (sz_simplify_check)
     min_floe_height::Float64
+    host_rows::Vector{Int}       # per host row the row it had at the last upload! (the device removes floes: origin, pull_state!)
 end
 
 const ENGINE = Ref{Union{Nothing, HIPEngine}}(nothing)
@@ -230,7 +231,7 @@ function enable!(sim; device::Integer = 0)
     model, c, cs, fs, cp = sim.model, sim.consts, sim.collision_settings, sim.floe_settings, sim.coupling_settings
     grid = model.grid
     eng = HIPEngine(ctx, cp.two_way_coupling_on, grid.Nx, grid.Ny, Int32(sim.simp_settings.max_vertices),
-                    Float64(fs.min_floe_area), Float64(fs.min_floe_height))
+                    Float64(fs.min_floe_area), Float64(fs.min_floe_height), Int[])
     λ = hasproperty(fs.stress_calculator, :λ) ? Float64(fs.stress_calculator.λ) :
         error("SubzeroHIP implements DecayAreaScaledCalculator (stress_calculators.jl:82) only")
     p = Ref(SzParams(c.E, c.ν, c.μ, c.ρo, c.ρa, c.Cd_io, c.Cd_ia, c.f, c.turnθ, cs.floe_floe_max_overlap,
@@ -375,6 +376,7 @@ function upload!(eng::HIPEngine, floes, n_parents)
         check(eng, @ccall lib.sz_upload_floes(eng.ctx::Ptr{Cvoid}, length(floes)::Int64, n_parents::Int64,
                                               P.cols::Ref{SzFloeColumns})::Cint)
     end
+    eng.host_rows = collect(1:length(floes))
     return P
 end
 
@@ -655,6 +657,54 @@ function timestep_welding!(floes, max_floe_id, table, weld_settings, floe_settin
     return max_floe_id
 end
 
+# ------------------------------------------------------------------------------------------------ removal and dissolution
+"""
+    set_removal!(eng, sim)
+
+`remove_floes!` (simplification.jl:279-314) on the device (`sz_set_removal`): `SimplificationSettings.max_vertices` (`typemax(Int32)` with
+`smooth_vertices_on == false`: no ring is then smoothed) and `FloeSettings.min_floe_area` / `min_floe_height`.  A batch of `sz_step` then goes
+on past a step that tagged a floe `remove`, unless that step needs the host (a `fuse` tag, a ring to smooth, a fracture candidate, a welding step).
+"""
+function set_removal!(eng::HIPEngine, sim)
+    maxv = sim.simp_settings.smooth_vertices_on ? Int32(min(sim.simp_settings.max_vertices, typemax(Int32))) : typemax(Int32)
+    check(eng, @ccall lib.sz_set_removal(eng.ctx::Ptr{Cvoid}, Int32(1)::Int32, maxv::Int32, eng.min_floe_area::Float64,
+                                         eng.min_floe_height::Float64)::Cint)
+    return
+end
+
+"""
+    remove_floes!(eng) -> (done, n_removed, n_dissolved)
+
+One pass of `remove_floes!` on the resident state (`sz_remove_floes`).  `done == false`: the pass was declined and nothing changed --
+`simplify_floes!` has more to do than removing, and runs on the host.
+"""
+function remove_floes!(eng::HIPEngine)
+    done, nr, nd = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    check(eng, @ccall lib.sz_remove_floes(eng.ctx::Ptr{Cvoid}, done::Ptr{Int32}, nr::Ptr{Int32}, nd::Ptr{Int32})::Cint)
+    return (done = done[] != 0, n_removed = Int(nr[]), n_dissolved = Int(nd[]))
+end
+
+# per resident parent the (1-based) row it had at the last upload!
+function origin(eng::HIPEngine)
+    n = Int(stats(eng).N)
+    o = Vector{Int32}(undef, max(n, 1))
+    check(eng, @ccall lib.sz_download_origin(eng.ctx::Ptr{Cvoid}, o::Ptr{Int32})::Cint)
+    return Int.(o[1:n]) .+ 1
+end
+
+# ocean.dissolved: the host's matrix to the device, and the device's running lattice back over it
+function push_dissolved!(eng::HIPEngine, ocean)
+    d = lattice(ocean.dissolved)
+    check(eng, @ccall lib.sz_upload_dissolved(eng.ctx::Ptr{Cvoid}, d::Ptr{Float64})::Cint)
+    return
+end
+function pull_dissolved!(eng::HIPEngine, ocean)
+    d = Vector{Float64}(undef, (eng.Nx + 1) * (eng.Ny + 1))
+    check(eng, @ccall lib.sz_download_dissolved(eng.ctx::Ptr{Cvoid}, d::Ptr{Float64})::Cint)
+    ocean.dissolved .= unlattice(d, eng.Nx, eng.Ny)
+    return
+end
+
 # ------------------------------------------------------------------------------------------------ resident mode
 """
     run_resident!(sim, eng; start_tstep = 0, batch = 500)
@@ -677,12 +727,17 @@ overlap table of the pairs `timestep_welding!` would clip, and a batch also ends
 state is then pulled and `timestep_welding!(floes, max_floe_id, table, ...)` of this module welds from the table, then `simplify_floes!` as in
 the reference.  With an empty table the reference's call changes nothing and draws no random number; it is skipped.  The reference hands
 `timestep_welding!` no `rng` (a fresh `Xoshiro()` per call), and so does this loop.
+
+Removal (`set_removal!`): where `simplify_floes!` reduces to `remove_floes!` -- nothing to fuse, no ring to smooth -- the device deletes the
+rows and adds the dissolved mass to its copy of `ocean.dissolved`, inside a batch (which then runs on) or, behind a batch's last step, through
+`remove_floes!(eng)`.  The host's rows follow at the next `pull_state!`, which deletes the rows `origin(eng)` no longer names.
 """
 function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Integer = 500)
     sim.ridgeraft_settings.ridge_raft_on &&
         error("run_resident!: ridging / rafting needs the floes on the host every step: use run!(sim)")
     set_fracture!(eng, sim)
     set_welding!(eng, sim)
+    set_removal!(eng, sim)
     fractures = sim.fracture_settings.fractures_on
     ws = sim.weld_settings
     Subzero.startup_sim(sim, nothing, 1)
@@ -692,11 +747,13 @@ function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Int
     max_floe_id = isempty(floes) ? 0 : maximum(floes.id)
     P = upload!(eng, floes, length(floes))
     upload_interactions!(eng, floes)
+    push_dissolved!(eng, sim.model.ocean)
+    ocean = sim.model.ocean
     tstep, last = start_tstep, start_tstep + sim.nΔt
     dirty = false                                    # the device state is ahead of the host's
     while tstep <= last
         if output_due(sim.writers, tstep, start_tstep)
-            dirty && (pull_state!(eng, floes, P); dirty = false)
+            dirty && (P = pull_state!(eng, floes, P, ocean); dirty = false)
             Subzero.add_ghosts!(floes, sim.model.domain)           # write_data! sees the ghosts (simulation.jl:102-105)
             Subzero.write_data!(sim, tstep, start_tstep)
             remove_ghosts!(floes)
@@ -709,7 +766,7 @@ function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Int
         # the batch's last step was a fracture step on which a floe fractures: fracture_floes! on the host, before simplify_floes!
         fracture_now = fractures && done[] > 0 && mod(tstep - 1, sim.fracture_settings.Δt) == 0 && fracture_candidates(eng) > 0
         if fracture_now
-            pull_state!(eng, floes, P)
+            P = pull_state!(eng, floes, P, ocean)
             max_floe_id = Subzero.fracture_floes!(floes, max_floe_id, sim.rng, sim.fracture_settings, sim.floe_settings, sim.Δt)
         end
         # ... and a welding step: the table of the floes as they are now (behind fracture_floes!, as in timestep_sim!), welded on the host
@@ -721,7 +778,7 @@ function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Int
             end
             table = weld_overlaps(eng, ws.Nxs[weld_idx], ws.Nys[weld_idx], ws.max_weld_area)
             if !isempty(table.i)
-                fracture_now || pull_state!(eng, floes, P)
+                fracture_now || (P = pull_state!(eng, floes, P, ocean))
                 max_floe_id = timestep_welding!(floes, max_floe_id, table, ws, sim.floe_settings, weld_idx, sim.Δt)
                 weld_now = true
             end
@@ -730,23 +787,41 @@ function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Int
         todo = Vector{Int64}(undef, 4)
         host_ahead || check(eng, @ccall lib.sz_simplify_check(eng.ctx::Ptr{Cvoid}, eng.max_vertices::Int32, eng.min_floe_area::Float64,
                                                               eng.min_floe_height::Float64, todo::Ptr{Int64})::Cint)
+        # only removals and dissolutions (nothing to fuse, no ring to smooth): the device's pass instead of pull, simplify_floes!, upload
+        if !host_ahead && any(!iszero, todo) && todo[2] == 0 && todo[3] == 0 && remove_floes!(eng).done
+            todo .= 0
+        end
         if host_ahead || any(!iszero, todo)        # simplify_floes! has work: it runs on the host, on the full state
-            host_ahead || pull_state!(eng, floes, P)
+            host_ahead || (P = pull_state!(eng, floes, P, ocean))
             max_floe_id = Subzero.simplify_floes!(sim.model, max_floe_id, sim.simp_settings, sim.collision_settings,
                                                   sim.floe_settings, sim.Δt, sim.rng)
             P = upload!(eng, floes, length(floes)); upload_interactions!(eng, floes)
+            push_dissolved!(eng, ocean)
             dirty = false
         end
     end
-    dirty && pull_state!(eng, floes, P)
+    dirty && (P = pull_state!(eng, floes, P, ocean))
     sim.coupling_settings.two_way_coupling_on && pull_ocean_stress!(eng, sim.model.ocean)
     pull_moving_boundaries!(eng, sim.model.domain)
     Subzero.teardown_sim(sim)
     return
 end
 
-# the whole floe state back into the StructArray (columns, geometry, interactions, status + fuse lists)
-function pull_state!(eng::HIPEngine, floes, P::Packed)
+# the whole floe state back into the StructArray (columns, geometry, interactions, status + fuse lists).  The device may have removed floes
+# since the upload (set_removal!): the host rows `origin` no longer names go first, `P` is made again for the rows that stay (the returned one
+# replaces the caller's), and the running ocean.dissolved lattice comes back with the floes.
+function pull_state!(eng::HIPEngine, floes, P::Packed, ocean = nothing)
+    o = origin(eng)
+    if length(o) != length(floes) && length(eng.host_rows) == length(floes)
+        named = Set(o)
+        for i in reverse(eachindex(eng.host_rows))
+            eng.host_rows[i] in named && continue
+            StructArrays.foreachfield(f -> deleteat!(f, i), floes)
+            deleteat!(eng.host_rows, i)
+        end
+        P = pack(floes, length(floes))
+    end
+    isnothing(ocean) || pull_dissolved!(eng, ocean)
     M = length(floes)
     download!(eng, floes, P)
     unpack_geometry!(floes, P); unpack_status!(floes, P)
@@ -763,7 +838,7 @@ function pull_state!(eng::HIPEngine, floes, P::Packed)
         floes.collision_force[i][1, 1] = P.coll_fx[i]; floes.collision_force[i][1, 2] = P.coll_fy[i]
         empty!(floes.status[i].fuse_idx); append!(floes.status[i].fuse_idx, Int.(fidx[foff[i]+1:foff[i+1]]) .+ 1)
     end
-    return
+    return P
 end
 
 # ghost rows off again (simulation.jl:138-144)

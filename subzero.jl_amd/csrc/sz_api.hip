@@ -21,6 +21,7 @@
 #include "sz_migrate.hpp"
 #include "sz_fracture.hpp"
 #include "sz_weld.hpp"
+#include "sz_remove.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 
 using namespace sz;
@@ -160,6 +161,10 @@ struct sz_ctx {
   WeldArgs weld{}; int *weld_cell_cnt = nullptr, *weld_cell_slots = nullptr, *weld_cell_ovf = nullptr, *weld_cell_items = nullptr; double* weld_bounds = nullptr;
   WeldDev weld_h{}; double weld_h_grid[8] = { 0 };          // host sides of the two small uploads of a pass
   int weld_npairs = 0;              // candidate pairs of the last pass (sz_debug_weld_npairs)
+  // removal (sz_set_removal; sz_remove.hpp): SimplificationSettings.max_vertices (INT32_MAX: smoothing off) and FloeSettings' minimum area / height;
+  // the running ocean.dissolved lattice (with the fields: zero after sz_set_fields); per parent the row it had at the last sz_upload_floes
+  bool rm_on = false; int rm_max_vertices = 0x7fffffff; double rm_min_area = 0, rm_min_height = 0;
+  double* dissolved = nullptr; int* origin = nullptr; Pool rm_allocs;
   bool last_stopped = false;        // the last batch of resident steps ended on a stop request (tag, fracture candidate), not at its last step
   bool maybe_tagged = false;        // a parent may be non-active on the device (an upload said so, a batch ended on a tag, a process-mode call ran):
                                     // the next batch then runs its first step on its own (see sz_step)
@@ -1000,6 +1005,7 @@ void sz_destroy(sz_ctx* c) {
   (void)hipFree(c->d_stats); (void)hipFree(c->S.acc);
   (void)hipFree(c->frac_d); (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx);
   free_pool(c->weld_allocs); (void)hipFree(c->weld_tmp);
+  free_pool(c->rm_allocs);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
   (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2);
   (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join);
@@ -1047,7 +1053,7 @@ int sz_set_fields(sz_ctx* c, int32_t Nx, int32_t Ny, double x0, double xf, doubl
   (void)hipSetDevice(c->device);
   State& S = c->S;
   size_t n = (size_t)(Nx + 1) * (Ny + 1);
-  free_pool(c->field_allocs);
+  free_pool(c->field_allocs); c->dissolved = nullptr;
   // the ocean / atmosphere temperatures (sz_set_temps) and the stress fields stay when the lattice keeps its shape:
   // re-uploading changing currents into one context must not reset them to zero
   if (c->tw_ncell != n) { free_pool(c->tw_field_allocs); c->tw_ncell = 0; c->temps_set = false; }
@@ -1065,6 +1071,13 @@ int sz_set_fields(sz_ctx* c, int32_t Nx, int32_t Ny, double x0, double xf, doubl
     HIPCHK(c, hipMalloc(&q, n * 8 * sizeof(double)));
     c->field_allocs.push_back(q);
     S.nodes = (double*)q;
+  }
+  {          // ocean.dissolved (sz_remove.hpp): starts at zero with every new set of fields
+    void* q = nullptr;
+    HIPCHK(c, hipMalloc(&q, n * sizeof(double)));
+    HIPCHK(c, hipMemset(q, 0, n * sizeof(double)));
+    c->field_allocs.push_back(q);
+    c->dissolved = (double*)q;
   }
   S.Nx = Nx; S.Ny = Ny; S.gx0 = x0; S.gxf = xf; S.gy0 = y0; S.gyf = yf; S.gdx = (xf - x0) / Nx; S.gdy = (yf - y0) / Ny; S.rdx = 1.0 / S.gdx; S.rdy = 1.0 / S.gdy;
   hipLaunchKernelGGL(sz_k_interleave_fields, dim3(grid_for((long long)n, 256)), dim3(256), 0, c->stream, S);
@@ -1274,6 +1287,8 @@ int sz_upload_floes(sz_ctx* c, int64_t M64, int64_t N64, const sz_floe_columns* 
   own_set_carved(c);          // (set 0 -- gpar above -- is what this upload carved)
   DA(tagA, S.capM + 1);
   if (!tag0.empty()) { H2D(S.tagA, tag0.data(), M, int); HIPCHK(c, hipStreamSynchronize(c->stream)); }
+  if ((rc = dalloc(c, &c->origin, (size_t)S.capM, c->allocs))) return rc;
+  { std::vector<int> o(std::max(M, 1)); for (int i = 0; i < M; i++) o[i] = i; H2D(c->origin, o.data(), M, int); HIPCHK(c, hipStreamSynchronize(c->stream)); }
   DA(stamps, 512 + 8 * 8000);
   trim_pool(c->allocs);
   free_pool(c->comm_allocs);          // (sized for the old field's capM; a migration keeps its capacities and these chunks with them)
@@ -2543,28 +2558,193 @@ int sz_debug_weld_npairs(sz_ctx* c, int32_t* n) {
   return SZ_OK;
 }
 
-// sz_step with welding set (sz_set_welding), in batches that stop: the batch is cut into segments that END on a welding step (tstep % dts[k] == 0,
+// ---------------------------------------------------------------- removal and dissolution on the device (sz_remove.hpp)
+int sz_set_removal(sz_ctx* c, int32_t on, int32_t max_vertices, double min_floe_area, double min_floe_height) {
+  if (!c) return SZ_E_ARG;
+  if (on && (max_vertices < 0 || !(min_floe_area >= 0.0) || !(min_floe_height >= 0.0))) { c->err = "sz_set_removal: max_vertices, min_floe_area and min_floe_height must not be negative"; return SZ_E_ARG; }
+  c->rm_on = on != 0;
+  if (on) { c->rm_max_vertices = max_vertices; c->rm_min_area = min_floe_area; c->rm_min_height = min_floe_height; }
+  return SZ_OK;
+}
+
+namespace {
+// remove_floes! on the parents as they lie (no ghosts in the list, a single context).  *done = 0: declined, nothing has changed.  Two host
+// synchronisations: the verdict (counts, what stays), then the end of the pass.  The capacities the context was carved with stay; what is derived
+// from the rows is rebuilt as a migration rebuilds it (field_placed: as sz_upload_floes leaves it).
+int remove_pass(sz_ctx* c, int* done, int* n_removed, int* n_dissolved) {
+  *done = 0; *n_removed = 0; *n_dissolved = 0;
+  State& S = c->S;
+  const int N = c->hostN;
+  int rc;
+  if (N <= 0) return SZ_OK;          // (no floe would be left)
+  world_rings(c);
+  Pool& P = c->rm_allocs;
+  reset_pool(P);
+  RmArgs A{};
+  A.n = N; A.max_vertices = c->rm_max_vertices; A.min_area = c->rm_min_area; A.min_height = c->rm_min_height;
+  const size_t n1 = (size_t)N + 2;
+  if ((rc = dalloc(c, &A.d, 1, P)) || (rc = dalloc(c, &A.keep, n1, P)) || (rc = dalloc(c, &A.dis, n1, P)) || (rc = dalloc(c, &A.kv, n1, P)) || (rc = dalloc(c, &A.ks, n1, P)) ||
+      (rc = dalloc(c, &A.newrow, n1, P)) || (rc = dalloc(c, &A.dpos, n1, P)) || (rc = dalloc(c, &A.ovoff, n1, P)) || (rc = dalloc(c, &A.osoff, n1, P)) ||
+      (rc = dalloc(c, &A.src, n1, P)) || (rc = dalloc(c, &A.nvoff, n1, P)) || (rc = dalloc(c, &A.nsoff, n1, P)) || (rc = dalloc(c, &A.dlist, n1, P))) return rc;
+  if (c->have_fields && c->dissolved) {
+    A.x0 = S.gx0; A.y0 = S.gy0; A.dx = S.gdx; A.dy = S.gdy; A.Nx = S.Nx; A.Ny = S.Ny; A.dissolved = c->dissolved;
+    A.per_e = c->h_kinds[SZ_EAST] == SZ_PERIODIC; A.per_n = c->h_kinds[SZ_NORTH] == SZ_PERIODIC;
+  }
+  HIPCHK(c, hipMemsetAsync(A.d, 0, sizeof(RmDev), c->stream));
+  const int nb = grid_for(N, 256, 2048);
+  hipLaunchKernelGGL(sz_k_rm_flags, dim3(nb), dim3(256), 0, c->stream, S, A);
+  scan(c, A.keep, A.newrow, N, C_N, 0, -1);
+  scan(c, A.dis, A.dpos, N, C_N, 0, -1);
+  scan(c, A.kv, A.ovoff, N, C_N, 0, -1);
+  scan(c, A.ks, A.osoff, N, C_N, 0, -1);
+  hipLaunchKernelGGL(sz_k_rm_rows, dim3(nb), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL(sz_k_rm_dissolve, dim3(1), dim3(64), 0, c->stream, S, A);
+  RmDev R{};
+  HIPCHK(c, hipMemcpyAsync(&R, A.d, sizeof(RmDev), hipMemcpyDeviceToHost, c->stream));
+  if ((rc = sync_and_check(c))) return rc;
+  if (R.declined & RM_NO_LATTICE) { c->err = "sz_remove_floes: a floe dissolves, and the ocean.dissolved lattice needs the grid (sz_set_fields)"; return SZ_E_STATE; }
+  if (R.declined) return SZ_OK;
+  const int Nn = R.Nn, Vn = R.Vn, NSn = R.NSn;
+  if (Nn <= 0 || Nn > N || Nn + R.n_removed + R.n_dissolved != N || Vn < 0 || NSn < 0) { c->err = "sz_remove_floes: bad counts"; return SZ_E_HIP; }
+  *done = 1; *n_removed = R.n_removed; *n_dissolved = R.n_dissolved;
+  if (Nn == N) return SZ_OK;          // nothing leaves, and every status is `active` already (no tag but remove / fuse exists)
+  if (c->gi_pending && c->gi_valid) { if ((rc = gi_fetch(c))) return rc; }
+  c->gi_pending = false;
+  // ---- the rows into their new places, gathered beside the old ones first
+  double** d_cols = nullptr; double *d_tmp = nullptr, *d_tsx = nullptr, *d_tsy = nullptr, *d_trows = nullptr; double2* d_tv = nullptr; int *d_torigin = nullptr, *d_tcnt = nullptr;
+  if ((rc = dalloc(c, &d_cols, 32, P)) || (rc = dalloc(c, &d_tmp, (size_t)39 * Nn, P)) || (rc = dalloc(c, &d_tv, (size_t)Vn, P)) || (rc = dalloc(c, &d_tsx, (size_t)NSn, P)) ||
+      (rc = dalloc(c, &d_tsy, (size_t)NSn, P)) || (rc = dalloc(c, &d_torigin, (size_t)Nn, P)) || (rc = dalloc(c, &d_tcnt, (size_t)Nn, P)) ||
+      (rc = dalloc(c, &d_trows, (size_t)Nn * S.rowcap * 7, P))) return rc;
+  double* const hcols[MIG_NSC + 3] = { S.cx, S.cy, S.rmax, S.area, S.height, S.mass, S.moment, S.alpha, S.u, S.v, S.xi, S.p_dxdt, S.p_dydt, S.p_dalphadt,
+                                       S.p_dudt, S.p_dvdt, S.p_dxidt, S.fxOA, S.fyOA, S.trqOA, S.hflx, S.overarea, S.cfx, S.cfy, S.ctrq, S.sa, S.si, S.strain };
+  HIPCHK(c, hipMemcpyAsync(d_cols, hcols, sizeof(hcols), hipMemcpyHostToDevice, c->stream));
+  const int nbw = grid_for((long long)Nn * 64, 256, 4096);
+  hipLaunchKernelGGL(sz_k_mig_gather, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, (const double*)nullptr, (const double*)nullptr,
+                     (double* const*)d_cols, d_tmp);
+  hipLaunchKernelGGL(sz_k_mig_points, dim3(nbw), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, (const double*)nullptr, (const double*)nullptr,
+                     (const int*)A.nvoff, (const int*)A.nsoff, d_tv, d_tsx, d_tsy);
+  hipLaunchKernelGGL(sz_k_rm_gather_rows, dim3(nbw), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, (const int*)c->origin, d_torigin, d_tcnt, d_trows);
+  hipLaunchKernelGGL(sz_k_mig_scatter, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (double* const*)d_cols, (const double*)d_tmp);
+  hipLaunchKernelGGL(sz_k_rm_scatter_rows, dim3(nbw), dim3(256), 0, c->stream, S, Nn, c->origin, (const int*)d_torigin, (const int*)d_tcnt, (const double*)d_trows);
+  HIPCHK(c, hipMemsetAsync(S.inter_cnt + Nn, 0, (size_t)(N - Nn) * sizeof(int), c->stream));
+  if (Vn) HIPCHK(c, hipMemcpyAsync(S.vxy, d_tv, (size_t)Vn * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(S.voff, A.nvoff, ((size_t)Nn + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  if (c->pts_N) {
+    if (NSn) {
+      HIPCHK(c, hipMemcpyAsync(S.sx, d_tsx, (size_t)NSn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(S.sy, d_tsy, (size_t)NSn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(S.soff, A.nsoff, ((size_t)Nn + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  }
+  // ---- the field is placed: as behind the copies of sz_upload_floes (the estimates and bounds the context held still bound the floes that stay)
+  const bool inter_any = c->inter_any, inter_lost = c->inter_lost;
+  if ((rc = field_placed(c, Nn, 0, Vn, c->pts_N ? Nn : 0, std::min(Nn, c->gl_est), c->rmax_max, c->rmax_hint))) return rc;
+  c->inter_any = inter_any; c->inter_lost = inter_lost;
+  c->maybe_tagged = false; c->grid_live = false;
+  c->max_ring = R.max_ring; if (c->pts_N) c->max_sub = R.max_sub;          // (as an upload of the floes that stay would find them)
+  return SZ_OK;
+}
+int removal_checks(sz_ctx* c, const char* who) {
+  if (!c->have_floes) { c->err = std::string(who) + ": no floes uploaded"; return SZ_E_STATE; }
+  if (c->S.tiled) { c->err = std::string(who) + ": tiled contexts do not remove floes on the device (row numbers are global there): sz_set_removal(0)"; return SZ_E_STATE; }
+  return SZ_OK;
+}
+}  // namespace
+
+int sz_remove_floes(sz_ctx* c, int32_t* done, int32_t* n_removed, int32_t* n_dissolved) {
+  if (done) *done = 0;
+  if (n_removed) *n_removed = 0;
+  if (n_dissolved) *n_dissolved = 0;
+  if (!c || !done) return SZ_E_ARG;
+  if (int rc = removal_checks(c, "sz_remove_floes")) return rc;
+  (void)hipSetDevice(c->device);
+  if (int rc = sync_and_check(c)) return rc;          // hostM / hostN current, nothing pending
+  if (c->hostM != c->hostN) { c->err = "sz_remove_floes: ghosts are in the list (sz_remove_ghosts first): the pass runs over the parents alone"; return SZ_E_STATE; }
+  leave_resident(c);
+  int d = 0, nr = 0, nd = 0;
+  if (int rc = remove_pass(c, &d, &nr, &nd)) return rc;
+  *done = d;
+  if (n_removed) *n_removed = nr;
+  if (n_dissolved) *n_dissolved = nd;
+  return SZ_OK;
+}
+int sz_upload_dissolved(sz_ctx* c, const double* dissolved) {
+  if (!c || !dissolved) return SZ_E_ARG;
+  if (!c->have_fields || !c->dissolved) { c->err = "sz_upload_dissolved: the lattice comes with the fields (sz_set_fields)"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->dissolved, dissolved, (size_t)(c->S.Nx + 1) * (c->S.Ny + 1) * sizeof(double), hipMemcpyHostToDevice));
+  return SZ_OK;
+}
+int sz_download_dissolved(sz_ctx* c, double* dissolved) {
+  if (!c || !dissolved) return SZ_E_ARG;
+  if (!c->have_fields || !c->dissolved) { c->err = "sz_download_dissolved: the lattice comes with the fields (sz_set_fields)"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(dissolved, c->dissolved, (size_t)(c->S.Nx + 1) * (c->S.Ny + 1) * sizeof(double), hipMemcpyDeviceToHost));
+  return SZ_OK;
+}
+int sz_download_origin(sz_ctx* c, int32_t* origin) {
+  if (!c || !origin) return SZ_E_ARG;
+  if (!c->have_floes || !c->origin) { c->err = "sz_download_origin: no floes uploaded"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  if (int rc = sync_and_check(c)) return rc;
+  if (c->hostN > 0) HIPCHK(c, hipMemcpy(origin, c->origin, (size_t)c->hostN * sizeof(int), hipMemcpyDeviceToHost));
+  return SZ_OK;
+}
+
+// sz_step with welding set (sz_set_welding) or removal set (sz_set_removal), in batches that stop.
+// Welding: the batch is cut into segments that END on a welding step (tstep % dts[k] == 0,
 // timestep_welding! runs behind timestep_floe_properties!, simulation.jl:184-202).  A segment is an ordinary batch through the drivers above -- its
 // last step keeps its ghosts, the rows come home behind it, segments of pipe_min_steps or more stay pipelined -- then the overlap table of that
 // step's (Nx, Ny): empty = the reference's call would change nothing and draw no random number, and the next segment starts; not empty = the batch
 // ends there (steps_done counts the welding step; sz_weld_overlaps gives the caller the same table again).  A tag or a fracture candidate ends the
 // segment and the batch first, as fracture_floes! runs before the welding.  The batch's own last step is not looked at: the caller sees that the
-// batch ended on a welding step and asks.  Batches that run through (SZ_NO_STOP) and contexts without welding take the driver as it is.
+// batch ended on a welding step and asks.
+// Removal: a segment that a tag ends before the batch's last step is followed by the pass of sz_remove.hpp (the segment's ghosts are detached by
+// then, as at the start of a new batch); done = the next segment starts at the following step and makes its ghosts from the compacted parents,
+// declined = the batch ends there as without removal.  The reference's order holds (simulation.jl:172-214: fracture, weld, simplify): a fracture
+// step with a candidate, or a welding step of a context with welding set, ends the batch as before -- the caller works through that step and calls
+// sz_remove_floes itself.
+// Batches that run through (SZ_NO_STOP) and contexts with neither set take the driver as it is.
 int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
-  if (!c || c->weld_dts.empty() || (flags & SZ_NO_STOP) || nsteps <= 0) return step_segment(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done);
+  const bool weld = c && !c->weld_dts.empty(), rem = c && c->rm_on && !c->S.tiled;
+  if (!c || (!weld && !rem) || (flags & SZ_NO_STOP) || nsteps <= 0) return step_segment(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done);
   if (steps_done) *steps_done = 0;
   if (!c->have_floes) return SZ_E_STATE;
-  if (c->S.tiled) { c->err = "tiled contexts do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
-  if (!c->have_domain || !c->have_fields) { c->err = "sz_step with welding set: the bins need the grid extents (sz_set_fields)"; return SZ_E_STATE; }
+  if (weld) {
+    if (c->S.tiled) { c->err = "tiled contexts do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
+    if (!c->have_domain || !c->have_fields) { c->err = "sz_step with welding set: the bins need the grid extents (sz_set_fields)"; return SZ_E_STATE; }
+  }
   int done = 0;
   while (done < nsteps) {
     int len = nsteps - done, set = -1;
-    for (int s = 0; s < nsteps - done; s++) { const int k = weld_set_at(c, tstep0 + done + s); if (k >= 0) { len = s + 1; set = k; break; } }
+    if (weld) for (int s = 0; s < nsteps - done; s++) { const int k = weld_set_at(c, tstep0 + done + s); if (k >= 0) { len = s + 1; set = k; break; } }
     int more = 0;
     const int rc = step_segment(c, len, tstep0 + done, dt, coupling_dt, flags, &more);
     done += more;
     if (steps_done) *steps_done = done;
-    if (rc || more < len || c->last_stopped || set < 0 || done == nsteps) return rc;
+    if (rc || done == nsteps) return rc;
+    if (more < len || c->last_stopped) {
+      // the segment ended on a stop request before the batch's last step: with removal set, and where neither the fracture nor the welding
+      // of that step is the host's, the pass -- and on with the batch
+      if (!rem || !c->last_stopped || more < 1) return rc;
+      const int tstep = tstep0 + done - 1;
+      if (weld && weld_set_at(c, tstep) >= 0) return SZ_OK;
+      if (c->frac_kind != SZ_FRAC_OFF && c->frac_dt > 0 && (tstep % c->frac_dt) == 0) {
+        int nc = 0;
+        if (int rc2 = sz_fracture_candidates(c, &nc, nullptr)) return rc2;
+        if (nc > 0) return SZ_OK;
+      }
+      if (c->hostM != c->hostN) return SZ_OK;
+      leave_resident(c);
+      int ok = 0, nr = 0, nd = 0;
+      if (int rc2 = remove_pass(c, &ok, &nr, &nd)) return rc2;
+      if (!ok) return SZ_OK;
+      c->last_stopped = false;
+      continue;
+    }
+    if (set < 0) return rc;
     int nt = 0;
     if (int rc2 = weld_pass(c, c->weld_nxs[set], c->weld_nys[set], c->weld_max_area, &nt)) return rc2;
     if (nt > 0) break;

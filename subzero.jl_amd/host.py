@@ -295,11 +295,19 @@ class World:
         self._chk(self.L.sz_get_stats(self.h, C.byref(s)))
         return {n: int(getattr(s, n)) for n, _ in capi.SzStats._fields_}
 
+    def _follow_count(self, st=None):
+        """a removal pass compacted the parents (remove_floes, run with set_removal): N is the device's, the sub-floe points are the library's"""
+        st = self.stats() if st is None else st
+        if st["N"] != self.N:
+            self.N = st["N"]; self._sub_on_device = "sub_off" in self.col or bool(self._sub); self._sub = {}
+            self._host_stale = True
+
     def _pull(self):
         if not self._host_stale:
             return
         st = self.stats()
         M, V = st["M"], st["n_ring_points"]
+        self._follow_count(st)
         col = {n: np.zeros(M, self._ft) for n in capi.DCOLS}
         for n in capi.TCOLS:
             col[n] = np.zeros((M, 4), self._ft)
@@ -560,6 +568,8 @@ class World:
         done = C.c_int32(0)
         self._chk(self.L.sz_step(self.h, int(nsteps), int(tstep0), int(dt), int(coupling_dt), flags, C.byref(done)))
         self._host_stale = True
+        if getattr(self, "_removal_on", False) and stop_on_tags:
+            self._follow_count()
         return int(done.value)
 
     def set_fracture(self, kind, dt=75, pstar=2.25e5, c=20.0, poly=None, alpha=0.0, min_floe_area=1e6):
@@ -626,6 +636,43 @@ class World:
         n = C.c_int32(0)
         self._chk(self.L.sz_debug_weld_npairs(self.h, C.byref(n)))
         return int(n.value)
+
+    # ---- removal and dissolution on the device (remove_floes!, simplification.jl:279-314)
+    def set_removal(self, on=True, max_vertices=30, min_floe_area=1e6, min_floe_height=0.1):
+        """SimplificationSettings.max_vertices (2**31 - 1 with smooth_vertices_on == false) and FloeSettings' minimum area / height.  run() then
+        goes on past a step that tagged a floe `remove`: the floes are removed (or dissolved into dissolved()) on the device, unless the host is
+        needed -- a `fuse` tag, a ring over max_vertices, a fracture candidate or a welding step on that step -- where the batch ends as before."""
+        self._chk(self.L.sz_set_removal(self.h, int(bool(on)), int(min(int(max_vertices), 2**31 - 1)), float(min_floe_area), float(min_floe_height)))
+        self._removal_on = bool(on)
+
+    def remove_floes(self):
+        """one pass of remove_floes! on the state as it is: (done, n_removed, n_dissolved); done == False: declined, nothing changed"""
+        self._push()
+        d, nr, nd = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._chk(self.L.sz_remove_floes(self.h, C.byref(d), C.byref(nr), C.byref(nd)))
+        if d.value and (nr.value or nd.value):
+            self._follow_count()
+        return bool(d.value), int(nr.value), int(nd.value)
+
+    def dissolved(self):
+        """the running ocean.dissolved lattice, (Nx+1) x (Ny+1)"""
+        Nx, Ny = self._grid
+        a = np.zeros((Nx + 1, Ny + 1))
+        self._chk(self.L.sz_download_dissolved(self.h, capi.ptr(a)))
+        return a
+
+    def set_dissolved(self, a):
+        Nx, Ny = self._grid
+        a = np.ascontiguousarray(np.broadcast_to(a, (Nx + 1, Ny + 1)), np.float64)
+        self._chk(self.L.sz_upload_dissolved(self.h, capi.ptr(a)))
+
+    def origin(self):
+        """per parent the row it had at the last upload (the identity until a removal pass compacts the rows)"""
+        self._push()
+        n = self.stats()["N"]
+        o = np.zeros(max(n, 1), _I32)
+        self._chk(self.L.sz_download_origin(self.h, capi.ptr(o, capi._ip)))
+        return o[:n].copy()
 
     def timestep_sim(self, tstep, dt, coupling_dt=10, collisions_on=True, coupling_on=True):
         self.run(1, tstep, dt, coupling_dt, collisions_on, coupling_on)
