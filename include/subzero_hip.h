@@ -294,8 +294,8 @@ int sz_debug_weld_npairs(sz_ctx *ctx, int32_t *n);
 
 /* ---- removal and dissolution on the device (csrc/sz_remove.hpp): remove_floes! (simplification.jl:279-314) where simplify_floes!
    reduces to it -- no floe tagged fuse and no ring over max_vertices, so the pass needs no polygon union, no smoothing and no random number.
-   sz_remove_floes runs the pass once on the state as it is, over the parents (ghosts in the list, or a tiled context -- row numbers are global
-   there --: SZ_E_STATE): in the reference's branch order a floe that is not tagged remove and lies under min_floe_area or min_floe_height
+   sz_remove_floes runs the pass once on the state as it is, over the parents (ghosts in the list: SZ_E_STATE; a tiled context: SZ_E_STATE, its
+   pass is the collective sz_tile_remove_floes below): in the reference's branch order a floe that is not tagged remove and lies under min_floe_area or min_floe_height
    dissolves, a floe tagged remove is removed (not dissolved as well), the others stay, in their order, with status active.  Every column
    sz_upload_floes takes moves to its new row, with the rings, the sub-floe points and the per-floe interaction rows (partner numbers left as they
    are, as the reference leaves them); everything derived is as sz_upload_floes leaves it.  *n_removed / *n_dissolved count the two kinds.
@@ -453,6 +453,27 @@ int sz_tile_run(sz_ctx *ctx, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t
    sz_download_subpoints: the sub-floe points of the floes the context holds (off: N + 1 entries; sx == NULL: offsets only). */
 int sz_tile_migrate(sz_ctx *ctx, int32_t px, int32_t py, const int32_t *owner_override, int64_t *n_sent, int64_t *n_owned);
 int sz_tile_owned_gidx(sz_ctx *ctx, int64_t *gidx, int64_t n_cap);
+/* Removal and dissolution on a tiled context (csrc/sz_remove_tile.hpp; DESIGN.md §9d, "tiled contexts"): sz_remove_floes over the ONE global floe
+   list whose rows live on the ranks' tiles.  Collective, between two sz_tile_run calls: it needs sz_tile_enable + sz_tile_setup and the
+   communicator (RCCL, the host transport, or one rank), the parents alone in the list, and the parameters of sz_set_removal.  Every rank is left
+   with what the single context's pass leaves for the same global list, restricted to the floes it owns:
+     - a floe that stays gets the global number the single context gives it -- its old one minus the floes that left, on ANY rank, with a smaller
+       number -- as its order key; sz_tile_owned_gidx reports the new numbers;
+     - the dissolving floes of all ranks are walked in descending global number on every rank, so every rank holds the same replica of
+       ocean.dissolved, bit for bit the single context's (sz_upload_dissolved: the same matrix on every rank; sz_download_dissolved: any rank's);
+     - the rows move and everything derived is rebuilt as in sz_remove_floes; owned boxes, halo capacities and peers are gathered again at the
+       next exchange, as after sz_tile_migrate; the ring / rmax maxima given to sz_tile_enable are kept.
+   *n_removed / *n_dissolved are GLOBAL counts, the same on every rank.  *done = 0: declined on EVERY rank and nothing has changed on any -- a fuse
+   tag or a ring over max_vertices on any rank, the index quirk of sz_remove_floes, no floe left, or ANY RANK left without a floe (a limit: the
+   tile drivers are not tested on empty tiles; the host's path takes over).  Every rank issues the same collectives whatever it holds, and an
+   error one rank finds -- device error bits, scratch memory it could not get, counts that do not add up -- is agreed on before the next
+   collective: all ranks return the same code, with the lattice and every row as they were.  A failure of the HIP runtime or of the channel
+   itself (SZ_E_HIP) is returned at once, as everywhere in the library.
+   sz_tile_run with removal set (sz_set_removal) and without SZ_NO_STOP: a segment that a tag ends before the batch's last step is followed by
+   this pass; done = the next segment starts at the following step and *steps_done counts on, declined = the batch ends there as without removal.
+   The batch's own last step is not looked at.  Tiled two-way coupling has no tag stop to hang the pass on: removal is not engaged there.
+   Fracture criteria and welding stay refused on tiles. */
+int sz_tile_remove_floes(sz_ctx *ctx, int32_t *done, int32_t *n_removed, int32_t *n_dissolved);
 int sz_debug_migrate_path(sz_ctx *ctx);
 /* diagnosis: the ghost / halo row that carried order key `key` in the last resident step that used ghost allocator `slot` (0-based step & 1), as the
    collision kernels saw it -- out56: row (-1: none), cx, cy, u, v, xi, rmax, area, height, box x0 x1 y0 y1, ring points, parent, status, ring x[20], y[20] */

@@ -85,7 +85,7 @@ EXPORTS = [
     "sz_comm_available", "sz_comm_unique_id", "sz_comm_init", "sz_comm_init_host", "sz_comm_destroy", "sz_comm_selftest", "sz_comm_allreduce", "sz_tile_setup", "sz_tile_set_center", "sz_tile_run", "sz_tile_migrate", "sz_tile_owned_gidx", "sz_debug_migrate_path", "sz_debug_find_key", "sz_debug_pairs_of_ids", "sz_download_subpoints",
     "sz_set_fracture", "sz_fracture_candidates", "sz_debug_fracture_mean",
     "sz_set_welding", "sz_weld_overlaps", "sz_debug_weld_bins", "sz_debug_weld_npairs",
-    "sz_set_removal", "sz_remove_floes", "sz_upload_dissolved", "sz_download_dissolved", "sz_download_origin",
+    "sz_set_removal", "sz_remove_floes", "sz_upload_dissolved", "sz_download_dissolved", "sz_download_origin", "sz_tile_remove_floes",
 ]
 
 EUL_PARTIAL = 17      # SZ_EUL_PARTIAL: per-cell partial fields of sz_eulerian_partial
@@ -203,6 +203,7 @@ def load(build_if_missing=True):
     L.sz_upload_dissolved.argtypes = [C.c_void_p, _dp]
     L.sz_download_dissolved.argtypes = [C.c_void_p, _dp]
     L.sz_download_origin.argtypes = [C.c_void_p, _ip]
+    L.sz_tile_remove_floes.argtypes = [C.c_void_p, _ip, _ip, _ip]
     for n in EXPORTS:
         if n not in ("sz_create", "sz_destroy", "sz_last_error", "sz_version"):
             getattr(L, n).restype = C.c_int

@@ -21,7 +21,7 @@
 #include "sz_migrate.hpp"
 #include "sz_fracture.hpp"
 #include "sz_weld.hpp"
-#include "sz_remove.hpp"
+#include "sz_remove_tile.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 
 using namespace sz;
@@ -2568,19 +2568,15 @@ int sz_set_removal(sz_ctx* c, int32_t on, int32_t max_vertices, double min_floe_
 }
 
 namespace {
-// remove_floes! on the parents as they lie (no ghosts in the list, a single context).  *done = 0: declined, nothing has changed.  Two host
-// synchronisations: the verdict (counts, what stays), then the end of the pass.  The capacities the context was carved with stay; what is derived
-// from the rows is rebuilt as a migration rebuilds it (field_placed: as sz_upload_floes leaves it).
-int remove_pass(sz_ctx* c, int* done, int* n_removed, int* n_dissolved) {
-  *done = 0; *n_removed = 0; *n_dissolved = 0;
+// The first half of a removal pass over the N parents as they lie, single context and tile alike: the arrays of RmArgs carved from the context's
+// scratch, the flags, the scans and what sz_k_rm_rows derives from them -- A.d then holds the counts (not yet a verdict).
+int rm_flag_rows(sz_ctx* c, int N, RmArgs& A) {
   State& S = c->S;
-  const int N = c->hostN;
   int rc;
-  if (N <= 0) return SZ_OK;          // (no floe would be left)
   world_rings(c);
   Pool& P = c->rm_allocs;
   reset_pool(P);
-  RmArgs A{};
+  A = RmArgs{};
   A.n = N; A.max_vertices = c->rm_max_vertices; A.min_area = c->rm_min_area; A.min_height = c->rm_min_height;
   const size_t n1 = (size_t)N + 2;
   if ((rc = dalloc(c, &A.d, 1, P)) || (rc = dalloc(c, &A.keep, n1, P)) || (rc = dalloc(c, &A.dis, n1, P)) || (rc = dalloc(c, &A.kv, n1, P)) || (rc = dalloc(c, &A.ks, n1, P)) ||
@@ -2598,16 +2594,16 @@ int remove_pass(sz_ctx* c, int* done, int* n_removed, int* n_dissolved) {
   scan(c, A.kv, A.ovoff, N, C_N, 0, -1);
   scan(c, A.ks, A.osoff, N, C_N, 0, -1);
   hipLaunchKernelGGL(sz_k_rm_rows, dim3(nb), dim3(256), 0, c->stream, A);
-  hipLaunchKernelGGL(sz_k_rm_dissolve, dim3(1), dim3(64), 0, c->stream, S, A);
-  RmDev R{};
-  HIPCHK(c, hipMemcpyAsync(&R, A.d, sizeof(RmDev), hipMemcpyDeviceToHost, c->stream));
-  if ((rc = sync_and_check(c))) return rc;
-  if (R.declined & RM_NO_LATTICE) { c->err = "sz_remove_floes: a floe dissolves, and the ocean.dissolved lattice needs the grid (sz_set_fields)"; return SZ_E_STATE; }
-  if (R.declined) return SZ_OK;
+  return SZ_OK;
+}
+// The second half, behind a verdict that lets the pass go ahead: the N parents compacted to the R.Nn that stay, through temporaries, and what is
+// derived from the rows rebuilt as a migration rebuilds it (field_placed: as sz_upload_floes leaves it -- a tile is a plain context behind it,
+// as behind any new field).  The capacities the context was carved with stay.
+int rm_move_rows(sz_ctx* c, int N, const RmArgs& A, const RmDev& R) {
+  State& S = c->S;
+  Pool& P = c->rm_allocs;
   const int Nn = R.Nn, Vn = R.Vn, NSn = R.NSn;
-  if (Nn <= 0 || Nn > N || Nn + R.n_removed + R.n_dissolved != N || Vn < 0 || NSn < 0) { c->err = "sz_remove_floes: bad counts"; return SZ_E_HIP; }
-  *done = 1; *n_removed = R.n_removed; *n_dissolved = R.n_dissolved;
-  if (Nn == N) return SZ_OK;          // nothing leaves, and every status is `active` already (no tag but remove / fuse exists)
+  int rc;
   if (c->gi_pending && c->gi_valid) { if ((rc = gi_fetch(c))) return rc; }
   c->gi_pending = false;
   // ---- the rows into their new places, gathered beside the old ones first
@@ -2626,7 +2622,7 @@ int remove_pass(sz_ctx* c, int* done, int* n_removed, int* n_dissolved) {
   hipLaunchKernelGGL(sz_k_rm_gather_rows, dim3(nbw), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, (const int*)c->origin, d_torigin, d_tcnt, d_trows);
   hipLaunchKernelGGL(sz_k_mig_scatter, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (double* const*)d_cols, (const double*)d_tmp);
   hipLaunchKernelGGL(sz_k_rm_scatter_rows, dim3(nbw), dim3(256), 0, c->stream, S, Nn, c->origin, (const int*)d_torigin, (const int*)d_tcnt, (const double*)d_trows);
-  HIPCHK(c, hipMemsetAsync(S.inter_cnt + Nn, 0, (size_t)(N - Nn) * sizeof(int), c->stream));
+  if (N > Nn) HIPCHK(c, hipMemsetAsync(S.inter_cnt + Nn, 0, (size_t)(N - Nn) * sizeof(int), c->stream));
   if (Vn) HIPCHK(c, hipMemcpyAsync(S.vxy, d_tv, (size_t)Vn * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(S.voff, A.nvoff, ((size_t)Nn + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
   if (c->pts_N) {
@@ -2644,9 +2640,29 @@ int remove_pass(sz_ctx* c, int* done, int* n_removed, int* n_dissolved) {
   c->max_ring = R.max_ring; if (c->pts_N) c->max_sub = R.max_sub;          // (as an upload of the floes that stay would find them)
   return SZ_OK;
 }
+// remove_floes! on the parents as they lie (no ghosts in the list, a single context).  *done = 0: declined, nothing has changed.  Two host
+// synchronisations: the verdict (counts, what stays), then the end of the pass.
+int remove_pass(sz_ctx* c, int* done, int* n_removed, int* n_dissolved) {
+  *done = 0; *n_removed = 0; *n_dissolved = 0;
+  const int N = c->hostN;
+  int rc;
+  if (N <= 0) return SZ_OK;          // (no floe would be left)
+  RmArgs A;
+  if ((rc = rm_flag_rows(c, N, A))) return rc;
+  hipLaunchKernelGGL(sz_k_rm_dissolve, dim3(1), dim3(64), 0, c->stream, c->S, A);
+  RmDev R{};
+  HIPCHK(c, hipMemcpyAsync(&R, A.d, sizeof(RmDev), hipMemcpyDeviceToHost, c->stream));
+  if ((rc = sync_and_check(c))) return rc;
+  if (R.declined & RM_NO_LATTICE) { c->err = "sz_remove_floes: a floe dissolves, and the ocean.dissolved lattice needs the grid (sz_set_fields)"; return SZ_E_STATE; }
+  if (R.declined) return SZ_OK;
+  if (R.Nn <= 0 || R.Nn > N || R.Nn + R.n_removed + R.n_dissolved != N || R.Vn < 0 || R.NSn < 0) { c->err = "sz_remove_floes: bad counts"; return SZ_E_HIP; }
+  *done = 1; *n_removed = R.n_removed; *n_dissolved = R.n_dissolved;
+  if (R.Nn == N) return SZ_OK;          // nothing leaves, and every status is `active` already (no tag but remove / fuse exists)
+  return rm_move_rows(c, N, A, R);
+}
 int removal_checks(sz_ctx* c, const char* who) {
   if (!c->have_floes) { c->err = std::string(who) + ": no floes uploaded"; return SZ_E_STATE; }
-  if (c->S.tiled) { c->err = std::string(who) + ": tiled contexts do not remove floes on the device (row numbers are global there): sz_set_removal(0)"; return SZ_E_STATE; }
+  if (c->S.tiled) { c->err = std::string(who) + ": the rows of a tiled context carry global numbers, and its pass is collective: sz_tile_remove_floes"; return SZ_E_STATE; }
   return SZ_OK;
 }
 }  // namespace
@@ -3729,6 +3745,130 @@ int sz_tile_owned_gidx(sz_ctx* c, int64_t* out, int64_t n_cap) {
   return SZ_OK;
 }
 
+// ---------------------------------------------------------------- removal and dissolution on a tiled context (sz_remove_tile.hpp)
+namespace {
+// remove_floes! over the ONE global floe list whose rows live on the ranks' tiles: collective.  Every rank ends with what the single context's
+// pass (remove_pass) leaves for that list, restricted to the floes it owns, numbered as the single context numbers them; *done = 0: declined on
+// EVERY rank, nothing has changed on any.  The counts are global.  The collectives, the same on every rank whatever it holds:
+//   1. the agreement on this rank's state (device error bits, ghosts in the list)
+//   2. the all-gather of the counts (RmDev of every rank): the verdict they allow -- a fuse tag, a ring over max_vertices, a rank or the world
+//      left without a floe -- is the same on every rank, and so is "nothing leaves"; both end the pass here, on all ranks
+//   3. the all-gather of the leaving records, as many slots per rank as the longest list needs
+//   4. the agreement on the verdict of the walk (the index quirk) and on this rank's counts, BEFORE the lattice or a row changes
+// In front of 2 and of 3 the ranks gather the code of what each prepared alone (scratch memory: N differs per rank), so a rank that fails there
+// takes the others with it instead of leaving them in the gather.  A failure of the HIP runtime or of the channel itself (SZ_E_HIP out of a
+// copy, a launch or a collective) is returned at once, as everywhere in the library: there is nothing left to agree over.
+// An empty tile is not a state the tile drivers are tested in: a pass that would leave one is declined.
+int tile_remove_pass(sz_ctx* c, int* done, int* n_removed, int* n_dissolved) {
+  *done = 0; *n_removed = 0; *n_dissolved = 0;
+  State& S = c->S;
+  const int n = c->comm_n, me = c->comm_rank;
+  int rc, all = 0;
+  // what this rank did on its own since the last collective came back with `local`: the first code a rank reports, in rank order, on EVERY rank
+  // (0: none) -- a rank that returned alone would leave its peers waiting in the next gather
+  auto agree_rc = [&](int local, int* first) {
+    int h[64];
+    if (const int r2 = comm_gather_int(c, local, h)) return r2;
+    *first = 0;
+    for (int r = 0; r < n && !*first; r++) if (h[r]) { *first = h[r]; if (!local) c->err = "sz_tile_remove_floes: rank " + std::to_string(r) + " could not prepare the pass (all ranks return together)"; }
+    return (int)SZ_OK;
+  };
+  // ---- 1
+  rc = sync_and_check(c);
+  if (rc == SZ_E_HIP) return rc;
+  constexpr int BIT_GHOSTS = 1 << 30, BIT_NONE = 1 << 29;
+  const int state = rc ? (c->last_err_bits ? c->last_err_bits & ~(BIT_GHOSTS | BIT_NONE) : 1) : c->hostM != c->hostN ? BIT_GHOSTS : c->hostN <= 0 ? BIT_NONE : 0;
+  if ((rc = comm_agree_bits(c, state, &all))) return rc;
+  if (all & ~(BIT_GHOSTS | BIT_NONE)) return SZ_E_CAPACITY;
+  if (all & BIT_GHOSTS) { c->err = "sz_tile_remove_floes: ghosts are in the list on some rank: the pass runs over the parents alone"; return SZ_E_STATE; }
+  c->err.clear();
+  if (all) return SZ_OK;          // (a rank without floes: declined)
+  const int N = c->hostN;
+  leave_resident(c);
+  // ---- 2
+  RmArgs A;
+  Pool& P = c->rm_allocs;
+  constexpr int RW = (int)(sizeof(RmDev) / sizeof(int));
+  int *d_counts = nullptr, *d_cnt = nullptr, *d_decl = nullptr, first = 0;
+  (void)((rc = rm_flag_rows(c, N, A)) || (rc = dalloc(c, &d_counts, (size_t)RW * 64, P)) || (rc = dalloc(c, &d_cnt, 64, P)) || (rc = dalloc(c, &d_decl, 1, P)));
+  if (const int r2 = agree_rc(rc, &first)) return r2;
+  if (first) return first;
+  if ((rc = comm_allgather(c, A.d, d_counts, RW, NCCL_INT32, sizeof(int)))) return rc;
+  std::vector<RmDev> Rs(n);
+  HIPCHK(c, hipMemcpyAsync(Rs.data(), d_counts, (size_t)n * sizeof(RmDev), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const RmDev R = Rs[me];
+  int decl = 0, slots = 0, total = 0, nr = 0, nd = 0, left = 0;
+  std::vector<int> cnt(64, 0);
+  for (int r = 0; r < n; r++) {
+    decl |= (Rs[r].n_fuse ? RM_DECL_FUSE : 0) | (Rs[r].n_over ? RM_DECL_VERTS : 0) | (Rs[r].Nn <= 0 ? RM_DECL_EMPTY : 0);
+    cnt[r] = Rs[r].n_removed + Rs[r].n_dissolved;
+    slots = std::max(slots, cnt[r]); total += cnt[r]; nr += Rs[r].n_removed; nd += Rs[r].n_dissolved; left += Rs[r].Nn;
+  }
+  if (decl || left <= 0) return SZ_OK;
+  if (total == 0) { *done = 1; return SZ_OK; }          // nothing leaves anywhere, and every status is `active` already
+  // ---- 3
+  const int Nn = std::max(R.Nn, 0);
+  double *d_rec = nullptr, *d_all = nullptr, *d_merged = nullptr; long long* d_newkey = nullptr;
+  (void)((rc = dalloc(c, &d_rec, (size_t)RMT_REC * slots, P)) || (rc = dalloc(c, &d_all, (size_t)RMT_REC * slots * n, P)) ||
+         (rc = dalloc(c, &d_merged, (size_t)RMT_REC * total, P)) || (rc = dalloc(c, &d_newkey, (size_t)Nn + 1, P)));
+  if (const int r2 = agree_rc(rc, &first)) return r2;
+  if (first) return first;
+  HIPCHK(c, hipMemsetAsync(d_rec, 0, (size_t)RMT_REC * slots * sizeof(double), c->stream));
+  HIPCHK(c, hipMemsetAsync(d_merged, 0, (size_t)RMT_REC * total * sizeof(double), c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_cnt, cnt.data(), 64 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  const bool counts_ok = Nn > 0 && Nn <= N && Nn + cnt[me] == N && R.Vn >= 0 && R.NSn >= 0;      // (the records go where the scans say: not with bad counts)
+  if (counts_ok) hipLaunchKernelGGL(sz_k_rmt_pack, dim3(grid_for(N, 256, 2048)), dim3(256), 0, c->stream, S, A, d_rec);
+  if ((rc = comm_allgather(c, d_rec, d_all, (size_t)RMT_REC * slots, NCCL_FLOAT64, sizeof(double)))) return rc;
+  hipLaunchKernelGGL(sz_k_rmt_merge, dim3(grid_for((long long)n * slots, 256)), dim3(256), 0, c->stream, (const double*)d_all, (const int*)d_cnt, n, slots, d_merged, total);
+  if (counts_ok) hipLaunchKernelGGL(sz_k_rmt_renumber, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, (const double*)d_merged, total, d_newkey);
+  hipLaunchKernelGGL(sz_k_rmt_walk, dim3(1), dim3(64), 0, c->stream, A, (const double*)d_merged, total, nd, (int)RM_WALK_CHECK, d_decl);
+  // ---- 4 (nothing has changed so far, on any rank: the walk has only looked)
+  int walk = 0;
+  std::vector<long long> newkey((size_t)Nn + 1, 0);
+  HIPCHK(c, hipMemcpyAsync(&walk, d_decl, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (counts_ok) HIPCHK(c, hipMemcpyAsync(newkey.data(), d_newkey, (size_t)Nn * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  rc = sync_and_check(c);
+  if (rc == SZ_E_HIP) return rc;
+  constexpr int BIT_ERR = 1, BIT_COUNTS = 2, BIT_INDEX = 4, BIT_LATTICE = 8, BIT_WENT = 16;
+  const int mine = (rc ? BIT_ERR : 0) | (counts_ok ? 0 : BIT_COUNTS) | (walk & RM_DECL_INDEX ? BIT_INDEX : 0) | (walk & RM_NO_LATTICE ? BIT_LATTICE : 0) | (walk ? 0 : BIT_WENT);
+  if ((rc = comm_agree_bits(c, mine, &all))) return rc;
+  if (all & BIT_ERR) return SZ_E_CAPACITY;
+  if (all & BIT_COUNTS) { c->err = "sz_tile_remove_floes: bad counts on some rank"; return SZ_E_HIP; }
+  if (all & BIT_LATTICE) { c->err = "sz_tile_remove_floes: a floe dissolves, and the ocean.dissolved lattice needs the grid (sz_set_fields)"; return SZ_E_STATE; }
+  if ((all & BIT_INDEX) && (all & BIT_WENT)) { c->err = "sz_tile_remove_floes: the ranks walked the same list to different ends: their grids (sz_set_fields) differ"; return SZ_E_STATE; }
+  c->err.clear();
+  if (all & BIT_INDEX) return SZ_OK;
+  *done = 1; *n_removed = nr; *n_dissolved = nd;
+  // ---- the pass goes ahead on every rank: the sums of the walk, then the rows move as in the single context -- on every rank, one that loses no
+  // floe included: its numbers change with the floes that left before them, and the next batch gathers the boxes anew on all ranks or on none.
+  // The tiling is taken before the new field forgets it and established again behind it, with the new numbers (S.okey, tile_gidx) and the
+  // centre the owned box was last gathered around.  Boxes, halo capacities and peers: the next exchange
+  if (nd > 0) hipLaunchKernelGGL(sz_k_rmt_walk, dim3(1), dim3(64), 0, c->stream, A, (const double*)d_merged, total, nd, (int)RM_WALK_SUM, d_decl);
+  const Retile tiling(c);
+  const bool ctr_valid = c->tile_box_valid; const double ctr[2] = { c->tile_box_ctr[0], c->tile_box_ctr[1] };
+  if ((rc = rm_move_rows(c, N, A, R))) return rc;
+  if ((rc = tiling.again(c, newkey.data(), 0, 0))) return rc;
+  if (ctr_valid) (void)sz_tile_set_center(c, ctr[0], ctr[1]);
+  return SZ_OK;
+}
+}  // namespace
+
+int sz_tile_remove_floes(sz_ctx* c, int32_t* done, int32_t* n_removed, int32_t* n_dissolved) {
+  if (done) *done = 0;
+  if (n_removed) *n_removed = 0;
+  if (n_dissolved) *n_dissolved = 0;
+  if (!c || !done) return SZ_E_ARG;
+  if (!c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0) { c->err = "sz_tile_remove_floes needs sz_tile_enable and sz_tile_setup after the last sz_upload_floes"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  int d = 0, nr = 0, nd = 0;
+  if (int rc = tile_remove_pass(c, &d, &nr, &nd)) return rc;
+  *done = d;
+  if (n_removed) *n_removed = nr;
+  if (n_dissolved) *n_dissolved = nd;
+  return SZ_OK;
+}
+
 namespace {
 int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_override, int64_t* n_sent, int64_t* n_owned) {
   State& S = c->S;
@@ -4203,11 +4343,31 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
   // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
   // Needs what the inline ghost maker needs (rings that fit the one-launch integrator, the static grid).  Otherwise: the list-based steps
-  // of sz_tile_step.  Either driver runs under this one scope.
-  const bool inl = (flags & SZ_COLLISIONS_ON) && c->grid_ok && !c->two_way &&
-                   std::max(c->max_ring, c->max_ring_tiled) <= MV_RING && ((flags & SZ_COUPLING_ON) == 0 || c->have_fields);
-  BatchModes modes(c);
-  return inl ? tile_run_inline(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done) : tile_run_listed(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done);
+  // of sz_tile_step.
+  // Either driver runs under one scope of its own per segment; the ring maxima may shrink behind a removal pass, so each segment asks again.
+  auto segment = [&](int len, int t0, int32_t* ran) {
+    const bool inl = (flags & SZ_COLLISIONS_ON) && c->grid_ok && !c->two_way &&
+                     std::max(c->max_ring, c->max_ring_tiled) <= MV_RING && ((flags & SZ_COUPLING_ON) == 0 || c->have_fields);
+    BatchModes modes(c);
+    return inl ? tile_run_inline(c, len, t0, dt, coupling_dt, flags, ran) : tile_run_listed(c, len, t0, dt, coupling_dt, flags, ran);
+  };
+  // Removal set (sz_set_removal), in batches that stop: the loop of sz_step.  A segment that a tag ends before the batch's last step -- the same
+  // step on every rank -- is followed by the collective pass; done = the next segment starts at the following step from the compacted tiles
+  // (boxes, halo capacities and peers are gathered again at its first exchange), declined = the batch ends there as without removal, on every
+  // rank.  Two-way coupling across tiles has no tag stop of its own to hang the pass on: removal is not engaged there.
+  if (!c->rm_on || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return segment(nsteps, tstep0, steps_done);
+  int done = 0;
+  while (done < nsteps) {
+    int32_t more = 0;
+    const int rc = segment(nsteps - done, tstep0 + done, &more);
+    done += more;
+    if (steps_done) *steps_done = done;
+    if (rc || done >= nsteps || more < 1) return rc;
+    int ok = 0, nr = 0, nd = 0;
+    if (int rc2 = tile_remove_pass(c, &ok, &nr, &nd)) return rc2;
+    if (!ok) return SZ_OK;
+  }
+  return SZ_OK;
 }
 
 // counts of the last sz_halo_pack per destination rank (synchronises); used to size the exchange buffers

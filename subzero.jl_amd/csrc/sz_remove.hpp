@@ -89,23 +89,44 @@ __device__ __forceinline__ long long rm_cell_idx(double p, double p0, double d, 
 
 // The reference writes dissolved[yidx, xidx] into its (Nx + 1) x (Ny + 1) matrix: in the lattice layout (element [ix][iy] at ix (Ny + 1) + iy)
 // that is element [yidx - 1][xidx - 1].  The quirk is kept; where it leaves the matrix (a BoundsError there, non-square grids only) the pass
-// is declined.
+// is declined.  The element a floe at (cx, cy) dissolves into: 1 and *elem, 0 = outside the grid (nothing is added), -1 = outside the matrix
+__device__ __forceinline__ int rm_dissolve_elem(double cx, double cy, const RmArgs& A, size_t* elem) {
+  const long long xidx = rm_cell_idx(cx, A.x0, A.dx, A.Nx, A.per_e), yidx = rm_cell_idx(cy, A.y0, A.dy, A.Ny, A.per_n);
+  if (!(0 < xidx && xidx <= A.Nx && 0 < yidx && yidx <= A.Ny)) return 0;
+  if (yidx > A.Nx + 1 || xidx > A.Ny + 1) return -1;
+  *elem = (size_t)(yidx - 1) * (A.Ny + 1) + (size_t)(xidx - 1);
+  return 1;
+}
+// The walk over nd dissolving floes in DESCENDING order, in two parts: RM_WALK_CHECK -- is any index outside the matrix -- and RM_WALK_SUM -- the
+// sums; a part runs only while nothing has declined.  at(k, &cx, &cy, &mass) gives floe k of the ascending list (false: not a dissolving one).
+// Returns decl with RM_DECL_INDEX / RM_NO_LATTICE added; only the sums touch the lattice.
+enum { RM_WALK_CHECK = 1, RM_WALK_SUM = 2 };
+template <typename At>
+__device__ __forceinline__ int rm_dissolve_walk(const RmArgs& A, int decl, int nd, int any_dissolves, int parts, At at) {
+  if (!decl && any_dissolves && !A.dissolved) decl = RM_NO_LATTICE;
+  for (int pass = 0; pass < 2 && !decl; pass++) {
+    if (!(parts >> pass & 1)) continue;
+    for (int k = nd - 1; k >= 0; k--) {
+      double cx, cy, mass; size_t e = 0;
+      if (!at(k, &cx, &cy, &mass)) continue;
+      const int in = rm_dissolve_elem(cx, cy, A, &e);
+      if (in == 0) continue;
+      if (pass == 0) { if (in < 0) { decl = RM_DECL_INDEX; break; } }
+      else if (in > 0) A.dissolved[e] += mass;
+    }
+  }
+  return decl;
+}
 __global__ void sz_k_rm_dissolve(State S, RmArgs A) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   RmDev* R = A.d;
-  int decl = (R->n_fuse ? RM_DECL_FUSE : 0) | (R->n_over ? RM_DECL_VERTS : 0) | (R->Nn == 0 ? RM_DECL_EMPTY : 0);
+  const int decl = (R->n_fuse ? RM_DECL_FUSE : 0) | (R->n_over ? RM_DECL_VERTS : 0) | (R->Nn == 0 ? RM_DECL_EMPTY : 0);
   const int nd = R->n_dissolved;
-  if (!decl && nd > 0 && !A.dissolved) decl = RM_NO_LATTICE;
-  for (int pass = 0; pass < 2 && !decl; pass++) {          // the walk twice: is any index outside the matrix; then the sums
-    for (int k = nd - 1; k >= 0; k--) {
-      const int i = A.dlist[k];
-      const long long xidx = rm_cell_idx(S.cx[i], A.x0, A.dx, A.Nx, A.per_e), yidx = rm_cell_idx(S.cy[i], A.y0, A.dy, A.Ny, A.per_n);
-      if (!(0 < xidx && xidx <= A.Nx && 0 < yidx && yidx <= A.Ny)) continue;
-      if (pass == 0) { if (yidx > A.Nx + 1 || xidx > A.Ny + 1) { decl = RM_DECL_INDEX; break; } }
-      else A.dissolved[(size_t)(yidx - 1) * (A.Ny + 1) + (size_t)(xidx - 1)] += S.mass[i];
-    }
-  }
-  R->declined = decl;
+  R->declined = rm_dissolve_walk(A, decl, nd, nd > 0, RM_WALK_CHECK | RM_WALK_SUM, [&](int k, double* cx, double* cy, double* mass) {
+    const int i = A.dlist[k];
+    *cx = S.cx[i]; *cy = S.cy[i]; *mass = S.mass[i];
+    return true;
+  });
 }
 
 // what a migration does not carry, one wavefront per new row: the interaction rows (count and the rows in use, partner numbers as they

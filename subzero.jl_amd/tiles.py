@@ -470,6 +470,44 @@ class TiledWorld:
         self.boxes = None; self._ref = None
         return int(sent.value)
 
+    # ---- removal and dissolution across tiles (sz_tile_remove_floes: library backends)
+    def set_removal(self, on=True, max_vertices=30, min_floe_area=1e6, min_floe_height=0.1):
+        """World.set_removal for this rank's tile (the same arguments on every rank).  run(..., stop_on_tags=True) then goes on past a step that
+        tagged a floe `remove` on any rank: the collective pass of remove_floes() follows it, unless it is declined -- where the batch ends as before."""
+        self.world.set_removal(on, max_vertices, min_floe_area, min_floe_height)
+
+    def _after_pass(self):
+        """a removal pass may have compacted the tile and renumbered its floes: N, the global indices and the host's caches follow, as in migrate()"""
+        w = self.world
+        n = w.stats()["N"]
+        g = np.zeros(max(n, 1), np.int64)
+        w._chk(w.L.sz_tile_owned_gidx(w.h, capi.ptr(g, capi._lp), int(g.size)))
+        if n == len(self.gidx) and np.array_equal(g[:n], self.gidx):
+            return
+        w.N = n; w._M = n; w._dirty = False; w._host_stale = True; w._sub = {}; w._sub_on_device = True
+        self.gidx = g[:n].copy()
+        self.boxes = None; self._ref = None
+
+    def remove_floes(self):
+        """one pass of remove_floes! over the global floe list (collective): (done, n_removed, n_dissolved) with GLOBAL counts, the same on every
+        rank; done == False: declined on every rank, nothing changed.  The floes that stay carry the single context's new numbers (self.gidx)."""
+        if self.backend not in ("library", "library-host"):
+            raise capi.SzError("TiledWorld.remove_floes needs a library backend (the pass is collective inside libsubzero_hip.so)")
+        w = self.world
+        d, nr, nd = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        w._chk(w.L.sz_tile_remove_floes(w.h, C.byref(d), C.byref(nr), C.byref(nd)))
+        if d.value and (nr.value or nd.value):
+            self._after_pass()
+        return bool(d.value), int(nr.value), int(nd.value)
+
+    def dissolved(self):
+        """this rank's replica of the running ocean.dissolved lattice: the same matrix on every rank"""
+        return self.world.dissolved()
+
+    def set_dissolved(self, a):
+        """the lattice to go on from: the same matrix on every rank"""
+        self.world.set_dissolved(a)
+
     def maybe_repartition(self):
         """Ownership is static between calls of repartition(); floes drift.  Collective: re-tile when more than
         `repartition_fraction` of all floes has left the tile that owns it (cheap test: the owned centroids against the
@@ -489,7 +527,11 @@ class TiledWorld:
     def run(self, nsteps, tstep0, dt, coupling_dt=10, collisions_on=True, coupling_on=True, stop_on_tags=False):
         """nsteps x timestep_sim! of the tiled run (collective).  Returns the steps run.  stop_on_tags (library backends): the batch ends
         after the first step that leaves a floe tagged remove / fuse on ANY rank -- the same step on every rank -- as World.run does
-        for the single context (the reference runs simplify_floes! after every step, simulation.jl:205-214)."""
+        for the single context (the reference runs simplify_floes! after every step, simulation.jl:205-214).  With set_removal() the batch
+        goes on past such a step where the collective removal pass is done, and ends there where it is declined.  A limit: with more than one
+        rank a batch is cut into calls of `repartition_every` steps (500), and the last step of a call is a batch's own last step, which is not
+        looked at -- a floe tagged on exactly that step is removed behind the first step of the next call, one step later than World.run(n) would;
+        a caller that needs the single context's timing there keeps nsteps within one call or calls remove_floes() itself."""
         done = 0
         while done < nsteps:
             k = min(nsteps - done, self.repartition_every - self._since_check) if self.nranks > 1 else nsteps - done
@@ -499,6 +541,8 @@ class TiledWorld:
                 ran = C.c_int32(0)
                 w._chk(w.L.sz_tile_run(w.h, int(k), int(tstep0 + done), int(dt), int(coupling_dt), flags, C.byref(ran)))
                 w._host_stale = True
+                if stop_on_tags and getattr(w, "_removal_on", False):
+                    self._after_pass()
                 if ran.value < k:
                     return done + int(ran.value)
             else:
