@@ -253,7 +253,8 @@ int sz_step(sz_ctx *ctx, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t cou
    fracture_floes!; the launches of the later steps return at once; no host synchronisation per step).  SZ_NO_STOP runs through.
    Batches with a criterion set run the three-launch steps, never the pipelined ones (csrc/sz_pipeline.hpp): the mean height is a
    grid-wide dependency between a step's update and the next step's neighbour search, which the pipelined launches overlap.
-   Tiled runs (sz_tile_run, sz_tile_step) with a criterion set return SZ_E_STATE (the mean would need an all-reduce over the ranks).
+   Tiled contexts: sz_tile_run evaluates the criterion collectively behind segments that end on fracture steps, sz_tile_fracture_candidates on
+   request (both below); sz_tile_step, the host-driven step, returns SZ_E_STATE with a criterion set.
    SZ_FRAC_OFF (the default) adds nothing to a step, not even a launch. */
 enum { SZ_FRAC_OFF = 0, SZ_FRAC_HIBLER = 1, SZ_FRAC_POLYGON = 2 };
 int sz_set_fracture(sz_ctx *ctx, int32_t kind, int32_t dt, double pstar, double c, int32_t npts,
@@ -401,6 +402,15 @@ int sz_set_stream(sz_ctx *ctx, void *hip_stream);
                          batch there before that step has touched anything.  *steps_done (may be NULL) is the same number on every
                          rank; status.fuse_idx (sz_download_fuse) of a tiled context names partners by GLOBAL floe index.
                          SZ_NO_STOP runs all steps.
+                         With a criterion set (sz_set_fracture) and without SZ_NO_STOP the batch is cut into segments that end on a
+                         fracture step (tstep % dt == 0); behind a segment whose last step ran, the ranks evaluate the criterion over
+                         the ONE global list (sz_tile_fracture_candidates below: the same pass) and a candidate ON ANY RANK ends the
+                         batch on every rank, *steps_done counting the fracture step -- where sz_step ends it for the undivided list.
+                         A tag raised on that step ends the batch there too when no floe fractures (with removal set: the removal
+                         pass, and on).  The batch's own last step is not looked at: the caller asks.  SZ_NO_STOP batches and
+                         contexts without a criterion launch and gather nothing for it.  Needs sz_tile_setup and a communicator
+                         (SZ_E_STATE without); with two-way coupling across tiles a criterion is refused (SZ_E_STATE: those batches
+                         have no tested stop).  Welding stays refused on tiles.
                          Device errors are per rank; the ranks agree on them at every box gather and at the end of the call,
                          so that EVERY rank returns the same code at the same step (a rank leaving on its own would hang the
                          others: RCCL has no timeout).  A new sz_upload_floes invalidates sz_tile_enable / sz_tile_setup.
@@ -472,8 +482,20 @@ int sz_tile_owned_gidx(sz_ctx *ctx, int64_t *gidx, int64_t n_cap);
    sz_tile_run with removal set (sz_set_removal) and without SZ_NO_STOP: a segment that a tag ends before the batch's last step is followed by
    this pass; done = the next segment starts at the following step and *steps_done counts on, declined = the batch ends there as without removal.
    The batch's own last step is not looked at.  Tiled two-way coupling has no tag stop to hang the pass on: removal is not engaged there.
-   Fracture criteria and welding stay refused on tiles. */
+   Welding stays refused on tiles. */
 int sz_tile_remove_floes(sz_ctx *ctx, int32_t *done, int32_t *n_removed, int32_t *n_dissolved);
+/* Fracture criteria on a tiled context (csrc/sz_fracture_tile.hpp; DESIGN.md §9b, "tiled contexts"): determine_fractures over the ONE global
+   floe list whose rows live on the ranks' tiles, on the state as it is.  Collective: it needs sz_tile_enable + sz_tile_setup, the communicator
+   (RCCL, the host transport, or one rank), the parents alone in the list and a criterion (sz_set_fracture, the same on every rank).  The heights
+   of all ranks are gathered by global number, and the single context's kernels run unchanged -- the mean and the polygon over the gathered
+   array, in the single context's order of additions (a reduce of per-rank sums would add in another order: other last bits of p), the test
+   over the owned rows -- so every rank holds the single context's mean, p and verdicts to the bit (sz_debug_fracture_mean).
+   *n_global = candidates on all ranks, the same number on every rank; *n_owned = this rank's; rows / gidx (each may be NULL: counts only;
+   room for the owned floes) = their local rows, ascending, and their global numbers.  The global numbers of the ranks must be
+   0 .. N_global - 1 once each: one out of range or held twice is SZ_E_STATE on EVERY rank, as is any error one rank finds (device error
+   bits: SZ_E_CAPACITY) -- the ranks agree before they return, and nothing of the floes has changed.  A failure of the HIP runtime or of the
+   channel itself (SZ_E_HIP) is returned at once. */
+int sz_tile_fracture_candidates(sz_ctx *ctx, int32_t *n_global, int32_t *n_owned, int32_t *rows, int64_t *gidx);
 int sz_debug_migrate_path(sz_ctx *ctx);
 /* diagnosis: the ghost / halo row that carried order key `key` in the last resident step that used ghost allocator `slot` (0-based step & 1), as the
    collision kernels saw it -- out56: row (-1: none), cx, cy, u, v, xi, rmax, area, height, box x0 x1 y0 y1, ring points, parent, status, ring x[20], y[20] */

@@ -945,12 +945,24 @@ end
 
 # nsteps x timestep_sim! of the tiled run, collectively (same arguments on every rank).  Returns the steps run: like sz_step the batch
 # ends after the first step that leaves a floe tagged remove / fuse on ANY rank (the same number on every rank), so that the host's
-# simplify_floes! runs at the step the reference runs it (simulation.jl:205-214)
+# simplify_floes! runs at the step the reference runs it (simulation.jl:205-214).  With a criterion set (`set_fracture!`: fractures need
+# not be turned off for a tiled run) it also ends after the first fracture step on which a floe of ANY rank would fracture; the batch's
+# own last step is not looked at -- `tile_fracture_candidates` answers for it
 function tile_run!(eng::HIPEngine, nsteps::Integer, tstep::Integer, Δt::Integer, coupling_Δt::Integer, flags::Integer)
     done = Ref{Int32}(0)
     check(eng, @ccall lib.sz_tile_run(eng.ctx::Ptr{Cvoid}, nsteps::Int32, tstep::Int32, Δt::Int32, coupling_Δt::Int32, flags::Int32,
                                       done::Ptr{Int32})::Cint)
     return Int(done[])
+end
+
+# determine_fractures over the global floe list whose rows live on the ranks' tiles (sz_tile_fracture_candidates): collective, on the state
+# as it is.  Returns (candidates on all ranks -- the same number on every rank, 1-based local rows of this rank's candidates ascending, their
+# 0-based global indices).  Mean height, p and verdicts are the undivided list's, to the bit.
+function tile_fracture_candidates(eng::HIPEngine, n_owned::Integer)
+    ng = Ref{Int32}(0); no = Ref{Int32}(0)
+    rows = Vector{Int32}(undef, max(n_owned, 1)); g = Vector{Int64}(undef, max(n_owned, 1))
+    check(eng, @ccall lib.sz_tile_fracture_candidates(eng.ctx::Ptr{Cvoid}, ng::Ptr{Int32}, no::Ptr{Int32}, rows::Ptr{Int32}, g::Ptr{Int64})::Cint)
+    return Int(ng[]), Int.(rows[1:no[]]) .+ 1, g[1:no[]]
 end
 
 # floes that left their tile go to the rank that owns the tile their centroid lies in now (px x py tiles over the domain), with their

@@ -22,6 +22,7 @@
 #include "sz_fracture.hpp"
 #include "sz_weld.hpp"
 #include "sz_remove_tile.hpp"
+#include "sz_fracture_tile.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 
 using namespace sz;
@@ -154,6 +155,10 @@ struct sz_ctx {
   int frac_kind = 0, frac_dt = 0, frac_npts = 0, frac_cap = 0;
   double frac_pstar = 0, frac_c = 0, frac_alpha = 0, frac_min_area = 0;
   FracDev* frac_d = nullptr; unsigned char* frac_flag = nullptr; int* frac_idx = nullptr;
+  Pool frac_allocs;                 // scratch of a tiled context's collective criterion pass (tile_frac_pass; sz_fracture_tile.hpp): kept between passes
+  int tile_stop_raised = 0;         // the batch-relative stop step the last tile driver ended with (0: none): the list-based driver's is THIS rank's own word -- a tag of its
+                                    // last step is not yet known to the peers --, the inline driver's is already the ranks' agreed one (comm_agree_steps)
+  std::vector<int> frac_cnt;        // owned counts of all ranks of the last criterion pass (the source of an asynchronous upload: outlives the call)
   // welding (sz_set_welding; sz_weld.hpp): WeldSettings' Δts / Nxs / Nys in the reference's order and max_weld_area; the buffers of the overlap-table
   // pass (its own search cells, bins, pair keys, areas, table), carved for weld_capN parents, weld_cells cells and weld_cap pairs
   std::vector<int> weld_dts, weld_nxs, weld_nys; double weld_max_area = 0;
@@ -1006,6 +1011,7 @@ void sz_destroy(sz_ctx* c) {
   (void)hipFree(c->frac_d); (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx);
   free_pool(c->weld_allocs); (void)hipFree(c->weld_tmp);
   free_pool(c->rm_allocs);
+  free_pool(c->frac_allocs);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
   (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2);
   (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join);
@@ -2935,11 +2941,9 @@ int tile_forcing(sz_ctx* c) {
 }
 }  // namespace
 
-int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int32_t tstep, int32_t dt, int32_t coupling_dt,
-                 int32_t flags) {
-  if (!c || !c->have_floes) return SZ_E_STATE;
-  if (c->frac_kind != SZ_FRAC_OFF) { c->err = "tiled runs do not evaluate fracture criteria (the mean height needs an all-reduce over the ranks): sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
-  if (!c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
+// one list-based tiled step: the body of the public sz_tile_step below, and the step of sz_tile_run's list-based driver (tile_run_listed), which
+// has checked the context and evaluates a criterion itself, between its segments
+static int tile_step_body(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int32_t tstep, int32_t dt, int32_t coupling_dt, int32_t flags) {
   (void)hipSetDevice(c->device);
   State& S = c->S;
   const bool coll = (flags & SZ_COLLISIONS_ON) != 0;
@@ -2974,6 +2978,13 @@ int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int
   if (gl) { c->gl_cur ^= 1; c->gl_est = std::max(c->gl_est, 64); }
   c->tile_dirty = true;
   return SZ_OK;
+}
+int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int32_t tstep, int32_t dt, int32_t coupling_dt,
+                 int32_t flags) {
+  if (!c || !c->have_floes) return SZ_E_STATE;
+  if (c->frac_kind != SZ_FRAC_OFF) { c->err = "sz_tile_step does not evaluate fracture criteria (the host drives its steps: no library channel to gather the mean height over): sz_tile_run, or sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
+  if (!c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
+  return tile_step_body(c, d_recv, nranks, cap, tstep, dt, coupling_dt, flags);
 }
 
 // Two-way coupling across tiles.  After a tiled coupling step: sz_two_way_partial writes this rank's per-cell sums
@@ -3869,6 +3880,111 @@ int sz_tile_remove_floes(sz_ctx* c, int32_t* done, int32_t* n_removed, int32_t* 
   return SZ_OK;
 }
 
+// ---------------------------------------------------------------- fracture criteria on a tiled context (sz_fracture_tile.hpp)
+namespace {
+// determine_fractures over the ONE global floe list whose rows live on the ranks' tiles: collective, over the parents with ghosts detached (as
+// behind a segment of sz_tile_run).  Every rank ends with the mean height, p and polygon of the single context, to the bit -- the heights of all
+// ranks gathered by global number, then sz_k_frac_criterion over that array, unchanged -- and with the flags of the rows it owns (sz_k_frac_test
+// over hostN rows; halo rows are never tested).  The collectives, the same on every rank whatever it holds:
+//   1. the gather of the owned counts; a rank that cannot take part (device error bits, ghosts in the list) sends its error code in place of its
+//      count, and all ranks return it together
+//   2. the all-gather of the {global number, height} records, as many slots per rank as the longest list needs
+//   3. the agreement (comm_agree_bits) on: a global number out of range or met twice, a device error, "I have a candidate", and my_tag -- "my stop
+//      word stood at the segment's last step".  Behind the list-based driver that is news to the peers: they would hear of such a tag in the unpack
+//      of a step that does not come.  The inline driver has agreed its stop step already (comm_agree_steps), and every rank sends the same bit
+// Nothing of the floes changes in a pass; what 3 refuses has only written the pass's scratch and the criterion block.  A failure of the HIP runtime
+// or of the channel itself is returned at once, as everywhere in the library.  compact: the owned candidates as ascending rows in frac_idx and
+// their exact number in *n_owned (otherwise *n_owned is only zero or not).
+constexpr int FRT_BIT_RANGE = 1, FRT_BIT_TWICE = 2, FRT_BIT_ERR = 4, FRT_BIT_CAND = 8, FRT_BIT_TAG = 16;
+int tile_frac_pass(sz_ctx* c, bool my_tag, bool compact, int* any_cand, int* any_tag, int* n_owned) {
+  *any_cand = 0; *any_tag = 0; *n_owned = 0;
+  State& S = c->S;
+  const int n = c->comm_n;
+  // ---- 1
+  int rc = sync_and_check(c);
+  if (rc == SZ_E_HIP) return rc;
+  if ((rc = rc ? rc : c->hostM != c->hostN ? (int)SZ_E_STATE : frac_ensure(c)) == SZ_E_HIP) return rc;
+  const int N = c->hostN;
+  c->frac_cnt.assign(64, 0);
+  int* const cnt = c->frac_cnt.data();
+  if (const int r2 = comm_gather_int(c, rc ? rc : N, cnt)) return r2;
+  for (int r = 0; r < n; r++) if (cnt[r] < 0) {
+    if (cnt[r] == SZ_E_STATE) c->err = "tiled fracture criteria: ghosts are in the list on rank " + std::to_string(r) + ": the pass runs over the parents alone";
+    else if (!rc) c->err = "tiled fracture criteria: rank " + std::to_string(r) + " reported a device error (this rank is clean; all ranks return together)";
+    return cnt[r];
+  }
+  long long total64 = 0; int slots = 1;
+  for (int r = 0; r < n; r++) { total64 += cnt[r]; slots = std::max(slots, cnt[r]); }
+  if (total64 > 0x7fffffff) { c->err = "tiled fracture criteria: more than 2^31 floes"; return SZ_E_CAPACITY; }          // (the same sum on every rank)
+  const int total = (int)total64;
+  // ---- 2
+  Pool& P = c->frac_allocs;
+  reset_pool(P);
+  double *d_rec = nullptr, *d_all = nullptr, *d_h = nullptr; int *d_mark = nullptr, *d_cnt = nullptr, *d_bad = nullptr;
+  if ((rc = dalloc(c, &d_rec, (size_t)FRT_REC * slots, P)) || (rc = dalloc(c, &d_all, (size_t)FRT_REC * slots * n, P)) || (rc = dalloc(c, &d_h, (size_t)total, P)) ||
+      (rc = dalloc(c, &d_mark, (size_t)total, P)) || (rc = dalloc(c, &d_cnt, 64, P)) || (rc = dalloc(c, &d_bad, 1, P))) return rc;
+  HIPCHK(c, hipMemsetAsync(d_mark, 0, (size_t)std::max(total, 1) * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_cnt, cnt, 64 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (N > 0) hipLaunchKernelGGL(sz_k_fract_pack, dim3(grid_for(N, 256, 2048)), dim3(256), 0, c->stream, S, N, d_rec);
+  if ((rc = comm_allgather(c, d_rec, d_all, (size_t)FRT_REC * slots, NCCL_FLOAT64, sizeof(double)))) return rc;
+  hipLaunchKernelGGL(sz_k_fract_scatter, dim3(grid_for((long long)n * slots, 256)), dim3(256), 0, c->stream, (const double*)d_all, (const int*)d_cnt, n, slots, d_h, d_mark, total, d_bad);
+  // ---- the single context's kernels: the criterion over the gathered heights, the test over the owned rows
+  State T = S; T.step = 0;
+  FracArgs F = frac_args(c);
+  State G = T; G.height = d_h;
+  FracArgs Fg = F; Fg.n = total;
+  hipLaunchKernelGGL(sz_k_frac_criterion, dim3(1), dim3(FRAC_TPB), 0, c->stream, G, Fg);
+  hipLaunchKernelGGL(sz_k_frac_test, dim3(grid_for(std::max(N, 1), 256, 2048)), dim3(256), 0, c->stream, T, F);
+  if (compact) hipLaunchKernelGGL(sz_k_frac_compact, dim3(1), dim3(FRAC_TPB), 0, c->stream, F);
+  int found = 0, bad = 0;
+  HIPCHK(c, hipMemcpyAsync(&found, &c->frac_d->count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  rc = sync_and_check(c);
+  if (rc == SZ_E_HIP) return rc;
+  // ---- 3
+  if (found < 0 || found > N) rc = SZ_E_CAPACITY;
+  const int mine = (bad & FRT_BAD_RANGE ? FRT_BIT_RANGE : 0) | (bad & FRT_BAD_TWICE ? FRT_BIT_TWICE : 0) | (rc ? FRT_BIT_ERR : 0) | (found > 0 ? FRT_BIT_CAND : 0) | (my_tag ? FRT_BIT_TAG : 0);
+  int all = 0;
+  if ((rc = comm_agree_bits(c, mine, &all))) return rc;
+  if (all & (FRT_BIT_RANGE | FRT_BIT_TWICE)) {
+    c->err = std::string("tiled fracture criteria: the global numbers of the ranks (sz_tile_enable) are not 0 .. N_global - 1 once each: ") +
+             (all & FRT_BIT_RANGE ? "one is out of range" : "one is held twice") + " (all ranks return together)";
+    return SZ_E_STATE;
+  }
+  if (all & FRT_BIT_ERR) { if (!(mine & FRT_BIT_ERR)) c->err = "tiled fracture criteria: a rank reported a device error (this rank is clean; all ranks return together)"; return SZ_E_CAPACITY; }
+  c->err.clear();
+  *any_cand = (all & FRT_BIT_CAND) != 0; *any_tag = (all & FRT_BIT_TAG) != 0; *n_owned = found;
+  return SZ_OK;
+}
+}  // namespace
+
+int sz_tile_fracture_candidates(sz_ctx* c, int32_t* n_global, int32_t* n_owned, int32_t* rows, int64_t* gidx) {
+  if (n_global) *n_global = 0;
+  if (n_owned) *n_owned = 0;
+  if (!c || !n_global || !n_owned) return SZ_E_ARG;
+  if (!c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0) { c->err = "sz_tile_fracture_candidates needs sz_tile_enable and sz_tile_setup after the last sz_upload_floes"; return SZ_E_STATE; }
+  if (c->frac_kind == SZ_FRAC_OFF) { c->err = "sz_tile_fracture_candidates: no fracture criterion set (sz_set_fracture)"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  int any = 0, tag = 0, mine = 0, per_rank[64] = { 0 };
+  if (int rc = tile_frac_pass(c, false, true, &any, &tag, &mine)) return rc;
+  if (int rc = comm_gather_int(c, mine, per_rank)) return rc;
+  long long total = 0;
+  for (int r = 0; r < c->comm_n; r++) total += per_rank[r];
+  if (mine > 0 && (rows || gidx)) {
+    std::vector<int> h((size_t)mine);
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->frac_idx, (size_t)mine * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < mine; k++) {
+      if (h[k] < 0 || h[k] >= (int)c->tile_gidx.size()) { c->err = "sz_tile_fracture_candidates: bad candidate row"; return SZ_E_HIP; }
+      if (rows) rows[k] = h[k];
+      if (gidx) gidx[k] = c->tile_gidx[h[k]];
+    }
+  }
+  *n_global = (int32_t)total; *n_owned = mine;
+  return SZ_OK;
+}
+
 namespace {
 int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_override, int64_t* n_sent, int64_t* n_owned) {
   State& S = c->S;
@@ -4120,7 +4236,7 @@ static int tile_run_listed(sz_ctx* c, int nsteps, int tstep0, int dt, int coupli
     // the forcings of the owned floes need nothing from the halo: they run beside the exchange
     if (coupling && !stopping && !(n > 1 && c->host_transport)) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return rc; }
     if (n > 1 && hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return SZ_E_HIP; }
-    int rc = sz_tile_step(c, c->d_recv, n, c->halo_cap, tstep, dt, coupling_dt, flags); if (rc) return rc;
+    int rc = tile_step_body(c, c->d_recv, n, c->halo_cap, tstep, dt, coupling_dt, flags); if (rc) return rc;
     if (c->two_way && coupling) {       // ice-on-ocean stress: per-cell partial sums, summed over the ranks, finished on every rank
       const size_t nc = 3 * c->tw_ncell;
       if (!c->d_tw_partial) { int r2 = dalloc(c, &c->d_tw_partial, nc, c->tw_part_allocs); if (r2) return r2; }
@@ -4134,6 +4250,7 @@ static int tile_run_listed(sz_ctx* c, int nsteps, int tstep0, int dt, int coupli
   const int rce = tile_sync_agree(c, hl);
   c->fuse_lists.resize(c->hostM);
   const int done = stopping && hl[C_STOP] > 0 ? std::min(hl[C_STOP], (int)nsteps) : nsteps;
+  c->tile_stop_raised = stopping ? hl[C_STOP] : 0;
   if (done < nsteps) { c->grid_live = false; c->gl_valid = false; }          // stopped early: cells and ghost-candidate lists belong to steps that did not come
   if (steps_done) *steps_done = done;
   return rce;
@@ -4310,6 +4427,7 @@ static int tile_run_inline(sz_ctx* c, int nsteps, int tstep0, int dt, int coupli
   }
   if (const int ra = tile_agree(c, rc)) return ra;
   const int done = h[C_STOP] > 0 ? std::min(h[C_STOP], (int)nsteps) : nsteps;
+  c->tile_stop_raised = plan.user_stop ? h[C_STOP] : 0;
   if (steps_done) *steps_done = done;
   frc.use(last_set(done)); frc.keep = true;          // the forcing outputs of the last step that ran (see `beside` above)
   if (done < nsteps) c->grid_live = false;          // stopped early: cells hold floes of a step that did not come
@@ -4335,10 +4453,12 @@ int sz_tile_set_center(sz_ctx* c, double x, double y) {
 // nsteps x timestep_sim! of a tiled run, collectively on every rank (same arguments everywhere)
 int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
   if (steps_done) *steps_done = 0;
-  if (c && c->frac_kind != SZ_FRAC_OFF) { c->err = "tiled runs do not evaluate fracture criteria (the mean height needs an all-reduce over the ranks): sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
   if (c && !c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
+  if (c && c->frac_kind != SZ_FRAC_OFF && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled fracture criteria gather the mean height over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
   if (!c || !c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0) { if (c) c->err = "sz_tile_run needs sz_tile_enable and sz_tile_setup after the last sz_upload_floes"; return SZ_E_STATE; }
   if (nsteps < 0) return SZ_E_ARG;
+  const bool frac = c->frac_kind != SZ_FRAC_OFF;
+  if (frac && c->two_way) { c->err = "tiled two-way coupling with a fracture criterion set: its per-step all-reduce path has no tested stop: sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
   // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
   // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
@@ -4351,18 +4471,36 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
     BatchModes modes(c);
     return inl ? tile_run_inline(c, len, t0, dt, coupling_dt, flags, ran) : tile_run_listed(c, len, t0, dt, coupling_dt, flags, ran);
   };
-  // Removal set (sz_set_removal), in batches that stop: the loop of sz_step.  A segment that a tag ends before the batch's last step -- the same
-  // step on every rank -- is followed by the collective pass; done = the next segment starts at the following step from the compacted tiles
-  // (boxes, halo capacities and peers are gathered again at its first exchange), declined = the batch ends there as without removal, on every
-  // rank.  Two-way coupling across tiles has no tag stop of its own to hang the pass on: removal is not engaged there.
-  if (!c->rm_on || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return segment(nsteps, tstep0, steps_done);
+  // In batches that stop, with a criterion set (sz_set_fracture) or removal set (sz_set_removal): the loop of sz_step.
+  // Fracture: the batch is cut into segments that END on a fracture step (tstep % frac_dt == 0), each an ordinary tiled batch.  Behind a segment
+  // whose last step ran comes the collective criterion pass (tile_frac_pass): a candidate on any rank ends the batch there on every rank
+  // (steps_done counts the fracture step), none = the next segment starts at the following step.  A tag raised on that very step is, behind the
+  // list-based driver, known to its rank alone -- the peers would hear of it in the unpack of a step that does not come; the inline driver has
+  // agreed it already -- so the pass's agreement carries it (tile_stop_raised), and what follows is the single context's order (simulation.jl:172-214: fracture, then simplify): without a candidate the batch ends on the tag as sz_step
+  // does, or -- removal set -- goes into the removal pass.  The batch's own last step is not looked at: the caller asks (sz_tile_fracture_candidates).
+  // Removal: a segment that a tag ends before its last step -- the same step on every rank, and never a fracture step: those end segments -- or
+  // on it (above) is followed by the collective pass; done = the next segment starts at the following step from the compacted tiles (boxes, halo
+  // capacities and peers are gathered again at its first exchange), declined = the batch ends there as without removal, on every rank.
+  // Two-way coupling across tiles has no tag stop of its own to hang a pass on: removal is not engaged there, a criterion refused.
+  // SZ_NO_STOP batches and contexts with neither set take the drivers as they are.
+  if ((!c->rm_on && !frac) || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return segment(nsteps, tstep0, steps_done);
   int done = 0;
   while (done < nsteps) {
+    int len = nsteps - done;
+    if (frac) for (int s = 0; s + 1 < nsteps - done; s++) if ((tstep0 + done + s) % c->frac_dt == 0) { len = s + 1; break; }
     int32_t more = 0;
-    const int rc = segment(nsteps - done, tstep0 + done, &more);
+    c->tile_stop_raised = 0;
+    const int rc = segment(len, tstep0 + done, &more);
     done += more;
     if (steps_done) *steps_done = done;
     if (rc || done >= nsteps || more < 1) return rc;
+    if (more == len) {          // the segment's last step ran, and the batch goes on behind it: it was cut here, on a fracture step
+      int cand = 0, tag = 0, mine = 0;
+      if (int rc2 = tile_frac_pass(c, c->tile_stop_raised == len, false, &cand, &tag, &mine)) return rc2;
+      if (cand) return SZ_OK;
+      if (!tag) continue;
+    }
+    if (!c->rm_on) return SZ_OK;
     int ok = 0, nr = 0, nd = 0;
     if (int rc2 = tile_remove_pass(c, &ok, &nr, &nd)) return rc2;
     if (!ok) return SZ_OK;

@@ -210,6 +210,7 @@ class TiledWorld:
         self.boxes = None
         self.steps_since_box = 0
         self.tw_buf = None                                    # per-cell partial sums of the two-way coupling
+        self._frac_dt = 0                                     # Δt of the criterion set through set_fracture (0: none): run() asks at its own cuts
 
     def _agree(self, ok, what):
         """collective: raise TileSetupError on every rank when `ok` is false on any of them"""
@@ -508,6 +509,44 @@ class TiledWorld:
         """the lattice to go on from: the same matrix on every rank"""
         self.world.set_dissolved(a)
 
+    # ---- fracture criteria across tiles (sz_tile_fracture_candidates, sz_tile_run with a criterion set: library backends)
+    def _library_only(self, what):
+        if self.backend not in ("library", "library-host"):
+            raise capi.SzError(f"TiledWorld.{what} needs a library backend (the criterion pass is collective inside libsubzero_hip.so)")
+
+    def set_fracture(self, kind, dt=75, pstar=2.25e5, c=20.0, poly=None, alpha=0.0, min_floe_area=1e6):
+        """World.set_fracture for this rank's tile (the same arguments on every rank).  run(..., stop_on_tags=True) then ends after the first
+        fracture step on which a floe of ANY rank would fracture -- the same step on every rank, the step World.run ends on for the undivided list.
+        Set it here, not on `self.world`: run() must know Δt to ask at its own cuts."""
+        self._library_only("set_fracture")
+        self.world.set_fracture(kind, dt, pstar, c, poly, alpha, min_floe_area)
+        self._frac_dt = int(dt) if kind != capi.FRAC_OFF else 0
+
+    def _fracture_pass(self, want_rows):
+        """one collective criterion pass: (global count, global numbers of this rank's candidates, ascending by local row)"""
+        self._library_only("fracture_candidates")
+        w = self.world
+        ng, no = C.c_int32(0), C.c_int32(0)
+        g = np.zeros(max(len(self.gidx), 1), np.int64) if want_rows else None
+        w._chk(w.L.sz_tile_fracture_candidates(w.h, C.byref(ng), C.byref(no), None, capi.ptr(g, capi._lp) if want_rows else None))
+        return int(ng.value), (g[:no.value].copy() if want_rows else None)
+
+    def fracture_candidates(self):
+        """determine_fractures over the global floe list (collective): the 0-based GLOBAL numbers of the floes that would fracture, ascending and
+        complete, identical on every rank -- what World.fracture_candidates() returns for the undivided list"""
+        ng, mine = self._fracture_pass(True)
+        if self.dist is None or self.nranks == 1:
+            return np.sort(mine)
+        parts = [None] * self.nranks
+        self.dist.all_gather_object(parts, mine)
+        out = np.sort(np.concatenate(parts))
+        assert len(out) == ng, (len(out), ng)
+        return out
+
+    def fracture_mean(self):
+        """(mean height over the global list, Hibler p) of the last evaluation: the single context's, to the bit, on every rank"""
+        return self.world.fracture_mean()
+
     def maybe_repartition(self):
         """Ownership is static between calls of repartition(); floes drift.  Collective: re-tile when more than
         `repartition_fraction` of all floes has left the tile that owns it (cheap test: the owned centroids against the
@@ -528,10 +567,13 @@ class TiledWorld:
         """nsteps x timestep_sim! of the tiled run (collective).  Returns the steps run.  stop_on_tags (library backends): the batch ends
         after the first step that leaves a floe tagged remove / fuse on ANY rank -- the same step on every rank -- as World.run does
         for the single context (the reference runs simplify_floes! after every step, simulation.jl:205-214).  With set_removal() the batch
-        goes on past such a step where the collective removal pass is done, and ends there where it is declined.  A limit: with more than one
-        rank a batch is cut into calls of `repartition_every` steps (500), and the last step of a call is a batch's own last step, which is not
-        looked at -- a floe tagged on exactly that step is removed behind the first step of the next call, one step later than World.run(n) would;
-        a caller that needs the single context's timing there keeps nsteps within one call or calls remove_floes() itself."""
+        goes on past such a step where the collective removal pass is done, and ends there where it is declined.  With set_fracture() it
+        ends after the first fracture step (tstep % dt == 0) on which a floe of any rank would fracture, however the batch is cut: with more
+        than one rank a batch is cut into calls of `repartition_every` steps (500), the last step of a call is a batch's own last step,
+        which sz_tile_run does not look at -- so when that step is a fracture step, run asks for the global candidate count itself and ends
+        there if it is positive: run(n) returns what World.run(n) returns.  A limit that stays: a floe TAGGED on exactly the last step of a
+        call is removed behind the first step of the next call, one step later than World.run(n) would; a caller that needs the single
+        context's timing there keeps nsteps within one call or calls remove_floes() itself."""
         done = 0
         while done < nsteps:
             k = min(nsteps - done, self.repartition_every - self._since_check) if self.nranks > 1 else nsteps - done
@@ -545,6 +587,10 @@ class TiledWorld:
                     self._after_pass()
                 if ran.value < k:
                     return done + int(ran.value)
+                fdt = self._frac_dt
+                if stop_on_tags and fdt > 0 and done + k < nsteps and (tstep0 + done + k - 1) % fdt == 0 and self._fracture_pass(False)[0] > 0:
+                    self._since_check += k
+                    return done + k
             else:
                 for s in range(k):
                     self.step(tstep0 + done + s, dt, coupling_dt, collisions_on, coupling_on)
