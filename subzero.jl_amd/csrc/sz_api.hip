@@ -1,6 +1,6 @@
-// sz_api.hip — context, HBM allocation, launch orchestration and the extern "C" boundary
-// declared in include/subzero_hip.h.  Host code here is plumbing; the arithmetic is in
-// sz_kernels.hpp / sz_geom.hpp.
+// sz_api.hip — the one translation unit of the library: uploads and downloads, launch orchestration, the single context's batch drivers and
+// passes, and the extern "C" boundary declared in include/subzero_hip.h.  The context and its allocations are sz_ctx.hpp, the channel
+// between ranks sz_comm.hpp, everything tiled sz_tile_host.hpp.  Host code is plumbing; the arithmetic is in sz_kernels.hpp / sz_geom.hpp.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <execinfo.h>
@@ -24,236 +24,10 @@
 #include "sz_remove_tile.hpp"
 #include "sz_fracture_tile.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
-
-using namespace sz;
-
-namespace {
-
-constexpr int NK = SZ_K_COUNT + 2;   // + large narrow variant, + the halo exchange of a tiled step (events on the communication stream)
-constexpr int K_NARROW_LARGE = SZ_K_COUNT, K_EXCHANGE = SZ_K_COUNT + 1;
-struct EvPair { int k; hipEvent_t a, b; };
-
-// Device allocations of one lifetime.  The ~130 columns and work arrays are carved out of a few large chunks
-// instead of one hipMalloc each: the chunks are mapped with 2 MB fragments, so a kernel that walks 60 columns
-// needs a handful of TLB entries instead of several per column.
-struct Pool {
-  std::vector<void*> chunks; std::vector<size_t> sizes;
-  size_t ci = 0;                 // chunk being carved
-  char* cur = nullptr; size_t left = 0, next = 8u << 20;
-  bool empty() const { return chunks.empty(); }
-  void push_back(void* q) { chunks.push_back(q); sizes.push_back(0); }      // a stand-alone allocation handed to the pool
-};
-
-}  // namespace
-
-struct sz_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = true;
-  hipStream_t stream2 = nullptr;        // forcings beside the collision kernels
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  State S{};
-  Params P{};
-  std::string err;
-  Pool allocs;        // per-upload allocations
-  Pool list_allocs;   // the lists whose capacity follows the field and GROWS on demand (grow_lists): neighbour lists, pair items, item rows
-  int callid = 0;     // collision calls so far (State::callid: a call run again after its lists grew adds its overlap to floe.overarea once)
-  Pool inter_allocs;  // floe.interactions (inter_cnt, inter_rows): survive an upload of the same size -- a shim uploads between
-                      // timestep_collisions! and timestep_floe_properties!, and calc_stress! reads the rows of the collisions
-  int inter_capM = 0, inter_rowcap = 0; bool inter_any = false, inter_lost = false;
-  int nb_count_max = 0;             // bounding-circle neighbours of the most crowded floe at upload (inflated circles): sizes State::maxnb
-  Pool static_allocs; // domain element table
-  Pool field_allocs;  // ocean / atmosphere lattices
-  bool have_floes = false, have_domain = false, have_fields = false;
-  int hostM = 0, hostN = 0;
-  // element table (host copy, rebuilt on set_domain / set_topography)
-  int h_kinds[4] = { 0, 0, 0, 0 };
-  double h_vals[4] = { 0, 0, 0, 0 }, h_rects[16] = { 0 }, h_bu[4] = { 0 }, h_bv[4] = { 0 };
-  std::vector<int> h_toff; std::vector<double> h_tx, h_ty, h_tcx, h_tcy, h_trmax;
-  // profiling
-  unsigned pmask = 0;               // bit k: kernel class k is event-timed
-  std::vector<EvPair> evs; size_t ev_used = 0;
-  double kms[NK] = { 0 }; long long kl[NK] = { 0 };
-  // fuse bookkeeping (status.fuse_idx lives on the host: it only changes on rare fuse events)
-  std::vector<std::vector<int>> fuse_lists;
-  long long* d_stats = nullptr;
-  int last_dt = 0;
-  bool any_moving = false;
-  int overlap_forcing = -1;       // -1: by size (fp64 fields above 65 536 floes, where the forcings have a launch of their own: 0.585 -> 0.567 ms/step at 100 k; not
-                                  // in mixed precision: 0.181 -> 0.187 on configs[4]); SZ_OVERLAP=0|1 forces it.  SZ_OVERLAP=1: forcings on a second stream beside the broad / narrow / reduce kernels.  The fork/join
-                                  // costs ~10 us; riding in the neighbour launch (fuse_forcing) is as good or better at every size
-  int max_sub = 0;                  // most sub-floe points of one floe (sizes the LDS of the two-way forcing kernel)
-  int max_ring = 0, max_elem_ring = 5, max_ring_tiled = 0;   // largest ring sizes (host knowledge: which narrow variants can be needed)
-  int narrow_grid0 = 0;
-  // mixed precision (sz_set_precision): fp32 copies for the forcing kernel, rebuilt when their sources change
-  int precision = 0; bool mixed_pts_ok = false, mixed_nodes_ok = false; Pool mixed_pt_allocs, mixed_node_allocs;
-  bool blk_pts_ok = false, no_block_points = false; Pool blk_pt_allocs; int pts_N = 0;      // State::sxy (ensure_block_points); pts_N: floes whose soff entries are set (upload, migration)
-  // mixed precision, geometry: fp32 broad-phase records and body-frame rings (sz_state.hpp); rings_stale: resident steps ran on the
-  // body rings, the world rings vx / vy are behind (rebuilt by world_rings() before anything else looks at them)
-  bool mixed_geom_ok = false, rings_stale = false; Pool mixed_geom_allocs;
-  // two-way coupling (off by default, like CouplingSettings())
-  bool two_way = false; int tw_dt = 10; int tw_capM = 0; size_t tw_ncell = 0; bool temps_set = false;
-  Pool tw_allocs, tw_field_allocs;
-  // static broad-phase grid of the resident steps (fixed by the host: no bounds reduction per step)
-  // inline ghosts (sz_kernels.hpp ghost_inline_make): the resident steps make a step's ghosts in the kernel that places their parents,
-  // in allocation order; the reference's ghost numbers are recovered from the order keys of the last step that ran
-  bool gi_valid = false;            // the interaction rows / pair lists on the device carry order keys of inline ghosts
-  std::vector<long long> gi_keys;   // order key of the ghost at storage offset k (floe N + k) in the last step that ran
-  bool gi_pending = false; int gi_pending_n = 0, gi_pending_slot = 0;      // ... still to be fetched from the device (gi_fetch)
-  std::vector<int> gi_ref;          // ... and its number among the ghosts in the reference's order (ghost N + gi_ref[k])
-  bool retry_seen = false;          // an item has needed the largest narrow variant: sz_step enqueues it in every step from now on
-  bool no_lean_narrow = false;      // SZ_LEAN_NARROW=0: always enqueue it
-  double* frc_alt[4] = { nullptr, nullptr, nullptr, nullptr };      // second set of the forcing outputs fxOA, fyOA, trqOA, hflx (tiled steps with peers, see sz_tile_run)
-  double2* crec_buf = nullptr;      // the records' memory (State::crec points at it only inside the batches that keep it current)
-  bool crec_was_live = false;       // the last resident batch ran on records (sz_debug_crec_mismatches)
-  int forcing_where = -1;           // sz_forcing_launch
-  int fuse_forcing_mode = 0;        // ... 1: in the neighbour launch, 2: in the narrow launch (its tail), 0: by size -- the narrow launch while the narrow phase is one
-                                    // round with a long tail (measured better up to 20 k floes, even at 40 k, worse at 65 k); SZ_FUSE_FORCING=1|2 forces one
-  bool fuse_forcing = true;         // forcings inside the neighbour launch (sz_k_neighbors_forcing); SZ_FUSE_FORCING=0: own launch
-  double rmax_max = 0.0, rmax_hint = 0.0; bool grid_ok = false, grid_live = false; double h_grid[8] = { 0 };
-  unsigned scan_epoch = 0;      // launch counter of the look-back scans (their flags carry it: no reset pass)
-  // ghost-candidate lists of the resident steps (sz_k_ghost_list): gl_cur = the list the next step consumes, gl_valid = it is
-  // current (kept so by the integrator / halo unpack; any process-mode call or upload makes it stale: it is then seeded again),
-  // gl_est = how long it is (host estimate at upload, device count after every batch): long lists take the two-launch path
-  int gl_cur = 0; bool gl_valid = false; int gl_est = 0; bool no_ghost_list = false; int gl_max = 2048;
-  // tiled runs with the exchange inside the library (sz_comm_init / sz_tile_setup / sz_tile_run): the RCCL communicator, a second
-  // stream for the sends / receives (the forcings of the owned floes run beside them), the exchange buffers and their layout
-  void* comm = nullptr; int comm_n = 0, comm_rank = 0;
-  sz_host_transport host_tr = { nullptr, nullptr, nullptr, nullptr }; bool host_transport = false;   // sz_comm_init_host: the collectives are the host's, staged through h_send / h_recv
-  std::vector<double> h_send, h_recv;
-  hipStream_t comm_stream = nullptr; hipEvent_t ev_packed = nullptr, ev_recv = nullptr;
-  Pool comm_allocs; double *d_send = nullptr, *d_recv = nullptr, *d_ref = nullptr, *d_gather = nullptr; int* d_dcap = nullptr;
-  int halo_cap = 0; std::vector<int> cap_send, cap_recv;      // slots per peer region (stride) and what is really sent to / received from each peer
-  double tile_Lx = 0, tile_Ly = 0, tile_margin = 0; int tile_per_x = 0, tile_per_y = 0, tile_rebox_every = 50, tile_since_box = -1, tile_rebox_cur = 8, tile_dt = 0; bool tile_rebox_fixed = false;    // rebox_cur: the gather interval in use (<= rebox_every, from the measured drift)
-  Pool tw_part_allocs; double* d_tw_partial = nullptr;
-  Pool mig_allocs;                  // scratch of sz_tile_migrate (streams, directory, the gathered rows): kept between migrations
-  Pool sub_allocs;                  // sub-floe points of a tile that outgrew State::capS in a migration (sz_tile_migrate): until the next upload
-  int upload_M = 0, upload_V = 0;   // floes and ring points of the last sz_upload_floes (what its capacities were carved for)
-  int migrate_path = 0;             // how the last sz_tile_migrate ran: 1 packed on the device, 2 staged through the host (sz_debug_migrate_path)
-  std::vector<long long> tile_gidx; // global index of every owned floe (sz_tile_enable): status.fuse_idx of a tiled context is reported in global numbers
-  bool tile_hdr_neighbours = false; // SZ_TILE_HEADERS=neighbours (measurement only, batches that run through): the inline steps trade with the neighbouring tiles only --
-                                    // no header record to the others, hence no tag stop and no pause agreement in that arm (the largest narrow variant stays in)
-  double tile_box_ctr[2] = { 0, 0 }; bool tile_box_valid = false;   // centre of this rank's owned box at the last gather (sz_k_owned_box: periodic images)
-  int tile_forcing_tstep = -1;      // timestep whose forcings sz_tile_forcing has already enqueued
-  bool tile_dirty = false;      // ghosts / halo floes of the last sz_tile_step still appended
-  // fixed-point totals (State::facc): resident batches only.  acc_mode: what the integrator is told (bit 0: totals / stress sums / tags from facc,
-  // bit 1: the batch's last step); reduce_mode: 0 sz_k_inter_fill does everything inside the step (process mode), 1 it only assembles rows inside
-  // the step, 2 it is left out of the steps and runs once behind the batch (the reduce-free steps)
-  long long* facc_buf = nullptr; int acc_mode = 0, reduce_mode = 0;
-  // pipelined resident steps (sz_pipeline.hpp): the second set of what is double-buffered by step parity.  pb[0] is what the upload carved
-  // (State::vxy, crec_buf, the cell lists, the work list, the ghost links), pb[1] its twin; gpar: the set that holds the context's state -- c->S
-  // points at pb[gpar]'s buffers, the records apart: State::crec is a batch mode, the set's records are crec_buf (own_set_carved, pipe_adopt).
-  StepSet pb[2] = {};
-  int gpar = 0;
-  bool no_pipeline = false;         // SZ_PIPELINE=0: the three-launch steps (A/B)
-  int pipe_min_steps = 4;           // batches shorter than this take the three-launch steps (a pipelined batch has a prologue and an epilogue)
-  int pipe_max_floes = 60000;       // larger fields keep the three-launch steps: they are throughput-bound, nothing idles beside the narrow phase (measured at 100 k: 0.486 against 0.476 ms; SZ_PIPE_MAX_FLOES)
-  int last_pipelined = 0;           // the last sz_step batch ran pipelined (sz_debug_pipelined)
-  bool crec_current = false;        // the collision records of set gpar hold the parents as they lie (a pipelined batch left them so; any call that moves or
-                                    // re-uploads floes outside such a batch clears it) and the twin set has the static quads: the next batch seeds neither
-  // fracture criterion (sz_set_fracture; sz_fracture.hpp): kind SZ_FRAC_*, FractureSettings.Δt, the device block and the per-parent buffers
-  int frac_kind = 0, frac_dt = 0, frac_npts = 0, frac_cap = 0;
-  double frac_pstar = 0, frac_c = 0, frac_alpha = 0, frac_min_area = 0;
-  FracDev* frac_d = nullptr; unsigned char* frac_flag = nullptr; int* frac_idx = nullptr;
-  Pool frac_allocs;                 // scratch of a tiled context's collective criterion pass (tile_frac_pass; sz_fracture_tile.hpp): kept between passes
-  int tile_stop_raised = 0;         // the batch-relative stop step the last tile driver ended with (0: none): the list-based driver's is THIS rank's own word -- a tag of its
-                                    // last step is not yet known to the peers --, the inline driver's is already the ranks' agreed one (comm_agree_steps)
-  std::vector<int> frac_cnt;        // owned counts of all ranks of the last criterion pass (the source of an asynchronous upload: outlives the call)
-  // welding (sz_set_welding; sz_weld.hpp): WeldSettings' Δts / Nxs / Nys in the reference's order and max_weld_area; the buffers of the overlap-table
-  // pass (its own search cells, bins, pair keys, areas, table), carved for weld_capN parents, weld_cells cells and weld_cap pairs
-  std::vector<int> weld_dts, weld_nxs, weld_nys; double weld_max_area = 0;
-  Pool weld_allocs; int weld_capN = 0, weld_cells = 0, weld_cap = 0; void* weld_tmp = nullptr; size_t weld_tmp_bytes = 0;
-  WeldArgs weld{}; int *weld_cell_cnt = nullptr, *weld_cell_slots = nullptr, *weld_cell_ovf = nullptr, *weld_cell_items = nullptr; double* weld_bounds = nullptr;
-  WeldDev weld_h{}; double weld_h_grid[8] = { 0 };          // host sides of the two small uploads of a pass
-  int weld_npairs = 0;              // candidate pairs of the last pass (sz_debug_weld_npairs)
-  // removal (sz_set_removal; sz_remove.hpp): SimplificationSettings.max_vertices (INT32_MAX: smoothing off) and FloeSettings' minimum area / height;
-  // the running ocean.dissolved lattice (with the fields: zero after sz_set_fields); per parent the row it had at the last sz_upload_floes
-  bool rm_on = false; int rm_max_vertices = 0x7fffffff; double rm_min_area = 0, rm_min_height = 0;
-  double* dissolved = nullptr; int* origin = nullptr; Pool rm_allocs;
-  bool last_stopped = false;        // the last batch of resident steps ended on a stop request (tag, fracture candidate), not at its last step
-  bool maybe_tagged = false;        // a parent may be non-active on the device (an upload said so, a batch ended on a tag, a process-mode call ran):
-                                    // the next batch then runs its first step on its own (see sz_step)
-  int last_err_bits = 0;   // device error bits the last sync_and_check found (tiled runs agree on them between the ranks)
-  int dbg = 0;   // SZ_DEBUG: read by the narrow kernel of a -DSZ_STAMPS build only (dbg >> 8: the workgroup it stamps, bit 16: its first round twice)
-};
+#include "sz_ctx.hpp"
+#include "sz_comm.hpp"
 
 namespace {
-
-#define HIPCHK(ctx, call)                                                              \
-  do {                                                                                 \
-    hipError_t e_ = (call);                                                            \
-    if (e_ != hipSuccess) {                                                            \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                  \
-      return SZ_E_HIP;                                                                 \
-    }                                                                                  \
-  } while (0)
-
-template <typename T>
-int dalloc(sz_ctx* c, T** p, size_t n, Pool& pool) {
-  const size_t bytes = (((n ? n : 1) * sizeof(T)) + 255) & ~(size_t)255;
-  if (bytes > pool.left) {
-    // a chunk kept from before the last reset_pool() that is large enough comes first (an upload of the same sizes
-    // as the previous one then allocates nothing)
-    size_t k = pool.cur ? pool.ci + 1 : 0;
-    while (k < pool.chunks.size() && pool.sizes[k] < bytes) {      // too small now: will not fit later either
-      (void)hipFree(pool.chunks[k]); pool.chunks.erase(pool.chunks.begin() + k); pool.sizes.erase(pool.sizes.begin() + k);
-    }
-    if (k < pool.chunks.size()) { pool.ci = k; pool.cur = (char*)pool.chunks[k]; pool.left = pool.sizes[k]; }
-    else {
-      const size_t chunk = std::max(bytes, pool.next);
-      void* q = nullptr;
-      HIPCHK(c, hipMalloc(&q, chunk));
-      pool.chunks.push_back(q); pool.sizes.push_back(chunk); pool.ci = pool.chunks.size() - 1; pool.cur = (char*)q; pool.left = chunk;
-      if (pool.next < ((size_t)256 << 20)) pool.next *= 2;
-    }
-    // allocations are handed out zeroed: one fill per chunk instead of one per array (~130 launches per upload)
-    HIPCHK(c, hipMemsetAsync(pool.cur, 0, pool.left, c->stream));
-  }
-  void* q = pool.cur; pool.cur += bytes; pool.left -= bytes;
-  *p = (T*)q;
-  return SZ_OK;
-}
-void free_pool(Pool& pool) { for (void* p : pool.chunks) (void)hipFree(p); pool.chunks.clear(); pool.sizes.clear(); pool.ci = 0; pool.cur = nullptr; pool.left = 0; pool.next = 8u << 20; }
-// forget the allocations, keep the memory for the next round of dalloc()s
-void reset_pool(Pool& pool) { pool.ci = 0; pool.cur = nullptr; pool.left = 0; }
-// after a round: chunks the round did not reach go back to the driver
-void trim_pool(Pool& pool) {
-  const size_t keep = pool.cur ? pool.ci + 1 : 0;
-  for (size_t k = keep; k < pool.chunks.size(); k++) (void)hipFree(pool.chunks[k]);
-  pool.chunks.resize(keep); pool.sizes.resize(keep);
-}
-
-struct PoolGuard { Pool v; PoolGuard() { v.next = 1u << 16; } ~PoolGuard() { free_pool(v); } };
-
-inline int grid_for(long long n, int tpb, int maxb = 4096) {
-  long long b = (n + tpb - 1) / tpb;
-  if (b < 1) b = 1;
-  if (b > maxb) b = maxb;
-  return (int)b;
-}
-// timestep tstep computes the forcings (a coupling step)
-inline bool coupling_at(int flags, int coupling_dt, int tstep) { return (flags & SZ_COUPLING_ON) && coupling_dt > 0 && (tstep % coupling_dt) == 0; }
-
-struct Timed {   // RAII-free helper: begin/end a timed kernel class
-  sz_ctx* c; int k; size_t idx = (size_t)-1; hipStream_t st;
-  Timed(sz_ctx* c_, int k_, hipStream_t st_ = nullptr) : c(c_), k(k_), st(st_ ? st_ : c_->stream) {
-    if (!(c->pmask >> k & 1u)) return;
-    if (c->ev_used == c->evs.size()) {
-      EvPair e; e.k = k; (void)hipEventCreate(&e.a); (void)hipEventCreate(&e.b); c->evs.push_back(e);
-    }
-    idx = c->ev_used++;
-    c->evs[idx].k = k;
-    (void)hipEventRecord(c->evs[idx].a, st);
-  }
-  void end() { if (idx != (size_t)-1) (void)hipEventRecord(c->evs[idx].b, st); }
-};
-void resolve_events(sz_ctx* c) {
-  for (size_t i = 0; i < c->ev_used; i++) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->evs[i].a, c->evs[i].b) == hipSuccess) { c->kms[c->evs[i].k] += ms; c->kl[c->evs[i].k] += 1; }
-  }
-  c->ev_used = 0;
-}
 
 // exclusive scan of in[0..n) into out[0..n], n = cnt[ci] + add; total also to cnt[co]
 constexpr int SCAN_ONE_MAX = 1 << 13;     // up to here a scan is one single-workgroup launch instead of three (measured: wins below ~5k floes)
@@ -264,48 +38,8 @@ void scan(sz_ctx* c, const int* in, int* out, int cap, int ci, int add, int co) 
   hipLaunchKernelGGL(sz_k_scan2, dim3(1), dim3(SCAN_B), 0, c->stream, c->S.blk, c->S.cnt, ci, add);
   hipLaunchKernelGGL(sz_k_scan3, dim3(nb), dim3(SCAN_B), 0, c->stream, in, out, c->S.blk, c->S.cnt, ci, add, co);
 }
-
-// after tiled steps: forget the ghosts and halo floes of the last one (simulation.jl:138-144; N := owned)
-void tile_cleanup(sz_ctx* c) {
-  if (!c->tile_dirty) return;
-  hipLaunchKernelGGL(sz_k_remove_ghosts, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, 1);
-  c->tile_dirty = false;
-}
-// the counter block as the stream leaves it: copied behind everything enqueued so far, and waited for
-int fetch_counters(sz_ctx* c, int* h) {
-  HIPCHK(c, hipMemcpyAsync(h, c->S.cnt, C_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SZ_OK;
-}
-// The words through which the kernels of a resident batch end or pause it (sz_state.hpp), cleared between (sub-)batches: one memset per word
-// of the mask, in the order of the list below
-constexpr unsigned W_STOP = 1u << C_STOP, W_RETRYSTOP = 1u << C_RETRYSTOP, W_PAUSED = 1u << C_PAUSED, W_FRCSTOP = 1u << C_FRCSTOP;
-hipError_t clear_stop_words(sz_ctx* c, unsigned mask) {
-  hipError_t e = hipSuccess;
-  for (int w : { C_STOP, C_RETRYSTOP, C_PAUSED, C_FRCSTOP }) if (e == hipSuccess && (mask >> w & 1u)) e = hipMemsetAsync(c->S.cnt + w, 0, sizeof(int), c->stream);
-  return e;
-}
 // collision records of the first n floes of T from their columns (State::crec must point at the records)
 void seed_records(sz_ctx* c, const State& T, int n) { hipLaunchKernelGGL(sz_k_crec_seed, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, T, n); }
-int sync_and_check(sz_ctx* c, int* cnt_out = nullptr) {
-  tile_cleanup(c);
-  int h[C_COUNT];
-  if (int rc = fetch_counters(c, h)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream2));
-  if (c->pmask) resolve_events(c);
-  c->hostM = h[C_M]; c->hostN = h[C_N];
-  if (cnt_out) memcpy(cnt_out, h, sizeof(h));
-  c->last_err_bits = h[C_ERR];
-  if (h[C_ERR]) {
-    char buf[400];
-    snprintf(buf, sizeof(buf),
-             "device capacity/consistency error bits 0x%x (ring=1 crossings=2 regions=4 rows=8 trace=16 neighbours=32 "
-             "pairs=64 elems=128 inter=256 floes=512 verts=1024 cells=2048 ghosts/parent=4096 scan=8192 halo-drift=16384 fixed-point-range=32768)", h[C_ERR]);
-    c->err = buf;
-    int z = 0; (void)hipMemcpy(c->S.cnt + C_ERR, &z, sizeof(int), hipMemcpyHostToDevice);
-    return SZ_E_CAPACITY;
-  }
-  return SZ_OK;
-}
 
 // ---------------------------------------------------------------- lists that follow the field
 // floe.interactions (rows at a stride of State::rowcap per floe): kept across an upload of the same size (see sz_upload_floes)
@@ -1541,6 +1275,22 @@ int sz_download_fuse(sz_ctx* c, int32_t* off, int32_t* idx) {
   return SZ_OK;
 }
 
+// sub-floe points of the floes the context holds (CSR: off has N + 1 entries; call with sx == NULL for the offsets alone): after a
+// migration the host's copy of these is the library's
+int sz_download_subpoints(sz_ctx* c, int32_t* off, double* sx, double* sy) {
+  if (!c || !c->have_floes || !off) return SZ_E_ARG;
+  (void)hipSetDevice(c->device);
+  tile_cleanup(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int N = c->hostN;
+  HIPCHK(c, hipMemcpy(off, c->S.soff, ((size_t)N + 1) * sizeof(int), hipMemcpyDeviceToHost));
+  if (sx && sy && off[N] > 0) {
+    HIPCHK(c, hipMemcpy(sx, c->S.sx, (size_t)off[N] * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(sy, c->S.sy, (size_t)off[N] * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return SZ_OK;
+}
+
 int sz_get_boundary_vals(sz_ctx* c, double* vals4) {
   if (!c || !vals4 || !c->have_domain) return SZ_E_ARG;
   (void)hipSetDevice(c->device);
@@ -1861,6 +1611,8 @@ struct BatchPlan {
   // the steps start without the largest narrow variant (a driver puts it in when an item needs it); the first step is enqueued on its own, as
   // a last step
   bool lean, first_alone;
+  // the stop words the batch starts with cleared; the first inline ghosts are the driver's (a tile seeds them behind its first pack)
+  unsigned stop_mask; bool own_first_ghosts;
   int reduce_mode;                     // sz_ctx::reduce_mode of the batch
   void set_rfree(bool r) { rfree = r; reduce_mode = !facc_on ? 0 : r ? 2 : 1; }
 };
@@ -1889,6 +1641,7 @@ static BatchPlan plan_batch(const sz_ctx* c, int nsteps, int flags) {
   // the batch ends after the first step that leaves a parent tagged remove / fuse (simplify_floes!, simulation.jl:205-214,
   // is the host's): the launches of the later steps are enqueued all the same and return at once (stopped())
   p.user_stop = !(flags & SZ_NO_STOP);
+  p.stop_mask = W_STOP | W_RETRYSTOP;
   p.sg = p.coll && c->grid_ok;
   p.gl = ghost_list_wanted(c, p.sg);
   // inline ghosts: no ghost launch in the steps at all (the integrator makes the next step's ghosts; needs the one-launch integrator)
@@ -2216,7 +1969,7 @@ int sz_debug_pipelined(sz_ctx* c) { return c ? c->last_pipelined : 0; }
 // records and totals.  The per-batch modes it sets are put back by the caller's BatchModes scope.  *gl0: the candidate list the batch starts on.
 static int batch_enter(sz_ctx* c, const BatchPlan& p, int* gl0) {
   c->S.stop_on_tags = p.user_stop ? 1 : 0;
-  HIPCHK(c, clear_stop_words(c, W_STOP | W_RETRYSTOP));
+  HIPCHK(c, clear_stop_words(c, p.stop_mask));
   if (p.sg) use_static_grid(c);
   // (ghosts a process-mode sz_add_ghosts left attached are dropped first: the list pass only visits the parents that get new ones)
   if (p.gl && p.periodic && c->hostM != c->hostN) hipLaunchKernelGGL(sz_k_remove_ghosts, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, 0);
@@ -2235,7 +1988,7 @@ static int batch_enter(sz_ctx* c, const BatchPlan& p, int* gl0) {
   if (!p.pipe) c->crec_current = false;          // (the three-launch steps seed the records they use; they may not keep the twin set's)
   if (p.cr && !p.pipe) seed_records(c, c->S, c->hostN);
   // the ghosts of the first step, from the parents as they lie (after the rings are in the batch's form)
-  if (p.gi && !p.pipe) { if (int rc = reseed_inline_ghosts(c, 0)) return rc; }
+  if (p.gi && !p.pipe && !p.own_first_ghosts) { if (int rc = reseed_inline_ghosts(c, 0)) return rc; }
   c->S.facc = p.facc_on ? c->facc_buf : nullptr; c->S.kexp = force_scale_exp(c); c->reduce_mode = p.reduce_mode;
   if (p.facc_on && !p.pipe) { if (int rc = clear_totals(c)) return rc; }          // (a pipelined batch clears them with the rest of its prologue: one launch)
   if (p.frac) { if (int rc = frac_ensure(c)) return rc; }
@@ -2813,47 +2566,12 @@ int sz_kernel_time_ms(sz_ctx* c, int32_t k, double* ms, int64_t* launches) {
   return SZ_OK;
 }
 
+}  // extern "C"
+// ---------------------------------------------------------------- tiled contexts: behind the batch drivers and passes they call into
+#include "sz_tile_host.hpp"
+extern "C" {
 
-// ---------------------------------------------------------------- multi-GPU halo API
-int sz_tile_enable(sz_ctx* c, const int64_t* gidx, double halo_capacity_factor, double max_rmax) {
-  if (!c || !c->have_floes || !gidx) return SZ_E_ARG;
-  (void)hipSetDevice(c->device);
-  leave_resident(c);
-  State& S = c->S;
-  if (c->hostM != c->hostN) { c->err = "sz_tile_enable needs a ghost-free upload"; return SZ_E_STATE; }
-  std::vector<long long>& ok = c->tile_gidx;
-  ok.assign(c->hostN, 0);
-  for (int i = 0; i < c->hostN; i++) ok[i] = gidx[i];
-  H2D(S.okey, ok.data(), c->hostN, long long);
-  if (c->facc_buf) HIPCHK(c, hipMemsetAsync(c->facc_buf, 0, (size_t)FX_WORDS * S.capM * sizeof(long long), c->stream));      // (rows change hands in a migration: no stale totals)
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  S.tiled = 1;
-  // largest ring among ALL ranks' floes (halo floes arrive unseen): decides which narrow variants can be needed
-  c->max_ring_tiled = halo_capacity_factor > 0 ? (int)halo_capacity_factor : HALO_RING;
-  // the halo records have room for the largest ring of ANY rank's floes (Floe rings are unbounded, floe.jl:24-77; the engine's narrow phase
-  // takes 255 points, and so do the tiles): 12 + 2 * halo_ring doubles per record
-  if (c->max_ring_tiled > NARROW_CAP2) { c->err = "a ring has more than 255 points: beyond the narrow phase's largest variant"; return SZ_E_CAPACITY; }
-  S.halo_ring = std::max(HALO_RING, (std::max(c->max_ring_tiled, c->max_ring) + 3) & ~3);
-  // largest rmax among ALL ranks' floes: the static broad-phase grid must hold for halo floes too (0: unknown ->
-  // the grid is fitted to the centroids every step instead)
-  c->rmax_hint = max_rmax; c->rmax_max = max_rmax > 0 ? c->rmax_max : 0.0;
-  setup_grid(c);
-  return SZ_OK;
-}
-
-int sz_owned_box(sz_ctx* c, double* out5) {
-  if (!c || !c->have_floes || !out5) return SZ_E_ARG;
-  (void)hipSetDevice(c->device);
-  hipLaunchKernelGGL(sz_k_owned_box, dim3(1), dim3(1024), 0, c->stream, c->S, c->S.bounds + 8, (const double*)nullptr, 0.0, 0.0, 0, 0);
-  HIPCHK(c, hipMemcpyAsync(out5, c->S.bounds + 8, 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SZ_OK;
-}
-
-int sz_halo_record_doubles(void) { return HALO_REC; }
-int sz_halo_record_doubles_ctx(sz_ctx* c) { return c ? halo_rec(c->S) : HALO_REC; }
-
-// diagnostic build only: cycles per narrow-phase stage, summed over groups (zeros otherwise)
+// ---------------------------------------------------------------- debug hooks
 // test hook: quads of the collision records (State::crec) of the owned parents that differ from the columns they cache; *n_bad = -1 when the last
 // resident batch did not run on records
 int sz_debug_crec_mismatches(sz_ctx* c, int64_t* n_bad) {
@@ -2899,109 +2617,12 @@ int sz_debug_pairs_of_ids(sz_ctx* c, int32_t slot, int64_t id_a, int64_t id_b, d
   (void)hipFree(d);
   return SZ_OK;
 }
+// diagnostic build only: cycles per narrow-phase stage, summed over groups (zeros otherwise)
 int sz_debug_stamps(sz_ctx* c, long long* out16) {
   if (!c || !c->have_floes || !out16) return SZ_E_ARG;
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipMemcpy(out16, c->S.stamps, (512 + 8 * 8000) * sizeof(long long), hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemset(c->S.stamps, 0, (512 + 8 * 8000) * sizeof(long long)));
-  return SZ_OK;
-}
-
-// boxes: nranks x {xmin, xmax, ymin, ymax}, already expanded by the interaction range (rarely changes)
-int sz_halo_set_boxes(sz_ctx* c, int32_t nranks, const double* boxes) {
-  if (!c || !c->have_floes || nranks < 1 || nranks > 64 || !boxes) return SZ_E_ARG;
-  (void)hipSetDevice(c->device);
-  HIPCHK(c, hipMemcpyAsync(c->S.bounds + 16, boxes, (size_t)nranks * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SZ_OK;
-}
-
-// asynchronous: fills d_send (nranks regions of (cap + 1) records, record 0 = header with the count)
-int sz_halo_pack(sz_ctx* c, int32_t nranks, int32_t me, double Lx, double Ly, int32_t per_x, int32_t per_y, void* d_send,
-                 int32_t cap) {
-  if (!c || !c->have_floes || nranks < 1 || nranks > 64 || cap < 1) return SZ_E_ARG;
-  (void)hipSetDevice(c->device);
-  State& S = c->S;
-  int* dcnt = S.cnt + C_COUNT;                  // 64 ints reserved behind the counter block
-  hipLaunchKernelGGL(sz_k_halo_pack, dim3(grid_for(std::max(c->hostN, 1), PACK_TPB)), dim3(PACK_TPB), 0, c->stream, S, nranks, me, S.bounds + 16, Lx, Ly,
-                     per_x, per_y, (double*)d_send, cap, dcnt, (const int*)nullptr, (const double*)nullptr, 0.0);
-  return SZ_OK;
-}
-
-// asynchronous: unpack d_recv (same layout, region r = records from rank r) and run one timestep_sim!
-// on owned + halo floes; only owned floes are integrated, the halo is dropped afterwards
-namespace {
-int tile_forcing(sz_ctx* c) {
-  if (!c->have_fields) { c->err = "sz_set_fields must be called before coupling"; return SZ_E_STATE; }
-  if (c->two_way) { int rc = ensure_two_way(c); if (rc) return rc; }
-  else if (c->precision == 1) { int rc = ensure_mixed(c); if (rc) return rc; }
-  else { int rc = ensure_block_points(c); if (rc) return rc; }
-  stage_forcing(c);
-  return SZ_OK;
-}
-}  // namespace
-
-// one list-based tiled step: the body of the public sz_tile_step below, and the step of sz_tile_run's list-based driver (tile_run_listed), which
-// has checked the context and evaluates a criterion itself, between its segments
-static int tile_step_body(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int32_t tstep, int32_t dt, int32_t coupling_dt, int32_t flags) {
-  (void)hipSetDevice(c->device);
-  State& S = c->S;
-  const bool coll = (flags & SZ_COLLISIONS_ON) != 0;
-  const bool sg = coll && c->grid_ok;
-  if (sg) use_static_grid(c);
-  const bool gl = ghost_list_wanted(c, sg);
-  if (gl) use_ghost_list(c); else c->gl_valid = false;
-  if (d_recv && nranks > 0) {
-    // halo floes join the candidate list of THIS step (the owned floes were appended by the last integrator)
-    hipLaunchKernelGGL(sz_k_halo_unpack, dim3(1), dim3(1024), 0, c->stream, S, (const double*)d_recv, nranks, cap, sg ? 1 : 0, gl ? c->gl_cur : -1);
-  }
-  const bool coupling = coupling_at(flags, coupling_dt, tstep);
-  const bool periodic = S.any_periodic_ew || S.any_periodic_ns;
-  // the forcings of this step: already enqueued by sz_tile_forcing (beside the exchange), else now -- in either
-  // case before the ghost pass, like sz_step
-  if (coupling && c->tile_forcing_tstep != tstep) { int rc = tile_forcing(c); if (rc) return rc; }
-  c->tile_forcing_tstep = -1;
-  // As in sz_step, the ghosts of the previous step are detached by this step's flag kernel and the new ones
-  // committed by the flag/scan kernel; the halo of the previous step was overwritten by the unpack kernel.  Nothing
-  // between two steps looks past the owned floes, so no clean-up launch is needed per step: the ghosts and halo
-  // floes of the LAST step are dropped when the host next looks at the state (tile_cleanup).
-  // n_init = every local parent (owned + halo): totals of halo floes are computed and then ignored
-  S.callid = ++c->callid;
-  // (fixed-point totals as in the resident steps of sz_step, so that a tile and the single context give the same bits; the reduce launch stays
-  //  inside the step here, assembling rows only)
-  const bool facc_on = coll && c->facc_buf != nullptr;
-  S.facc = facc_on ? c->facc_buf : nullptr; S.kexp = force_scale_exp(c); c->reduce_mode = facc_on ? 1 : 0; c->acc_mode = facc_on ? 1 : 0;
-  if (coll) stage_ghosts(c, true, sg, gl);
-  if (coll) collisions(c, -1, dt, periodic && !sg, sg);
-  stage_integrate(c, dt, false, coupling, sg, gl ? 1 - c->gl_cur : -1);
-  S.facc = nullptr; c->reduce_mode = 0; c->acc_mode = 0;
-  if (gl) { c->gl_cur ^= 1; c->gl_est = std::max(c->gl_est, 64); }
-  c->tile_dirty = true;
-  return SZ_OK;
-}
-int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int32_t tstep, int32_t dt, int32_t coupling_dt,
-                 int32_t flags) {
-  if (!c || !c->have_floes) return SZ_E_STATE;
-  if (c->frac_kind != SZ_FRAC_OFF) { c->err = "sz_tile_step does not evaluate fracture criteria (the host drives its steps: no library channel to gather the mean height over): sz_tile_run, or sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
-  if (!c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
-  return tile_step_body(c, d_recv, nranks, cap, tstep, dt, coupling_dt, flags);
-}
-
-// Two-way coupling across tiles.  After a tiled coupling step: sz_two_way_partial writes this rank's per-cell sums
-// (3 x (Nx+1)(Ny+1) doubles: stress numerators x / y, ice area) to a DEVICE buffer of the caller, the caller adds
-// the buffers of all ranks up (all-reduce), sz_two_way_finish turns the sums into the ocean fields on every rank.
-int sz_two_way_partial(sz_ctx* c, void* d_partial) {
-  if (!c || !c->have_floes || !c->two_way || !d_partial) return SZ_E_STATE;
-  (void)hipSetDevice(c->device);
-  const int ncell = (int)c->tw_ncell;
-  hipLaunchKernelGGL(sz_k_tw_partial, dim3(grid_for(ncell, 256)), dim3(256), 0, c->stream, c->S, ncell, (double*)d_partial);
-  return SZ_OK;
-}
-int sz_two_way_finish(sz_ctx* c, const void* d_partial, int32_t dt) {
-  if (!c || !c->have_floes || !c->two_way || !d_partial) return SZ_E_STATE;
-  (void)hipSetDevice(c->device);
-  const int ncell = (int)c->tw_ncell;
-  hipLaunchKernelGGL(sz_k_tw_finish, dim3(grid_for(ncell, 256)), dim3(256), 0, c->stream, c->S, c->P, ncell, dt, (const double*)d_partial);
   return SZ_OK;
 }
 
@@ -3119,1401 +2740,6 @@ int sz_simplify_check(sz_ctx* c, int32_t max_vertices, double min_floe_area, dou
   rc = sync_and_check(c);
   if (rc) return rc;
   for (int k = 0; k < 4; k++) out4[k] = (int64_t)h[k];
-  return SZ_OK;
-}
-
-// ASYNC: the forcings of step `tstep` (owned floes only; they need nothing from the halo), to be enqueued between
-// sz_halo_pack and the collective so that they run beside the exchange; sz_tile_step(tstep) then skips them
-int sz_tile_forcing(sz_ctx* c, int32_t tstep, int32_t coupling_dt, int32_t flags) {
-  if (!c || !c->have_floes) return SZ_E_STATE;
-  (void)hipSetDevice(c->device);
-  const bool coupling = coupling_at(flags, coupling_dt, tstep);
-  if (!coupling) return SZ_OK;
-  int rc = tile_forcing(c); if (rc) return rc;
-  c->tile_forcing_tstep = tstep;
-  return SZ_OK;
-}
-
-// ---------------------------------------------------------------- the halo exchange inside the library (RCCL over xGMI)
-// "library owns device buffers, streams, RCCL communicators inside the opaque sz_ctx".  A host that is not
-// Python (the reference's is Julia: one process per GPU, e.g. under MPI.jl) drives a tiled run with
-//     sz_comm_unique_id (rank 0)  ->  the 128 bytes to every rank by any host channel  ->  sz_comm_init
-//     sz_upload_floes (the owned floes) / sz_tile_enable  ->  sz_tile_setup  ->  sz_tile_run(nsteps) on every rank.
-// Per step: pack kernel -> grouped ncclSend / ncclRecv with the NEIGHBOUR tiles only (the all-to-all-v of the halo records;
-// a peer's region carries its real count in the header record and is sized per pair from the counts at the last box gather)
-// on a second stream, beside the forcings of the owned floes -> unpack + the ordinary step.  The boxes are gathered again
-// (ncclAllGather) every `rebox_every` steps; a floe that out-runs the drift margin in between raises ERR_HALO_DRIFT.
-// RCCL is bound at run time (dlopen: the library has no link-time dependency on it, and a process that already holds an
-// RCCL -- torch's -- shares that copy).
-namespace {
-struct UId { char b[128]; };
-struct Rccl {
-  void* h = nullptr;
-  int (*GetUniqueId)(UId*) = nullptr;
-  int (*CommInitRank)(void**, int, UId, int) = nullptr;
-  int (*CommDestroy)(void*) = nullptr;
-  int (*Send)(const void*, size_t, int, int, void*, hipStream_t) = nullptr;
-  int (*Recv)(void*, size_t, int, int, void*, hipStream_t) = nullptr;
-  int (*AllGather)(const void*, void*, size_t, int, void*, hipStream_t) = nullptr;
-  int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-  int (*GroupStart)() = nullptr;
-  int (*GroupEnd)() = nullptr;
-  const char* (*GetErrorString)(int) = nullptr;
-};
-Rccl g_rccl;
-constexpr int NCCL_INT32 = 2, NCCL_FLOAT64 = 8, NCCL_SUM = 0;
-bool rccl_load(std::string& err) {
-  if (g_rccl.h) return true;
-  if (getenv("SZ_RCCL_DISABLE")) { err = "RCCL binding switched off (SZ_RCCL_DISABLE)"; return false; }     // (to rehearse the callers' fallback)
-  // an RCCL the process already holds comes first (a host framework's: two RCCL builds in one process each bring their own
-  // runtime threads), then the system's
-  const char* names[] = { "librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so.1" };
-  for (const char* n : names) if ((g_rccl.h = dlopen(n, RTLD_NOW | RTLD_NOLOAD))) break;
-  if (!g_rccl.h) for (const char* n : names) if ((g_rccl.h = dlopen(n, RTLD_NOW | RTLD_GLOBAL))) break;
-  if (!g_rccl.h) { err = std::string("RCCL not found: ") + dlerror(); return false; }
-#define RSYM(field, name) g_rccl.field = (decltype(g_rccl.field))dlsym(g_rccl.h, name); if (!g_rccl.field) { err = std::string("RCCL symbol missing: ") + name; g_rccl.h = nullptr; return false; }
-  RSYM(GetUniqueId, "ncclGetUniqueId") RSYM(CommInitRank, "ncclCommInitRank") RSYM(CommDestroy, "ncclCommDestroy")
-  RSYM(Send, "ncclSend") RSYM(Recv, "ncclRecv") RSYM(AllGather, "ncclAllGather") RSYM(AllReduce, "ncclAllReduce")
-  RSYM(GroupStart, "ncclGroupStart") RSYM(GroupEnd, "ncclGroupEnd") RSYM(GetErrorString, "ncclGetErrorString")
-#undef RSYM
-  return true;
-}
-#define NCCLCHK(ctx, call)                                                                             \
-  do {                                                                                                 \
-    int r_ = (call);                                                                                   \
-    if (r_ != 0) { (ctx)->err = std::string(#call) + ": " + g_rccl.GetErrorString(r_); return SZ_E_HIP; } \
-  } while (0)
-
-#define HOSTCHK(ctx, call, what)                                                                        \
-  do {                                                                                                 \
-    int r_ = (call);                                                                                   \
-    if (r_ != 0) { (ctx)->err = std::string("host transport: ") + what + " returned " + std::to_string(r_); return SZ_E_HIP; } \
-  } while (0)
-
-// all-gather of `bytes` per rank between device buffers on the context's stream (host transport: through the host, synchronous)
-int comm_allgather(sz_ctx* c, const void* d_src, void* d_dst, size_t count, int nccl_type, size_t elem) {
-  const int n = c->comm_n;
-  if (n == 1) { HIPCHK(c, hipMemcpyAsync(d_dst, d_src, count * elem, hipMemcpyDeviceToDevice, c->stream)); return SZ_OK; }
-  if (!c->host_transport) { NCCLCHK(c, g_rccl.AllGather(d_src, d_dst, count, nccl_type, c->comm, c->stream)); return SZ_OK; }
-  std::vector<char> hs(count * elem), hr(count * elem * n);
-  HIPCHK(c, hipMemcpyAsync(hs.data(), d_src, hs.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HOSTCHK(c, c->host_tr.allgather(c->host_tr.user, hs.data(), hr.data(), (int64_t)hs.size()), "allgather");
-  HIPCHK(c, hipMemcpyAsync(d_dst, hr.data(), hr.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SZ_OK;
-}
-
-// one int of every rank (n <= 64), on every rank
-int comm_gather_int(sz_ctx* c, int local, int* all64) {
-  const int n = c->comm_n;
-  all64[0] = local;
-  if (n == 1) return SZ_OK;
-  int* d = (int*)(c->d_gather + 8 + 8 * 64 + 64 * 64 / 2);       // the 64 spare doubles behind the count matrix: word | words of all ranks
-  HIPCHK(c, hipMemcpyAsync(d, &local, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  int rc = comm_allgather(c, d, d + 32, 1, NCCL_INT32, sizeof(int));
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(all64, d + 32, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SZ_OK;
-}
-// Collective: the OR of a word over the ranks.  Device errors (capacity bits, halo drift) are per rank and sticky; a rank that returned
-// on its own while its peers went on into the next collective would leave them waiting forever (RCCL has no timeout).  Every point
-// at which sz_tile_run looks at the error word therefore agrees on it first: all ranks return the same code at the same step.
-int comm_agree_bits(sz_ctx* c, int local, int* all) {
-  int h[64];
-  if (const int rc = comm_gather_int(c, local, h)) return rc;
-  int bits = 0, who = -1;
-  for (int r = 0; r < c->comm_n; r++) { if (h[r] && who < 0) who = r; bits |= h[r]; }
-  *all = bits;
-  if (bits && !local) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "rank %d of the tiled run reported device error bits 0x%x (this rank is clean; all ranks stop together)", who, bits);
-    c->err = buf;
-  }
-  return SZ_OK;
-}
-// The two words that decide how a tiled batch goes on -- the step a tag ended it at (C_STOP) and the step that paused for the largest narrow
-// variant or a list that outgrew its capacity (C_RETRYSTOP) -- as ALL ranks must see them before anyone branches: the smallest non-zero
-// value of each.  A rank's own counters are not enough: a pause on one rank and a tag on another in the SAME step are not heard by either
-// (the unpack kernels of the next step return at their stop test before they read the peers' headers), and ranks that then take
-// different branches wait for each other in different collectives.
-int comm_agree_steps(sz_ctx* c, int stop_local, int pause_local, int* stop_all, int* pause_all) {
-  int a[64], b[64];
-  int rc = comm_gather_int(c, stop_local, a); if (rc) return rc;
-  rc = comm_gather_int(c, pause_local, b); if (rc) return rc;
-  int s = 0, p = 0;
-  for (int r = 0; r < c->comm_n; r++) { if (a[r] > 0 && (s == 0 || a[r] < s)) s = a[r]; if (b[r] > 0 && (p == 0 || b[r] < p)) p = b[r]; }
-  *stop_all = s; *pause_all = p;
-  return SZ_OK;
-}
-// the agreement on this rank's sync_and_check status rc
-static int tile_agree(sz_ctx* c, int rc) {
-  int all = 0;
-  if (const int rc2 = comm_agree_bits(c, rc ? (c->last_err_bits ? c->last_err_bits : 1) : 0, &all)) return rc2;
-  return all ? SZ_E_CAPACITY : SZ_OK;
-}
-// sync + sticky device errors of THIS rank + agreement: SZ_OK on every rank or the same error code on every rank
-int tile_sync_agree(sz_ctx* c, int* cnt_out = nullptr) {
-  const int rc = sync_and_check(c, cnt_out);
-  return rc == SZ_E_HIP ? rc : tile_agree(c, rc);              // (the runtime itself failed: nothing to agree on)
-}
-
-// do the expanded box of rank d and the (margin-expanded) owned box of rank s meet, periodic images included?
-bool tiles_adjacent(const double* owned_s, const double* expanded_d, double margin, double Lx, double Ly, int per_x, int per_y) {
-  for (int kx = (per_x ? -1 : 0); kx <= (per_x ? 1 : 0); kx++)
-    for (int ky = (per_y ? -1 : 0); ky <= (per_y ? 1 : 0); ky++) {
-      const double x0 = owned_s[0] - margin + kx * Lx, x1 = owned_s[1] + margin + kx * Lx;
-      const double y0 = owned_s[2] - margin + ky * Ly, y1 = owned_s[3] + margin + ky * Ly;
-      if (!(x1 < expanded_d[0] || expanded_d[1] < x0 || y1 < expanded_d[2] || expanded_d[3] < y0)) return true;
-    }
-  return false;
-}
-
-// collective: owned boxes of all ranks -> expanded boxes on the device, neighbour relation, per-pair slot counts, buffers,
-// reference positions of the drift check.  Synchronises (it runs once per rebox_every steps).
-int tile_rebox(sz_ctx* c) {
-  State& S = c->S;
-  const int n = c->comm_n, me = c->comm_rank;
-  int rc = tile_sync_agree(c); if (rc) return rc;
-  // (every gather after the first: centroids at their periodic image nearest to the centre of the last box -- d_gather[8 + 8 me ..] still holds it)
-  double* d_ctr = c->d_gather + 8 + 8 * 64 + 64 * 64 / 2 + 48;          // two of the spare doubles
-  if (c->tile_box_valid) {
-    const double ctr[2] = { c->tile_box_ctr[0], c->tile_box_ctr[1] };
-    HIPCHK(c, hipMemcpyAsync(d_ctr, ctr, sizeof(ctr), hipMemcpyHostToDevice, c->stream));
-  }
-  hipLaunchKernelGGL(sz_k_owned_box, dim3(1), dim3(1024), 0, c->stream, S, c->d_gather, c->tile_box_valid ? (const double*)d_ctr : (const double*)nullptr,
-                     c->tile_Lx, c->tile_Ly, c->tile_per_x, c->tile_per_y);
-  constexpr int GB = 8;      // doubles per rank in the gather: box, rmax, drift, speed, (spare)
-  std::vector<double> all((size_t)GB * n);
-  if ((rc = comm_allgather(c, c->d_gather, c->d_gather + 8, GB, NCCL_FLOAT64, sizeof(double)))) return rc;
-  HIPCHK(c, hipMemcpyAsync(all.data(), c->d_gather + 8, all.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->tile_box_ctr[0] = 0.5 * (all[GB * me] + all[GB * me + 1]); c->tile_box_ctr[1] = 0.5 * (all[GB * me + 2] + all[GB * me + 3]); c->tile_box_valid = true;
-  double rmax = 0.0, drift = 0.0, speed = 0.0;
-  for (int r = 0; r < n; r++) { rmax = std::max(rmax, all[GB * r + 4]); drift = std::max(drift, all[GB * r + 5]); speed = std::max(speed, all[GB * r + 6]); }
-  // the gather interval follows the floes (every rank computes the same number): at the faster of the measured displacement per step since
-  // the last gather and the largest velocity component now, they may use 30 % of the margin before the next gather (half of it is the
-  // error threshold); the interval at most doubles from one gather to the next, and a new setup starts with a short one -- floes that
-  // start from rest are slower in their first steps than later
-  {
-    const double per_step = std::max(c->tile_since_box > 0 ? drift / c->tile_since_box : 0.0, speed * std::fabs((double)c->tile_dt));
-    int want = per_step > 0.0 ? (int)std::max(1.0, std::min((double)c->tile_rebox_every, 0.3 * c->tile_margin / per_step)) : c->tile_rebox_every;
-    if (c->tile_since_box > 0) want = std::min(want, 2 * c->tile_rebox_cur);
-    else want = std::min(want, c->tile_rebox_cur);
-    c->tile_rebox_cur = c->tile_rebox_fixed ? c->tile_rebox_every : std::max(1, want);
-  }
-  const double reach = 2.0 * rmax + c->tile_margin;
-  std::vector<double> boxes((size_t)4 * n);
-  for (int r = 0; r < n; r++) { boxes[4 * r] = all[GB * r] - reach; boxes[4 * r + 1] = all[GB * r + 1] + reach; boxes[4 * r + 2] = all[GB * r + 2] - reach; boxes[4 * r + 3] = all[GB * r + 3] + reach; }
-  HIPCHK(c, hipMemcpyAsync(S.bounds + 16, boxes.data(), boxes.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  // counting pass, then the count matrix of all ranks (row s: what s sends to every d)
-  int* dcnt = S.cnt + C_COUNT;
-  hipLaunchKernelGGL(sz_k_halo_pack, dim3(grid_for(std::max(c->hostN, 1), PACK_TPB)), dim3(PACK_TPB), 0, c->stream, S, n, me, S.bounds + 16, c->tile_Lx, c->tile_Ly, c->tile_per_x,
-                     c->tile_per_y, (double*)nullptr, 1, dcnt, (const int*)nullptr, (const double*)nullptr, 0.0);
-  int* d_mat = (int*)(c->d_gather + 8 + GB * 64);
-  std::vector<int> mat((size_t)n * n);
-  if ((rc = comm_allgather(c, dcnt, d_mat, (size_t)n, NCCL_INT32, sizeof(int)))) return rc;
-  HIPCHK(c, hipMemcpyAsync(mat.data(), d_mat, mat.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  // slots per ordered pair: neighbours get 1.5 x the present count + 32, the others nothing (every rank computes the same table)
-  c->cap_send.assign(n, 0); c->cap_recv.assign(n, 0);
-  int cap = 32;
-  for (int s = 0; s < n; s++)
-    for (int d = 0; d < n; d++) {
-      if (s == d) continue;
-      const bool adj = tiles_adjacent(&all[GB * s], &boxes[4 * d], c->tile_margin, c->tile_Lx, c->tile_Ly, c->tile_per_x, c->tile_per_y);
-      const int k = adj || mat[(size_t)s * n + d] > 0 ? mat[(size_t)s * n + d] * 3 / 2 + 32 : 0;
-      if (s == me) c->cap_send[d] = k;
-      if (d == me) c->cap_recv[s] = k;
-      cap = std::max(cap, k);
-    }
-  if (cap > c->halo_cap || !c->d_send) {
-    reset_pool(c->comm_allocs);          // (chunks that are large enough are carved again: a set-up after a migration allocates nothing)
-    c->halo_cap = cap;
-    const size_t nd = (size_t)n * (cap + 1) * halo_rec(c->S);
-    if ((rc = dalloc(c, &c->d_send, nd, c->comm_allocs)) || (rc = dalloc(c, &c->d_recv, nd, c->comm_allocs)) ||
-        (rc = dalloc(c, &c->d_ref, (size_t)2 * S.capM, c->comm_allocs)) || (rc = dalloc(c, &c->d_dcap, 64, c->comm_allocs))) return rc;
-    trim_pool(c->comm_allocs);
-  }
-  // regions of ranks that send nothing keep a zero count in their header record
-  HIPCHK(c, hipMemsetAsync(c->d_recv, 0, (size_t)n * (c->halo_cap + 1) * halo_rec(c->S) * sizeof(double), c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_dcap, c->cap_send.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_ref, S.cx, (size_t)c->hostN * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_ref + S.capM, S.cy, (size_t)c->hostN * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->tile_since_box = 0;
-  return SZ_OK;
-}
-}  // namespace
-
-// can the RCCL binding be made in this process (run-time loading)?  Hosts ask on EVERY rank and agree on the answer over their own
-// channel before the collective sz_comm_init: a rank that cannot bind would leave the others waiting inside ncclCommInitRank
-int sz_comm_available(void) {
-  std::string err;
-  return rccl_load(err) ? SZ_OK : SZ_E_STATE;
-}
-int sz_comm_unique_id(void* id128) {
-  std::string err;
-  if (!id128 || !rccl_load(err)) return SZ_E_STATE;
-  return g_rccl.GetUniqueId((UId*)id128) == 0 ? SZ_OK : SZ_E_HIP;
-}
-int sz_comm_init(sz_ctx* c, int32_t nranks, int32_t rank, const void* id128) {
-  if (!c || nranks < 1 || nranks > 64 || rank < 0 || rank >= nranks || (nranks > 1 && !id128)) return SZ_E_ARG;
-  (void)hipSetDevice(c->device);
-  (void)sz_comm_destroy(c);
-  if (nranks > 1) {
-    if (!rccl_load(c->err)) return SZ_E_STATE;
-    UId id; memcpy(&id, id128, sizeof(id));
-    NCCLCHK(c, g_rccl.CommInitRank(&c->comm, nranks, id, rank));
-  }
-  c->comm_n = nranks; c->comm_rank = rank;
-  HIPCHK(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
-  HIPCHK(c, hipEventCreateWithFlags(&c->ev_packed, hipEventDisableTiming));
-  HIPCHK(c, hipEventCreateWithFlags(&c->ev_recv, hipEventDisableTiming));
-  return SZ_OK;
-}
-// the host's own channel instead of RCCL (include/subzero_hip.h: sz_host_transport)
-int sz_comm_init_host(sz_ctx* c, int32_t nranks, int32_t rank, const sz_host_transport* t) {
-  if (!c || nranks < 1 || nranks > 64 || rank < 0 || rank >= nranks) return SZ_E_ARG;
-  if (nranks > 1 && (!t || !t->allgather || !t->sendrecv || !t->allreduce_sum_f64)) { c->err = "sz_comm_init_host: the transport needs all three collectives"; return SZ_E_ARG; }
-  (void)hipSetDevice(c->device);
-  (void)sz_comm_destroy(c);
-  if (nranks > 1) { c->host_tr = *t; c->host_transport = true; }
-  c->comm_n = nranks; c->comm_rank = rank;
-  HIPCHK(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
-  HIPCHK(c, hipEventCreateWithFlags(&c->ev_packed, hipEventDisableTiming));
-  HIPCHK(c, hipEventCreateWithFlags(&c->ev_recv, hipEventDisableTiming));
-  return SZ_OK;
-}
-// One-rank self test of the RCCL binding (the build box has one GPU, so the multi-rank exchange cannot run there): the
-// run-time binding, ncclGetUniqueId / ncclCommInitRank with the id passed by value, an all-gather, an all-reduce and a
-// grouped send / receive to self on the communication stream with the event hand-shake sz_tile_run uses.  Returns SZ_OK
-// when every buffer holds what it should.
-int sz_comm_selftest(sz_ctx* c) {
-  if (!c) return SZ_E_ARG;
-  (void)hipSetDevice(c->device);
-  if (!rccl_load(c->err)) return SZ_E_STATE;
-  UId id;
-  NCCLCHK(c, g_rccl.GetUniqueId(&id));
-  void* comm = nullptr;
-  NCCLCHK(c, g_rccl.CommInitRank(&comm, 1, id, 0));
-  hipStream_t cs = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPCHK(c, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-  HIPCHK(c, hipEventCreateWithFlags(&e0, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-  const int n = 4096;
-  double* d = nullptr;
-  HIPCHK(c, hipMalloc((void**)&d, (size_t)4 * n * sizeof(double)));
-  std::vector<double> h((size_t)4 * n, 0.0);
-  for (int k = 0; k < n; k++) h[k] = 1.0 + k;
-  HIPCHK(c, hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(e0, c->stream));
-  HIPCHK(c, hipStreamWaitEvent(cs, e0, 0));
-  int rc = SZ_OK;
-  NCCLCHK(c, g_rccl.GroupStart());
-  NCCLCHK(c, g_rccl.Send(d, (size_t)n, NCCL_FLOAT64, 0, comm, cs));
-  NCCLCHK(c, g_rccl.Recv(d + n, (size_t)n, NCCL_FLOAT64, 0, comm, cs));
-  NCCLCHK(c, g_rccl.GroupEnd());
-  HIPCHK(c, hipEventRecord(e1, cs));
-  HIPCHK(c, hipStreamWaitEvent(c->stream, e1, 0));
-  NCCLCHK(c, g_rccl.AllGather(d + n, d + 2 * n, (size_t)n, NCCL_FLOAT64, comm, c->stream));
-  NCCLCHK(c, g_rccl.AllReduce(d + 2 * n, d + 3 * n, (size_t)n, NCCL_FLOAT64, NCCL_SUM, comm, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < n && rc == SZ_OK; k++)
-    if (h[n + k] != 1.0 + k || h[2 * n + k] != 1.0 + k || h[3 * n + k] != 1.0 + k) { c->err = "RCCL self test: wrong data"; rc = SZ_E_HIP; }
-  (void)hipFree(d); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipStreamDestroy(cs);
-  (void)g_rccl.CommDestroy(comm);
-  return rc;
-}
-int sz_comm_destroy(sz_ctx* c) {
-  if (!c) return SZ_E_ARG;
-  if (c->comm) { (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
-  if (c->comm_stream) { (void)hipStreamDestroy(c->comm_stream); c->comm_stream = nullptr; }
-  if (c->ev_packed) { (void)hipEventDestroy(c->ev_packed); c->ev_packed = nullptr; }
-  if (c->ev_recv) { (void)hipEventDestroy(c->ev_recv); c->ev_recv = nullptr; }
-  c->host_transport = false; c->host_tr = sz_host_transport{ nullptr, nullptr, nullptr, nullptr };
-  c->comm_n = 0; c->d_send = c->d_recv = c->d_ref = nullptr; c->d_dcap = nullptr; c->halo_cap = 0; c->tile_since_box = -1;
-  if (c->d_gather) { (void)hipFree(c->d_gather); c->d_gather = nullptr; }
-  free_pool(c->comm_allocs);
-  return SZ_OK;
-}
-// sum of n doubles in device memory over all ranks, in place, on the context's stream (per-cell partial sums of the
-// two-way coupling and of the grid output)
-int sz_comm_allreduce(sz_ctx* c, void* d_buf, int64_t n) {
-  if (!c || !d_buf || n < 0 || c->comm_n < 1) return SZ_E_STATE;
-  (void)hipSetDevice(c->device);
-  if (c->comm_n > 1 && c->host_transport) {
-    std::vector<double> h((size_t)n);
-    HIPCHK(c, hipMemcpyAsync(h.data(), d_buf, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HOSTCHK(c, c->host_tr.allreduce_sum_f64(c->host_tr.user, h.data(), n), "allreduce_sum_f64");
-    HIPCHK(c, hipMemcpyAsync(d_buf, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  } else if (c->comm_n > 1) NCCLCHK(c, g_rccl.AllReduce(d_buf, d_buf, (size_t)n, NCCL_FLOAT64, NCCL_SUM, c->comm, c->stream));
-  return SZ_OK;
-}
-int sz_tile_setup(sz_ctx* c, double Lx, double Ly, int32_t per_x, int32_t per_y, double drift_margin, int32_t rebox_every) {
-  if (!c || !c->have_floes || !c->S.tiled || c->comm_n < 1 || !(drift_margin > 0) || rebox_every == 0) {
-    if (c) c->err = "sz_tile_setup needs sz_upload_floes, sz_tile_enable and sz_comm_init first, a positive drift margin and rebox interval";
-    return SZ_E_STATE;
-  }
-  (void)hipSetDevice(c->device);
-  c->tile_Lx = Lx; c->tile_Ly = Ly; c->tile_per_x = per_x; c->tile_per_y = per_y; c->tile_margin = drift_margin; c->tile_rebox_every = std::abs(rebox_every); c->tile_rebox_fixed = rebox_every < 0;
-  c->tile_since_box = -1; c->halo_cap = 0; c->d_send = nullptr; c->tile_rebox_cur = rebox_every < 0 ? -rebox_every : std::min(rebox_every, 8);
-  c->tile_box_valid = false;
-  if (!c->d_gather) {          // own box | all boxes | count matrix (ints): lives as long as the communicator
-    HIPCHK(c, hipMalloc((void**)&c->d_gather, (8 + 8 * 64 + 64 * 64 / 2 + 64) * sizeof(double)));
-  }
-  return SZ_OK;
-}
-// ---------------------------------------------------------------- migration
-// Floes drift; ownership follows the tile that holds the centroid.  sz_tile_migrate re-assigns every owned floe (collective): the floes
-// that changed tile travel with their COMPLETE state -- every column incl. the previous-step tendencies and the stress / strain tensors,
-// status, ring, sub-floe points -- over the library's own channel (RCCL send / receive between device buffers, or the host's transport),
-// and every rank's context is rebuilt from the floes it keeps and the ones it received, ordered by global index, through the same path an
-// upload takes (capacities, neighbour counts, grid, ghost-candidate estimate are all re-derived).  The re-assignment is host-staged inside
-// the library -- a rare operation (floes move metres per step against tiles of hundreds of km) whose cost is a download and an upload of
-// the tile; the in-reference analogue is the parent / ghost swap of collisions.jl:942-950.  floe.interactions of the last collision call do
-// not travel (the next step's collision call rebuilds them before anything reads them).
-namespace {
-// One trade over the host's transport: per peer what goes out and what comes in (pointer and bytes each; a site names a peer with neither, or
-// leaves it out, as the transport's pairing of the calls on both sides needs).  The five parallel arrays sz_host_transport::sendrecv takes.
-struct HostTrade {
-  std::vector<int32_t> peer; std::vector<const void*> sp; std::vector<void*> rp; std::vector<int64_t> sb, rb;
-  void add(int d, const void* s, size_t s_bytes, void* r, size_t r_bytes) {
-    peer.push_back(d);
-    sp.push_back(s); sb.push_back((int64_t)s_bytes);
-    rp.push_back(r); rb.push_back((int64_t)r_bytes);
-  }
-  int run(sz_ctx* c) {
-    HOSTCHK(c, c->host_tr.sendrecv(c->host_tr.user, (int32_t)peer.size(), peer.data(), sp.data(), sb.data(), rp.data(), rb.data()), "sendrecv");
-    return SZ_OK;
-  }
-};
-// sizes of a variable-size all-to-all: mine[d] doubles go to rank d; all[s * n + d] = what rank s sends to rank d
-int comm_sizes(sz_ctx* c, const std::vector<int>& mine, std::vector<int>& all) {
-  const int n = c->comm_n;
-  all.assign((size_t)n * n, 0);
-  if (n == 1) { all[0] = mine[0]; return SZ_OK; }
-  int* d_row = (int*)(c->d_gather + 8 + 8 * 64);          // (the count-matrix area of the box gather: free between gathers)
-  HIPCHK(c, hipMemcpyAsync(d_row, mine.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  int* d_all = d_row + 64;
-  int rc = comm_allgather(c, d_row, d_all, (size_t)n, NCCL_INT32, sizeof(int));
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(all.data(), d_all, all.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SZ_OK;
-}
-// variable-size all-to-all of doubles between the ranks: sendv[d] to rank d, recvv[s] (sized here) from rank s
-int comm_alltoallv(sz_ctx* c, const std::vector<std::vector<double>>& sendv, std::vector<std::vector<double>>& recvv) {
-  const int n = c->comm_n, me = c->comm_rank;
-  recvv.assign(n, {});
-  if (n == 1) return SZ_OK;
-  // sizes first: every rank's row of the size matrix
-  std::vector<int> mine(n), all;
-  for (int d = 0; d < n; d++) mine[d] = (int)sendv[d].size();
-  int rc = comm_sizes(c, mine, all);
-  if (rc) return rc;
-  for (int s2 = 0; s2 < n; s2++) if (s2 != me) recvv[s2].assign((size_t)all[(size_t)s2 * n + me], 0.0);
-  if (c->host_transport) {
-    HostTrade tr;
-    for (int d = 0; d < n; d++) if (d != me) tr.add(d, sendv[d].data(), sendv[d].size() * sizeof(double), recvv[d].data(), recvv[d].size() * sizeof(double));
-    return tr.run(c);
-  }
-  // RCCL: device staging buffers, one grouped send / receive
-  size_t ts = 0, tr = 0;
-  for (int d = 0; d < n; d++) { if (d == me) continue; ts += sendv[d].size(); tr += recvv[d].size(); }
-  PoolGuard pool; double *ds = nullptr, *dr = nullptr;
-  if ((rc = dalloc(c, &ds, ts, pool.v)) || (rc = dalloc(c, &dr, tr, pool.v))) return rc;
-  size_t os = 0;
-  for (int d = 0; d < n; d++) { if (d == me || sendv[d].empty()) continue; HIPCHK(c, hipMemcpyAsync(ds + os, sendv[d].data(), sendv[d].size() * sizeof(double), hipMemcpyHostToDevice, c->stream)); os += sendv[d].size(); }
-  NCCLCHK(c, g_rccl.GroupStart());
-  os = 0; size_t orr = 0;
-  for (int d = 0; d < n; d++) {
-    if (d == me) continue;
-    if (!sendv[d].empty()) { NCCLCHK(c, g_rccl.Send(ds + os, sendv[d].size(), NCCL_FLOAT64, d, c->comm, c->stream)); os += sendv[d].size(); }
-    if (!recvv[d].empty()) { NCCLCHK(c, g_rccl.Recv(dr + orr, recvv[d].size(), NCCL_FLOAT64, d, c->comm, c->stream)); orr += recvv[d].size(); }
-  }
-  NCCLCHK(c, g_rccl.GroupEnd());
-  orr = 0;
-  for (int d = 0; d < n; d++) { if (d == me || recvv[d].empty()) continue; HIPCHK(c, hipMemcpyAsync(recvv[d].data(), dr + orr, recvv[d].size() * sizeof(double), hipMemcpyDeviceToHost, c->stream)); orr += recvv[d].size(); }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SZ_OK;
-}
-// The tiling of a context, taken before a migration replaces its field (the new field forgets it, as after any upload) and established again
-// behind it with the same parameters: collective.  px > 0: the tiles are the px x py boxes of the domain, and the owned box of the first gather
-// takes its centroids at the image nearest to this rank's box centre (sz_tile_set_center).
-struct Retile {
-  double Lx, Ly, margin, ring_hint, rmax_hint; int per_x, per_y, rebox, precision;
-  explicit Retile(const sz_ctx* c) : Lx(c->tile_Lx), Ly(c->tile_Ly), margin(c->tile_margin), ring_hint((double)c->max_ring_tiled), rmax_hint(c->rmax_hint), per_x(c->tile_per_x),
-                                     per_y(c->tile_per_y), rebox(c->tile_rebox_fixed ? -c->tile_rebox_every : c->tile_rebox_every), precision(c->precision) {}
-  int again(sz_ctx* c, const long long* gidx, int px, int py) const {
-    if (int rc = sz_tile_enable(c, (const int64_t*)gidx, ring_hint, rmax_hint)) return rc;
-    if (int rc = sz_tile_setup(c, Lx, Ly, per_x, per_y, margin, rebox)) return rc;
-    const double x0 = c->h_vals[3], y0 = c->h_vals[1], DLx = c->h_vals[2] - c->h_vals[3], DLy = c->h_vals[0] - c->h_vals[1];
-    const int me = c->comm_rank;
-    if (px > 0) (void)sz_tile_set_center(c, x0 + ((me % px) + 0.5) * DLx / px, y0 + ((me / px) + 0.5) * DLy / py);
-    c->precision = precision;
-    return SZ_OK;
-  }
-};
-// sz_tile_migrate with the movers packed on the device (sz_migrate.hpp): owners, pack, exchange device to device, merge of the directories, the
-// rows gathered into the new order, then what sz_upload_floes does behind its copies (counters, ring signs and boxes, cleared per-floe counts).
-// The capacities the context was carved with stay; *fell_back = 1 (and nothing has changed) when some rank's new tile would crowd them --
-// every rank then takes the host-staged path below, which carves anew.  The host reads the owner and offset columns (ints) and the merged
-// directory; no floe column, ring or sub-floe point crosses to the host (a host transport stages the movers' streams).
-int tile_migrate_device(sz_ctx* c, int px, int py, const int32_t* owner_override, int64_t* n_sent, int64_t* n_owned, int* fell_back) {
-  State& S = c->S;
-  const int n = c->comm_n, me = c->comm_rank, N = c->hostN;
-  *fell_back = 0;
-  int rc;
-  if (c->gi_pending && c->gi_valid) { if ((rc = gi_fetch(c))) return rc; }
-  c->gi_pending = false;
-  struct Scratch { Pool& v; } pool{ c->mig_allocs };      // (the scratch of the last migration is carved again: no allocation in the common case)
-  reset_pool(pool.v);
-  // ---- owners, and how much goes where
-  int *d_owner = nullptr, *d_override = nullptr, *d_bad = nullptr, *d_cntd = nullptr;
-  unsigned long long *d_tally = nullptr, *d_cur = nullptr; long long *d_base = nullptr, *d_rbase = nullptr, *d_rsize = nullptr; double** d_cols = nullptr;
-  if ((rc = dalloc(c, &d_owner, (size_t)N + 1, pool.v)) || (rc = dalloc(c, &d_tally, 128, pool.v)) || (rc = dalloc(c, &d_cur, 128, pool.v)) ||
-      (rc = dalloc(c, &d_base, 64, pool.v)) || (rc = dalloc(c, &d_rbase, 64, pool.v)) || (rc = dalloc(c, &d_rsize, 64, pool.v)) ||
-      (rc = dalloc(c, &d_cntd, 64, pool.v)) || (rc = dalloc(c, &d_bad, 1, pool.v)) || (rc = dalloc(c, &d_cols, 32, pool.v))) return rc;
-  if (owner_override) {
-    if ((rc = dalloc(c, &d_override, (size_t)N + 1, pool.v))) return rc;
-    if (N) HIPCHK(c, hipMemcpyAsync(d_override, owner_override, (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  }
-  const double x0 = c->h_vals[3], y0 = c->h_vals[1], Lx = c->h_vals[2] - c->h_vals[3], Ly = c->h_vals[0] - c->h_vals[1];
-  hipLaunchKernelGGL(sz_k_mig_owner, dim3(grid_for(std::max(N, 1), 256)), dim3(256), 0, c->stream, S, N, (const int*)d_override, x0, y0, Lx, Ly, px, py,
-                     c->tile_per_x, c->tile_per_y, me, n, d_owner, d_tally, d_bad);
-  unsigned long long tally[128]; int bad = 0;
-  std::vector<int> owner((size_t)N + 1), voff((size_t)N + 1), soff((size_t)N + 1);
-  HIPCHK(c, hipMemcpyAsync(tally, d_tally, sizeof(tally), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (N) HIPCHK(c, hipMemcpyAsync(owner.data(), d_owner, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(voff.data(), S.voff, ((size_t)N + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(soff.data(), S.soff, ((size_t)N + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  int any_bad = 0;
-  if ((rc = comm_agree_bits(c, bad ? 1 : 0, &any_bad))) return rc;
-  if (any_bad) { c->err = "sz_tile_migrate: owner out of range"; return SZ_E_ARG; }
-  // ---- the movers' records, one stream per destination
-  std::vector<int> mine(n, 0), all, cntd(64, 0); std::vector<long long> base(64, 0);
-  size_t ts = 0; int nmove = 0; bool too_long = false;
-  for (int d = 0; d < n; d++) {
-    const unsigned long long cnt = tally[2 * d];
-    if (d == me || !cnt) continue;
-    const unsigned long long sz = 1 + (unsigned long long)MIG_DIR * cnt + tally[2 * d + 1];
-    if (sz > 0x7fffffffull) { too_long = true; break; }
-    mine[d] = (int)sz; base[d] = (long long)ts; ts += (size_t)sz; cntd[d] = (int)cnt; nmove += (int)cnt;
-  }
-  if (too_long) { for (int d = 0; d < n; d++) { mine[d] = 0; cntd[d] = 0; } ts = 0; }      // (says so in the agreement below; nothing is sent)
-  double* d_sendb = nullptr;
-  if ((rc = dalloc(c, &d_sendb, ts, pool.v))) return rc;
-  double* const hcols[MIG_NSC + 3] = { S.cx, S.cy, S.rmax, S.area, S.height, S.mass, S.moment, S.alpha, S.u, S.v, S.xi, S.p_dxdt, S.p_dydt, S.p_dalphadt,
-                                       S.p_dudt, S.p_dvdt, S.p_dxidt, S.fxOA, S.fyOA, S.trqOA, S.hflx, S.overarea, S.cfx, S.cfy, S.ctrq, S.sa, S.si, S.strain };
-  HIPCHK(c, hipMemcpyAsync(d_cols, hcols, sizeof(hcols), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_base, base.data(), 64 * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_cntd, cntd.data(), 64 * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (ts) hipLaunchKernelGGL(sz_k_mig_pack, dim3(grid_for((long long)N * 64, 256, 2048)), dim3(256), 0, c->stream, S, N, (const int*)d_owner, me, d_sendb,
-                             (const long long*)d_base, (const int*)d_cntd, d_cur, (double* const*)d_cols);
-  // ---- sizes, then the streams: device to device (a host transport: staged, the movers only)
-  if ((rc = comm_sizes(c, mine, all))) return rc;
-  std::vector<long long> rbase(64, 0), rsize(64, 0);
-  size_t tr = 0;
-  for (int s2 = 0; s2 < n; s2++) { if (s2 == me) continue; rbase[s2] = (long long)tr; rsize[s2] = all[(size_t)s2 * n + me]; tr += (size_t)rsize[s2]; }
-  double* d_recvb = nullptr;
-  if ((rc = dalloc(c, &d_recvb, tr, pool.v))) return rc;
-  if (n > 1 && c->host_transport) {
-    std::vector<double> hs(std::max<size_t>(ts, 1)), hr(std::max<size_t>(tr, 1));
-    if (ts) HIPCHK(c, hipMemcpyAsync(hs.data(), d_sendb, ts * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HostTrade trade;
-    for (int d = 0; d < n; d++) if (d != me) trade.add(d, hs.data() + base[d], (size_t)mine[d] * sizeof(double), hr.data() + rbase[d], (size_t)rsize[d] * sizeof(double));
-    if ((rc = trade.run(c))) return rc;
-    if (tr) HIPCHK(c, hipMemcpyAsync(d_recvb, hr.data(), tr * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  } else if (n > 1) {
-    NCCLCHK(c, g_rccl.GroupStart());
-    for (int d = 0; d < n; d++) {
-      if (d == me) continue;
-      if (mine[d]) NCCLCHK(c, g_rccl.Send(d_sendb + base[d], (size_t)mine[d], NCCL_FLOAT64, d, c->comm, c->stream));
-      if (rsize[d]) NCCLCHK(c, g_rccl.Recv(d_recvb + rbase[d], (size_t)rsize[d], NCCL_FLOAT64, d, c->comm, c->stream));
-    }
-    NCCLCHK(c, g_rccl.GroupEnd());
-  }
-  // ---- what arrived: the merged directory is all the host reads of it
-  const int dcap = (int)(tr / (size_t)(MIG_DIR + MIG_NCOL)) + 1;
-  double* d_dirs = nullptr;
-  if ((rc = dalloc(c, &d_dirs, (size_t)MIG_DIR * (1 + (size_t)dcap), pool.v))) return rc;
-  HIPCHK(c, hipMemcpyAsync(d_rbase, rbase.data(), 64 * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_rsize, rsize.data(), 64 * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(sz_k_mig_dirs, dim3(1), dim3(256), 0, c->stream, (const double*)d_recvb, (const long long*)d_rbase, (const long long*)d_rsize, n, d_dirs, dcap);
-  std::vector<double> dirs((size_t)MIG_DIR * (1 + (size_t)dcap));
-  HIPCHK(c, hipMemcpyAsync(dirs.data(), d_dirs, dirs.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const int R = (int)dirs[0];
-  // ---- the new tile: kept floes + received ones, ordered by global index
-  struct Src { long long g; int s; };
-  std::vector<Src> src;
-  for (int i = 0; i < N; i++) if (owner[i] == me) src.push_back({ c->tile_gidx[i], i });
-  for (int e = 0; e < R; e++) src.push_back({ (long long)dirs[(size_t)MIG_DIR * (1 + e)], -(e + 1) });
-  std::sort(src.begin(), src.end(), [](const Src& a, const Src& b2) { return a.g < b2.g; });
-  const int Nn = (int)src.size();
-  std::vector<int> hsrc((size_t)Nn + 1), nvoff((size_t)Nn + 1, 0), nsoff((size_t)Nn + 1, 0); std::vector<long long> ngid((size_t)Nn + 1);
-  int ring_in = 0, sub_in = 0; double rmax_in = 0.0;
-  for (int r = 0; r < Nn; r++) {
-    const int s2 = src[r].s;
-    int nv, ns;
-    if (s2 >= 0) { nv = voff[s2 + 1] - voff[s2]; ns = soff[s2 + 1] - soff[s2]; }
-    else {
-      const double* e = dirs.data() + (size_t)MIG_DIR * (size_t)(-s2);
-      nv = (int)e[1]; ns = (int)e[2]; ring_in = std::max(ring_in, nv); sub_in = std::max(sub_in, ns); rmax_in = std::max(rmax_in, e[4]);
-    }
-    hsrc[r] = s2; ngid[r] = src[r].g; nvoff[r + 1] = nvoff[r] + nv; nsoff[r + 1] = nsoff[r] + ns;
-  }
-  const int Vn = nvoff[Nn], NSn = nsoff[Nn];
-  // does it fit what the context was carved for (sz_upload_floes: at least 2 M + 64 rows and 2 V + 4096 ring points, for the owned floes, their
-  // ghosts and the halo)?  An eighth more than the upload held is let in.
-  const bool fits = Nn <= c->upload_M + c->upload_M / 8 && Vn <= c->upload_V + c->upload_V / 8 && !too_long;
-  int bits = (nmove > 0 ? 1 : 0) | (fits ? 0 : 2) | (Nn == 0 ? 4 : 0) | (R < 0 ? 8 : 0), allb = 0;
-  if ((rc = comm_agree_bits(c, bits, &allb))) return rc;
-  if (allb & 8) { c->err = "sz_tile_migrate: a stream of movers arrived inconsistent"; return SZ_E_STATE; }
-  if (n_sent) *n_sent = nmove;
-  if (!(allb & 1)) { c->err.clear(); if (n_owned) *n_owned = N; return SZ_OK; }
-  if (allb & 4) { c->err = "sz_tile_migrate: a tile without floes (every rank must own at least one)"; return SZ_E_STATE; }
-  if (allb & 2) { c->err.clear(); *fell_back = 1; return SZ_OK; }
-  c->err.clear();
-  // ---- the rows into their new order: gathered beside the old ones first (a row's source may lie on either side of it)
-  int *d_src = nullptr, *d_nvoff = nullptr, *d_nsoff = nullptr; double *d_tmp = nullptr, *d_tsx = nullptr, *d_tsy = nullptr; double2* d_tv = nullptr;
-  if ((rc = dalloc(c, &d_src, (size_t)Nn + 1, pool.v)) || (rc = dalloc(c, &d_nvoff, (size_t)Nn + 1, pool.v)) || (rc = dalloc(c, &d_nsoff, (size_t)Nn + 1, pool.v)) ||
-      (rc = dalloc(c, &d_tmp, (size_t)39 * Nn, pool.v)) || (rc = dalloc(c, &d_tv, (size_t)Vn, pool.v)) ||
-      (rc = dalloc(c, &d_tsx, (size_t)NSn, pool.v)) || (rc = dalloc(c, &d_tsy, (size_t)NSn, pool.v))) return rc;
-  HIPCHK(c, hipMemcpyAsync(d_src, hsrc.data(), (size_t)Nn * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_nvoff, nvoff.data(), ((size_t)Nn + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_nsoff, nsoff.data(), ((size_t)Nn + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(sz_k_mig_gather, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (const int*)d_src, (const double*)d_dirs, (const double*)d_recvb,
-                     (double* const*)d_cols, d_tmp);
-  hipLaunchKernelGGL(sz_k_mig_points, dim3(grid_for((long long)Nn * 64, 256, 4096)), dim3(256), 0, c->stream, S, Nn, (const int*)d_src, (const double*)d_dirs,
-                     (const double*)d_recvb, (const int*)d_nvoff, (const int*)d_nsoff, d_tv, d_tsx, d_tsy);
-  hipLaunchKernelGGL(sz_k_mig_scatter, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (double* const*)d_cols, (const double*)d_tmp);
-  if (Vn) HIPCHK(c, hipMemcpyAsync(S.vxy, d_tv, (size_t)Vn * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(S.voff, d_nvoff, ((size_t)Nn + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-  Pool old_sub;
-  if (NSn > S.capS) {          // the sub-floe points have no slack at upload (they are the largest array of a field): a tile that gained points gets a new pair
-    old_sub = c->sub_allocs; c->sub_allocs = Pool();
-    S.capS = NSn + NSn / 4;
-    if ((rc = dalloc(c, &S.sx, (size_t)S.capS, c->sub_allocs)) || (rc = dalloc(c, &S.sy, (size_t)S.capS, c->sub_allocs))) return rc;
-  }
-  if (NSn) {
-    HIPCHK(c, hipMemcpyAsync(S.sx, d_tsx, (size_t)NSn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(S.sy, d_tsy, (size_t)NSn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
-  HIPCHK(c, hipMemcpyAsync(S.soff, d_nsoff, ((size_t)Nn + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-  // ---- the field is placed: as behind the copies of sz_upload_floes (no ghosts; every floe's sub-floe offsets are set; the estimates and bounds the
-  // context held still bound the floes it kept, those of the floes that arrived come on top).  No interaction rows until the next collision call
-  // -- an upload keeps those of a field of the same size.
-  HIPCHK(c, hipMemsetAsync(S.inter_cnt, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
-  const Retile tiling(c);
-  if ((rc = field_placed(c, Nn, 0, Vn, Nn, std::min(Nn, c->gl_est + R), std::max(c->rmax_max, rmax_in), c->rmax_hint))) return rc;
-  free_pool(old_sub);
-  c->max_ring = std::max(c->max_ring, ring_in); c->max_sub = std::max(c->max_sub, sub_in);
-  c->inter_lost = false; c->inter_any = true;
-  if ((rc = tiling.again(c, ngid.data(), owner_override ? 0 : px, py))) return rc;
-  trim_pool(pool.v);
-  if (n_owned) *n_owned = Nn;
-  return SZ_OK;
-}
-int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_override, int64_t* n_sent, int64_t* n_owned);
-}  // namespace
-
-int sz_tile_migrate(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_override, int64_t* n_sent, int64_t* n_owned) {
-  if (n_sent) *n_sent = 0;
-  if (!c || !c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0 || px < 1 || py < 1 || (!owner_override && px * py != c->comm_n)) {
-    if (c) c->err = "sz_tile_migrate needs a tiled context after sz_tile_setup, and px * py == the number of ranks";
-    return SZ_E_STATE;
-  }
-  (void)hipSetDevice(c->device);
-  int rc = tile_sync_agree(c); if (rc) return rc;             // (ghosts and halo floes of the last step are dropped: the state is the owned floes)
-  world_rings(c);
-  c->migrate_path = 0;
-  const char* e = getenv("SZ_MIGRATE_HOST");                  // (A/B switch, the same on every rank: the host-staged path only)
-  if (!(e && atoi(e) != 0)) {
-    int fell_back = 0;
-    rc = tile_migrate_device(c, px, py, owner_override, n_sent, n_owned, &fell_back);
-    if (rc) return rc;
-    if (!fell_back) { c->migrate_path = 1; return SZ_OK; }
-  }
-  rc = tile_migrate_host(c, px, py, owner_override, n_sent, n_owned);
-  if (rc == SZ_OK) c->migrate_path = 2;
-  return rc;
-}
-// how the last sz_tile_migrate ran: 1 = movers packed on the device, 2 = staged through the host (0: it did not get that far)
-int sz_debug_migrate_path(sz_ctx* c) { return c ? c->migrate_path : 0; }
-// global indices of the owned floes (sz_tile_enable; after sz_tile_migrate: of the new tile), n_cap >= the number of owned floes
-int sz_tile_owned_gidx(sz_ctx* c, int64_t* out, int64_t n_cap) {
-  if (!c || !c->have_floes || !c->S.tiled || !out || n_cap < (int64_t)c->tile_gidx.size()) return SZ_E_ARG;
-  for (size_t i = 0; i < c->tile_gidx.size(); i++) out[i] = c->tile_gidx[i];
-  return SZ_OK;
-}
-
-// ---------------------------------------------------------------- removal and dissolution on a tiled context (sz_remove_tile.hpp)
-namespace {
-// remove_floes! over the ONE global floe list whose rows live on the ranks' tiles: collective.  Every rank ends with what the single context's
-// pass (remove_pass) leaves for that list, restricted to the floes it owns, numbered as the single context numbers them; *done = 0: declined on
-// EVERY rank, nothing has changed on any.  The counts are global.  The collectives, the same on every rank whatever it holds:
-//   1. the agreement on this rank's state (device error bits, ghosts in the list)
-//   2. the all-gather of the counts (RmDev of every rank): the verdict they allow -- a fuse tag, a ring over max_vertices, a rank or the world
-//      left without a floe -- is the same on every rank, and so is "nothing leaves"; both end the pass here, on all ranks
-//   3. the all-gather of the leaving records, as many slots per rank as the longest list needs
-//   4. the agreement on the verdict of the walk (the index quirk) and on this rank's counts, BEFORE the lattice or a row changes
-// In front of 2 and of 3 the ranks gather the code of what each prepared alone (scratch memory: N differs per rank), so a rank that fails there
-// takes the others with it instead of leaving them in the gather.  A failure of the HIP runtime or of the channel itself (SZ_E_HIP out of a
-// copy, a launch or a collective) is returned at once, as everywhere in the library: there is nothing left to agree over.
-// An empty tile is not a state the tile drivers are tested in: a pass that would leave one is declined.
-int tile_remove_pass(sz_ctx* c, int* done, int* n_removed, int* n_dissolved) {
-  *done = 0; *n_removed = 0; *n_dissolved = 0;
-  State& S = c->S;
-  const int n = c->comm_n, me = c->comm_rank;
-  int rc, all = 0;
-  // what this rank did on its own since the last collective came back with `local`: the first code a rank reports, in rank order, on EVERY rank
-  // (0: none) -- a rank that returned alone would leave its peers waiting in the next gather
-  auto agree_rc = [&](int local, int* first) {
-    int h[64];
-    if (const int r2 = comm_gather_int(c, local, h)) return r2;
-    *first = 0;
-    for (int r = 0; r < n && !*first; r++) if (h[r]) { *first = h[r]; if (!local) c->err = "sz_tile_remove_floes: rank " + std::to_string(r) + " could not prepare the pass (all ranks return together)"; }
-    return (int)SZ_OK;
-  };
-  // ---- 1
-  rc = sync_and_check(c);
-  if (rc == SZ_E_HIP) return rc;
-  constexpr int BIT_GHOSTS = 1 << 30, BIT_NONE = 1 << 29;
-  const int state = rc ? (c->last_err_bits ? c->last_err_bits & ~(BIT_GHOSTS | BIT_NONE) : 1) : c->hostM != c->hostN ? BIT_GHOSTS : c->hostN <= 0 ? BIT_NONE : 0;
-  if ((rc = comm_agree_bits(c, state, &all))) return rc;
-  if (all & ~(BIT_GHOSTS | BIT_NONE)) return SZ_E_CAPACITY;
-  if (all & BIT_GHOSTS) { c->err = "sz_tile_remove_floes: ghosts are in the list on some rank: the pass runs over the parents alone"; return SZ_E_STATE; }
-  c->err.clear();
-  if (all) return SZ_OK;          // (a rank without floes: declined)
-  const int N = c->hostN;
-  leave_resident(c);
-  // ---- 2
-  RmArgs A;
-  Pool& P = c->rm_allocs;
-  constexpr int RW = (int)(sizeof(RmDev) / sizeof(int));
-  int *d_counts = nullptr, *d_cnt = nullptr, *d_decl = nullptr, first = 0;
-  (void)((rc = rm_flag_rows(c, N, A)) || (rc = dalloc(c, &d_counts, (size_t)RW * 64, P)) || (rc = dalloc(c, &d_cnt, 64, P)) || (rc = dalloc(c, &d_decl, 1, P)));
-  if (const int r2 = agree_rc(rc, &first)) return r2;
-  if (first) return first;
-  if ((rc = comm_allgather(c, A.d, d_counts, RW, NCCL_INT32, sizeof(int)))) return rc;
-  std::vector<RmDev> Rs(n);
-  HIPCHK(c, hipMemcpyAsync(Rs.data(), d_counts, (size_t)n * sizeof(RmDev), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const RmDev R = Rs[me];
-  int decl = 0, slots = 0, total = 0, nr = 0, nd = 0, left = 0;
-  std::vector<int> cnt(64, 0);
-  for (int r = 0; r < n; r++) {
-    decl |= (Rs[r].n_fuse ? RM_DECL_FUSE : 0) | (Rs[r].n_over ? RM_DECL_VERTS : 0) | (Rs[r].Nn <= 0 ? RM_DECL_EMPTY : 0);
-    cnt[r] = Rs[r].n_removed + Rs[r].n_dissolved;
-    slots = std::max(slots, cnt[r]); total += cnt[r]; nr += Rs[r].n_removed; nd += Rs[r].n_dissolved; left += Rs[r].Nn;
-  }
-  if (decl || left <= 0) return SZ_OK;
-  if (total == 0) { *done = 1; return SZ_OK; }          // nothing leaves anywhere, and every status is `active` already
-  // ---- 3
-  const int Nn = std::max(R.Nn, 0);
-  double *d_rec = nullptr, *d_all = nullptr, *d_merged = nullptr; long long* d_newkey = nullptr;
-  (void)((rc = dalloc(c, &d_rec, (size_t)RMT_REC * slots, P)) || (rc = dalloc(c, &d_all, (size_t)RMT_REC * slots * n, P)) ||
-         (rc = dalloc(c, &d_merged, (size_t)RMT_REC * total, P)) || (rc = dalloc(c, &d_newkey, (size_t)Nn + 1, P)));
-  if (const int r2 = agree_rc(rc, &first)) return r2;
-  if (first) return first;
-  HIPCHK(c, hipMemsetAsync(d_rec, 0, (size_t)RMT_REC * slots * sizeof(double), c->stream));
-  HIPCHK(c, hipMemsetAsync(d_merged, 0, (size_t)RMT_REC * total * sizeof(double), c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_cnt, cnt.data(), 64 * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  const bool counts_ok = Nn > 0 && Nn <= N && Nn + cnt[me] == N && R.Vn >= 0 && R.NSn >= 0;      // (the records go where the scans say: not with bad counts)
-  if (counts_ok) hipLaunchKernelGGL(sz_k_rmt_pack, dim3(grid_for(N, 256, 2048)), dim3(256), 0, c->stream, S, A, d_rec);
-  if ((rc = comm_allgather(c, d_rec, d_all, (size_t)RMT_REC * slots, NCCL_FLOAT64, sizeof(double)))) return rc;
-  hipLaunchKernelGGL(sz_k_rmt_merge, dim3(grid_for((long long)n * slots, 256)), dim3(256), 0, c->stream, (const double*)d_all, (const int*)d_cnt, n, slots, d_merged, total);
-  if (counts_ok) hipLaunchKernelGGL(sz_k_rmt_renumber, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, (const double*)d_merged, total, d_newkey);
-  hipLaunchKernelGGL(sz_k_rmt_walk, dim3(1), dim3(64), 0, c->stream, A, (const double*)d_merged, total, nd, (int)RM_WALK_CHECK, d_decl);
-  // ---- 4 (nothing has changed so far, on any rank: the walk has only looked)
-  int walk = 0;
-  std::vector<long long> newkey((size_t)Nn + 1, 0);
-  HIPCHK(c, hipMemcpyAsync(&walk, d_decl, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (counts_ok) HIPCHK(c, hipMemcpyAsync(newkey.data(), d_newkey, (size_t)Nn * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-  rc = sync_and_check(c);
-  if (rc == SZ_E_HIP) return rc;
-  constexpr int BIT_ERR = 1, BIT_COUNTS = 2, BIT_INDEX = 4, BIT_LATTICE = 8, BIT_WENT = 16;
-  const int mine = (rc ? BIT_ERR : 0) | (counts_ok ? 0 : BIT_COUNTS) | (walk & RM_DECL_INDEX ? BIT_INDEX : 0) | (walk & RM_NO_LATTICE ? BIT_LATTICE : 0) | (walk ? 0 : BIT_WENT);
-  if ((rc = comm_agree_bits(c, mine, &all))) return rc;
-  if (all & BIT_ERR) return SZ_E_CAPACITY;
-  if (all & BIT_COUNTS) { c->err = "sz_tile_remove_floes: bad counts on some rank"; return SZ_E_HIP; }
-  if (all & BIT_LATTICE) { c->err = "sz_tile_remove_floes: a floe dissolves, and the ocean.dissolved lattice needs the grid (sz_set_fields)"; return SZ_E_STATE; }
-  if ((all & BIT_INDEX) && (all & BIT_WENT)) { c->err = "sz_tile_remove_floes: the ranks walked the same list to different ends: their grids (sz_set_fields) differ"; return SZ_E_STATE; }
-  c->err.clear();
-  if (all & BIT_INDEX) return SZ_OK;
-  *done = 1; *n_removed = nr; *n_dissolved = nd;
-  // ---- the pass goes ahead on every rank: the sums of the walk, then the rows move as in the single context -- on every rank, one that loses no
-  // floe included: its numbers change with the floes that left before them, and the next batch gathers the boxes anew on all ranks or on none.
-  // The tiling is taken before the new field forgets it and established again behind it, with the new numbers (S.okey, tile_gidx) and the
-  // centre the owned box was last gathered around.  Boxes, halo capacities and peers: the next exchange
-  if (nd > 0) hipLaunchKernelGGL(sz_k_rmt_walk, dim3(1), dim3(64), 0, c->stream, A, (const double*)d_merged, total, nd, (int)RM_WALK_SUM, d_decl);
-  const Retile tiling(c);
-  const bool ctr_valid = c->tile_box_valid; const double ctr[2] = { c->tile_box_ctr[0], c->tile_box_ctr[1] };
-  if ((rc = rm_move_rows(c, N, A, R))) return rc;
-  if ((rc = tiling.again(c, newkey.data(), 0, 0))) return rc;
-  if (ctr_valid) (void)sz_tile_set_center(c, ctr[0], ctr[1]);
-  return SZ_OK;
-}
-}  // namespace
-
-int sz_tile_remove_floes(sz_ctx* c, int32_t* done, int32_t* n_removed, int32_t* n_dissolved) {
-  if (done) *done = 0;
-  if (n_removed) *n_removed = 0;
-  if (n_dissolved) *n_dissolved = 0;
-  if (!c || !done) return SZ_E_ARG;
-  if (!c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0) { c->err = "sz_tile_remove_floes needs sz_tile_enable and sz_tile_setup after the last sz_upload_floes"; return SZ_E_STATE; }
-  (void)hipSetDevice(c->device);
-  int d = 0, nr = 0, nd = 0;
-  if (int rc = tile_remove_pass(c, &d, &nr, &nd)) return rc;
-  *done = d;
-  if (n_removed) *n_removed = nr;
-  if (n_dissolved) *n_dissolved = nd;
-  return SZ_OK;
-}
-
-// ---------------------------------------------------------------- fracture criteria on a tiled context (sz_fracture_tile.hpp)
-namespace {
-// determine_fractures over the ONE global floe list whose rows live on the ranks' tiles: collective, over the parents with ghosts detached (as
-// behind a segment of sz_tile_run).  Every rank ends with the mean height, p and polygon of the single context, to the bit -- the heights of all
-// ranks gathered by global number, then sz_k_frac_criterion over that array, unchanged -- and with the flags of the rows it owns (sz_k_frac_test
-// over hostN rows; halo rows are never tested).  The collectives, the same on every rank whatever it holds:
-//   1. the gather of the owned counts; a rank that cannot take part (device error bits, ghosts in the list) sends its error code in place of its
-//      count, and all ranks return it together
-//   2. the all-gather of the {global number, height} records, as many slots per rank as the longest list needs
-//   3. the agreement (comm_agree_bits) on: a global number out of range or met twice, a device error, "I have a candidate", and my_tag -- "my stop
-//      word stood at the segment's last step".  Behind the list-based driver that is news to the peers: they would hear of such a tag in the unpack
-//      of a step that does not come.  The inline driver has agreed its stop step already (comm_agree_steps), and every rank sends the same bit
-// Nothing of the floes changes in a pass; what 3 refuses has only written the pass's scratch and the criterion block.  A failure of the HIP runtime
-// or of the channel itself is returned at once, as everywhere in the library.  compact: the owned candidates as ascending rows in frac_idx and
-// their exact number in *n_owned (otherwise *n_owned is only zero or not).
-constexpr int FRT_BIT_RANGE = 1, FRT_BIT_TWICE = 2, FRT_BIT_ERR = 4, FRT_BIT_CAND = 8, FRT_BIT_TAG = 16;
-int tile_frac_pass(sz_ctx* c, bool my_tag, bool compact, int* any_cand, int* any_tag, int* n_owned) {
-  *any_cand = 0; *any_tag = 0; *n_owned = 0;
-  State& S = c->S;
-  const int n = c->comm_n;
-  // ---- 1
-  int rc = sync_and_check(c);
-  if (rc == SZ_E_HIP) return rc;
-  if ((rc = rc ? rc : c->hostM != c->hostN ? (int)SZ_E_STATE : frac_ensure(c)) == SZ_E_HIP) return rc;
-  const int N = c->hostN;
-  c->frac_cnt.assign(64, 0);
-  int* const cnt = c->frac_cnt.data();
-  if (const int r2 = comm_gather_int(c, rc ? rc : N, cnt)) return r2;
-  for (int r = 0; r < n; r++) if (cnt[r] < 0) {
-    if (cnt[r] == SZ_E_STATE) c->err = "tiled fracture criteria: ghosts are in the list on rank " + std::to_string(r) + ": the pass runs over the parents alone";
-    else if (!rc) c->err = "tiled fracture criteria: rank " + std::to_string(r) + " reported a device error (this rank is clean; all ranks return together)";
-    return cnt[r];
-  }
-  long long total64 = 0; int slots = 1;
-  for (int r = 0; r < n; r++) { total64 += cnt[r]; slots = std::max(slots, cnt[r]); }
-  if (total64 > 0x7fffffff) { c->err = "tiled fracture criteria: more than 2^31 floes"; return SZ_E_CAPACITY; }          // (the same sum on every rank)
-  const int total = (int)total64;
-  // ---- 2
-  Pool& P = c->frac_allocs;
-  reset_pool(P);
-  double *d_rec = nullptr, *d_all = nullptr, *d_h = nullptr; int *d_mark = nullptr, *d_cnt = nullptr, *d_bad = nullptr;
-  if ((rc = dalloc(c, &d_rec, (size_t)FRT_REC * slots, P)) || (rc = dalloc(c, &d_all, (size_t)FRT_REC * slots * n, P)) || (rc = dalloc(c, &d_h, (size_t)total, P)) ||
-      (rc = dalloc(c, &d_mark, (size_t)total, P)) || (rc = dalloc(c, &d_cnt, 64, P)) || (rc = dalloc(c, &d_bad, 1, P))) return rc;
-  HIPCHK(c, hipMemsetAsync(d_mark, 0, (size_t)std::max(total, 1) * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_cnt, cnt, 64 * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (N > 0) hipLaunchKernelGGL(sz_k_fract_pack, dim3(grid_for(N, 256, 2048)), dim3(256), 0, c->stream, S, N, d_rec);
-  if ((rc = comm_allgather(c, d_rec, d_all, (size_t)FRT_REC * slots, NCCL_FLOAT64, sizeof(double)))) return rc;
-  hipLaunchKernelGGL(sz_k_fract_scatter, dim3(grid_for((long long)n * slots, 256)), dim3(256), 0, c->stream, (const double*)d_all, (const int*)d_cnt, n, slots, d_h, d_mark, total, d_bad);
-  // ---- the single context's kernels: the criterion over the gathered heights, the test over the owned rows
-  State T = S; T.step = 0;
-  FracArgs F = frac_args(c);
-  State G = T; G.height = d_h;
-  FracArgs Fg = F; Fg.n = total;
-  hipLaunchKernelGGL(sz_k_frac_criterion, dim3(1), dim3(FRAC_TPB), 0, c->stream, G, Fg);
-  hipLaunchKernelGGL(sz_k_frac_test, dim3(grid_for(std::max(N, 1), 256, 2048)), dim3(256), 0, c->stream, T, F);
-  if (compact) hipLaunchKernelGGL(sz_k_frac_compact, dim3(1), dim3(FRAC_TPB), 0, c->stream, F);
-  int found = 0, bad = 0;
-  HIPCHK(c, hipMemcpyAsync(&found, &c->frac_d->count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  rc = sync_and_check(c);
-  if (rc == SZ_E_HIP) return rc;
-  // ---- 3
-  if (found < 0 || found > N) rc = SZ_E_CAPACITY;
-  const int mine = (bad & FRT_BAD_RANGE ? FRT_BIT_RANGE : 0) | (bad & FRT_BAD_TWICE ? FRT_BIT_TWICE : 0) | (rc ? FRT_BIT_ERR : 0) | (found > 0 ? FRT_BIT_CAND : 0) | (my_tag ? FRT_BIT_TAG : 0);
-  int all = 0;
-  if ((rc = comm_agree_bits(c, mine, &all))) return rc;
-  if (all & (FRT_BIT_RANGE | FRT_BIT_TWICE)) {
-    c->err = std::string("tiled fracture criteria: the global numbers of the ranks (sz_tile_enable) are not 0 .. N_global - 1 once each: ") +
-             (all & FRT_BIT_RANGE ? "one is out of range" : "one is held twice") + " (all ranks return together)";
-    return SZ_E_STATE;
-  }
-  if (all & FRT_BIT_ERR) { if (!(mine & FRT_BIT_ERR)) c->err = "tiled fracture criteria: a rank reported a device error (this rank is clean; all ranks return together)"; return SZ_E_CAPACITY; }
-  c->err.clear();
-  *any_cand = (all & FRT_BIT_CAND) != 0; *any_tag = (all & FRT_BIT_TAG) != 0; *n_owned = found;
-  return SZ_OK;
-}
-}  // namespace
-
-int sz_tile_fracture_candidates(sz_ctx* c, int32_t* n_global, int32_t* n_owned, int32_t* rows, int64_t* gidx) {
-  if (n_global) *n_global = 0;
-  if (n_owned) *n_owned = 0;
-  if (!c || !n_global || !n_owned) return SZ_E_ARG;
-  if (!c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0) { c->err = "sz_tile_fracture_candidates needs sz_tile_enable and sz_tile_setup after the last sz_upload_floes"; return SZ_E_STATE; }
-  if (c->frac_kind == SZ_FRAC_OFF) { c->err = "sz_tile_fracture_candidates: no fracture criterion set (sz_set_fracture)"; return SZ_E_STATE; }
-  (void)hipSetDevice(c->device);
-  int any = 0, tag = 0, mine = 0, per_rank[64] = { 0 };
-  if (int rc = tile_frac_pass(c, false, true, &any, &tag, &mine)) return rc;
-  if (int rc = comm_gather_int(c, mine, per_rank)) return rc;
-  long long total = 0;
-  for (int r = 0; r < c->comm_n; r++) total += per_rank[r];
-  if (mine > 0 && (rows || gidx)) {
-    std::vector<int> h((size_t)mine);
-    HIPCHK(c, hipMemcpyAsync(h.data(), c->frac_idx, (size_t)mine * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < mine; k++) {
-      if (h[k] < 0 || h[k] >= (int)c->tile_gidx.size()) { c->err = "sz_tile_fracture_candidates: bad candidate row"; return SZ_E_HIP; }
-      if (rows) rows[k] = h[k];
-      if (gidx) gidx[k] = c->tile_gidx[h[k]];
-    }
-  }
-  *n_global = (int32_t)total; *n_owned = mine;
-  return SZ_OK;
-}
-
-namespace {
-int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_override, int64_t* n_sent, int64_t* n_owned) {
-  State& S = c->S;
-  const int n = c->comm_n, me = c->comm_rank;
-  int rc;
-  const int N = c->hostN;
-  // ---- the tile's state on the host
-  double* const dcol[25] = { S.cx, S.cy, S.rmax, S.area, S.height, S.mass, S.moment, S.alpha, S.u, S.v, S.xi, S.p_dxdt, S.p_dydt, S.p_dalphadt, S.p_dudt, S.p_dvdt, S.p_dxidt,
-                             S.fxOA, S.fyOA, S.trqOA, S.hflx, S.overarea, S.cfx, S.cfy, S.ctrq };
-  std::vector<std::vector<double>> col(25, std::vector<double>((size_t)N));
-  std::vector<double> ten[3] = { std::vector<double>((size_t)4 * N), std::vector<double>((size_t)4 * N), std::vector<double>((size_t)4 * N) };
-  std::vector<long long> id((size_t)N); std::vector<int> status((size_t)N), voff((size_t)N + 1), soff((size_t)N + 1);
-  for (int k = 0; k < 25; k++) if (N) HIPCHK(c, hipMemcpy(col[k].data(), dcol[k], (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-  double* const dten[3] = { S.sa, S.si, S.strain };
-  for (int k = 0; k < 3; k++) if (N) HIPCHK(c, hipMemcpy(ten[k].data(), dten[k], (size_t)4 * N * sizeof(double), hipMemcpyDeviceToHost));
-  if (N) { HIPCHK(c, hipMemcpy(id.data(), S.id, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost)); HIPCHK(c, hipMemcpy(status.data(), S.status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost)); }
-  HIPCHK(c, hipMemcpy(voff.data(), S.voff, ((size_t)N + 1) * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(soff.data(), S.soff, ((size_t)N + 1) * sizeof(int), hipMemcpyDeviceToHost));
-  const int V = voff[N], NS = soff[N];
-  std::vector<double> vx((size_t)std::max(V, 1)), vy((size_t)std::max(V, 1)), sx((size_t)std::max(NS, 1)), sy((size_t)std::max(NS, 1));
-  if (V) {
-    std::vector<double> xy((size_t)2 * V);
-    HIPCHK(c, hipMemcpy(xy.data(), S.vxy, (size_t)2 * V * sizeof(double), hipMemcpyDeviceToHost));
-    for (int k = 0; k < V; k++) { vx[k] = xy[(size_t)2 * k]; vy[k] = xy[(size_t)2 * k + 1]; }
-  }
-  if (NS) { HIPCHK(c, hipMemcpy(sx.data(), S.sx, (size_t)NS * sizeof(double), hipMemcpyDeviceToHost)); HIPCHK(c, hipMemcpy(sy.data(), S.sy, (size_t)NS * sizeof(double), hipMemcpyDeviceToHost)); }
-  // ---- who owns what now: the tile that holds the centroid (periodic: of its image inside the domain), px x py tiles over the domain
-  const double x0 = c->h_vals[3], y0 = c->h_vals[1], Lx = c->h_vals[2] - c->h_vals[3], Ly = c->h_vals[0] - c->h_vals[1];
-  std::vector<int> owner((size_t)N);
-  for (int i = 0; i < N; i++) {
-    if (owner_override) { owner[i] = owner_override[i]; if (owner[i] < 0 || owner[i] >= n) { c->err = "sz_tile_migrate: owner out of range"; return SZ_E_ARG; } continue; }
-    double x = col[0][i] - x0, y = col[1][i] - y0;
-    if (c->tile_per_x) { x = std::fmod(x, Lx); if (x < 0) x += Lx; }
-    if (c->tile_per_y) { y = std::fmod(y, Ly); if (y < 0) y += Ly; }
-    const int ix = std::max(0, std::min(px - 1, (int)(x / Lx * px))), iy = std::max(0, std::min(py - 1, (int)(y / Ly * py)));
-    owner[i] = iy * px + ix;
-  }
-  // ---- movers, one stream of doubles per destination: MIG_NCOL scalars, then ring x / y, then sub-floe points x / y of every floe
-  std::vector<std::vector<double>> sendv(n), recvv;
-  int nmove = 0;
-  for (int i = 0; i < N; i++) {
-    if (owner[i] == me) continue;
-    nmove++;
-    std::vector<double>& b = sendv[owner[i]];
-    for (int k = 0; k < 25; k++) b.push_back(col[k][i]);
-    for (int k = 0; k < 3; k++) for (int q = 0; q < 4; q++) b.push_back(ten[k][(size_t)4 * i + q]);
-    const int nv = voff[i + 1] - voff[i], ns = soff[i + 1] - soff[i];
-    b.push_back((double)id[i]); b.push_back((double)status[i]); b.push_back((double)c->tile_gidx[i]); b.push_back((double)nv); b.push_back((double)ns);
-    b.insert(b.end(), vx.begin() + voff[i], vx.begin() + voff[i + 1]); b.insert(b.end(), vy.begin() + voff[i], vy.begin() + voff[i + 1]);
-    b.insert(b.end(), sx.begin() + soff[i], sx.begin() + soff[i + 1]); b.insert(b.end(), sy.begin() + soff[i], sy.begin() + soff[i + 1]);
-  }
-  if ((rc = comm_alltoallv(c, sendv, recvv))) return rc;
-  // did anything move anywhere?  (every rank must take the same branch: the rebuild below ends in collective set-up calls)
-  int moved_all = 0;
-  if ((rc = comm_agree_bits(c, nmove > 0 ? 1 : 0, &moved_all))) return rc;
-  if (n_sent) *n_sent = nmove;
-  if (!moved_all) { if (n_owned) *n_owned = N; return SZ_OK; }
-  // ---- the new tile: kept floes + received ones, ordered by global index
-  struct Src { long long g; int from; size_t at; };          // from < 0: local row `at`; else stream `from`, offset `at`
-  std::vector<Src> src;
-  for (int i = 0; i < N; i++) if (owner[i] == me) src.push_back({ c->tile_gidx[i], -1, (size_t)i });
-  for (int s2 = 0; s2 < n; s2++) {
-    const std::vector<double>& b = recvv[s2];
-    for (size_t at = 0; at < b.size();) {
-      if (at + MIG_NCOL > b.size()) { c->err = "sz_tile_migrate: truncated record"; return SZ_E_STATE; }
-      const int nv = (int)b[at + 40], ns = (int)b[at + 41];
-      src.push_back({ (long long)b[at + 39], s2, at });
-      at += (size_t)MIG_NCOL + 2 * (size_t)nv + 2 * (size_t)ns;
-    }
-  }
-  std::sort(src.begin(), src.end(), [](const Src& a, const Src& b2) { return a.g < b2.g; });
-  const int Nn = (int)src.size();
-  if (Nn == 0) { c->err = "sz_tile_migrate: a tile without floes (every rank must own at least one)"; return SZ_E_STATE; }
-  std::vector<std::vector<double>> ncol(25, std::vector<double>((size_t)Nn));
-  std::vector<double> nten[3] = { std::vector<double>((size_t)4 * Nn), std::vector<double>((size_t)4 * Nn), std::vector<double>((size_t)4 * Nn) };
-  std::vector<long long> nid((size_t)Nn), ngid((size_t)Nn); std::vector<int> nstatus((size_t)Nn), nvoff((size_t)Nn + 1, 0), nsoff((size_t)Nn + 1, 0);
-  std::vector<double> nvx, nvy, nsx, nsy;
-  for (int r = 0; r < Nn; r++) {
-    const Src& q = src[r];
-    ngid[r] = q.g;
-    if (q.from < 0) {
-      const size_t i = q.at;
-      for (int k = 0; k < 25; k++) ncol[k][r] = col[k][i];
-      for (int k = 0; k < 3; k++) for (int t = 0; t < 4; t++) nten[k][(size_t)4 * r + t] = ten[k][4 * i + t];
-      nid[r] = id[i]; nstatus[r] = status[i];
-      nvx.insert(nvx.end(), vx.begin() + voff[i], vx.begin() + voff[i + 1]); nvy.insert(nvy.end(), vy.begin() + voff[i], vy.begin() + voff[i + 1]);
-      nsx.insert(nsx.end(), sx.begin() + soff[i], sx.begin() + soff[i + 1]); nsy.insert(nsy.end(), sy.begin() + soff[i], sy.begin() + soff[i + 1]);
-    } else {
-      const double* b = recvv[q.from].data() + q.at;
-      for (int k = 0; k < 25; k++) ncol[k][r] = b[k];
-      for (int k = 0; k < 3; k++) for (int t = 0; t < 4; t++) nten[k][(size_t)4 * r + t] = b[25 + 4 * k + t];
-      nid[r] = (long long)b[37]; nstatus[r] = (int)b[38];
-      const int nv = (int)b[40], ns = (int)b[41];
-      const double* p = b + MIG_NCOL;
-      nvx.insert(nvx.end(), p, p + nv); nvy.insert(nvy.end(), p + nv, p + 2 * nv);
-      p += 2 * (size_t)nv;
-      nsx.insert(nsx.end(), p, p + ns); nsy.insert(nsy.end(), p + ns, p + 2 * ns);
-    }
-    nvoff[r + 1] = (int)nvx.size(); nsoff[r + 1] = (int)nsx.size();
-  }
-  if (nvx.empty()) { nvx.push_back(0.0); nvy.push_back(0.0); }
-  if (nsx.empty()) { nsx.push_back(0.0); nsy.push_back(0.0); }
-  // ---- rebuild through the upload path, then the tile set-up again
-  const Retile tiling(c);
-  sz_floe_columns f; memset(&f, 0, sizeof(f));
-  f.cx = ncol[0].data(); f.cy = ncol[1].data(); f.rmax = ncol[2].data(); f.area = ncol[3].data(); f.height = ncol[4].data(); f.mass = ncol[5].data(); f.moment = ncol[6].data();
-  f.alpha = ncol[7].data(); f.u = ncol[8].data(); f.v = ncol[9].data(); f.xi = ncol[10].data(); f.p_dxdt = ncol[11].data(); f.p_dydt = ncol[12].data(); f.p_dalphadt = ncol[13].data();
-  f.p_dudt = ncol[14].data(); f.p_dvdt = ncol[15].data(); f.p_dxidt = ncol[16].data(); f.fxOA = ncol[17].data(); f.fyOA = ncol[18].data(); f.trqOA = ncol[19].data();
-  f.hflx_factor = ncol[20].data(); f.overarea = ncol[21].data(); f.coll_fx = ncol[22].data(); f.coll_fy = ncol[23].data(); f.coll_trq = ncol[24].data();
-  f.stress_accum = nten[0].data(); f.stress_instant = nten[1].data(); f.strain = nten[2].data();
-  f.id = (int64_t*)nid.data(); f.status = nstatus.data(); f.vert_off = nvoff.data(); f.vx = nvx.data(); f.vy = nvy.data(); f.sub_off = nsoff.data(); f.sx = nsx.data(); f.sy = nsy.data();
-  if ((rc = sz_upload_floes(c, Nn, Nn, &f))) return rc;
-  c->inter_lost = false; c->inter_any = true;
-  HIPCHK(c, hipMemsetAsync(S.inter_cnt, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));          // (no rows until the next collision call)
-  if ((rc = tiling.again(c, ngid.data(), owner_override ? 0 : px, py))) return rc;
-  if (n_owned) *n_owned = Nn;
-  return SZ_OK;
-}
-}  // namespace
-// sub-floe points of the floes the context holds (CSR: off has N + 1 entries; call with sx == NULL for the offsets alone): after a
-// migration the host's copy of these is the library's
-int sz_download_subpoints(sz_ctx* c, int32_t* off, double* sx, double* sy) {
-  if (!c || !c->have_floes || !off) return SZ_E_ARG;
-  (void)hipSetDevice(c->device);
-  tile_cleanup(c);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const int N = c->hostN;
-  HIPCHK(c, hipMemcpy(off, c->S.soff, ((size_t)N + 1) * sizeof(int), hipMemcpyDeviceToHost));
-  if (sx && sy && off[N] > 0) {
-    HIPCHK(c, hipMemcpy(sx, c->S.sx, (size_t)off[N] * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(sy, c->S.sy, (size_t)off[N] * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  return SZ_OK;
-}
-
-// The exchange of one step: the regions of d_send to the peers, theirs into d_recv, on the communication stream behind the pack kernel
-// (ev_packed) -- ev_recv is recorded when the halo is in.  all_ranks: every rank gets at least the header record (the stop agreement of the
-// inline steps reads the flags of ALL ranks); otherwise only the neighbouring tiles take part.
-namespace {
-int tile_exchange(sz_ctx* c, bool all_ranks) {
-  const int n = c->comm_n, me = c->comm_rank;
-  if (n <= 1) return SZ_OK;
-  const int HREC = halo_rec(c->S);
-  const size_t stride = (size_t)(c->halo_cap + 1) * HREC;
-  HIPCHK(c, hipEventRecord(c->ev_packed, c->stream));
-  HIPCHK(c, hipStreamWaitEvent(c->comm_stream, c->ev_packed, 0));
-  if (c->host_transport) {
-    Timed tx(c, K_EXCHANGE, c->comm_stream);
-    c->h_send.resize((size_t)n * stride); c->h_recv.resize((size_t)n * stride);
-    HostTrade tr;
-    for (int d = 0; d < n; d++) {
-      if (d == me || (!all_ranks && c->cap_send[d] <= 0 && c->cap_recv[d] <= 0)) continue;
-      const size_t ns = (all_ranks || c->cap_send[d] > 0) ? (size_t)(c->cap_send[d] + 1) * HREC : 0;
-      const size_t nr = (all_ranks || c->cap_recv[d] > 0) ? (size_t)(c->cap_recv[d] + 1) * HREC : 0;
-      if (ns) HIPCHK(c, hipMemcpyAsync(c->h_send.data() + d * stride, c->d_send + d * stride, ns * sizeof(double), hipMemcpyDeviceToHost, c->comm_stream));
-      tr.add(d, c->h_send.data() + d * stride, ns * sizeof(double), c->h_recv.data() + d * stride, nr * sizeof(double));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->comm_stream));
-    if (int rc = tr.run(c)) return rc;
-    for (size_t k = 0; k < tr.peer.size(); k++)
-      if (tr.rb[k]) HIPCHK(c, hipMemcpyAsync(c->d_recv + tr.peer[k] * stride, tr.rp[k], (size_t)tr.rb[k], hipMemcpyHostToDevice, c->comm_stream));
-    HIPCHK(c, hipStreamSynchronize(c->comm_stream));       // (h_recv is reused by the next step)
-    tx.end();
-  } else {
-    Timed tx(c, K_EXCHANGE, c->comm_stream);          // (class "exchange" of sz_kernel_time_ms: the grouped send / receive on the communication stream)
-    NCCLCHK(c, g_rccl.GroupStart());
-    for (int d = 0; d < n; d++) {
-      if (d == me) continue;
-      if (all_ranks || c->cap_send[d] > 0) NCCLCHK(c, g_rccl.Send(c->d_send + d * stride, (size_t)(c->cap_send[d] + 1) * HREC, NCCL_FLOAT64, d, c->comm, c->comm_stream));
-      if (all_ranks || c->cap_recv[d] > 0) NCCLCHK(c, g_rccl.Recv(c->d_recv + d * stride, (size_t)(c->cap_recv[d] + 1) * HREC, NCCL_FLOAT64, d, c->comm, c->comm_stream));
-    }
-    NCCLCHK(c, g_rccl.GroupEnd());
-    tx.end();
-  }
-  HIPCHK(c, hipEventRecord(c->ev_recv, c->comm_stream));
-  return SZ_OK;
-}
-// what a pack is given (sz_k_halo_pack; the integrator of a tiled step that packs for the next one: sz_k_integrate<true, true>)
-PackInl tile_pack_args(sz_ctx* c) {
-  State& S = c->S;
-  PackInl a;
-  a.send = c->d_send; a.boxes = S.bounds + 16; a.dcap = c->d_dcap; a.ref = c->d_ref; a.counts = S.cnt + C_COUNT;
-  a.Lx = c->tile_Lx; a.Ly = c->tile_Ly; a.margin = c->tile_margin;
-  a.nranks = c->comm_n; a.me = c->comm_rank; a.cap = c->halo_cap; a.per_x = c->tile_per_x; a.per_y = c->tile_per_y;
-  return a;
-}
-void tile_pack(sz_ctx* c) {
-  State& S = c->S;
-  hipLaunchKernelGGL(sz_k_halo_pack, dim3(grid_for(std::max(c->hostN, 1), PACK_TPB)), dim3(PACK_TPB), 0, c->stream, S, c->comm_n, c->comm_rank, S.bounds + 16,
-                     c->tile_Lx, c->tile_Ly, c->tile_per_x, c->tile_per_y, c->d_send, c->halo_cap, S.cnt + C_COUNT, (const int*)c->d_dcap, (const double*)c->d_ref, c->tile_margin);
-}
-// status.fuse_idx of a tiled context, in GLOBAL floe numbers: the order keys of the local rows of the step that ended the batch (owned
-// floes: their global index; halo floes and ghosts: the step's key table), the replay of host_fuse_fixup in key order, and the partners
-// renamed -- a ghost by its parent
-int tile_fuse_replay(sz_ctx* c, const int* h, bool last_coupled) {
-  int rc = gi_fetch(c); if (rc) return rc;
-  const int M = h[C_N] + h[C_NGHOSTS];
-  std::vector<long long> keys(M, 0);
-  for (int i = 0; i < M; i++) keys[i] = i < c->hostN ? c->tile_gidx[i] : (i - c->hostN < (int)c->gi_keys.size() ? c->gi_keys[i - c->hostN] : ((long long)3 << 40) + i);
-  rc = host_fuse_fixup(c, h, true, true, last_coupled, &keys);
-  if (rc) return rc;
-  const long long lim = (long long)1 << 40;
-  for (int i = 0; i < c->hostN && i < (int)c->fuse_lists.size(); i++)
-    for (int& v : c->fuse_lists[i]) { if (v < 0 || v >= (int)keys.size()) continue; long long key = keys[v]; if (key >= lim) key = (key & (lim - 1)) >> 2; v = (int)key; }
-  return SZ_OK;
-}
-// The plan of a tiled batch of inline steps (sz_tile_run has checked what they need: collisions, the static grid, rings that fit the one-launch
-// integrator, no two-way coupling).  The ghosts are made by whoever places the parent (integrator: owned floes, unpack: halo floes): inline
-// ghosts without a candidate list.  Records and totals: plan_batch's rules.  A tile's own:
-//  - rfree.  With peers and the tag stop a rank learns that a step was the batch's last only in the unpack of the NEXT one -- after its
-//    integrator has made that step's ghosts over the rows of this one -- so the rows are then assembled inside every step (rows only); alone,
-//    or in batches that run through (SZ_NO_STOP), once behind the batch.  (Moving walls do not enter the rule.)
-//  - lean.  Not under SZ_SYNC_DEBUG (dbgsync: the stages run one by one), and not without the all-pairs headers (hdr_all): a pause must
-//    reach every rank.
-static BatchPlan plan_tile_batch(const sz_ctx* c, int nsteps, int flags, bool hdr_all, bool dbgsync) {
-  BatchPlan p{};
-  p.periodic = c->S.any_periodic_ew || c->S.any_periodic_ns;
-  p.coll = p.sg = p.gi = true;
-  p.user_stop = !(flags & SZ_NO_STOP);
-  p.mixed = c->precision == 1;
-  plan_records_totals(p, c, nsteps);
-  p.set_rfree(p.facc_on && !(c->comm_n > 1 && p.user_stop));
-  p.lean = lean_wanted(c) && !dbgsync && hdr_all;
-  return p;
-}
-// sz_tile_run on the list-based steps of sz_tile_step
-static int tile_run_listed(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling_dt, int flags, int32_t* steps_done) {
-  State& S = c->S; const int n = c->comm_n;
-  // The tag stop of these steps (one-way coupling): the pack kernel's header records carry every rank's stop word to EVERY rank, the unpack
-  // kernel of the next step reads them before that step has touched anything and ends the batch there (sz_k_halo_unpack), as in the inline
-  // steps.  The forcings then run behind the unpack instead of beside the exchange: a rank must not compute the forcings of a step its
-  // peers have already called off.  Two-way coupling across tiles (round 4): the same stop -- the steps behind it are enqueued and return at
-  // once; their all-reduces of the per-cell sums still run on every rank (collectives must), on the sums of the step that ended the
-  // batch, and sz_two_way_finish writes the ocean fields of that step once more: the same values.
-  const bool stopping = !(flags & SZ_NO_STOP);
-  S.stop_on_tags = stopping ? 1 : 0;
-  HIPCHK(c, clear_stop_words(c, W_STOP | W_RETRYSTOP));
-  for (int s = 0; s < nsteps; s++) {
-    const int tstep = tstep0 + s;
-    c->tile_dt = dt;
-    S.step = stopping ? s + 1 : 0;
-    if (c->tile_since_box < 0 || c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }
-    c->tile_since_box++;
-    const bool coupling = coupling_at(flags, coupling_dt, tstep);
-    tile_pack(c);
-    // (the host's channel blocks: the forcings go to the device first and run while the host trades the regions)
-    if (coupling && !stopping && n > 1 && c->host_transport) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return rc; }
-    { int rc = tile_exchange(c, stopping); if (rc) return rc; }
-    // the forcings of the owned floes need nothing from the halo: they run beside the exchange
-    if (coupling && !stopping && !(n > 1 && c->host_transport)) { int rc = sz_tile_forcing(c, tstep, coupling_dt, flags); if (rc) return rc; }
-    if (n > 1 && hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return SZ_E_HIP; }
-    int rc = tile_step_body(c, c->d_recv, n, c->halo_cap, tstep, dt, coupling_dt, flags); if (rc) return rc;
-    if (c->two_way && coupling) {       // ice-on-ocean stress: per-cell partial sums, summed over the ranks, finished on every rank
-      const size_t nc = 3 * c->tw_ncell;
-      if (!c->d_tw_partial) { int r2 = dalloc(c, &c->d_tw_partial, nc, c->tw_part_allocs); if (r2) return r2; }
-      if ((rc = sz_two_way_partial(c, c->d_tw_partial)) || (rc = sz_comm_allreduce(c, c->d_tw_partial, (int64_t)nc)) ||
-          (rc = sz_two_way_finish(c, c->d_tw_partial, dt))) return rc;
-    }
-  }
-  // (the ranks agree on the error word: a rank with a device error and a clean one return the same code)
-  S.step = 0;
-  int hl[C_COUNT] = { 0 };
-  const int rce = tile_sync_agree(c, hl);
-  c->fuse_lists.resize(c->hostM);
-  const int done = stopping && hl[C_STOP] > 0 ? std::min(hl[C_STOP], (int)nsteps) : nsteps;
-  c->tile_stop_raised = stopping ? hl[C_STOP] : 0;
-  if (done < nsteps) { c->grid_live = false; c->gl_valid = false; }          // stopped early: cells and ghost-candidate lists belong to steps that did not come
-  if (steps_done) *steps_done = done;
-  return rce;
-}
-// sz_tile_run on the inline steps: the single context's (step_batch_three_launch with inline ghosts), plus the pack and unpack kernels and the
-// exchange, and the restarts the ranks agree on
-static int tile_run_inline(sz_ctx* c, int nsteps, int tstep0, int dt, int coupling_dt, int flags, int32_t* steps_done) {
-  State& S = c->S; const int n = c->comm_n, me = c->comm_rank;
-  // SZ_SYNC_DEBUG=1 (diagnosis of a faulting kernel): wait after every stage of every step and say so on stderr -- the last line names the stage
-  const bool dbgsync = getenv("SZ_SYNC_DEBUG") != nullptr;
-  const bool hdr_all = !(c->tile_hdr_neighbours && (flags & SZ_NO_STOP));      // (the A/B arm without the all-pairs headers: see tile_hdr_neighbours)
-  const BatchPlan plan = plan_tile_batch(c, nsteps, flags, hdr_all, dbgsync);
-  const bool periodic = plan.periodic, facc_on = plan.facc_on, rfree = plan.rfree;
-  tile_cleanup(c);                                  // (the halo floes / ghosts a list-based call may have left attached)
-  c->gi_pending = false; c->gi_valid = false; c->gl_valid = false;
-  world_rings(c);
-  S.stop_on_tags = plan.user_stop ? 1 : 0;
-  HIPCHK(c, clear_stop_words(c, W_STOP | W_RETRYSTOP | W_PAUSED));
-  use_static_grid(c);
-  if (plan.mixed) { int rc = ensure_mixed(c); if (rc) return rc; }
-  else if (!c->two_way && c->have_fields) { int rc = ensure_block_points(c); if (rc) return rc; }
-  S.ginline = 1; S.famrec = 1;
-  HIPCHK(c, hipMemsetAsync(S.galloc, 0, 32 * sizeof(unsigned long long), c->stream));
-  // the periodic ghosts of the owned floes for the first step (and the swap of parents that lie outside the domain), BEFORE the first pack
-  // collision records of the owned floes (the halo floes get theirs from the unpack kernel, ghosts from their maker; see sz_step)
-  S.crec = plan.cr ? c->crec_buf : nullptr; c->crec_was_live = plan.cr;
-  if (plan.cr) seed_records(c, S, c->hostN);
-  // (the periodic ghosts of the owned floes for the first step, and the swap of parents that lie outside the domain: in the loop, BEHIND the
-  //  first pack -- see there)
-  // fixed-point totals and reduce-free steps as in sz_step (plan_tile_batch)
-  S.facc = facc_on ? c->facc_buf : nullptr; S.kexp = force_scale_exp(c); c->reduce_mode = plan.reduce_mode;
-  if (facc_on) { if (int rc = clear_totals(c)) return rc; }
-  // the forcing output set in use (see `beside` below): a way out before the end of the batch takes the columns back to set 0, as at entry
-  struct FrcSets {
-    sz_ctx* c; int cur; bool keep;
-    void use(int set) { if (set != cur) { std::swap(c->S.fxOA, c->frc_alt[0]); std::swap(c->S.fyOA, c->frc_alt[1]); std::swap(c->S.trqOA, c->frc_alt[2]); std::swap(c->S.hflx, c->frc_alt[3]); cur = set; } }
-    ~FrcSets() { if (!keep) use(0); }
-  } frc{ c, 0, false };
-  auto stage_done = [&](int s, const char* what) {
-    if (!dbgsync) return;
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    int h4[C_COUNT]; (void)hipMemcpy(h4, S.cnt, sizeof(h4), hipMemcpyDeviceToHost);
-    fprintf(stderr, "[sz rank %d] step %d: %s done (%s) M=%d N=%d own=%d halo=%d ghosts=%d err=0x%x\n", me, s, what, hipGetErrorString(e), h4[C_M], h4[C_N], h4[C_NOWN], h4[C_NHALO], h4[C_NGHOSTS], h4[C_ERR]);
-    fflush(stderr);
-  };
-  stage_done(-1, "seed");
-  std::vector<signed char> fset((size_t)std::max(nsteps, 1), (signed char)-1);      // the output set the forcings of step s wrote (-1: none of this kind)
-  auto last_set = [&](int upto) { int set = 0; for (int s2 = 0; s2 < upto; s2++) if (fset[s2] >= 0) set = fset[s2]; return set; };      // (of steps [0, upto); 0: as at entry)
-  // The largest narrow variant is left out of the steps until an item needs it, as in sz_step (-4 us and a launch boundary per step).  A
-  // rank whose narrow phase meets such an item pauses inside that step (C_RETRYSTOP); its pause rides in the header records of the next
-  // exchange (sz_k_halo_pack hdr[2]), whose unpack kernel stops every other rank before that step has touched anything.  After the sync
-  // all ranks know the step: the rank that paused finishes it (the variant, the reduce, the integrator), and everybody runs the rest of
-  // the batch again from the step after it, as a batch that starts there (cells, ghosts, records seeded anew) with the variant in.
-  bool lean = plan.lean;
-  std::vector<int> callid_of((size_t)std::max(nsteps, 1), 0);
-  int h[C_COUNT]; int rc = SZ_OK;
-  // The halo records of step s + 1 are written by the integrator of step s: the thread that has just placed the floe holds all a record
-  // carries, and it packs the floe as the update left it, BEFORE the swap of a parent that left the domain -- the receiving rank makes
-  // the ghosts with the routine the owner runs on the same values (see sz_k_integrate<true, true>).  A pack launch remains for the first
-  // step of a batch (and the step a paused batch is taken up again at): it runs BEFORE the launch that makes the owned floes' first
-  // ghosts and swaps the parents that lie outside, for the same reason.  New boxes for step s + 1 are therefore gathered before the
-  // integrator of step s (from the positions that step started with; the drift margin covers the step in between).
-  // fresh: this rank starts the (sub-)batch from its parents as they lie -- boxes, the first pack, the first ghosts.  After a pause only the
-  // rank that paused does: it finished its step without making anything for the next one.  The others have that step behind them as any other
-  // -- their integrator has made the next step's ghosts (from the parents BEFORE their swap, like the single context and the reference:
-  // collisions.jl:942-950) and packed the halo records -- and simply take up the steps where the pause stopped them.
-  bool fresh = true;
-  for (int s_begin = 0;;) {
-    S.retry_stop = lean ? 1 : 0;
-    for (int s = s_begin; s < nsteps; s++) {
-      const int tstep = tstep0 + s;
-      S.step = s + 1; S.gslot = s & 1;
-      c->tile_dt = dt;
-      if (s == s_begin && s_begin == 0) {
-        if (c->tile_since_box < 0 || c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }
-        stage_done(s, "rebox");
-      }
-      if (s == s_begin && fresh) {
-        tile_pack(c);
-        if (periodic) hipLaunchKernelGGL(sz_k_ghost_inline_seed, dim3(grid_for(S.capM, 256)), dim3(256), 0, c->stream, S, s & 1, c->hostN);
-      }
-      c->tile_since_box++;
-      const bool coupling = coupling_at(flags, coupling_dt, tstep);
-      stage_done(s, "pack");
-      // With peers the forcings of the owned floes (they need nothing from the halo) run BESIDE the exchange -- on the main stream while the
-      // communication stream trades the regions, before the host's channel blocks -- and the narrow launch carries no forcing tail; without
-      // peers there is nothing to hide them behind and they ride in the narrow launch's tail as in sz_step.
-      const bool beside = coupling && n > 1 && !(c->pmask >> SZ_K_FORCING & 1u);
-      // (these forcings run before this rank knows whether a peer has asked for the batch to end at the previous step -- the unpack kernel
-      //  below finds out.  They therefore write a SECOND set of the four output columns, alternating step by step, and the set the last
-      //  step that really ran has written is made the context's at the end of the call: a batch that ends early leaves fxOA .. hflx of the
-      //  step it ended with, as sz_step does.)
-      if (beside) { frc.use(frc.cur ^ 1); fset[s] = (signed char)frc.cur; }
-      if (beside && c->host_transport) stage_forcing(c, dt);
-      { int rc = tile_exchange(c, hdr_all); if (rc) return rc; }
-      if (beside && !c->host_transport) stage_forcing(c, dt);
-      if (n > 1) {
-        if (hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return SZ_E_HIP; }
-        const long long slots = (long long)n * c->halo_cap;
-        hipLaunchKernelGGL(sz_k_halo_unpack_inline, dim3(grid_for(slots, UNPACK_TPB, 1 << 20)), dim3(UNPACK_TPB), 0, c->stream, S, (const double*)c->d_recv, n, me, c->halo_cap,
-                           S.gslot, c->hostN);
-      }
-      stage_done(s, "exchange + unpack");
-      // the forcings that did not run beside the exchange: where sz_step puts them (forcing_fuse_mode)
-      const int fmode = forcing_fuse_mode(c, coupling && !beside);
-      if (coupling && !fmode && !beside) stage_forcing(c, dt);
-      if (coupling) c->forcing_where = fmode;
-      S.callid = ++c->callid; callid_of[s] = S.callid;
-      if (facc_on && !(S.crec && S.maxnb <= MAXNB)) (void)hipMemsetAsync(c->facc_buf + (size_t)FX_WORDS * c->hostN, 0, (size_t)FX_WORDS * (S.capM - c->hostN) * sizeof(long long), c->stream);      // (see sz_step)
-      if (dbgsync) {          // (the stages of collisions_step one by one)
-        stage_broad(c, false, true, fmode == 1, false); stage_done(s, "neighbour search");
-        stage_elems(c, true); stage_done(s, "element items");
-        stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, fmode == 2 ? (c->precision == 1 ? 2 : 1) : 0, 0); stage_done(s, "narrow phase");
-        stage_reduce(c, 1, -1, dt, 0); stage_done(s, "reduce");
-      } else collisions_step(c, -1, dt, false, true, fmode, lean, false);
-      const bool pack_next = s + 1 < nsteps;
-      if (pack_next && c->tile_since_box >= c->tile_rebox_cur) { int rc = tile_rebox(c); if (rc) return rc; }      // (synchronises: once per gather interval)
-      const PackInl pk = tile_pack_args(c);
-      c->acc_mode = integrator_acc_mode(facc_on, rfree, s + 1 == nsteps);
-      stage_integrate(c, dt, false, coupling, true, -1, periodic && s + 1 < nsteps ? 1 - (s & 1) : -1, pack_next ? &pk : nullptr);
-      stage_done(s, "integrate");
-    }
-    S.step = 0;
-    if (rfree && nsteps > 0) stage_reduce(c, 1, -1, dt, 0, true);          // floe.interactions of the step that ended the batch
-    c->tile_dirty = nsteps > 0;
-    rc = sync_and_check(c, h);                     // (drops the halo floes and ghosts of the last step: tile_cleanup -- unless a step is paused)
-    if (rc == SZ_E_HIP) return rc;
-    // (the ranks agree on the error word BEFORE anybody decides to run steps again: a rank leaving on its own would hang the others)
-    if (const int ra = tile_agree(c, rc)) return ra;
-    // the step that was paused (here or on a peer) and the step a tag ended the batch at, as every rank sees them (comm_agree_steps)
-    int sp = h[C_RETRYSTOP], st_all = h[C_STOP];
-    { const int rc3 = comm_agree_steps(c, h[C_STOP], h[C_RETRYSTOP], &st_all, &sp); if (rc3) return rc3; }
-    if (st_all > 0) h[C_STOP] = st_all;
-    if (!lean || sp <= 0 || (st_all > 0 && st_all < sp)) break;
-    // ---- a pause for the largest narrow variant in step sp
-    const bool coupling_sp = coupling_at(flags, coupling_dt, tstep0 + sp - 1);
-    HIPCHK(c, clear_stop_words(c, W_RETRYSTOP | W_PAUSED));
-    S.retry_stop = 0; c->retry_seen = true; lean = false;
-    // the forcing outputs as of step sp (the steps after it are run again).  BEFORE that step is finished: its integrator reads them, and
-    // the steps enqueued behind it have gone on alternating the sets on the host while their forcing kernels returned at once
-    frc.use(last_set(sp));
-    for (int s2 = sp; s2 < nsteps; s2++) fset[s2] = -1;
-    if (h[C_PAUSED] == sp) {          // this rank's step: the variant, then what the pause held back
-      S.step = sp; S.gslot = (sp - 1) & 1; S.callid = callid_of[sp - 1];
-      stage_narrow(c, dt, c->P.ff_max_overlap, c->P.fd_max_overlap, 0, 2);
-      stage_reduce(c, 1, -1, dt, 0);
-      c->acc_mode = integrator_acc_mode(facc_on, rfree, sp >= nsteps);
-      stage_integrate(c, dt, false, coupling_sp, true, -1, -1);
-      S.step = 0;
-      if (rfree && sp >= nsteps) stage_reduce(c, 1, -1, dt, 0, true);
-    }
-    c->tile_dirty = true;
-    if (sp >= nsteps || (st_all > 0 && st_all <= sp)) {               // (the last step of the batch -- or a peer tagged a floe in this very step: the batch ends with it -- nothing is run again)
-      rc = sync_and_check(c, h);
-      if (rc == SZ_E_HIP) return rc;
-      if (st_all > 0) h[C_STOP] = h[C_STOP] > 0 ? std::min(h[C_STOP], st_all) : st_all;
-      break;
-    }
-    // the rest of the batch again.  The rank that paused: from its floes as they lie after step sp (sz_step's capacity restart does the same);
-    // the others: on from where the pause stopped them (see `fresh`)
-    fresh = h[C_PAUSED] == sp;
-    if (fresh) {
-      tile_cleanup(c);
-      c->grid_live = false; use_static_grid(c);
-      HIPCHK(c, hipMemsetAsync(S.galloc, 0, 32 * sizeof(unsigned long long), c->stream));
-      if (plan.cr) seed_records(c, S, c->hostN);
-    } else {
-      c->tile_dirty = false;          // (nothing to drop: the rows behind the owned floes are the NEXT step's ghosts)
-      // the header records this rank's last pack left say "paused" (the launches enqueued behind the pause wrote the word there): not any more
-      const size_t hstride = (size_t)(c->halo_cap + 1) * halo_rec(S);
-      for (int d = 0; d < n; d++) HIPCHK(c, hipMemsetAsync(c->d_send + (size_t)d * hstride + 2, 0, sizeof(double), c->stream));
-    }
-    s_begin = sp;          // (the ghosts of that step: behind its pack, at the top of the loop)
-  }
-  if (const int ra = tile_agree(c, rc)) return ra;
-  const int done = h[C_STOP] > 0 ? std::min(h[C_STOP], (int)nsteps) : nsteps;
-  c->tile_stop_raised = plan.user_stop ? h[C_STOP] : 0;
-  if (steps_done) *steps_done = done;
-  frc.use(last_set(done)); frc.keep = true;          // the forcing outputs of the last step that ran (see `beside` above)
-  if (done < nsteps) c->grid_live = false;          // stopped early: cells hold floes of a step that did not come
-  c->inter_any = true; c->inter_lost = false;
-  // status.fuse_idx of the step that ended the batch (as sz_step: only that step can have produced fuse pairs)
-  if (done > 0 && (h[C_STOP] > 0 || (flags & SZ_NO_STOP))) {
-    c->gi_pending_n = h[C_NGHOSTS]; c->gi_pending_slot = (done - 1) & 1; c->gi_pending = true;
-    rc = tile_fuse_replay(c, h, coupling_at(flags, coupling_dt, tstep0 + done - 1));
-    c->gi_pending = false;
-  }
-  c->fuse_lists.resize(c->hostM);
-  return rc;
-}
-}  // namespace
-
-// the centre of this rank's tile (optional, after sz_tile_setup): in a periodic direction the owned box of the FIRST gather then takes every
-// centroid at its image nearest to it, as the later gathers do with the centre of the box before (sz_k_owned_box)
-int sz_tile_set_center(sz_ctx* c, double x, double y) {
-  if (!c || !c->S.tiled || c->tile_margin <= 0) { if (c) c->err = "sz_tile_set_center needs sz_tile_setup"; return SZ_E_STATE; }
-  c->tile_box_ctr[0] = x; c->tile_box_ctr[1] = y; c->tile_box_valid = true;
-  return SZ_OK;
-}
-// nsteps x timestep_sim! of a tiled run, collectively on every rank (same arguments everywhere)
-int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
-  if (steps_done) *steps_done = 0;
-  if (c && !c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
-  if (c && c->frac_kind != SZ_FRAC_OFF && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled fracture criteria gather the mean height over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
-  if (!c || !c->have_floes || !c->S.tiled || c->comm_n < 1 || c->tile_margin <= 0) { if (c) c->err = "sz_tile_run needs sz_tile_enable and sz_tile_setup after the last sz_upload_floes"; return SZ_E_STATE; }
-  if (nsteps < 0) return SZ_E_ARG;
-  const bool frac = c->frac_kind != SZ_FRAC_OFF;
-  if (frac && c->two_way) { c->err = "tiled two-way coupling with a fracture criterion set: its per-step all-reduce path has no tested stop: sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
-  (void)hipSetDevice(c->device);
-  // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
-  // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
-  // Needs what the inline ghost maker needs (rings that fit the one-launch integrator, the static grid).  Otherwise: the list-based steps
-  // of sz_tile_step.
-  // Either driver runs under one scope of its own per segment; the ring maxima may shrink behind a removal pass, so each segment asks again.
-  auto segment = [&](int len, int t0, int32_t* ran) {
-    const bool inl = (flags & SZ_COLLISIONS_ON) && c->grid_ok && !c->two_way &&
-                     std::max(c->max_ring, c->max_ring_tiled) <= MV_RING && ((flags & SZ_COUPLING_ON) == 0 || c->have_fields);
-    BatchModes modes(c);
-    return inl ? tile_run_inline(c, len, t0, dt, coupling_dt, flags, ran) : tile_run_listed(c, len, t0, dt, coupling_dt, flags, ran);
-  };
-  // In batches that stop, with a criterion set (sz_set_fracture) or removal set (sz_set_removal): the loop of sz_step.
-  // Fracture: the batch is cut into segments that END on a fracture step (tstep % frac_dt == 0), each an ordinary tiled batch.  Behind a segment
-  // whose last step ran comes the collective criterion pass (tile_frac_pass): a candidate on any rank ends the batch there on every rank
-  // (steps_done counts the fracture step), none = the next segment starts at the following step.  A tag raised on that very step is, behind the
-  // list-based driver, known to its rank alone -- the peers would hear of it in the unpack of a step that does not come; the inline driver has
-  // agreed it already -- so the pass's agreement carries it (tile_stop_raised), and what follows is the single context's order (simulation.jl:172-214: fracture, then simplify): without a candidate the batch ends on the tag as sz_step
-  // does, or -- removal set -- goes into the removal pass.  The batch's own last step is not looked at: the caller asks (sz_tile_fracture_candidates).
-  // Removal: a segment that a tag ends before its last step -- the same step on every rank, and never a fracture step: those end segments -- or
-  // on it (above) is followed by the collective pass; done = the next segment starts at the following step from the compacted tiles (boxes, halo
-  // capacities and peers are gathered again at its first exchange), declined = the batch ends there as without removal, on every rank.
-  // Two-way coupling across tiles has no tag stop of its own to hang a pass on: removal is not engaged there, a criterion refused.
-  // SZ_NO_STOP batches and contexts with neither set take the drivers as they are.
-  if ((!c->rm_on && !frac) || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return segment(nsteps, tstep0, steps_done);
-  int done = 0;
-  while (done < nsteps) {
-    int len = nsteps - done;
-    if (frac) for (int s = 0; s + 1 < nsteps - done; s++) if ((tstep0 + done + s) % c->frac_dt == 0) { len = s + 1; break; }
-    int32_t more = 0;
-    c->tile_stop_raised = 0;
-    const int rc = segment(len, tstep0 + done, &more);
-    done += more;
-    if (steps_done) *steps_done = done;
-    if (rc || done >= nsteps || more < 1) return rc;
-    if (more == len) {          // the segment's last step ran, and the batch goes on behind it: it was cut here, on a fracture step
-      int cand = 0, tag = 0, mine = 0;
-      if (int rc2 = tile_frac_pass(c, c->tile_stop_raised == len, false, &cand, &tag, &mine)) return rc2;
-      if (cand) return SZ_OK;
-      if (!tag) continue;
-    }
-    if (!c->rm_on) return SZ_OK;
-    int ok = 0, nr = 0, nd = 0;
-    if (int rc2 = tile_remove_pass(c, &ok, &nr, &nd)) return rc2;
-    if (!ok) return SZ_OK;
-  }
-  return SZ_OK;
-}
-
-// counts of the last sz_halo_pack per destination rank (synchronises); used to size the exchange buffers
-int sz_halo_counts(sz_ctx* c, int32_t nranks, int32_t* counts_out) {
-  if (!c || !c->have_floes || nranks < 1 || nranks > 64 || !counts_out) return SZ_E_ARG;
-  (void)hipSetDevice(c->device);
-  HIPCHK(c, hipMemcpyAsync(counts_out, c->S.cnt + C_COUNT, (size_t)nranks * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   return SZ_OK;
 }
 

@@ -64,7 +64,7 @@ def test_the_tiled_entry_point_in_header_capi_and_refusals():
     assert hasattr(L, "sz_tile_fracture_candidates")
     assert L.sz_tile_fracture_candidates.argtypes == [capi.C.c_void_p, capi._ip, capi._ip, capi._ip, capi._lp]
     # what still refuses a criterion on a tiled context: sz_tile_step, a context without set-up or communicator, two-way coupling
-    api = open(os.path.join(ROOT, "subzero.jl_amd", "csrc", "sz_api.hip")).read()
+    api = "".join(open(os.path.join(ROOT, "subzero.jl_amd", "csrc", f)).read() for f in ("sz_api.hip", "sz_tile_host.hpp"))      # (the tiled entry points)
     refusals = [l for l in api.splitlines() if "frac_kind != SZ_FRAC_OFF" in l and "SZ_E_STATE" in l]
     assert len(refusals) == 2
     step = api[api.index("int sz_tile_step("):]
