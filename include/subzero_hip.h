@@ -281,7 +281,8 @@ int sz_debug_fracture_mean(sz_ctx *ctx, double *mean_h, double *p);
    for bit.  A tag or a fracture candidate on the same step ends the batch first (fracture_floes! runs before the welding).  The table of the batch's
    own last step is left to the caller.  The steps between two welding steps run as ordinary batches (pipelined where those are); one host
    synchronisation per welding step.  SZ_NO_STOP runs through and evaluates nothing.
-   Tiled runs (sz_tile_run, sz_tile_step) with welding set return SZ_E_STATE (the bins span ranks).
+   Tiled contexts: sz_tile_run computes the table collectively behind segments that end on welding steps, sz_tile_weld_overlaps on request (both
+   below); sz_tile_step, the host-driven step, and sz_weld_overlaps on a tiled context return SZ_E_STATE.
    Limits: Nx * Ny * N^2 < 9e18 (the 64-bit pair key); rings of up to 254 vertices (the largest clip working set; beyond it SZ_E_CAPACITY). */
 int sz_set_welding(sz_ctx *ctx, int32_t n, const int32_t *dts, const int32_t *nxs, const int32_t *nys, double max_weld_area);
 /* the table of the state as it is now: *n entries; idx_i / idx_j (0-based parents) / inter_area have room for cap entries, or are all NULL to
@@ -410,7 +411,15 @@ int sz_set_stream(sz_ctx *ctx, void *hip_stream);
                          pass, and on).  The batch's own last step is not looked at: the caller asks.  SZ_NO_STOP batches and
                          contexts without a criterion launch and gather nothing for it.  Needs sz_tile_setup and a communicator
                          (SZ_E_STATE without); with two-way coupling across tiles a criterion is refused (SZ_E_STATE: those batches
-                         have no tested stop).  Welding stays refused on tiles.
+                         have no tested stop).
+                         With welding set (sz_set_welding) and without SZ_NO_STOP the segments also end on welding steps (the first k
+                         with tstep % dts[k] == 0 gives Nx, Ny).  Behind a segment whose last step ran the order is the single
+                         context's: the fracture pass on a fracture step, then the collective overlap table (sz_tile_weld_overlaps
+                         below: the same pass), then removal.  A table that is not empty ends the batch on every rank, *steps_done
+                         counting the welding step; an empty one lets the next segment start.  A tag or a fracture candidate on that
+                         step ends the batch first, where sz_step ends it, with removal set too.  The batch's own last step is not
+                         looked at.  SZ_NO_STOP batches and contexts without welding launch and gather nothing for it.  Needs
+                         sz_tile_setup and a communicator; refused with two-way coupling across tiles, like a criterion.
                          Device errors are per rank; the ranks agree on them at every box gather and at the end of the call,
                          so that EVERY rank returns the same code at the same step (a rank leaving on its own would hang the
                          others: RCCL has no timeout).  A new sz_upload_floes invalidates sz_tile_enable / sz_tile_setup.
@@ -481,8 +490,7 @@ int sz_tile_owned_gidx(sz_ctx *ctx, int64_t *gidx, int64_t n_cap);
    itself (SZ_E_HIP) is returned at once, as everywhere in the library.
    sz_tile_run with removal set (sz_set_removal) and without SZ_NO_STOP: a segment that a tag ends before the batch's last step is followed by
    this pass; done = the next segment starts at the following step and *steps_done counts on, declined = the batch ends there as without removal.
-   The batch's own last step is not looked at.  Tiled two-way coupling has no tag stop to hang the pass on: removal is not engaged there.
-   Welding stays refused on tiles. */
+   The batch's own last step is not looked at.  Tiled two-way coupling has no tag stop to hang the pass on: removal is not engaged there. */
 int sz_tile_remove_floes(sz_ctx *ctx, int32_t *done, int32_t *n_removed, int32_t *n_dissolved);
 /* Fracture criteria on a tiled context (csrc/sz_fracture_tile.hpp; DESIGN.md §9b, "tiled contexts"): determine_fractures over the ONE global
    floe list whose rows live on the ranks' tiles, on the state as it is.  Collective: it needs sz_tile_enable + sz_tile_setup, the communicator
@@ -496,6 +504,23 @@ int sz_tile_remove_floes(sz_ctx *ctx, int32_t *done, int32_t *n_removed, int32_t
    bits: SZ_E_CAPACITY) -- the ranks agree before they return, and nothing of the floes has changed.  A failure of the HIP runtime or of the
    channel itself (SZ_E_HIP) is returned at once. */
 int sz_tile_fracture_candidates(sz_ctx *ctx, int32_t *n_global, int32_t *n_owned, int32_t *rows, int64_t *gidx);
+/* Welding overlaps on a tiled context (csrc/sz_weld_tile.hpp; DESIGN.md §9c, "tiled contexts"): the table of sz_weld_overlaps over the ONE global
+   floe list whose rows live on the ranks' tiles, on the state as it is.  Collective: it needs sz_tile_enable + sz_tile_setup, the communicator
+   (RCCL, the host transport, or one rank), the parents alone in the list, the domain and the grid extents.  The bins, the break at the first
+   out-of-bounds centroid (the smallest such global number over all ranks) and the candidate pairs are those of the global list; the rank that
+   owns the floe with the smaller number clips the pair, with the other floe's ring sent over when it lives elsewhere, by the single context's
+   clipper on the same ring bits.  Every rank gets the WHOLE table: *n entries, idx_i / idx_j in GLOBAL numbers (i < j), inter_area -- the rows of
+   the single context's table in its order, areas to the bit, identical on every rank.  n, cap and SZ_E_ARG for a cap under *n as in
+   sz_weld_overlaps (the same cap on every rank).  The global numbers of the ranks must be 0 .. N_global - 1 once each (SZ_E_STATE on EVERY rank
+   otherwise), and any error one rank finds (device error bits, scratch memory) is agreed on before the next collective: all ranks return the
+   same code, and nothing of the floes has changed.  A failure of the HIP runtime or of the channel itself (SZ_E_HIP) is returned at once.
+   Limits: Nx * Ny * N_global^2 < 9e18; rings of up to 254 vertices.
+   Test hooks (collective): per OWNED row the 0-based bin or -1, with the break of the global list; the candidate pairs of the last pass, summed
+   over the ranks. */
+int sz_tile_weld_overlaps(sz_ctx *ctx, int32_t nx, int32_t ny, double max_weld_area,
+                          int32_t *n, int32_t cap, int64_t *idx_i, int64_t *idx_j, double *inter_area);
+int sz_tile_debug_weld_bins(sz_ctx *ctx, int32_t nx, int32_t ny, int32_t *bin);
+int sz_tile_debug_weld_npairs(sz_ctx *ctx, int64_t *n);
 int sz_debug_migrate_path(sz_ctx *ctx);
 /* diagnosis: the ghost / halo row that carried order key `key` in the last resident step that used ghost allocator `slot` (0-based step & 1), as the
    collision kernels saw it -- out56: row (-1: none), cx, cy, u, v, xi, rmax, area, height, box x0 x1 y0 y1, ring points, parent, status, ring x[20], y[20] */

@@ -947,7 +947,8 @@ end
 # ends after the first step that leaves a floe tagged remove / fuse on ANY rank (the same number on every rank), so that the host's
 # simplify_floes! runs at the step the reference runs it (simulation.jl:205-214).  With a criterion set (`set_fracture!`: fractures need
 # not be turned off for a tiled run) it also ends after the first fracture step on which a floe of ANY rank would fracture; the batch's
-# own last step is not looked at -- `tile_fracture_candidates` answers for it
+# own last step is not looked at -- `tile_fracture_candidates` answers for it.  With welding set (`set_welding!`) it likewise ends after the
+# first welding step whose overlap table of the global list is not empty (`tile_weld_overlaps`)
 function tile_run!(eng::HIPEngine, nsteps::Integer, tstep::Integer, Δt::Integer, coupling_Δt::Integer, flags::Integer)
     done = Ref{Int32}(0)
     check(eng, @ccall lib.sz_tile_run(eng.ctx::Ptr{Cvoid}, nsteps::Int32, tstep::Int32, Δt::Int32, coupling_Δt::Int32, flags::Int32,
@@ -963,6 +964,21 @@ function tile_fracture_candidates(eng::HIPEngine, n_owned::Integer)
     rows = Vector{Int32}(undef, max(n_owned, 1)); g = Vector{Int64}(undef, max(n_owned, 1))
     check(eng, @ccall lib.sz_tile_fracture_candidates(eng.ctx::Ptr{Cvoid}, ng::Ptr{Int32}, no::Ptr{Int32}, rows::Ptr{Int32}, g::Ptr{Int64})::Cint)
     return Int(ng[]), Int.(rows[1:no[]]) .+ 1, g[1:no[]]
+end
+
+# the welding overlap table of the global floe list whose rows live on the ranks' tiles (sz_tile_weld_overlaps): collective, on the state as it
+# is.  Returns (i, j, inter_area) with 1-based GLOBAL numbers i < j, the whole table on every rank: the rows `weld_overlaps` gives for the
+# undivided list, in its order, areas to the bit.  `tile_run!` with `set_welding!` ends after the first welding step whose table is not empty;
+# its own last step is not looked at -- this answers for it
+function tile_weld_overlaps(eng::HIPEngine, nx::Integer, ny::Integer, max_weld_area::Real)
+    n = Ref{Int32}(0)
+    check(eng, @ccall lib.sz_tile_weld_overlaps(eng.ctx::Ptr{Cvoid}, Int32(nx)::Int32, Int32(ny)::Int32, Float64(max_weld_area)::Float64, n::Ptr{Int32},
+                                                Int32(0)::Int32, C_NULL::Ptr{Int64}, C_NULL::Ptr{Int64}, C_NULL::Ptr{Float64})::Cint)
+    cap = max(Int(n[]), 1)
+    i = Vector{Int64}(undef, cap); j = Vector{Int64}(undef, cap); a = Vector{Float64}(undef, cap)
+    check(eng, @ccall lib.sz_tile_weld_overlaps(eng.ctx::Ptr{Cvoid}, Int32(nx)::Int32, Int32(ny)::Int32, Float64(max_weld_area)::Float64, n::Ptr{Int32},
+                                                Int32(cap)::Int32, i::Ptr{Int64}, j::Ptr{Int64}, a::Ptr{Float64})::Cint)
+    return i[1:n[]] .+ 1, j[1:n[]] .+ 1, a[1:n[]]
 end
 
 # floes that left their tile go to the rank that owns the tile their centroid lies in now (px x py tiles over the domain), with their

@@ -23,6 +23,7 @@
 #include "sz_weld.hpp"
 #include "sz_remove_tile.hpp"
 #include "sz_fracture_tile.hpp"
+#include "sz_weld_tile.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 #include "sz_ctx.hpp"
 #include "sz_comm.hpp"
@@ -743,7 +744,7 @@ void sz_destroy(sz_ctx* c) {
   for (auto& e : c->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   (void)hipFree(c->d_stats); (void)hipFree(c->S.acc);
   (void)hipFree(c->frac_d); (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx);
-  free_pool(c->weld_allocs); (void)hipFree(c->weld_tmp);
+  free_pool(c->weld_allocs); free_pool(c->weldt_allocs); (void)hipFree(c->weld_tmp);
   free_pool(c->rm_allocs);
   free_pool(c->frac_allocs);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -2262,9 +2263,9 @@ int weld_pass(sz_ctx* c, int nx, int ny, double max_area, int* ntable) {
         c->weld_tmp_bytes = tmp_bytes + tmp_bytes / 2;
       }
       HIPCHK(c, rocprim::radix_sort_keys(c->weld_tmp, tmp_bytes, W.keys_in, W.keys, (size_t)P, 0u, bits, c->stream));
-      hipLaunchKernelGGL((sz_k_weld_area<WELD_G0, WELD_CAP0, WELD_KC0, WELD_RC0, WELD_RM0, 0>), dim3(grid_for(P, 64 / WELD_G0, 1 << 16)), dim3(64), 0, c->stream, S, W, P);
+      hipLaunchKernelGGL((sz_k_weld_area<WELD_G0, WELD_CAP0, WELD_KC0, WELD_RC0, WELD_RM0, 0>), dim3(grid_for(P, 64 / WELD_G0, 1 << 16)), dim3(64), 0, c->stream, S, W, P, WeldRowRings{});
       // (what the small working set handed on; its count lives on the device: a fixed grid, most of it returns at once)
-      hipLaunchKernelGGL((sz_k_weld_area<WELD_G1, WELD_CAP1, WELD_KC1, WELD_RC1, WELD_RM1, 1>), dim3(grid_for(P, 1, 512)), dim3(64), 0, c->stream, S, W, P);
+      hipLaunchKernelGGL((sz_k_weld_area<WELD_G1, WELD_CAP1, WELD_KC1, WELD_RC1, WELD_RM1, 1>), dim3(grid_for(P, 1, 512)), dim3(64), 0, c->stream, S, W, P, WeldRowRings{});
       hipLaunchKernelGGL(sz_k_weld_table, dim3(1), dim3(WELD_TPB), 0, c->stream, W, P);
       HIPCHK(c, hipMemcpyAsync(&c->weld_h, W.d, sizeof(WeldDev), hipMemcpyDeviceToHost, c->stream));
     }

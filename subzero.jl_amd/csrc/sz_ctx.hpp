@@ -14,6 +14,7 @@
 #include "sz_pipeline.hpp"
 #include "sz_fracture.hpp"
 #include "sz_weld.hpp"
+#include "sz_weld_tile.hpp"
 
 using namespace sz;
 
@@ -156,6 +157,11 @@ struct sz_ctx {
   WeldArgs weld{}; int *weld_cell_cnt = nullptr, *weld_cell_slots = nullptr, *weld_cell_ovf = nullptr, *weld_cell_items = nullptr; double* weld_bounds = nullptr;
   WeldDev weld_h{}; double weld_h_grid[8] = { 0 };          // host sides of the two small uploads of a pass
   int weld_npairs = 0;              // candidate pairs of the last pass (sz_debug_weld_npairs)
+  // ... on a tiled context (tile_weld_pass; sz_weld_tile.hpp): the scratch of the collective pass, kept between passes; the pair capacity a pass
+  // that ran out asked for; the host sides of its small transfers; the whole table in global numbers, as every rank ends a pass with it
+  Pool weldt_allocs; int weldt_need = 0, weldt_npairs = 0; int* weldt_bin = nullptr;
+  WeldTileDev weldt_h{}; WeldDev weldt_hw{}; double weldt_h_grid[8] = { 0 }; std::vector<int> weldt_cnt;
+  std::vector<long long> weldt_i, weldt_j; std::vector<double> weldt_a;
   // removal (sz_set_removal; sz_remove.hpp): SimplificationSettings.max_vertices (INT32_MAX: smoothing off) and FloeSettings' minimum area / height;
   // the running ocean.dissolved lattice (with the fields: zero after sz_set_fields); per parent the row it had at the last sz_upload_floes
   bool rm_on = false; int rm_max_vertices = 0x7fffffff; double rm_min_area = 0, rm_min_height = 0;

@@ -1,5 +1,5 @@
 // sz_tile_host.hpp — the host code of tiled (multi-GPU) contexts: set-up, the steps a host drives itself (sz_halo_* / sz_tile_step), the box
-// gather and the halo exchange, migration, the collective removal and fracture passes, and the batch drivers of sz_tile_run.  Host code of
+// gather and the halo exchange, migration, the collective removal, fracture and welding passes, and the batch drivers of sz_tile_run.  Host code of
 // the one translation unit sz_api.hip, which includes it behind the single context's batch drivers and passes: a tile's steps are theirs.
 #pragma once
 #include "sz_comm.hpp"
@@ -142,7 +142,7 @@ int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int
                  int32_t flags) {
   if (!c || !c->have_floes) return SZ_E_STATE;
   if (c->frac_kind != SZ_FRAC_OFF) { c->err = "sz_tile_step does not evaluate fracture criteria (the host drives its steps: no library channel to gather the mean height over): sz_tile_run, or sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
-  if (!c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
+  if (!c->weld_dts.empty()) { c->err = "sz_tile_step does not compute welding overlaps (the host drives its steps: no library channel to gather the candidates over): sz_tile_run, or sz_set_welding(0)"; return SZ_E_STATE; }
   return tile_step_body(c, d_recv, nranks, cap, tstep, dt, coupling_dt, flags);
 }
 
@@ -908,6 +908,248 @@ int sz_tile_fracture_candidates(sz_ctx* c, int32_t* n_global, int32_t* n_owned, 
   return SZ_OK;
 }
 
+// ---------------------------------------------------------------- the welding overlap table on a tiled context (sz_weld_tile.hpp)
+namespace {
+// The overlap table (weld_pass) over the ONE global floe list whose rows live on the ranks' tiles: collective, over the parents with ghosts
+// detached.  Every rank ends with the single context's whole table in global numbers (c->weldt_i / _j / _a), to the bit.  The collectives, the
+// same on every rank whatever it holds:
+//   1. the gather of the owned counts; a rank that cannot take part (device error bits, ghosts in the list, no grid) sends its error code in
+//      place of its count, and all ranks return it together
+//   2. the all-gather of the candidate records, one per owned row (ListGather)
+//   3. the agreement on: a global number out of range or met twice, a device error, "my pair arrays are too small" -- all ranks then grow what
+//      they must and run the pass again together
+//   4. the gather of {wanted rings, largest wanted ring} per rank, then the all-gather of the ring records, the slot sized by the largest
+//      wanted ring of any rank (not by a rank's own max_ring: ADVICE.md, the halo_ring item)
+//   5. the gather of the table counts (an error code in place of the count, as in 1), then the all-gather of the {key, area} entries
+//   6. the agreement on: a device error, "the table is not empty", and my_tag -- "my stop word stood at the segment's last step", news to
+//      the peers behind the list-based driver (see tile_frac_pass)
+// In front of 2, 4 and 5's all-gather the ranks gather the code of what each prepared alone (scratch memory), so a rank that fails there takes the
+// others with it instead of leaving them in the gather.  A failure of the HIP runtime or of the channel itself is returned at once, as everywhere
+// in the library.  Nothing of the floes changes in a pass: it writes its own scratch (c->weldt_allocs, kept between passes) and the sort's.
+constexpr int WT_BIT_RANGE = 1, WT_BIT_TWICE = 2, WT_BIT_ERR = 4, WT_BIT_GROW = 8, WT_BIT_TABLE = 16, WT_BIT_TAG = 32;
+int tile_weld_pass(sz_ctx* c, int nx, int ny, double max_area, bool my_tag, int* ntable, int* any_tag) {
+  *ntable = 0; *any_tag = 0;
+  State& S = c->S;
+  const int n = c->comm_n, me = c->comm_rank;
+  constexpr const char* who = "tiled welding overlaps";
+  // ---- 1
+  int rc = sync_and_check(c);
+  if (rc == SZ_E_HIP) return rc;
+  if (!rc && c->hostM != c->hostN) rc = SZ_E_STATE;
+  if (!rc && (!c->have_domain || !c->have_fields || !(S.gxf > S.gx0) || !(S.gyf > S.gy0))) { c->err = "tiled welding overlaps: the bins need the domain's boundary kinds and the grid extents (sz_set_domain, sz_set_fields)"; rc = SZ_E_STATE; }
+  const int N = c->hostN;
+  c->weldt_cnt.assign(64, 0);
+  int* const cnt = c->weldt_cnt.data();
+  if (const int r2 = comm_gather_int(c, rc ? rc : N, cnt)) return r2;
+  for (int r = 0; r < n; r++) if (cnt[r] < 0) {
+    if (cnt[r] == SZ_E_STATE && !(rc && r == c->comm_rank && c->hostM == c->hostN)) c->err = "tiled welding overlaps: rank " + std::to_string(r) + " has ghosts in its list (the pass runs over the parents alone) or no grid";
+    else if (!rc) c->err = "tiled welding overlaps: rank " + std::to_string(r) + " reported a device error (this rank is clean; all ranks return together)";
+    return cnt[r];
+  }
+  long long Ng64 = 0;
+  for (int r = 0; r < n; r++) Ng64 += cnt[r];
+  // (the same sums on every rank)
+  if (Ng64 <= 0) { c->err = "tiled welding overlaps: no floes"; return SZ_E_STATE; }
+  if (Ng64 > 0x3fffffff) { c->err = "tiled welding overlaps: more than 2^30 floes"; return SZ_E_CAPACITY; }
+  const int Ng = (int)Ng64;
+  if ((long double)nx * (long double)ny * (long double)Ng * (long double)Ng >= 9.0e18L) { c->err = "tiled welding overlaps: Nx * Ny * N^2 does not fit the 64-bit pair key"; return SZ_E_ARG; }
+  world_rings(c);
+  Pool& P = c->weldt_allocs;
+  for (int round = 0;; round++) {
+    reset_pool(P);
+    // ---- 2: the scratch of this rank (the search cells take the most a field of Ng floes can need), then the candidates of the whole field
+    ListGather LG(c, cnt, WTC_REC, 1);
+    const int slots = LG.slots;
+    const long long nslot = (long long)n * slots;
+    const long long cell_max = std::max(4LL * Ng, 1024LL);
+    const size_t cap = (size_t)std::max((long long)c->weldt_need, 8LL * N + 1024);
+    int first = 0;
+    WeldArgs W{};
+    WeldTileDev* d_dev = nullptr; int *d_mark = nullptr, *d_wslot = nullptr, *d_src = nullptr, *cell_cnt = nullptr, *cell_ovf = nullptr, *cell_slots = nullptr, *cell_items = nullptr;
+    double *d_bounds = nullptr, *d_trec = nullptr;
+    rc = nslot > 0x3fffffff || cap > ((size_t)1 << 30) ? (int)SZ_E_CAPACITY : (int)SZ_OK;
+    (void)(rc || (rc = LG.carve(c, P)) || (rc = dalloc(c, &d_dev, 1, P)) || (rc = dalloc(c, &W.d, 1, P)) || (rc = dalloc(c, &d_mark, (size_t)Ng, P)) || (rc = dalloc(c, &d_src, (size_t)Ng, P)) ||
+           (rc = dalloc(c, &W.bin, (size_t)N + 1, P)) || (rc = dalloc(c, &d_wslot, (size_t)N + 1, P)) || (rc = dalloc(c, &d_bounds, 8, P)) ||
+           (rc = dalloc(c, &cell_cnt, (size_t)cell_max + 1, P)) || (rc = dalloc(c, &cell_ovf, (size_t)cell_max + 1, P)) || (rc = dalloc(c, &cell_slots, (size_t)cell_max * CELL_K, P)) ||
+           (rc = dalloc(c, &cell_items, (size_t)nslot + 1, P)) || (rc = dalloc(c, &W.keys_in, cap, P)) || (rc = dalloc(c, &W.keys, cap, P)) || (rc = dalloc(c, &W.area, cap, P)) ||
+           (rc = dalloc(c, &W.retry, cap, P)) || (rc = dalloc(c, &d_trec, (size_t)WTT_REC * cap, P)));
+    if (const int r2 = comm_agree_rc(c, who, rc, &first)) return r2;
+    if (first) return first;
+    c->weldt_bin = W.bin;
+    W.n = Ng; W.nx = nx; W.ny = ny; W.cap = (int)cap; W.max_area = max_area;
+    c->weldt_h = WeldTileDev{ 0ull, Ng, 0, 0, 0 }; c->weldt_hw = WeldDev{ Ng, 0, 0, 0 };
+    HIPCHK(c, hipMemcpyAsync(d_dev, &c->weldt_h, sizeof(WeldTileDev), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(W.d, &c->weldt_hw, sizeof(WeldDev), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_mark, 0, (size_t)Ng * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(d_src, 0xff, (size_t)Ng * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(LG.d_rec, 0, (size_t)WTC_REC * slots * sizeof(double), c->stream));
+    if ((rc = LG.upload_counts(c, cnt))) return rc;
+    if (N > 0) hipLaunchKernelGGL(sz_k_weldt_pack, dim3(grid_for(N, 256, 2048)), dim3(256), 0, c->stream, S, N, nx, ny, max_area, LG.d_rec);
+    if ((rc = LG.gather(c))) return rc;
+    hipLaunchKernelGGL(sz_k_weldt_scan, dim3(grid_for(nslot, 256, 2048)), dim3(256), 0, c->stream, (const double*)LG.d_all, (const int*)LG.d_cnt, n, slots, Ng, d_mark, d_dev);
+    HIPCHK(c, hipMemcpyAsync(&c->weldt_h, d_dev, sizeof(WeldTileDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int bad = c->weldt_h.bad;
+    // ---- the pair search: cells of at least 2 max(rmax) over the gathered records (setup_grid's rule), indices clamped: no periodic wrap
+    int npairs = 0, nwant = 0, maxring = 0;
+    if (!bad) {
+      double rm; { const long long b = (long long)c->weldt_h.rmax_bits; memcpy(&rm, &b, sizeof(rm)); }
+      if (!(rm > 0.0)) rm = std::max(S.gxf - S.gx0, S.gyf - S.gy0);          // (no rmax anywhere: one cell)
+      const double cmin = 2.0 * rm * (1.0 + 1e-9);
+      long long ncx = std::max(1LL, (long long)std::floor(std::min((S.gxf - S.gx0) / cmin, 1e6)));
+      long long ncy = std::max(1LL, (long long)std::floor(std::min((S.gyf - S.gy0) / cmin, 1e6)));
+      while (ncx * ncy > cell_max) { ncx = std::max(1LL, ncx / 2); ncy = std::max(1LL, ncy / 2); }
+      const int cells = (int)(ncx * ncy);
+      double* g = c->weldt_h_grid;
+      g[0] = S.gx0; g[1] = S.gy0; g[2] = (S.gxf - S.gx0) / (double)ncx; g[3] = (S.gyf - S.gy0) / (double)ncy; g[4] = (double)ncx; g[5] = (double)ncy; g[6] = 0.0; g[7] = 0.0;
+      State T = S; T.step = 0;
+      T.bounds = d_bounds; T.cell_cnt = cell_cnt; T.cell_slots = cell_slots; T.cell_ovf = cell_ovf; T.cell_items = cell_items;
+      HIPCHK(c, hipMemcpyAsync(d_bounds, g, 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemsetAsync(cell_cnt, 0, ((size_t)cells + 1) * sizeof(int), c->stream));
+      HIPCHK(c, hipMemsetAsync(cell_ovf, 0, ((size_t)cells + 1) * sizeof(int), c->stream));
+      hipLaunchKernelGGL(sz_k_weldt_insert, dim3(grid_for(nslot, 256, 2048)), dim3(256), 0, c->stream, T, (const double*)LG.d_all, (const int*)LG.d_cnt, n, slots, (const WeldTileDev*)d_dev);
+      if (N > 0) hipLaunchKernelGGL(sz_k_weldt_pairs, dim3(grid_for(N, 256, 2048)), dim3(256), 0, c->stream, T, W, (const double*)LG.d_all, slots, me, N, d_dev, W.bin, d_wslot, d_src);
+      HIPCHK(c, hipMemcpyAsync(&c->weldt_h, d_dev, sizeof(WeldTileDev), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(&c->weldt_hw, W.d, sizeof(WeldDev), hipMemcpyDeviceToHost, c->stream));
+    }
+    rc = sync_and_check(c);
+    if (rc == SZ_E_HIP) return rc;
+    if (!bad) { npairs = c->weldt_hw.npairs; nwant = c->weldt_h.nwant; maxring = c->weldt_h.maxring; }
+    if (npairs < 0 || nwant < 0 || nwant > N || nwant >= (1 << 22) || maxring < 0) rc = SZ_E_CAPACITY;
+    const bool grow = !rc && npairs > (int)cap;
+    // ---- 3
+    const int mine = (bad & WT_BAD_RANGE ? WT_BIT_RANGE : 0) | (bad & WT_BAD_TWICE ? WT_BIT_TWICE : 0) | (rc ? WT_BIT_ERR : 0) | (grow ? WT_BIT_GROW : 0);
+    int all = 0;
+    if ((rc = comm_agree_bits(c, mine, &all))) return rc;
+    if (all & (WT_BIT_RANGE | WT_BIT_TWICE)) {
+      c->err = std::string("tiled welding overlaps: the global numbers of the ranks (sz_tile_enable) are not 0 .. N_global - 1 once each: ") +
+               (all & WT_BIT_RANGE ? "one is out of range" : "one is held twice") + " (all ranks return together)";
+      return SZ_E_STATE;
+    }
+    if (all & WT_BIT_ERR) { if (!(mine & WT_BIT_ERR)) c->err = "tiled welding overlaps: a rank reported a device error (this rank is clean; all ranks return together)"; return SZ_E_CAPACITY; }
+    c->err.clear();
+    if (all & WT_BIT_GROW) {          // the pair arrays grow like the other lists; nothing is truncated
+      if (round > 0) { c->err = "tiled welding overlaps: the pair arrays did not grow enough"; return SZ_E_CAPACITY; }
+      if (grow) c->weldt_need = npairs + npairs / 4;
+      continue;
+    }
+    // ---- 4: the rings the owners of cross-rank pairs asked for
+    int word[64] = { 0 }, wcnt[64] = { 0 }, ringcap = 4;
+    if ((rc = comm_gather_int(c, nwant << 8 | std::min(maxring, 255), word))) return rc;
+    for (int r = 0; r < n; r++) { wcnt[r] = word[r] >> 8; ringcap = std::max(ringcap, ((word[r] & 255) + 1) & ~1); }
+    const int RW = WTR_HEAD + 2 * ringcap;
+    ListGather LR(c, wcnt, RW, 1);
+    rc = (long long)n * LR.slots > 0x3fffffff ? (int)SZ_E_CAPACITY : LR.carve(c, P);
+    if (const int r2 = comm_agree_rc(c, who, rc, &first)) return r2;
+    if (first) return first;
+    if ((rc = LR.upload_counts(c, wcnt))) return rc;
+    if (nwant > 0) hipLaunchKernelGGL(sz_k_weldt_rings, dim3(grid_for((long long)N * 64, 256, 2048)), dim3(256), 0, c->stream, S, N, (const int*)d_wslot, RW, LR.d_rec);
+    if ((rc = LR.gather(c))) return rc;
+    hipLaunchKernelGGL(sz_k_weldt_src, dim3(grid_for((long long)n * LR.slots, 256, 2048)), dim3(256), 0, c->stream, (const double*)LR.d_all, (const int*)LR.d_cnt, n, LR.slots, RW, me, Ng, d_src);
+    // ---- the clip: the single context's kernels over this rank's pairs, sorted by key
+    c->weldt_hw.ntable = 0;
+    if (npairs > 0) {
+      const int Pn = npairs;
+      const WeldTileRings RS{ d_src, LR.d_all, RW };
+      const unsigned long long top = (unsigned long long)nx * ny * (unsigned long long)Ng * (unsigned long long)Ng;
+      unsigned bits = 1; while (bits < 64 && (top >> bits)) bits++;
+      size_t tmp_bytes = 0;
+      HIPCHK(c, rocprim::radix_sort_keys(nullptr, tmp_bytes, W.keys_in, W.keys, (size_t)Pn, 0u, bits, c->stream));
+      if (tmp_bytes > c->weld_tmp_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->weld_tmp); c->weld_tmp = nullptr; c->weld_tmp_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->weld_tmp, tmp_bytes + tmp_bytes / 2));
+        c->weld_tmp_bytes = tmp_bytes + tmp_bytes / 2;
+      }
+      HIPCHK(c, rocprim::radix_sort_keys(c->weld_tmp, tmp_bytes, W.keys_in, W.keys, (size_t)Pn, 0u, bits, c->stream));
+      hipLaunchKernelGGL((sz_k_weld_area<WELD_G0, WELD_CAP0, WELD_KC0, WELD_RC0, WELD_RM0, 0, WeldTileRings>), dim3(grid_for(Pn, 64 / WELD_G0, 1 << 16)), dim3(64), 0, c->stream, S, W, Pn, RS);
+      hipLaunchKernelGGL((sz_k_weld_area<WELD_G1, WELD_CAP1, WELD_KC1, WELD_RC1, WELD_RM1, 1, WeldTileRings>), dim3(grid_for(Pn, 1, 512)), dim3(64), 0, c->stream, S, W, Pn, RS);
+      hipLaunchKernelGGL(sz_k_weldt_table, dim3(1), dim3(WELD_TPB), 0, c->stream, W, Pn, d_trec);
+      HIPCHK(c, hipMemcpyAsync(&c->weldt_hw, W.d, sizeof(WeldDev), hipMemcpyDeviceToHost, c->stream));
+    }
+    rc = sync_and_check(c);
+    if (rc == SZ_E_HIP) return rc;
+    const int nt = c->weldt_hw.ntable;
+    if (!rc && (nt < 0 || nt > npairs)) rc = SZ_E_CAPACITY;
+    // ---- 5: one table everywhere
+    int tcnt[64] = { 0 };
+    if (const int r2 = comm_gather_int(c, rc ? rc : nt, tcnt)) return r2;
+    for (int r = 0; r < n; r++) if (tcnt[r] < 0) {
+      if (!rc) c->err = "tiled welding overlaps: rank " + std::to_string(r) + " reported a device error (this rank is clean; all ranks return together)";
+      return tcnt[r];
+    }
+    ListGather LT(c, tcnt, WTT_REC, 1);
+    const long long total = LT.total;
+    long long *d_ti = nullptr, *d_tj = nullptr; double* d_ta = nullptr;
+    rc = total > 0x3fffffff || (long long)n * LT.slots > 0x3fffffff ? (int)SZ_E_CAPACITY : (int)SZ_OK;
+    (void)(rc || (rc = LT.carve(c, P)) || (rc = dalloc(c, &d_ti, (size_t)total + 1, P)) || (rc = dalloc(c, &d_tj, (size_t)total + 1, P)) || (rc = dalloc(c, &d_ta, (size_t)total + 1, P)));
+    if (const int r2 = comm_agree_rc(c, who, rc, &first)) return r2;
+    if (first) return first;
+    if ((rc = LT.upload_counts(c, tcnt))) return rc;
+    if (nt > 0) HIPCHK(c, hipMemcpyAsync(LT.d_rec, d_trec, (size_t)WTT_REC * nt * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = LT.gather(c))) return rc;
+    c->weldt_i.assign((size_t)total, 0); c->weldt_j.assign((size_t)total, 0); c->weldt_a.assign((size_t)total, 0.0);
+    if (total > 0) {
+      hipLaunchKernelGGL(sz_k_weldt_merge, dim3(grid_for((long long)n * LT.slots, 256, 2048)), dim3(256), 0, c->stream, (const double*)LT.d_all, (const int*)LT.d_cnt, n, LT.slots, Ng, d_ti, d_tj, d_ta);
+      HIPCHK(c, hipMemcpyAsync(c->weldt_i.data(), d_ti, (size_t)total * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->weldt_j.data(), d_tj, (size_t)total * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->weldt_a.data(), d_ta, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    rc = sync_and_check(c);
+    if (rc == SZ_E_HIP) return rc;
+    // ---- 6
+    const int last = (rc ? WT_BIT_ERR : 0) | (total > 0 ? WT_BIT_TABLE : 0) | (my_tag ? WT_BIT_TAG : 0);
+    if ((rc = comm_agree_bits(c, last, &all))) return rc;
+    if (all & WT_BIT_ERR) { if (!(last & WT_BIT_ERR)) c->err = "tiled welding overlaps: a rank reported a device error (this rank is clean; all ranks return together)"; return SZ_E_CAPACITY; }
+    c->err.clear();
+    trim_pool(P);
+    c->weldt_npairs = npairs;
+    *ntable = (int)total; *any_tag = (all & WT_BIT_TAG) != 0;
+    return SZ_OK;
+  }
+}
+}  // namespace
+int sz_tile_weld_overlaps(sz_ctx* c, int32_t nx, int32_t ny, double max_weld_area, int32_t* n, int32_t cap, int64_t* idx_i, int64_t* idx_j, double* inter_area) {
+  if (n) *n = 0;
+  if (!c || !n) return SZ_E_ARG;
+  if (nx < 1 || ny < 1) { c->err = "sz_tile_weld_overlaps: Nx and Ny must be at least 1"; return SZ_E_ARG; }
+  if (!(max_weld_area > 0.0)) { c->err = "sz_tile_weld_overlaps: max_weld_area must be positive"; return SZ_E_ARG; }
+  if (int rc = tiled_ready(c, "sz_tile_weld_overlaps")) return rc;
+  (void)hipSetDevice(c->device);
+  int nt = 0, tag = 0;
+  if (int rc = tile_weld_pass(c, nx, ny, max_weld_area, false, &nt, &tag)) return rc;
+  *n = nt;
+  if (!idx_i && !idx_j && !inter_area) return SZ_OK;
+  if (cap < nt) { c->err = "sz_tile_weld_overlaps: cap is smaller than the table (*n)"; return SZ_E_ARG; }          // (the same table on every rank: with the same cap, the same answer)
+  for (int k = 0; k < nt; k++) {
+    if (idx_i) idx_i[k] = c->weldt_i[k];
+    if (idx_j) idx_j[k] = c->weldt_j[k];
+    if (inter_area) inter_area[k] = c->weldt_a[k];
+  }
+  return SZ_OK;
+}
+// per owned row the 0-based bin or -1, with the `break` of the global list (collective: it runs a pass)
+int sz_tile_debug_weld_bins(sz_ctx* c, int32_t nx, int32_t ny, int32_t* bin) {
+  if (!c || !bin || nx < 1 || ny < 1) return SZ_E_ARG;
+  if (int rc = tiled_ready(c, "sz_tile_debug_weld_bins")) return rc;
+  (void)hipSetDevice(c->device);
+  int nt = 0, tag = 0;
+  if (int rc = tile_weld_pass(c, nx, ny, INFINITY, false, &nt, &tag)) return rc;
+  if (c->hostN > 0) HIPCHK(c, hipMemcpy(bin, c->weldt_bin, (size_t)c->hostN * sizeof(int), hipMemcpyDeviceToHost));
+  return SZ_OK;
+}
+// the candidate pairs (before the clip) of the last pass, over all ranks (collective)
+int sz_tile_debug_weld_npairs(sz_ctx* c, int64_t* n) {
+  if (!c || !n) return SZ_E_ARG;
+  *n = 0;
+  if (int rc = tiled_ready(c, "sz_tile_debug_weld_npairs")) return rc;
+  (void)hipSetDevice(c->device);
+  int per_rank[64] = { 0 };
+  if (int rc = comm_gather_int(c, c->weldt_npairs, per_rank)) return rc;
+  for (int r = 0; r < c->comm_n; r++) *n += per_rank[r];
+  return SZ_OK;
+}
+
 // ---------------------------------------------------------------- the batch drivers of sz_tile_run
 namespace {
 // status.fuse_idx of a tiled context, in GLOBAL floe numbers: the order keys of the local rows of the step that ended the batch (owned
@@ -1170,13 +1412,14 @@ static int tile_run_inline(sz_ctx* c, int nsteps, int tstep0, int dt, int coupli
 // nsteps x timestep_sim! of a tiled run, collectively on every rank (same arguments everywhere)
 int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
   if (steps_done) *steps_done = 0;
-  if (c && !c->weld_dts.empty()) { c->err = "tiled runs do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
+  if (c && !c->weld_dts.empty() && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled welding overlaps gather the candidates and rings over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
   if (c && c->frac_kind != SZ_FRAC_OFF && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled fracture criteria gather the mean height over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
   if (!c) return SZ_E_STATE;
   if (int rc = tiled_ready(c, "sz_tile_run")) return rc;
   if (nsteps < 0) return SZ_E_ARG;
   const bool frac = c->frac_kind != SZ_FRAC_OFF;
-  if (frac && c->two_way) { c->err = "tiled two-way coupling with a fracture criterion set: its per-step all-reduce path has no tested stop: sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
+  const bool weld = !c->weld_dts.empty();
+  if ((frac || weld) && c->two_way) { c->err = std::string("tiled two-way coupling with ") + (frac ? "a fracture criterion set: its per-step all-reduce path has no tested stop: sz_set_fracture(SZ_FRAC_OFF)" : "welding set: its per-step all-reduce path has no tested stop: sz_set_welding(0)"); return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
   // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
   // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
@@ -1199,23 +1442,43 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   // Removal: a segment that a tag ends before its last step -- the same step on every rank, and never a fracture step: those end segments -- or
   // on it (above) is followed by the collective pass; done = the next segment starts at the following step from the compacted tiles (boxes, halo
   // capacities and peers are gathered again at its first exchange), declined = the batch ends there as without removal, on every rank.
-  // Two-way coupling across tiles has no tag stop of its own to hang a pass on: removal is not engaged there, a criterion refused.
-  // SZ_NO_STOP batches and contexts with neither set take the drivers as they are.
-  if ((!c->rm_on && !frac) || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return segment(nsteps, tstep0, steps_done);
+  // Welding (sz_set_welding): the segments also END on welding steps (weld_set_at: the first k with tstep % dts[k] == 0 gives Nx, Ny).  Behind a segment
+  // whose last step ran the order is the single context's (simulation.jl:172-214, sz_step): the fracture pass on a fracture step, then the collective
+  // overlap table (tile_weld_pass), then removal.  A table that is not empty ends the batch on every rank (steps_done counts the welding step), an empty
+  // one lets the next segment start.  A tag on a welding step ends the batch there, with removal set too, as in sz_step; where the fracture pass has
+  // not agreed it already, the welding pass's last agreement does.
+  // Two-way coupling across tiles has no tag stop of its own to hang a pass on: removal is not engaged there, a criterion or welding refused.
+  // SZ_NO_STOP batches and contexts with none of the three set take the drivers as they are.
+  if ((!c->rm_on && !frac && !weld) || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return segment(nsteps, tstep0, steps_done);
   int done = 0;
   while (done < nsteps) {
-    int len = nsteps - done;
-    if (frac) for (int s = 0; s + 1 < nsteps - done; s++) if ((tstep0 + done + s) % c->frac_dt == 0) { len = s + 1; break; }
+    int len = nsteps - done, set = -1; bool fstep = false;
+    for (int s = 0; s + 1 < nsteps - done; s++) {
+      const int tstep = tstep0 + done + s;
+      fstep = frac && tstep % c->frac_dt == 0;
+      set = weld ? weld_set_at(c, tstep) : -1;
+      if (fstep || set >= 0) { len = s + 1; break; }
+    }
     int32_t more = 0;
     c->tile_stop_raised = 0;
     const int rc = segment(len, tstep0 + done, &more);
     done += more;
     if (steps_done) *steps_done = done;
     if (rc || done >= nsteps || more < 1) return rc;
-    if (more == len) {          // the segment's last step ran, and the batch goes on behind it: it was cut here, on a fracture step
-      int cand = 0, tag = 0, mine = 0;
-      if (int rc2 = tile_frac_pass(c, c->tile_stop_raised == len, false, &cand, &tag, &mine)) return rc2;
-      if (cand) return SZ_OK;
+    if (more == len && (fstep || set >= 0)) {          // the segment's last step ran, and the batch goes on behind it: it was cut here, on a fracture or a welding step
+      int tag = 0;
+      const bool my_tag = c->tile_stop_raised == len;
+      if (fstep) {
+        int cand = 0, mine = 0;
+        if (int rc2 = tile_frac_pass(c, my_tag, false, &cand, &tag, &mine)) return rc2;
+        if (cand) return SZ_OK;
+      }
+      if (set >= 0) {          // a tag ends the batch on a welding step, as in sz_step; the fracture pass has agreed it, else the welding pass does
+        if (fstep && tag) return SZ_OK;
+        int nt = 0;
+        if (int rc2 = tile_weld_pass(c, c->weld_nxs[set], c->weld_nys[set], c->weld_max_area, my_tag, &nt, &tag)) return rc2;
+        if (tag || nt > 0) return SZ_OK;
+      }
       if (!tag) continue;
     }
     if (!c->rm_on) return SZ_OK;

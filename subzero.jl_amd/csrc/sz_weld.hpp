@@ -118,8 +118,24 @@ __global__ void __launch_bounds__(256) sz_k_weld_pairs(State T, WeldArgs W) {
 }
 
 // ---- areas
-template <int G, int CAP, int KC, int RC, int RM, int LARGE>
-__global__ void __launch_bounds__(64) sz_k_weld_area(State S, WeldArgs W, int npairs) {
+// Where the two rings of a pair come from is the ring source's business (RS): the kernel asks it for both rings of a key and stages, clips and sums
+// whatever it is given.  A ring the source cannot produce is reported with more points than any working set holds, so it ends in the capacity error
+// like a ring that is too long.
+struct WeldRing { const double2* p; int n, osign; Box box; };
+// the single context: both floes are rows of the state, the key is in row numbers
+struct WeldRowRings {
+  static __device__ __forceinline__ WeldRing row(const State& S, int i) {
+    const int o = S.voff[i];
+    return { S.vxy + o, S.voff[i + 1] - o, (int)S.osign[i], Box{ S.bbx0[i], S.bbx1[i], S.bby0[i], S.bby1[i] } };
+  }
+  __device__ __forceinline__ void pair(const State& S, const WeldArgs& W, unsigned long long key, WeldRing& a, WeldRing& b) const {
+    const unsigned long long n64 = (unsigned long long)W.n;
+    a = row(S, (int)((key / n64) % n64)); b = row(S, (int)(key % n64));
+  }
+};
+
+template <int G, int CAP, int KC, int RC, int RM, int LARGE, class RS = WeldRowRings>
+__global__ void __launch_bounds__(64) sz_k_weld_area(State S, WeldArgs W, int npairs, RS rings) {
   constexpr int GPB = 64 / G;
   using Mem = GroupMem<CAP, KC, RC, RM>;
   __shared__ Mem mem[GPB];
@@ -129,25 +145,22 @@ __global__ void __launch_bounds__(64) sz_k_weld_area(State S, WeldArgs W, int np
   Stamps st; STAMP_INIT(st);
   int bad = 0;
   const int nitem = LARGE ? W.d->nretry : npairs;
-  const unsigned long long n64 = (unsigned long long)W.n;
   for (int q0 = blockIdx.x * GPB; q0 < nitem; q0 += gridDim.x * GPB) {
     const int q = q0 + gi;
     if (q >= nitem) continue;
     const int t = LARGE ? W.retry[q] : q;
-    const unsigned long long key = W.keys[t];
-    const int j = (int)(key % n64), i = (int)((key / n64) % n64);
-    const int ao = S.voff[i], na = S.voff[i + 1] - ao, bo = S.voff[j], nb = S.voff[j + 1] - bo;
+    WeldRing ra, rb;
+    rings.pair(S, W, W.keys[t], ra, rb);
+    const int na = ra.n, nb = rb.n;
     gsync();
     bool fits = na <= CAP && nb <= CAP;
     double a = 0.0;
     if (fits) {
-      for (int k = gl; k < na; k += G) { const double2 p = S.vxy[ao + k]; m.ax[k] = p.x; m.ay[k] = p.y; }
-      for (int k = gl; k < nb; k += G) { const double2 p = S.vxy[bo + k]; m.bx[k] = p.x; m.by[k] = p.y; }
+      for (int k = gl; k < na; k += G) { const double2 p = ra.p[k]; m.ax[k] = p.x; m.ay[k] = p.y; }
+      for (int k = gl; k < nb; k += G) { const double2 p = rb.p[k]; m.bx[k] = p.x; m.by[k] = p.y; }
       gsync();
-      const Box ba{ S.bbx0[i], S.bbx1[i], S.bby0[i], S.bby1[i] };
-      const Box bb{ S.bbx0[j], S.bbx1[j], S.bby0[j], S.bby1[j] };
       // buffer 0: a contained ring is measured where it lies (one floe inside the other: the smaller floe's area)
-      clip<G>(m, gl, 0.0, 0.0, na, (int)S.osign[i], nb, (int)S.osign[j], 0, ba, bb, st);
+      clip<G>(m, gl, 0.0, 0.0, na, ra.osign, nb, rb.osign, 0, ra.box, rb.box, st);
       gsync();
       const int e = m.err;
       if (e & (ERR_CAP_XING | ERR_CAP_REGION)) {

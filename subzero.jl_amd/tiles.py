@@ -211,6 +211,7 @@ class TiledWorld:
         self.steps_since_box = 0
         self.tw_buf = None                                    # per-cell partial sums of the two-way coupling
         self._frac_dt = 0                                     # Δt of the criterion set through set_fracture (0: none): run() asks at its own cuts
+        self._weld = None                                     # (dts, nxs, nys, max_weld_area) set through set_welding (None: off): run() asks at its own cuts
 
     def _agree(self, ok, what):
         """collective: raise TileSetupError on every rank when `ok` is false on any of them"""
@@ -512,7 +513,7 @@ class TiledWorld:
     # ---- fracture criteria across tiles (sz_tile_fracture_candidates, sz_tile_run with a criterion set: library backends)
     def _library_only(self, what):
         if self.backend not in ("library", "library-host"):
-            raise capi.SzError(f"TiledWorld.{what} needs a library backend (the criterion pass is collective inside libsubzero_hip.so)")
+            raise capi.SzError(f"TiledWorld.{what} needs a library backend (the pass is collective inside libsubzero_hip.so)")
 
     def set_fracture(self, kind, dt=75, pstar=2.25e5, c=20.0, poly=None, alpha=0.0, min_floe_area=1e6):
         """World.set_fracture for this rank's tile (the same arguments on every rank).  run(..., stop_on_tags=True) then ends after the first
@@ -547,6 +548,53 @@ class TiledWorld:
         """(mean height over the global list, Hibler p) of the last evaluation: the single context's, to the bit, on every rank"""
         return self.world.fracture_mean()
 
+    # ---- welding overlaps across tiles (sz_tile_weld_overlaps, sz_tile_run with welding set: library backends)
+    def set_welding(self, dts, nxs, nys, max_weld_area=2e9):
+        """World.set_welding for this rank's tile (the same arguments on every rank).  run(..., stop_on_tags=True) then ends after the first
+        welding step on which two floes of the global list that could weld overlap -- the same step on every rank, the step World.run ends on
+        for the undivided list.  Set it here, not on `self.world`: run() must know the sets to ask at its own cuts."""
+        self._library_only("set_welding")
+        self.world.set_welding(dts, nxs, nys, max_weld_area)
+        d = [int(x) for x in np.ravel(dts)]
+        self._weld = (d, [int(x) for x in np.ravel(nxs)], [int(x) for x in np.ravel(nys)], float(max_weld_area)) if d else None
+
+    def _weld_set_at(self, tstep):
+        """(nx, ny) of the first welding set with tstep % dt == 0, or None"""
+        if self._weld:
+            for dt, nx, ny in zip(*self._weld[:3]):
+                if tstep % dt == 0:
+                    return nx, ny
+        return None
+
+    def weld_overlaps(self, nx, ny, max_weld_area=2e9):
+        """the welding overlap table of the global floe list (collective): (i, j, inter_area) with 0-based GLOBAL numbers i < j (int64), the whole
+        table on every rank -- the rows World.weld_overlaps() returns for the undivided list, in its order, areas to the bit"""
+        self._library_only("weld_overlaps")
+        w = self.world
+        n = C.c_int32(0)
+        w._chk(w.L.sz_tile_weld_overlaps(w.h, int(nx), int(ny), float(max_weld_area), C.byref(n), 0, None, None, None))
+        cap = max(int(n.value), 1)
+        i = np.zeros(cap, np.int64); j = np.zeros(cap, np.int64); a = np.zeros(cap)
+        w._chk(w.L.sz_tile_weld_overlaps(w.h, int(nx), int(ny), float(max_weld_area), C.byref(n), cap, capi.ptr(i, capi._lp), capi.ptr(j, capi._lp), capi.ptr(a)))
+        return i[:n.value].copy(), j[:n.value].copy(), a[:n.value].copy()
+
+    def weld_bins(self, nx, ny):
+        """per owned floe (self.gidx) the 0-based bin of the global list's bin_floe_centroids, or -1 at and behind its first out-of-bounds
+        centroid, on whichever rank that floe lives (collective)"""
+        self._library_only("weld_bins")
+        w = self.world
+        b = np.zeros(max(len(self.gidx), 1), np.int32)
+        w._chk(w.L.sz_tile_debug_weld_bins(w.h, int(nx), int(ny), capi.ptr(b, capi._ip)))
+        return b[:len(self.gidx)].copy()
+
+    def weld_candidate_pairs(self):
+        """pairs the last table pass clipped, over all ranks (collective): World.weld_candidate_pairs() of the undivided list"""
+        self._library_only("weld_candidate_pairs")
+        w = self.world
+        n = C.c_int64(0)
+        w._chk(w.L.sz_tile_debug_weld_npairs(w.h, C.byref(n)))
+        return int(n.value)
+
     def maybe_repartition(self):
         """Ownership is static between calls of repartition(); floes drift.  Collective: re-tile when more than
         `repartition_fraction` of all floes has left the tile that owns it (cheap test: the owned centroids against the
@@ -571,7 +619,8 @@ class TiledWorld:
         ends after the first fracture step (tstep % dt == 0) on which a floe of any rank would fracture, however the batch is cut: with more
         than one rank a batch is cut into calls of `repartition_every` steps (500), the last step of a call is a batch's own last step,
         which sz_tile_run does not look at -- so when that step is a fracture step, run asks for the global candidate count itself and ends
-        there if it is positive: run(n) returns what World.run(n) returns.  A limit that stays: a floe TAGGED on exactly the last step of a
+        there if it is positive: run(n) returns what World.run(n) returns.  With set_welding() it likewise ends after the first welding step
+        whose overlap table of the global list is not empty, and asks for the table itself where a call's last step is a welding step.  A limit that stays: a floe TAGGED on exactly the last step of a
         call is removed behind the first step of the next call, one step later than World.run(n) would; a caller that needs the single
         context's timing there keeps nsteps within one call or calls remove_floes() itself."""
         done = 0
@@ -591,6 +640,13 @@ class TiledWorld:
                 if stop_on_tags and fdt > 0 and done + k < nsteps and (tstep0 + done + k - 1) % fdt == 0 and self._fracture_pass(False)[0] > 0:
                     self._since_check += k
                     return done + k
+                wset = self._weld_set_at(tstep0 + done + k - 1) if stop_on_tags and done + k < nsteps else None
+                if wset is not None:          # (behind the fracture pass, as in timestep_sim!)
+                    nt = C.c_int32(0)
+                    w._chk(w.L.sz_tile_weld_overlaps(w.h, wset[0], wset[1], self._weld[3], C.byref(nt), 0, None, None, None))
+                    if nt.value > 0:
+                        self._since_check += k
+                        return done + k
             else:
                 for s in range(k):
                     self.step(tstep0 + done + s, dt, coupling_dt, collisions_on, coupling_on)
