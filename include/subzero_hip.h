@@ -323,6 +323,47 @@ int sz_upload_dissolved(sz_ctx *ctx, const double *dissolved);
 int sz_download_dissolved(sz_ctx *ctx, double *dissolved);
 int sz_download_origin(sz_ctx *ctx, int32_t *origin);
 
+/* ---- ridge / raft candidates on the device (csrc/sz_ridgeraft.hpp): what tells whether timestep_ridging_rafting!
+   (src/physical_processes/ridge_raft.jl:676-837) has anything to do.  The reference calls it on the list WITH its ghosts, between
+   timestep_collisions! and the ghost removal, on every step with tstep % Δt == 0 (simulation.jl:121-136); the ridging and rafting themselves are
+   serial, topology-changing host work that consumes sim.rng.  The device evaluates
+     the per-floe draws: every list row draws once if height <= max_floe_ridge_height, then once if height <= max_floe_raft_height (:694-697);
+       *n_draws is their count over all rows, ghosts included;
+     the CANDIDATE TABLE: the gates of :698-753 and :757-831 with every draw assumed to pass.  (i, j) is an entry when row i is active and has
+       interaction rows, one of them names j and passes valid_interaction as written there (j > 0: i < j, j active, potential_interaction;
+       -1..-4: the boundary distance against rmax; below -4: the topography test), 1e-6 < overlap / min_area < 0.95 (both strict; min_area =
+       min(area_i, area_j) for a floe partner, area_i otherwise), and the heights allow an action that changes state or draws: kind bit 1
+       (ridge) for a floe partner = both heights <= max_floe_ridge_height and one of them >= min_ridge_height, for a domain partner = h_i <=
+       min(max_floe_ridge_height, max_domain_ridge_height); bit 2 (raft) = both <= max_floe_raft_height, resp. h_i <= min(max_floe_raft_height,
+       max_domain_raft_height).  One entry per (i, j), from the first passing row.
+   The table is a superset of what the reference acts on: the probabilities are left out, and so is its never-cleared interactions_list buffer,
+   which can only suppress entries.  An EMPTY table means the call changes no floe and draws exactly *n_draws numbers rand(rng, FT).
+   sz_set_ridgeraft: RidgeRaftSettings (process_settings.jl).  Off by default: nothing changes, not even a launch.  dt <= 0 with on: SZ_E_ARG.
+   sz_ridgeraft_candidates: the table of the state as it is, which must be the list with its ghosts and this step's rows (after sz_add_ghosts +
+   sz_timestep_collisions, or sz_upload_interactions on such a list) or a pending stop -- SZ_E_STATE otherwise.  *n entries in ascending i, then
+   row order: idx_i (0-based list row), idx_j (the partner as the rows name it: 1-based list row, -1..-4, -(4 + k)), kind, frac = overlap /
+   min_area; the arrays have room for cap entries, or are all NULL to ask for the counts only.  Two calls on one state give the same bits.
+   sz_step with ridge / raft set, in batches that stop (SZ_COLLISIONS_ON required): the batch is cut into segments that end BEFORE a ridge /
+   raft step; that step runs through the process calls (sz_add_ghosts, sz_timestep_collisions), then the pass, one host synchronisation.
+     Empty table: the draws are added to the batch's counter (sz_ridgeraft_draws: the sum over the ridge / raft steps the LAST sz_step ran
+       through; the host advances its rng by that many rand(rng, FT)), the step is finished as sz_step_finish finishes it, and it ends as a
+       segment's last step does -- a tag, a fracture candidate, a welding table, removal, in the reference's order.
+     Non-empty table: the batch ends, *steps_done does NOT count the step, the context is PENDING at that timestep (sz_ridgeraft_pending: the
+       timestep, or -1) and holds the reference's state between timestep_collisions! and timestep_ridging_rafting!: ghosts in the list; rows, fuse
+       lists and ghost lists downloadable; sz_ridgeraft_candidates gives the same table, bit for bit.  While pending, sz_step returns SZ_E_STATE.
+   sz_step_finish: the second half of the pending step on whatever state the device holds now (the host may have uploaded the floes its
+   timestep_ridging_rafting! left, with their interactions): exactly sz_remove_ghosts; sz_timestep_coupling when flags and tstep % coupling_dt
+   say so; sz_timestep_floe_properties -- and the pending mark is cleared.  SZ_E_STATE when nothing is pending; the batch goes on with
+   sz_step(.., tstep + 1, ..) after the host's end-of-step processes.
+   SZ_NO_STOP batches run through and evaluate nothing.  Tiled contexts (sz_tile_run, sz_tile_step, sz_step) with ridge / raft set: SZ_E_STATE. */
+int sz_set_ridgeraft(sz_ctx *ctx, int32_t on, int32_t dt, double min_ridge_height, double max_floe_ridge_height,
+                     double max_domain_ridge_height, double max_floe_raft_height, double max_domain_raft_height);
+int sz_ridgeraft_candidates(sz_ctx *ctx, int32_t *n, int32_t cap, int32_t *idx_i, int32_t *idx_j, int32_t *kind, double *frac,
+                            int64_t *n_draws);
+int sz_ridgeraft_pending(sz_ctx *ctx, int32_t *tstep);
+int sz_ridgeraft_draws(sz_ctx *ctx, int64_t *n);
+int sz_step_finish(sz_ctx *ctx, int32_t tstep, int32_t dt, int32_t coupling_dt, int32_t flags);
+
 /* ---- measurement: HIP-event time per kernel class, accumulated since the last reset, on the
    stream the kernels are launched on; launches = number of timed launches of that class.
    on = 0: off; 1: every class; otherwise a mask, bit (k+1) = class k (e.g. 2 << SZ_K_NARROW: only

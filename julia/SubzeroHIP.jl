@@ -705,12 +705,114 @@ function pull_dissolved!(eng::HIPEngine, ocean)
     return
 end
 
+# ------------------------------------------------------------------------------------------------ ridging and rafting
+"""
+    set_ridgeraft!(eng, sim)
+
+The simulation's `RidgeRaftSettings` on the device (`sz_set_ridgeraft`): `Δt` and the five heights the gates of `timestep_ridging_rafting!`
+(ridge_raft.jl:676-837) read.  A batch of `sz_step` then stops in the middle of a ridge / raft step (`mod(tstep, Δt) == 0`) whose candidate
+table is not empty -- ghosts in the list, between `timestep_collisions!` and `timestep_ridging_rafting!` -- and runs through the others.
+"""
+function set_ridgeraft!(eng::HIPEngine, sim)
+    rs = sim.ridgeraft_settings
+    check(eng, @ccall lib.sz_set_ridgeraft(eng.ctx::Ptr{Cvoid}, Int32(rs.ridge_raft_on)::Int32, Int32(rs.Δt)::Int32,
+                                           Float64(rs.min_ridge_height)::Float64, Float64(rs.max_floe_ridge_height)::Float64,
+                                           Float64(rs.max_domain_ridge_height)::Float64, Float64(rs.max_floe_raft_height)::Float64,
+                                           Float64(rs.max_domain_raft_height)::Float64)::Cint)
+    return
+end
+
+# the timestep whose ridge / raft step is pending (sz_step stopped in its middle), or -1
+function ridgeraft_pending(eng::HIPEngine)
+    t = Ref{Int32}(-1)
+    check(eng, @ccall lib.sz_ridgeraft_pending(eng.ctx::Ptr{Cvoid}, t::Ptr{Int32})::Cint)
+    return Int(t[])
+end
+
+# per-floe draws of the ridge / raft steps the last sz_step ran through with an empty table
+function ridgeraft_draws(eng::HIPEngine)
+    n = Ref{Int64}(0)
+    check(eng, @ccall lib.sz_ridgeraft_draws(eng.ctx::Ptr{Cvoid}, n::Ptr{Int64})::Cint)
+    return Int(n[])
+end
+
+"""
+    ridgeraft_candidates(eng) -> (i, j, kind, frac, n_draws)
+
+The candidate table of the list as the device holds it (`sz_ridgeraft_candidates`; at a pending stop, or after `sz_add_ghosts` +
+`sz_timestep_collisions`): `i` 1-based list rows, `j` the partner as `floe.interactions` names it, `kind` bit 1 ridge / bit 2 raft,
+`frac = overlap / min_area`.
+"""
+function ridgeraft_candidates(eng::HIPEngine)
+    n, nd = Ref{Int32}(0), Ref{Int64}(0)
+    check(eng, @ccall lib.sz_ridgeraft_candidates(eng.ctx::Ptr{Cvoid}, n::Ptr{Int32}, Int32(0)::Int32, C_NULL::Ptr{Int32}, C_NULL::Ptr{Int32},
+                                                  C_NULL::Ptr{Int32}, C_NULL::Ptr{Float64}, nd::Ptr{Int64})::Cint)
+    cap = max(Int(n[]), 1)
+    i = Vector{Int32}(undef, cap); j = Vector{Int32}(undef, cap); k = Vector{Int32}(undef, cap); f = Vector{Float64}(undef, cap)
+    check(eng, @ccall lib.sz_ridgeraft_candidates(eng.ctx::Ptr{Cvoid}, n::Ptr{Int32}, Int32(cap)::Int32, i::Ptr{Int32}, j::Ptr{Int32},
+                                                  k::Ptr{Int32}, f::Ptr{Float64}, nd::Ptr{Int64})::Cint)
+    m = Int(n[])
+    return (i = Int.(i[1:m]) .+ 1, j = Int.(j[1:m]), kind = Int.(k[1:m]), frac = f[1:m], n_draws = Int(nd[]))
+end
+
+# At a pending stop the device list holds the ghosts: the host rows follow the parents (pull_state!'s removal bookkeeping), then one row per
+# device ghost is appended -- a copy of its parent, overwritten by the download -- with the ghost lists, ids and ghost ids of the device.
+function pull_state_with_ghosts!(eng::HIPEngine, floes, P::Packed, ocean = nothing)
+    st = stats(eng)
+    M, N = Int(st.M), Int(st.N)
+    o = origin(eng)
+    if length(o) != length(floes) && length(eng.host_rows) == length(floes)
+        named = Set(o)
+        for i in reverse(eachindex(eng.host_rows))
+            eng.host_rows[i] in named && continue
+            StructArrays.foreachfield(f -> deleteat!(f, i), floes)
+            deleteat!(eng.host_rows, i)
+        end
+    end
+    length(floes) == N || error("pull_state_with_ghosts!: the host holds $(length(floes)) parents, the device $N")
+    goff = Vector{Int32}(undef, M + 1); gidx = Vector{Int32}(undef, max(3M, 1))
+    only = SzFloeColumns()
+    only.ghost_off = pointer(goff); only.ghost_idx = pointer(gidx)
+    GC.@preserve goff gidx begin
+        check(eng, @ccall lib.sz_download_floes(eng.ctx::Ptr{Cvoid}, only::Ref{SzFloeColumns})::Cint)
+    end
+    parent_of = zeros(Int, M)
+    for i in 1:N, g in gidx[goff[i]+1:goff[i+1]]
+        parent_of[g+1] = i
+    end
+    for g in N+1:M
+        parent_of[g] > 0 || error("pull_state_with_ghosts!: ghost row $g has no parent")
+        push!(floes, Subzero.deepcopy_floe(LazyRow(floes, parent_of[g])))
+    end
+    for i in 1:M
+        floes.ghosts[i] = i <= N ? Int.(gidx[goff[i]+1:goff[i+1]]) .+ 1 : Int[]
+    end
+    isnothing(ocean) || pull_dissolved!(eng, ocean)
+    P = pack(floes, N)
+    download!(eng, floes, P)
+    unpack_geometry!(floes, P); unpack_status!(floes, P)
+    floes.id .= P.id; floes.ghost_id .= P.ghost_id
+    off = Vector{Int32}(undef, M + 1); rows = Matrix{Float64}(undef, 7, max(Int(st.n_inter_rows), 1))
+    check(eng, @ccall lib.sz_download_interactions(eng.ctx::Ptr{Cvoid}, off::Ptr{Int32}, rows::Ptr{Float64})::Cint)
+    foff = Vector{Int32}(undef, M + 1)
+    check(eng, @ccall lib.sz_download_fuse(eng.ctx::Ptr{Cvoid}, foff::Ptr{Int32}, C_NULL::Ptr{Int32})::Cint)
+    fidx = Vector{Int32}(undef, max(Int(foff[end]), 1))
+    check(eng, @ccall lib.sz_download_fuse(eng.ctx::Ptr{Cvoid}, foff::Ptr{Int32}, fidx::Ptr{Int32})::Cint)
+    for i in 1:M
+        r = off[i]+1:off[i+1]
+        floes.interactions[i] = permutedims(rows[:, r]); floes.num_inters[i] = length(r)
+        floes.collision_force[i][1, 1] = P.coll_fx[i]; floes.collision_force[i][1, 2] = P.coll_fy[i]
+        empty!(floes.status[i].fuse_idx); append!(floes.status[i].fuse_idx, Int.(fidx[foff[i]+1:foff[i+1]]) .+ 1)
+    end
+    return N
+end
+
 # ------------------------------------------------------------------------------------------------ resident mode
 """
     run_resident!(sim, eng; start_tstep = 0, batch = 500)
 
-`run!(sim)` for simulations in which only the hot path, fracture and welding touch the floes between output steps (ridging /
-rafting off: the default).  Whole batches of `timestep_sim!` run on the device with the state resident in
+`run!(sim)` for simulations in which only the hot path, ridging / rafting, fracture and welding touch the floes between output steps.
+Whole batches of `timestep_sim!` run on the device with the state resident in
 HBM (`sz_step`); a batch never crosses an output step of a writer, and it ends after the first step that leaves a floe
 tagged `remove` / `fuse`, so `simplify_floes!` (simulation.jl:205-214) runs exactly where the reference runs it.
 `sz_simplify_check` covers its other two triggers (rings over `max_vertices`, floes under the minimum area / height).
@@ -728,13 +830,24 @@ state is then pulled and `timestep_welding!(floes, max_floe_id, table, ...)` of 
 the reference.  With an empty table the reference's call changes nothing and draws no random number; it is skipped.  The reference hands
 `timestep_welding!` no `rng` (a fresh `Xoshiro()` per call), and so does this loop.
 
+Ridging and rafting (`RidgeRaftSettings.ridge_raft_on`): on a ridge / raft step (`mod(tstep, Δt) == 0`, simulation.jl:121-136) the device runs
+the step's first half (`add_ghosts!`, `timestep_collisions!`) and evaluates the candidate table: the gates of `timestep_ridging_rafting!` with
+every random draw assumed to pass.  With an empty table the reference's call changes no floe and draws exactly the per-floe numbers
+(ridge_raft.jl:694-697); the batch runs on and, after every `sz_step`, `sim.rng` is advanced by `sz_ridgeraft_draws` calls of `rand(sim.rng,
+FT)` before any host process of that batch end uses it.  With candidates the batch stops in the middle of the step: the state is pulled
+WITH its ghosts, `Subzero.timestep_ridging_rafting!` runs unchanged with `sim.rng` and a fresh pieces buffer, the ghosts are removed and the
+pieces appended as simulation.jl:137-147 does, the floes and their interactions are uploaded, `sz_step_finish` runs the rest of the step,
+and the step ends like any other (fracture, weld, simplify).
+
 Removal (`set_removal!`): where `simplify_floes!` reduces to `remove_floes!` -- nothing to fuse, no ring to smooth -- the device deletes the
 rows and adds the dissolved mass to its copy of `ocean.dissolved`, inside a batch (which then runs on) or, behind a batch's last step, through
 `remove_floes!(eng)`.  The host's rows follow at the next `pull_state!`, which deletes the rows `origin(eng)` no longer names.
 """
 function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Integer = 500)
-    sim.ridgeraft_settings.ridge_raft_on &&
-        error("run_resident!: ridging / rafting needs the floes on the host every step: use run!(sim)")
+    # (the candidates are read from the step's own interaction rows: sz_step refuses ridge / raft without SZ_COLLISIONS_ON)
+    sim.ridgeraft_settings.ridge_raft_on && !sim.collision_settings.collisions_on &&
+        error("run_resident!: ridging / rafting with collisions off works on rows no step refreshes: use run!(sim)")
+    set_ridgeraft!(eng, sim)
     set_fracture!(eng, sim)
     set_welding!(eng, sim)
     set_removal!(eng, sim)
@@ -763,14 +876,36 @@ function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Int
         check(eng, @ccall lib.sz_step(eng.ctx::Ptr{Cvoid}, n::Int32, tstep::Int32, sim.Δt::Int32,
                                       sim.coupling_settings.Δt::Int32, flags::Int32, done::Ptr{Int32})::Cint)
         tstep += done[]; dirty = true
+        # ridge / raft steps the batch ran through with an empty table: their per-floe draws, before anything below uses sim.rng
+        if sim.ridgeraft_settings.ridge_raft_on
+            for _ in 1:ridgeraft_draws(eng)
+                rand(sim.rng, Float64)
+            end
+        end
+        # the batch stopped in the middle of a ridge / raft step with candidates: the reference's own function on the pulled list, then the
+        # rest of the step on the device
+        stepped = done[] > 0
+        if sim.ridgeraft_settings.ridge_raft_on && ridgeraft_pending(eng) >= 0
+            pend = ridgeraft_pending(eng)
+            pull_state_with_ghosts!(eng, floes, P, ocean)
+            pieces = StructArray{Floe{Float64}}(undef, 0)
+            max_floe_id = Subzero.timestep_ridging_rafting!(floes, pieces, sim.model.domain, max_floe_id, sim.ridgeraft_settings,
+                                                            sim.floe_settings, sim.simp_settings, sim.Δt, sim.rng)
+            remove_ghosts!(floes)
+            append!(floes, pieces)
+            P = upload!(eng, floes, length(floes)); upload_interactions!(eng, floes)
+            check(eng, @ccall lib.sz_step_finish(eng.ctx::Ptr{Cvoid}, Int32(pend)::Int32, sim.Δt::Int32, sim.coupling_settings.Δt::Int32,
+                                                 flags::Int32)::Cint)
+            tstep = pend + 1; stepped = true
+        end
         # the batch's last step was a fracture step on which a floe fractures: fracture_floes! on the host, before simplify_floes!
-        fracture_now = fractures && done[] > 0 && mod(tstep - 1, sim.fracture_settings.Δt) == 0 && fracture_candidates(eng) > 0
+        fracture_now = fractures && stepped && mod(tstep - 1, sim.fracture_settings.Δt) == 0 && fracture_candidates(eng) > 0
         if fracture_now
             P = pull_state!(eng, floes, P, ocean)
             max_floe_id = Subzero.fracture_floes!(floes, max_floe_id, sim.rng, sim.fracture_settings, sim.floe_settings, sim.Δt)
         end
         # ... and a welding step: the table of the floes as they are now (behind fracture_floes!, as in timestep_sim!), welded on the host
-        weld_idx = sim.weld_settings.weld_on && done[] > 0 ? findfirst(x -> mod(tstep - 1, x) == 0, ws.Δts) : nothing
+        weld_idx = sim.weld_settings.weld_on && stepped ? findfirst(x -> mod(tstep - 1, x) == 0, ws.Δts) : nothing
         weld_now = false
         if !isnothing(weld_idx)
             if fracture_now          # the device still holds the floes from before fracture_floes!

@@ -88,6 +88,7 @@ EXPORTS = [
     "sz_set_removal", "sz_remove_floes", "sz_upload_dissolved", "sz_download_dissolved", "sz_download_origin", "sz_tile_remove_floes",
     "sz_tile_fracture_candidates",
     "sz_tile_weld_overlaps", "sz_tile_debug_weld_bins", "sz_tile_debug_weld_npairs",
+    "sz_set_ridgeraft", "sz_ridgeraft_candidates", "sz_ridgeraft_pending", "sz_ridgeraft_draws", "sz_step_finish",
 ]
 
 EUL_PARTIAL = 17      # SZ_EUL_PARTIAL: per-cell partial fields of sz_eulerian_partial
@@ -210,6 +211,11 @@ def load(build_if_missing=True):
     L.sz_tile_weld_overlaps.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, _ip, C.c_int32, _lp, _lp, _dp]
     L.sz_tile_debug_weld_bins.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip]
     L.sz_tile_debug_weld_npairs.argtypes = [C.c_void_p, _lp]
+    L.sz_set_ridgeraft.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]
+    L.sz_ridgeraft_candidates.argtypes = [C.c_void_p, _ip, C.c_int32, _ip, _ip, _ip, _dp, _lp]
+    L.sz_ridgeraft_pending.argtypes = [C.c_void_p, _ip]
+    L.sz_ridgeraft_draws.argtypes = [C.c_void_p, _lp]
+    L.sz_step_finish.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     for n in EXPORTS:
         if n not in ("sz_create", "sz_destroy", "sz_last_error", "sz_version"):
             getattr(L, n).restype = C.c_int

@@ -21,6 +21,7 @@
 #include "sz_migrate.hpp"
 #include "sz_fracture.hpp"
 #include "sz_weld.hpp"
+#include "sz_ridgeraft.hpp"
 #include "sz_remove_tile.hpp"
 #include "sz_fracture_tile.hpp"
 #include "sz_weld_tile.hpp"
@@ -744,7 +745,7 @@ void sz_destroy(sz_ctx* c) {
   for (auto& e : c->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   (void)hipFree(c->d_stats); (void)hipFree(c->S.acc);
   (void)hipFree(c->frac_d); (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx);
-  free_pool(c->weld_allocs); free_pool(c->weldt_allocs); (void)hipFree(c->weld_tmp);
+  free_pool(c->weld_allocs); free_pool(c->weldt_allocs); (void)hipFree(c->weld_tmp); free_pool(c->rr_allocs);
   free_pool(c->rm_allocs);
   free_pool(c->frac_allocs);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -891,6 +892,7 @@ int field_placed(sz_ctx* c, int N, int G, int V, int pts_N, int gl_est, double r
   State& S = c->S;
   int h[C_COUNT + 64 + 72] = { 0 };
   h[C_M] = N + G; h[C_N] = N; h[C_NV] = V; h[C_NGHOSTS] = G; h[C_NOWN] = N;
+  c->ghosts_staged = G > 0; c->rr_rows = false;          // (ghosts the host staged itself; the rows are not known to be this list's)
   H2D(S.cnt, h, C_COUNT + 64 + 72, int);
   HIPCHK(c, hipMemsetAsync(S.over_stamp, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
   HIPCHK(c, hipMemsetAsync(S.n_out, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));
@@ -1363,6 +1365,7 @@ int sz_add_ghosts(sz_ctx* c) {
     c->fuse_lists.resize(c->hostM);
     for (int g = oldM; g < c->hostM; g++) c->fuse_lists[g] = c->fuse_lists[parent[g]];
   }
+  c->ghosts_staged = true; c->rr_rows = false;
   return SZ_OK;
 }
 
@@ -1374,6 +1377,7 @@ int sz_remove_ghosts(sz_ctx* c) {
   int rc = sync_and_check(c);
   if (rc) return rc;
   c->fuse_lists.resize(c->hostM);
+  c->ghosts_staged = false; c->rr_rows = false;
   return SZ_OK;
 }
 
@@ -1394,6 +1398,7 @@ int sz_timestep_collisions(sz_ctx* c, int64_t n_init, int32_t dt) {
     if (rc) return rc;
     break;
   }
+  c->rr_rows = true;
   return host_fuse_fixup(c, h, true);
 }
 
@@ -1525,7 +1530,7 @@ int sz_upload_interactions(sz_ctx* c, const int32_t* off, const double* rows) {
   if (off[M] == 0) {           // no floe has interactions (fresh floes): the counts are all there is to say
     HIPCHK(c, hipMemsetAsync(S.inter_cnt, 0, (size_t)M * sizeof(int), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->inter_any = true; c->inter_lost = false;
+    c->inter_any = true; c->inter_lost = false; c->rr_rows = true;
     return SZ_OK;
   }
   if (!rows) return SZ_E_ARG;
@@ -1540,7 +1545,7 @@ int sz_upload_interactions(sz_ctx* c, const int32_t* off, const double* rows) {
   H2D(S.inter_cnt, cnt.data(), M, int);
   H2D(S.inter_rows, buf.data(), (size_t)M * ROWCAP * 7, double);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->inter_any = true; c->inter_lost = false;
+  c->inter_any = true; c->inter_lost = false; c->rr_rows = true;
   return SZ_OK;
 }
 // calc_stress! (update_floe.jl:392-414) and calc_strain! (:425-453) on their own, for every floe
@@ -2148,6 +2153,7 @@ static int step_segment(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, i
     int rc = ensure_two_way(c); if (rc) return rc;
   }
   if (!(flags & SZ_COLLISIONS_ON)) { if (int rc = need_interactions(c)) return rc; }
+  c->ghosts_staged = false; c->rr_rows = false;          // (a batch detaches the ghosts it finds and leaves its own last step's rows)
   const BatchPlan plan = plan_batch(c, nsteps, flags);
   BatchModes modes(c);
   int h[C_COUNT], gl0 = 0, done = 0, slot = 0; bool rest = false;
@@ -2469,7 +2475,132 @@ int sz_download_origin(sz_ctx* c, int32_t* origin) {
   return SZ_OK;
 }
 
-// sz_step with welding set (sz_set_welding) or removal set (sz_set_removal), in batches that stop.
+// ---------------------------------------------------------------- ridge / raft candidates (sz_ridgeraft.hpp)
+int sz_set_ridgeraft(sz_ctx* c, int32_t on, int32_t dt, double min_ridge_height, double max_floe_ridge_height, double max_domain_ridge_height,
+                     double max_floe_raft_height, double max_domain_raft_height) {
+  if (!c) return SZ_E_ARG;
+  if (!on) { c->rr_on = false; return SZ_OK; }
+  if (dt <= 0) { c->err = "sz_set_ridgeraft: dt (RidgeRaftSettings.Δt) must be positive"; return SZ_E_ARG; }
+  const double h[5] = { min_ridge_height, max_floe_ridge_height, max_domain_ridge_height, max_floe_raft_height, max_domain_raft_height };
+  for (double v : h) if (v != v) { c->err = "sz_set_ridgeraft: a height is NaN"; return SZ_E_ARG; }
+  c->rr_on = true; c->rr_dt = dt;
+  for (int k = 0; k < 5; k++) c->rr_h[k] = h[k];
+  return SZ_OK;
+}
+
+namespace {
+int rr_ensure(sz_ctx* c, int M, int need) {
+  if (c->rr.d && M <= c->rr_capM && need <= c->rr_cap) return SZ_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  free_pool(c->rr_allocs);
+  c->rr = RrArgs{}; c->rr_capM = c->rr_cap = 0;
+  const size_t capM = (size_t)std::max(M, c->S.capM), cap = (size_t)std::max(need, RR_CAP0);
+  Pool& P = c->rr_allocs; RrArgs& A = c->rr; int rc;
+  if ((rc = dalloc(c, &A.d, 1, P)) || (rc = dalloc(c, &A.cnt, capM + 1, P)) || (rc = dalloc(c, &A.off, capM + 1, P)) ||
+      (rc = dalloc(c, &A.ti, cap, P)) || (rc = dalloc(c, &A.tj, cap, P)) || (rc = dalloc(c, &A.tk, cap, P)) || (rc = dalloc(c, &A.tf, cap, P))) return rc;
+  c->rr_capM = (int)capM; c->rr_cap = (int)cap;
+  return SZ_OK;
+}
+// what the pass may be asked on: the list as add_ghosts! leaves it, with the rows of a collision call (or hand-made ones) on that list
+int rr_state_checks(sz_ctx* c, const char* who) {
+  if (!c->have_floes) { c->err = std::string(who) + ": no floes uploaded"; return SZ_E_STATE; }
+  if (c->S.tiled) { c->err = std::string(who) + ": the ghosts of a tiled list are halo rows: tiled contexts have no ridge / raft candidate pass"; return SZ_E_STATE; }
+  if (!c->ghosts_staged || !c->rr_rows || !c->inter_any || c->inter_lost || c->gi_valid) {
+    c->err = std::string(who) + ": needs the list with its ghosts and this step's interaction rows (sz_add_ghosts + sz_timestep_collisions, or a pending ridge / raft stop)";
+    return SZ_E_STATE;
+  }
+  return SZ_OK;
+}
+// The candidate table of the list as it lies (hostM rows, current): *nt entries in c->rr.ti / tj / tk / tf, *draws per-floe draws.  One host
+// synchronisation (two when the table outgrew its arrays); reads the floes' columns and rows only.
+int rr_pass(sz_ctx* c, const double* h5, int* nt, long long* draws) {
+  *nt = 0; *draws = 0;
+  const int M = c->hostM;
+  if (M <= 0) return SZ_OK;
+  int need = c->rr_cap;
+  for (int round = 0;; round++) {
+    if (int rc = rr_ensure(c, M, need)) return rc;
+    RrArgs A = c->rr;
+    A.m = M; A.cap = c->rr_cap;
+    A.min_ridge_h = h5[0]; A.max_floe_ridge_h = h5[1]; A.max_domain_ridge_h = h5[2]; A.max_floe_raft_h = h5[3]; A.max_domain_raft_h = h5[4];
+    HIPCHK(c, hipMemsetAsync(A.d, 0, sizeof(RrDev), c->stream));
+    const int nb = grid_for(M, 256, 2048);
+    hipLaunchKernelGGL(sz_k_rr_count, dim3(nb), dim3(256), 0, c->stream, c->S, A);
+    hipLaunchKernelGGL(sz_k_rr_scan, dim3(1), dim3(RR_TPB), 0, c->stream, A);
+    hipLaunchKernelGGL(sz_k_rr_write, dim3(nb), dim3(256), 0, c->stream, c->S, A);
+    HIPCHK(c, hipMemcpyAsync(&c->rr_hd, A.d, sizeof(RrDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int T = c->rr_hd.total;
+    if (T < 0 || (long long)T > (long long)M * c->S.rowcap) { c->err = "ridge / raft candidates: bad table count"; return SZ_E_HIP; }
+    if (T > c->rr_cap) {          // more than the arrays hold: larger arrays, the pass again -- nothing is truncated
+      if (round > 0) { c->err = "ridge / raft candidates: the table did not grow enough"; return SZ_E_CAPACITY; }
+      need = std::max(T, 2 * c->rr_cap);
+      continue;
+    }
+    *nt = T; *draws = (long long)c->rr_hd.draws;
+    return SZ_OK;
+  }
+}
+// the second half of a timestep whose first half (add_ghosts!, timestep_collisions!) has run: sz_remove_ghosts; sz_timestep_coupling when due;
+// sz_timestep_floe_properties
+int rr_second_half(sz_ctx* c, int tstep, int dt, int coupling_dt, int flags) {
+  if (int rc = sz_remove_ghosts(c)) return rc;
+  if (coupling_at(flags, coupling_dt, tstep)) { if (int rc = sz_timestep_coupling(c)) return rc; }
+  return sz_timestep_floe_properties(c, dt);
+}
+}  // namespace
+
+int sz_ridgeraft_candidates(sz_ctx* c, int32_t* n, int32_t cap, int32_t* idx_i, int32_t* idx_j, int32_t* kind, double* frac, int64_t* n_draws) {
+  if (n) *n = 0;
+  if (n_draws) *n_draws = 0;
+  if (!c || !n) return SZ_E_ARG;
+  if (!c->rr_on) { c->err = "sz_ridgeraft_candidates: ridge / raft is not set (sz_set_ridgeraft)"; return SZ_E_STATE; }
+  if (int rc = rr_state_checks(c, "sz_ridgeraft_candidates")) return rc;
+  (void)hipSetDevice(c->device);
+  if (int rc = sync_and_check(c)) return rc;          // hostM current
+  int nt = 0; long long nd = 0;
+  if (int rc = rr_pass(c, c->rr_h, &nt, &nd)) return rc;
+  *n = nt;
+  if (n_draws) *n_draws = nd;
+  if (!idx_i && !idx_j && !kind && !frac) return SZ_OK;
+  if (cap < nt) { c->err = "sz_ridgeraft_candidates: cap is smaller than the table (*n)"; return SZ_E_ARG; }
+  if (nt > 0) {
+    if (idx_i) HIPCHK(c, hipMemcpyAsync(idx_i, c->rr.ti, (size_t)nt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (idx_j) HIPCHK(c, hipMemcpyAsync(idx_j, c->rr.tj, (size_t)nt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (kind) HIPCHK(c, hipMemcpyAsync(kind, c->rr.tk, (size_t)nt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (frac) HIPCHK(c, hipMemcpyAsync(frac, c->rr.tf, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return SZ_OK;
+}
+int sz_ridgeraft_pending(sz_ctx* c, int32_t* tstep) {
+  if (!c || !tstep) return SZ_E_ARG;
+  *tstep = c->rr_pending;
+  return SZ_OK;
+}
+int sz_ridgeraft_draws(sz_ctx* c, int64_t* n) {
+  if (!c || !n) return SZ_E_ARG;
+  *n = c->rr_draws;
+  return SZ_OK;
+}
+int sz_step_finish(sz_ctx* c, int32_t tstep, int32_t dt, int32_t coupling_dt, int32_t flags) {
+  if (!c) return SZ_E_ARG;
+  if (c->rr_pending < 0) { c->err = "sz_step_finish: no ridge / raft step is pending"; return SZ_E_STATE; }
+  if (tstep != c->rr_pending) { c->err = "sz_step_finish: tstep is not the pending timestep (sz_ridgeraft_pending)"; return SZ_E_ARG; }
+  if ((flags & SZ_COUPLING_ON) && !c->have_fields) { c->err = "sz_set_fields must be called before coupling"; return SZ_E_STATE; }
+  if (int rc = rr_second_half(c, tstep, dt, coupling_dt, flags)) return rc;
+  c->rr_pending = -1;
+  return SZ_OK;
+}
+
+// sz_step with ridge / raft set (sz_set_ridgeraft), welding set (sz_set_welding) or removal set (sz_set_removal), in batches that stop.
+// Ridge / raft: the batch is cut into segments that end BEFORE a ridge / raft step (tstep % dt == 0; timestep_ridging_rafting! runs in the middle
+// of the step, simulation.jl:121-136).  That step runs through the process calls: sz_add_ghosts, sz_timestep_collisions, then the candidate pass
+// of sz_ridgeraft.hpp with one host synchronisation.  Empty table = the reference's call would change no floe and draw exactly the per-floe draws,
+// which are added to the batch's counter (sz_ridgeraft_draws); the step is finished as sz_step_finish finishes it and then ends as a segment's
+// last step does: a tag, a fracture candidate, a welding table and the removal pass apply in that order, as below.  Not empty = the batch ends
+// with the step pending (sz_ridgeraft_pending): *steps_done does not count it, the state is the reference's between timestep_collisions! and
+// timestep_ridging_rafting!, and sz_ridgeraft_candidates gives the same table again.
 // Welding: the batch is cut into segments that END on a welding step (tstep % dts[k] == 0,
 // timestep_welding! runs behind timestep_floe_properties!, simulation.jl:184-202).  A segment is an ordinary batch through the drivers above -- its
 // last step keeps its ghosts, the rows come home behind it, segments of pipe_min_steps or more stay pipelined -- then the overlap table of that
@@ -2482,29 +2613,69 @@ int sz_download_origin(sz_ctx* c, int32_t* origin) {
 // declined = the batch ends there as without removal.  The reference's order holds (simulation.jl:172-214: fracture, weld, simplify): a fracture
 // step with a candidate, or a welding step of a context with welding set, ends the batch as before -- the caller works through that step and calls
 // sz_remove_floes itself.
-// Batches that run through (SZ_NO_STOP) and contexts with neither set take the driver as it is.
+// Batches that run through (SZ_NO_STOP) and contexts with none of the three set take the driver as it is.
 int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
-  const bool weld = c && !c->weld_dts.empty(), rem = c && c->rm_on && !c->S.tiled;
-  if (!c || (!weld && !rem) || (flags & SZ_NO_STOP) || nsteps <= 0) return step_segment(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done);
+  if (c && c->rr_pending >= 0) {
+    if (steps_done) *steps_done = 0;
+    c->err = "sz_step: a ridge / raft step is pending (sz_ridgeraft_pending): sz_step_finish runs its second half first";
+    return SZ_E_STATE;
+  }
+  if (c) c->rr_draws = 0;
+  if (c && c->rr_on && c->S.tiled) {
+    if (steps_done) *steps_done = 0;
+    c->err = "tiled contexts have no ridge / raft candidate pass (the ghosts of a tiled list are halo rows): sz_set_ridgeraft(0)";
+    return SZ_E_STATE;
+  }
+  const bool weld = c && !c->weld_dts.empty(), rem = c && c->rm_on && !c->S.tiled, rr = c && c->rr_on;
+  if (!c || (!weld && !rem && !rr) || (flags & SZ_NO_STOP) || nsteps <= 0) return step_segment(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done);
   if (steps_done) *steps_done = 0;
   if (!c->have_floes) return SZ_E_STATE;
   if (weld) {
     if (c->S.tiled) { c->err = "tiled contexts do not compute welding overlaps (the bins span ranks): sz_set_welding(0)"; return SZ_E_STATE; }
     if (!c->have_domain || !c->have_fields) { c->err = "sz_step with welding set: the bins need the grid extents (sz_set_fields)"; return SZ_E_STATE; }
   }
+  if (rr && !(flags & SZ_COLLISIONS_ON)) { c->err = "sz_step with ridge / raft set: the candidates are read from this step's interaction rows (SZ_COLLISIONS_ON)"; return SZ_E_STATE; }
+  if (rr && (flags & SZ_COUPLING_ON) && !c->have_fields) { c->err = "sz_set_fields must be called before coupling"; return SZ_E_STATE; }
   int done = 0;
   while (done < nsteps) {
-    int len = nsteps - done, set = -1;
-    if (weld) for (int s = 0; s < nsteps - done; s++) { const int k = weld_set_at(c, tstep0 + done + s); if (k >= 0) { len = s + 1; set = k; break; } }
-    int more = 0;
-    const int rc = step_segment(c, len, tstep0 + done, dt, coupling_dt, flags, &more);
+    int len = nsteps - done, set = -1, more = 0, rc = SZ_OK;
+    if (rr && (tstep0 + done) % c->rr_dt == 0) {
+      // the ridge / raft step, through the process calls
+      const int tstep = tstep0 + done;
+      (void)hipSetDevice(c->device);
+      if (c->ghosts_staged && (rc = sz_remove_ghosts(c))) return rc;          // (ghosts a process-mode call left attached: a batch drops them too)
+      if ((rc = sz_add_ghosts(c)) || (rc = sz_timestep_collisions(c, c->hostN, dt))) return rc;
+      int nt = 0; long long nd = 0;
+      if ((rc = rr_pass(c, c->rr_h, &nt, &nd))) return rc;
+      if (nt > 0) { c->rr_pending = tstep; return SZ_OK; }
+      c->rr_draws += nd;
+      if ((rc = rr_second_half(c, tstep, dt, coupling_dt, flags))) return rc;
+      len = more = 1; set = weld ? weld_set_at(c, tstep) : -1;
+      // ... which ends as a segment's last step does: a tag, or a fracture candidate on a fracture step, is a stop request
+      // (the batch's own last step is not looked at)
+      int64_t todo[4] = { 0, 0, 0, 0 };
+      if (done + 1 < nsteps && (rc = sz_simplify_check(c, 0x7fffffff, 0.0, 0.0, todo))) return rc;
+      c->last_stopped = todo[0] + todo[1] > 0;
+      if (done + 1 < nsteps && !c->last_stopped && c->frac_kind != SZ_FRAC_OFF && c->frac_dt > 0 && (tstep % c->frac_dt) == 0) {
+        int nc = 0;
+        if ((rc = sz_fracture_candidates(c, &nc, nullptr))) return rc;
+        c->last_stopped = nc > 0;
+      }
+    } else {
+      for (int s = 0; s < nsteps - done; s++) {
+        if (rr && s > 0 && (tstep0 + done + s) % c->rr_dt == 0) { len = s; break; }
+        const int k = weld ? weld_set_at(c, tstep0 + done + s) : -1;
+        if (k >= 0) { len = s + 1; set = k; break; }
+      }
+      rc = step_segment(c, len, tstep0 + done, dt, coupling_dt, flags, &more);
+    }
     done += more;
     if (steps_done) *steps_done = done;
-    if (rc || done == nsteps) return rc;
+    if (rc) return rc;
     if (more < len || c->last_stopped) {
-      // the segment ended on a stop request before the batch's last step: with removal set, and where neither the fracture nor the welding
-      // of that step is the host's, the pass -- and on with the batch
-      if (!rem || !c->last_stopped || more < 1) return rc;
+      // the segment ended on a stop request: where it is the batch's last step the caller looks; before that, with removal set, and where
+      // neither the fracture nor the welding of that step is the host's, the pass -- and on with the batch
+      if (done == nsteps || !rem || !c->last_stopped || more < 1) return rc;
       const int tstep = tstep0 + done - 1;
       if (weld && weld_set_at(c, tstep) >= 0) return SZ_OK;
       if (c->frac_kind != SZ_FRAC_OFF && c->frac_dt > 0 && (tstep % c->frac_dt) == 0) {
@@ -2520,10 +2691,12 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
       c->last_stopped = false;
       continue;
     }
-    if (set < 0) return rc;
-    int nt = 0;
-    if (int rc2 = weld_pass(c, c->weld_nxs[set], c->weld_nys[set], c->weld_max_area, &nt)) return rc2;
-    if (nt > 0) break;
+    if (done == nsteps) return rc;
+    if (set >= 0) {
+      int nt = 0;
+      if (int rc2 = weld_pass(c, c->weld_nxs[set], c->weld_nys[set], c->weld_max_area, &nt)) return rc2;
+      if (nt > 0) break;
+    } else if (!rr) return rc;
   }
   return SZ_OK;
 }

@@ -15,6 +15,7 @@
 #include "sz_fracture.hpp"
 #include "sz_weld.hpp"
 #include "sz_weld_tile.hpp"
+#include "sz_ridgeraft.hpp"
 
 using namespace sz;
 
@@ -166,6 +167,14 @@ struct sz_ctx {
   // the running ocean.dissolved lattice (with the fields: zero after sz_set_fields); per parent the row it had at the last sz_upload_floes
   bool rm_on = false; int rm_max_vertices = 0x7fffffff; double rm_min_area = 0, rm_min_height = 0;
   double* dissolved = nullptr; int* origin = nullptr; Pool rm_allocs;
+  // ridge / raft (sz_set_ridgeraft; sz_ridgeraft.hpp): RidgeRaftSettings' Δt and the five heights the gates read; the buffers of the candidate pass,
+  // carved for rr_capM list rows and rr_cap entries.  rr_pending: the timestep whose ridge / raft step stopped between timestep_collisions! and
+  // timestep_ridging_rafting! (-1: none; sz_step_finish runs its second half); rr_draws: the per-floe draws of the ridge / raft steps the last
+  // sz_step ran through with an empty table.  ghosts_staged / rr_rows: the list is as add_ghosts! leaves it, and floe.interactions is of that
+  // list (a collision call, sz_upload_interactions) -- what the pass may be asked on
+  bool rr_on = false; int rr_dt = 0; double rr_h[5] = { 0, 0, 0, 0, 0 };
+  Pool rr_allocs; RrArgs rr{}; int rr_capM = 0, rr_cap = 0; RrDev rr_hd{};
+  int rr_pending = -1; long long rr_draws = 0; bool ghosts_staged = false, rr_rows = false;
   bool last_stopped = false;        // the last batch of resident steps ended on a stop request (tag, fracture candidate), not at its last step
   bool maybe_tagged = false;        // a parent may be non-active on the device (an upload said so, a batch ended on a tag, a process-mode call ran):
                                     // the next batch then runs its first step on its own (see sz_step)

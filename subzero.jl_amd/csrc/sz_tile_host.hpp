@@ -143,6 +143,7 @@ int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int
   if (!c || !c->have_floes) return SZ_E_STATE;
   if (c->frac_kind != SZ_FRAC_OFF) { c->err = "sz_tile_step does not evaluate fracture criteria (the host drives its steps: no library channel to gather the mean height over): sz_tile_run, or sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
   if (!c->weld_dts.empty()) { c->err = "sz_tile_step does not compute welding overlaps (the host drives its steps: no library channel to gather the candidates over): sz_tile_run, or sz_set_welding(0)"; return SZ_E_STATE; }
+  if (c->rr_on) { c->err = "sz_tile_step has no ridge / raft candidate pass (the ghosts of a tiled list are halo rows): sz_set_ridgeraft(0)"; return SZ_E_STATE; }
   return tile_step_body(c, d_recv, nranks, cap, tstep, dt, coupling_dt, flags);
 }
 
@@ -1415,6 +1416,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   if (c && !c->weld_dts.empty() && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled welding overlaps gather the candidates and rings over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
   if (c && c->frac_kind != SZ_FRAC_OFF && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled fracture criteria gather the mean height over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
   if (!c) return SZ_E_STATE;
+  if (c->rr_on) { c->err = "sz_tile_run has no ridge / raft candidate pass (the ghosts of a tiled list are halo rows): sz_set_ridgeraft(0)"; return SZ_E_STATE; }
   if (int rc = tiled_ready(c, "sz_tile_run")) return rc;
   if (nsteps < 0) return SZ_E_ARG;
   const bool frac = c->frac_kind != SZ_FRAC_OFF;

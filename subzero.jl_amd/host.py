@@ -560,9 +560,14 @@ class World:
         simulation.jl:205-214), or -- with a criterion set (set_fracture) -- after the first fracture step on which a floe would
         fracture (fracture_floes! is the host's), or -- with welding set (set_welding) -- after the first welding step on which two floes that
         could weld overlap (weld_overlaps() then gives the table timestep_welding! works from; the fuse is the host's);
+        or -- with ridge / raft set (set_ridgeraft) -- BEFORE the second half of the first ridge / raft step (tstep % dt == 0) whose candidate
+        table is not empty: that step is not counted, ridgeraft_pending() names it, the state is the reference's between timestep_collisions!
+        and timestep_ridging_rafting! (ghosts in the list), ridgeraft_candidates() gives the table, and finish_step() runs the rest of the step
+        after the host's ridging and rafting; ridge / raft steps with an empty table are run through, and ridgeraft_draws() says by how many
+        rand(rng, FT) calls the host's rng has to advance for them;
         stop_on_tags=False runs on regardless (measurement / soak runs)."""
         self._push()
-        flags = (capi.COLLISIONS_ON if collisions_on else 0) | (capi.COUPLING_ON if coupling_on else 0)
+        flags = self._flags(collisions_on, coupling_on)
         if not stop_on_tags:
             flags |= capi.NO_STOP
         done = C.c_int32(0)
@@ -571,6 +576,52 @@ class World:
         if getattr(self, "_removal_on", False) and stop_on_tags:
             self._follow_count()
         return int(done.value)
+
+    @staticmethod
+    def _flags(collisions_on, coupling_on):
+        return (capi.COLLISIONS_ON if collisions_on else 0) | (capi.COUPLING_ON if coupling_on else 0)
+
+    # ---- ridge / raft candidates on the device (timestep_ridging_rafting!, ridge_raft.jl:676-837)
+    def set_ridgeraft(self, on=True, dt=150, min_ridge_height=0.2, max_floe_ridge_height=5.0, max_domain_ridge_height=1.25,
+                      max_floe_raft_height=0.25, max_domain_raft_height=0.25):
+        """RidgeRaftSettings(ridge_raft_on = on, Δt = dt, ...) with the reference's default heights.  run() then stops in the middle of a ridge /
+        raft step whose candidate table is not empty (see run())."""
+        self._chk(self.L.sz_set_ridgeraft(self.h, int(bool(on)), int(dt), float(min_ridge_height), float(max_floe_ridge_height),
+                                          float(max_domain_ridge_height), float(max_floe_raft_height), float(max_domain_raft_height)))
+
+    def ridgeraft_candidates(self):
+        """the candidate table of the list as it is -- after add_ghosts() + timestep_collisions(), hand-made rows on such a list, or at a pending
+        stop: (i, j, kind, frac, n_draws).  i: 0-based list row; j: the partner as the interaction rows name it (1-based list row, -1..-4 for the
+        N/S/E/W boundary, -(4 + k) for topography element k); kind: bit 1 ridge, bit 2 raft; frac = overlap / min_area; n_draws: the per-floe
+        draws of the call (all list rows).  Ascending i, then first-passing-row order."""
+        self._push_interactions()
+        n = C.c_int32(0); nd = C.c_int64(0)
+        self._chk(self.L.sz_ridgeraft_candidates(self.h, C.byref(n), 0, None, None, None, None, C.byref(nd)))
+        cap = max(int(n.value), 1)
+        i = np.zeros(cap, _I32); j = np.zeros(cap, _I32); k = np.zeros(cap, _I32); f = np.zeros(cap)
+        self._chk(self.L.sz_ridgeraft_candidates(self.h, C.byref(n), cap, capi.ptr(i, capi._ip), capi.ptr(j, capi._ip), capi.ptr(k, capi._ip),
+                                                 capi.ptr(f), C.byref(nd)))
+        m = int(n.value)
+        return i[:m].copy(), j[:m].copy(), k[:m].copy(), f[:m].copy(), int(nd.value)
+
+    def ridgeraft_pending(self):
+        """the timestep whose ridge / raft step is pending (run() stopped in its middle), or -1"""
+        t = C.c_int32(-1)
+        self._chk(self.L.sz_ridgeraft_pending(self.h, C.byref(t)))
+        return int(t.value)
+
+    def ridgeraft_draws(self):
+        """per-floe draws of the ridge / raft steps the last run() ran through with an empty table"""
+        n = C.c_int64(0)
+        self._chk(self.L.sz_ridgeraft_draws(self.h, C.byref(n)))
+        return int(n.value)
+
+    def finish_step(self, tstep, dt, coupling_dt=10, collisions_on=True, coupling_on=True):
+        """the second half of the pending ridge / raft step on the state the device holds now (floes and interactions the host changed are
+        uploaded first): remove_ghosts, timestep_coupling when due, timestep_floe_properties"""
+        self._push_interactions()
+        self._chk(self.L.sz_step_finish(self.h, int(tstep), int(dt), int(coupling_dt), self._flags(collisions_on, coupling_on)))
+        self._host_stale = True
 
     def set_fracture(self, kind, dt=75, pstar=2.25e5, c=20.0, poly=None, alpha=0.0, min_floe_area=1e6):
         """FractureSettings(fractures_on, criteria, Δt = dt) with FloeSettings.min_floe_area and DecayAreaScaledCalculator.α:
