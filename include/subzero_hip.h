@@ -355,7 +355,9 @@ int sz_download_origin(sz_ctx *ctx, int32_t *origin);
    timestep_ridging_rafting! left, with their interactions): exactly sz_remove_ghosts; sz_timestep_coupling when flags and tstep % coupling_dt
    say so; sz_timestep_floe_properties -- and the pending mark is cleared.  SZ_E_STATE when nothing is pending; the batch goes on with
    sz_step(.., tstep + 1, ..) after the host's end-of-step processes.
-   SZ_NO_STOP batches run through and evaluate nothing.  Tiled contexts (sz_tile_run, sz_tile_step, sz_step) with ridge / raft set: SZ_E_STATE. */
+   SZ_NO_STOP batches run through and evaluate nothing.  Tiled contexts: sz_tile_run stops the same way, collectively (sz_tile_ridgeraft_candidates,
+   sz_tile_list_numbers and sz_tile_step_finish below); sz_tile_step, sz_step and sz_ridgeraft_candidates on a tiled context with ridge / raft set
+   return SZ_E_STATE. */
 int sz_set_ridgeraft(sz_ctx *ctx, int32_t on, int32_t dt, double min_ridge_height, double max_floe_ridge_height,
                      double max_domain_ridge_height, double max_floe_raft_height, double max_domain_raft_height);
 int sz_ridgeraft_candidates(sz_ctx *ctx, int32_t *n, int32_t cap, int32_t *idx_i, int32_t *idx_j, int32_t *kind, double *frac,
@@ -461,6 +463,16 @@ int sz_set_stream(sz_ctx *ctx, void *hip_stream);
                          step ends the batch first, where sz_step ends it, with removal set too.  The batch's own last step is not
                          looked at.  SZ_NO_STOP batches and contexts without welding launch and gather nothing for it.  Needs
                          sz_tile_setup and a communicator; refused with two-way coupling across tiles, like a criterion.
+                         With ridge / raft set (sz_set_ridgeraft) and without SZ_NO_STOP (SZ_COLLISIONS_ON required) the segments also end
+                         BEFORE a ridge / raft step (tstep % dt == 0), and that step is a segment of its own: pack, exchange, the first
+                         half of the step (unpack, ghosts, collisions), then the collective candidate pass over the ONE global list
+                         (sz_tile_ridgeraft_candidates below: the same pass).  An empty table: the draws of all ranks go to the batch's
+                         counter (sz_ridgeraft_draws: the same sum on every rank), the second half runs, and the step ends as a
+                         segment's last step does -- a tag ANY rank raised, the fracture pass, the welding pass, removal.  A table that
+                         is not empty ends the batch on every rank with the step PENDING (sz_ridgeraft_pending): *steps_done does NOT
+                         count it, the lists keep their halo rows and ghosts, and sz_tile_run and sz_tile_migrate return SZ_E_STATE
+                         until sz_tile_step_finish has run.  SZ_NO_STOP batches and contexts without ridge / raft launch and gather
+                         nothing for it.  Needs sz_tile_setup and a communicator; refused with two-way coupling across tiles.
                          Device errors are per rank; the ranks agree on them at every box gather and at the end of the call,
                          so that EVERY rank returns the same code at the same step (a rank leaving on its own would hang the
                          others: RCCL has no timeout).  A new sz_upload_floes invalidates sz_tile_enable / sz_tile_setup.
@@ -562,6 +574,27 @@ int sz_tile_weld_overlaps(sz_ctx *ctx, int32_t nx, int32_t ny, double max_weld_a
                           int32_t *n, int32_t cap, int64_t *idx_i, int64_t *idx_j, double *inter_area);
 int sz_tile_debug_weld_bins(sz_ctx *ctx, int32_t nx, int32_t ny, int32_t *bin);
 int sz_tile_debug_weld_npairs(sz_ctx *ctx, int64_t *n);
+/* Ridge / raft candidates on a tiled context (csrc/sz_ridgeraft_tile.hpp; DESIGN.md §9e, "tiled contexts"), at a PENDING stop of sz_tile_run: the
+   local list holds the owned floes, the halo floes and the ghosts of both, with this step's rows.  Every local row has an order key (a parent: its
+   global number; a ghost: (pass << 40) + 4 gid + k); sorted, the distinct keys of all ranks are the single context's list order.  A list row is
+   evaluated by ONE rank, the owner of its root parent, and the reference's i < j gate is the comparison of the keys.
+   sz_tile_ridgeraft_candidates (collective: it runs the pass again): the WHOLE table of sz_ridgeraft_candidates for the undivided list on every
+   rank, in its numbering (idx_i: 0-based list row -- a parent's global number, a ghost's N_global + its place among the ghosts; idx_j: the partner
+   as the rows name it, 1-based list row or the negative boundary / topography number) and its order, kind and frac to the bit; *n_draws is the
+   exact integer sum over the ranks.  Two calls give the same bits.  A cap under *n: SZ_E_ARG on every rank (the same cap everywhere), and the
+   context goes on.  Any error one rank finds is agreed on before the next collective: all ranks return the same code.
+   sz_tile_list_numbers: the single context's list number of every LOCAL row -- owned floes, halo floes, ghosts, in local order (-1: a ghost of a
+   halo floe that its owner does not hold) -- of the pass that stopped the batch or of the last sz_tile_ridgeraft_candidates: with it a host reads
+   the partner column of downloaded rows: the column holds order key + 1, and sz_tile_list_keys gives the order key of every local row in the
+   same order (every partner a row names is a local row).
+   sz_tile_step_finish (collective): the second half of the pending step on what the device holds -- the forcings of a coupling step, the
+   integrator -- then the halo rows and ghosts are dropped and the mark is cleared.  SZ_E_ARG for a tstep that is not the pending one, SZ_E_STATE
+   when nothing is pending.  What an upload does to a pending tiled context is not defined yet. */
+int sz_tile_ridgeraft_candidates(sz_ctx *ctx, int32_t *n, int32_t cap, int64_t *idx_i, int64_t *idx_j, int32_t *kind, double *frac,
+                                 int64_t *n_draws);
+int sz_tile_list_numbers(sz_ctx *ctx, int64_t *out, int64_t cap);
+int sz_tile_list_keys(sz_ctx *ctx, int64_t *out, int64_t cap);
+int sz_tile_step_finish(sz_ctx *ctx, int32_t tstep, int32_t dt, int32_t coupling_dt, int32_t flags);
 int sz_debug_migrate_path(sz_ctx *ctx);
 /* diagnosis: the ghost / halo row that carried order key `key` in the last resident step that used ghost allocator `slot` (0-based step & 1), as the
    collision kernels saw it -- out56: row (-1: none), cx, cy, u, v, xi, rmax, area, height, box x0 x1 y0 y1, ring points, parent, status, ring x[20], y[20] */

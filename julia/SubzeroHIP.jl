@@ -1116,6 +1116,51 @@ function tile_weld_overlaps(eng::HIPEngine, nx::Integer, ny::Integer, max_weld_a
     return i[1:n[]] .+ 1, j[1:n[]] .+ 1, a[1:n[]]
 end
 
+# Ridging and rafting in a tiled run (written against the C-ABI and not run: no Julia was available).  `tile_set_ridgeraft!` puts the simulation's
+# RidgeRaftSettings on this rank's context (the same on every rank); `tile_run!` then stops on every rank in the middle of the first ridge / raft
+# step whose candidate table of the global list is not empty: the step is not counted, `ridgeraft_pending(eng)` names it, the lists keep their
+# halo rows and ghosts, and `tile_run!` / `tile_migrate!` refuse until `tile_step_finish!` has run.  Steps with an empty table are run through;
+# `ridgeraft_draws(eng)` is the sum over the ranks, by which EVERY rank advances its copy of sim.rng.  The host's side of a non-empty table on tiles
+# -- gathering the list, timestep_ridging_rafting!, handing the floes back to their tiles -- is not written yet (DESIGN.md §10): these calls give
+# that host the table, the list numbers and the finish.
+function tile_set_ridgeraft!(eng::HIPEngine, sim)
+    set_ridgeraft!(eng, sim)
+    return
+end
+
+# at a pending stop (collective): (i, j, kind, frac, n_draws) of the global list, the whole table on every rank, as `ridgeraft_candidates` gives it
+# for the undivided list: i 1-based list row, j as the rows name the partner (1-based list row, -1..-4, -(4 + k)), in its order, to the bit
+function tile_ridgeraft_candidates(eng::HIPEngine)
+    n = Ref{Int32}(0); nd = Ref{Int64}(0)
+    check(eng, @ccall lib.sz_tile_ridgeraft_candidates(eng.ctx::Ptr{Cvoid}, n::Ptr{Int32}, Int32(0)::Int32, C_NULL::Ptr{Int64}, C_NULL::Ptr{Int64},
+                                                       C_NULL::Ptr{Int32}, C_NULL::Ptr{Float64}, nd::Ptr{Int64})::Cint)
+    cap = max(Int(n[]), 1)
+    i = Vector{Int64}(undef, cap); j = Vector{Int64}(undef, cap); k = Vector{Int32}(undef, cap); f = Vector{Float64}(undef, cap)
+    check(eng, @ccall lib.sz_tile_ridgeraft_candidates(eng.ctx::Ptr{Cvoid}, n::Ptr{Int32}, Int32(cap)::Int32, i::Ptr{Int64}, j::Ptr{Int64},
+                                                       k::Ptr{Int32}, f::Ptr{Float64}, nd::Ptr{Int64})::Cint)
+    return i[1:n[]] .+ 1, j[1:n[]], Int.(k[1:n[]]), f[1:n[]], Int(nd[])
+end
+
+# at a pending stop: the 1-based list number the undivided list gives every local row (owned floes, halo floes, the ghosts of both; n_local rows)
+function tile_list_numbers(eng::HIPEngine, n_local::Integer)
+    out = Vector{Int64}(undef, max(n_local, 1))
+    check(eng, @ccall lib.sz_tile_list_numbers(eng.ctx::Ptr{Cvoid}, out::Ptr{Int64}, length(out)::Int64)::Cint)
+    return out[1:n_local] .+ 1
+end
+
+# ... and the order key of every local row: the partner column of a downloaded interaction row holds key + 1
+function tile_list_keys(eng::HIPEngine, n_local::Integer)
+    out = Vector{Int64}(undef, max(n_local, 1))
+    check(eng, @ccall lib.sz_tile_list_keys(eng.ctx::Ptr{Cvoid}, out::Ptr{Int64}, length(out)::Int64)::Cint)
+    return out[1:n_local]
+end
+
+# the second half of the pending step on what the device holds, collectively; the halo rows and ghosts are dropped behind it
+function tile_step_finish!(eng::HIPEngine, tstep::Integer, Δt::Integer, coupling_Δt::Integer, flags::Integer)
+    check(eng, @ccall lib.sz_tile_step_finish(eng.ctx::Ptr{Cvoid}, Int32(tstep)::Int32, Int32(Δt)::Int32, Int32(coupling_Δt)::Int32, Int32(flags)::Int32)::Cint)
+    return
+end
+
 # floes that left their tile go to the rank that owns the tile their centroid lies in now (px x py tiles over the domain), with their
 # complete state, over the library's channel; collective, between two tile_run! calls.  Returns (floes given away, floes owned now).
 function tile_migrate!(eng::HIPEngine, px::Integer, py::Integer)

@@ -25,6 +25,7 @@
 #include "sz_remove_tile.hpp"
 #include "sz_fracture_tile.hpp"
 #include "sz_weld_tile.hpp"
+#include "sz_ridgeraft_tile.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 #include "sz_ctx.hpp"
 #include "sz_comm.hpp"
@@ -745,7 +746,7 @@ void sz_destroy(sz_ctx* c) {
   for (auto& e : c->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   (void)hipFree(c->d_stats); (void)hipFree(c->S.acc);
   (void)hipFree(c->frac_d); (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx);
-  free_pool(c->weld_allocs); free_pool(c->weldt_allocs); (void)hipFree(c->weld_tmp); free_pool(c->rr_allocs);
+  free_pool(c->weld_allocs); free_pool(c->weldt_allocs); (void)hipFree(c->weld_tmp); free_pool(c->rr_allocs); free_pool(c->rrt_allocs);
   free_pool(c->rm_allocs);
   free_pool(c->frac_allocs);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -2504,7 +2505,7 @@ int rr_ensure(sz_ctx* c, int M, int need) {
 // what the pass may be asked on: the list as add_ghosts! leaves it, with the rows of a collision call (or hand-made ones) on that list
 int rr_state_checks(sz_ctx* c, const char* who) {
   if (!c->have_floes) { c->err = std::string(who) + ": no floes uploaded"; return SZ_E_STATE; }
-  if (c->S.tiled) { c->err = std::string(who) + ": the ghosts of a tiled list are halo rows: tiled contexts have no ridge / raft candidate pass"; return SZ_E_STATE; }
+  if (c->S.tiled) { c->err = std::string(who) + ": a tiled list is one rank's share of the table: sz_tile_ridgeraft_candidates (collective, at a pending stop of sz_tile_run)"; return SZ_E_STATE; }
   if (!c->ghosts_staged || !c->rr_rows || !c->inter_any || c->inter_lost || c->gi_valid) {
     c->err = std::string(who) + ": needs the list with its ghosts and this step's interaction rows (sz_add_ghosts + sz_timestep_collisions, or a pending ridge / raft stop)";
     return SZ_E_STATE;
@@ -2623,7 +2624,7 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   if (c) c->rr_draws = 0;
   if (c && c->rr_on && c->S.tiled) {
     if (steps_done) *steps_done = 0;
-    c->err = "tiled contexts have no ridge / raft candidate pass (the ghosts of a tiled list are halo rows): sz_set_ridgeraft(0)";
+    c->err = "sz_step on a tiled context has no ridge / raft candidate pass (a tile's rows are named by order keys, its ghosts' partners live on other ranks): sz_tile_run, or sz_set_ridgeraft(0)";
     return SZ_E_STATE;
   }
   const bool weld = c && !c->weld_dts.empty(), rem = c && c->rm_on && !c->S.tiled, rr = c && c->rr_on;

@@ -16,6 +16,7 @@
 #include "sz_weld.hpp"
 #include "sz_weld_tile.hpp"
 #include "sz_ridgeraft.hpp"
+#include "sz_ridgeraft_tile.hpp"
 
 using namespace sz;
 
@@ -175,6 +176,12 @@ struct sz_ctx {
   bool rr_on = false; int rr_dt = 0; double rr_h[5] = { 0, 0, 0, 0, 0 };
   Pool rr_allocs; RrArgs rr{}; int rr_capM = 0, rr_cap = 0; RrDev rr_hd{};
   int rr_pending = -1; long long rr_draws = 0; bool ghosts_staged = false, rr_rows = false;
+  // ... on a tiled context (tile_rr_pass; sz_ridgeraft_tile.hpp): the scratch of the collective pass, kept between passes; the host sides of its
+  // small transfers; the whole table in the single context's list numbers, as every rank ends a pass with it, the list number and the order key of every local
+  // row of that pass (sz_tile_list_numbers, sz_tile_list_keys), and the draws of all ranks.  tile_split_gl: the first half of a split step took the ghost-candidate list
+  Pool rrt_allocs; RrDev rrt_hd{}; RrTileDev rrt_hg{}; int rrt_hw[4] = { 0, 0, 0, 0 }, rrt_hbad = 0; std::vector<int> rrt_cnt;
+  std::vector<long long> rrt_i, rrt_j, rrt_rownum, rrt_rowkey; std::vector<int> rrt_k; std::vector<double> rrt_f;
+  bool tile_split_gl = false;
   bool last_stopped = false;        // the last batch of resident steps ended on a stop request (tag, fracture candidate), not at its last step
   bool maybe_tagged = false;        // a parent may be non-active on the device (an upload said so, a batch ended on a tag, a process-mode call ran):
                                     // the next batch then runs its first step on its own (see sz_step)

@@ -13,6 +13,7 @@
 //   sz_k_rr_scan    ONE workgroup: exclusive offsets of the counts, the total
 //   sz_k_rr_write   the entries at their offsets: ascending i, then first-passing-row order -- columns i, j (the reference's numbering of rows:
 //                   partner index, -1..-4, -(4 + k)), kind, frac.  No atomic decides a position: the same table on every run
+// The gates are stated once, in rr_row, which takes a policy for how a list names its rows: RrSingle here, RrTiled in sz_ridgeraft_tile.hpp.
 // A dependent-load chain over the rows of floe.interactions (ROWCAP rows of 7 doubles per floe), one thread per list row.  fp64 in every precision mode.
 #pragma once
 #include "sz_kernels.hpp"
@@ -33,24 +34,41 @@ struct RrArgs {
   double min_ridge_h, max_floe_ridge_h, max_domain_ridge_h, max_floe_raft_h, max_domain_raft_h;
 };
 
-// The entries of list row i, in row order, handed to emit(j, kind, frac); returns the row's draws.
-template <class Emit>
-__device__ __forceinline__ int rr_row(const State& S, const RrArgs& A, int i, Emit&& emit) {
+// How a list names its rows.  The single context: a row's number is its position, the partner column of floe.interactions holds position + 1, and
+// every row is evaluated.  The tiled policy (sz_ridgeraft_tile.hpp) names rows by their order keys instead.  A policy gives:
+//   J                     the type of a partner number as the rows hold it (and as emit() is handed it)
+//   evaluated(S, i)       does this context evaluate list row i at all?
+//   partner(S, A, i, j)   the local row the positive partner number j names, or -1 (a row that names no list row: the reference would throw)
+//   before(S, i, p)       the reference's i < j gate for local rows i and p
+//   active(S, i)          is local row i `active` behind this step's timestep_collisions!?
+struct RrSingle {
+  using J = int;
+  __device__ __forceinline__ bool evaluated(const State&, int) const { return true; }
+  __device__ __forceinline__ int partner(const State&, const RrArgs& A, int, int j) const { return j > A.m ? -1 : j - 1; }
+  __device__ __forceinline__ bool before(const State&, int i, int p) const { return i < p; }
+  __device__ __forceinline__ bool active(const State& S, int i) const { return S.status[i] == SZ_ACTIVE; }
+};
+
+// The entries of list row i, in row order, handed to emit(j, kind, frac); returns the row's draws (0 for a row this context does not evaluate).
+template <class Pol, class Emit>
+__device__ __forceinline__ int rr_row(const State& S, const RrArgs& A, const Pol& pol, int i, Emit&& emit) {
+  using J = typename Pol::J;
+  if (!pol.evaluated(S, i)) return 0;
   const double hi = S.height[i];
   const bool ridge = hi <= A.max_floe_ridge_h, raft = hi <= A.max_floe_raft_h;
   const int nrows = min(S.inter_cnt[i], S.rowcap);
-  if ((ridge || raft) && S.status[i] == SZ_ACTIVE && nrows > 0) {
+  if ((ridge || raft) && pol.active(S, i) && nrows > 0) {
     const double* rows = S.inter_rows + (size_t)i * S.rowcap * 7;
     const double xi = S.cx[i], yi = S.cy[i], ri = S.rmax[i], ai = S.area[i];
     for (int r = 0; r < nrows; r++) {
-      const int j = (int)rows[(size_t)r * 7];
+      const J j = (J)rows[(size_t)r * 7];
       double min_area = ai, hj = 0.0;
       bool valid = false;
       if (j > 0) {
-        if (j > A.m) continue;          // (a row that names no list row: the reference would throw)
-        const int p = j - 1;
+        const int p = pol.partner(S, A, i, j);
+        if (p < 0) continue;
         min_area = fmin(ai, S.area[p]);
-        if (i + 1 < j && S.status[p] == SZ_ACTIVE) {
+        if (pol.before(S, i, p) && pol.active(S, p)) {
           // potential_interaction (collisions.jl:705-710), the collision search's expression
           const double ddx = xi - S.cx[p], ddy = yi - S.cy[p], rr = ri + S.rmax[p];
           valid = (ddx * ddx + ddy * ddy) < rr * rr;
@@ -62,7 +80,7 @@ __device__ __forceinline__ int rr_row(const State& S, const RrArgs& A, int i, Em
       else if (j == -3) valid = fabs(xi - S.eval[SZ_EAST]) < ri;
       else if (j == -4) valid = fabs(xi - S.eval[SZ_WEST]) < ri;
       else if (j < 0) {
-        const int e = -j - 1;           // topography element k = -(j + 4), 1-based, behind the four boundaries
+        const int e = (int)(-j - 1);    // topography element k = -(j + 4), 1-based, behind the four boundaries
         if (e >= S.nelem) continue;
         const double ddx = xi - S.ecx[e], ddy = yi - S.ecy[e], rr = ri + S.ermax[e];
         valid = (ddx * ddx + ddy * ddy) < rr * rr;
@@ -82,7 +100,7 @@ __device__ __forceinline__ int rr_row(const State& S, const RrArgs& A, int i, Em
       // one entry per (i, j): an earlier row for the same j passes or fails on its own overlap alone (everything else is the pair's)
       bool dup = false;
       for (int q = 0; q < r && !dup; q++) {
-        if ((int)rows[(size_t)q * 7] != j) continue;
+        if ((J)rows[(size_t)q * 7] != j) continue;
         const double fq = rows[(size_t)q * 7 + 6] / min_area;
         dup = 1e-6 < fq && fq < 0.95;
       }
@@ -96,7 +114,7 @@ __global__ void __launch_bounds__(256) sz_k_rr_count(State S, RrArgs A) {
   unsigned long long draws = 0;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < A.m; i += gridDim.x * blockDim.x) {
     int n = 0;
-    draws += (unsigned long long)rr_row(S, A, i, [&](int, int, double) { n++; });
+    draws += (unsigned long long)rr_row(S, A, RrSingle{}, i, [&](int, int, double) { n++; });
     A.cnt[i] = n;
   }
   for (int d = 32; d >= 1; d >>= 1) draws += __shfl_xor(draws, d);
@@ -127,7 +145,7 @@ __global__ void __launch_bounds__(256) sz_k_rr_write(State S, RrArgs A) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < A.m; i += gridDim.x * blockDim.x) {
     if (A.cnt[i] == 0) continue;
     int o = A.off[i];
-    rr_row(S, A, i, [&](int j, int kind, double frac) {
+    rr_row(S, A, RrSingle{}, i, [&](int j, int kind, double frac) {
       if (o >= 0 && o < A.cap) { A.ti[o] = i; A.tj[o] = j; A.tk[o] = kind; A.tf[o] = frac; }
       o++;
     });

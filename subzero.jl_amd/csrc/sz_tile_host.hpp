@@ -1,5 +1,5 @@
 // sz_tile_host.hpp — the host code of tiled (multi-GPU) contexts: set-up, the steps a host drives itself (sz_halo_* / sz_tile_step), the box
-// gather and the halo exchange, migration, the collective removal, fracture and welding passes, and the batch drivers of sz_tile_run.  Host code of
+// gather and the halo exchange, migration, the collective removal, fracture, welding and ridge / raft passes, and the batch drivers of sz_tile_run.  Host code of
 // the one translation unit sz_api.hip, which includes it behind the single context's batch drivers and passes: a tile's steps are theirs.
 #pragma once
 #include "sz_comm.hpp"
@@ -33,41 +33,52 @@ int tile_forcing(sz_ctx* c) {
 }
 
 // one list-based tiled step: the body of the public sz_tile_step below, and the step of sz_tile_run's list-based driver (tile_run_listed), which
-// has checked the context and evaluates a criterion itself, between its segments
-static int tile_step_body(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int32_t tstep, int32_t dt, int32_t coupling_dt, int32_t flags) {
+// has checked the context and evaluates a criterion itself, between its segments.
+// halves: TILE_STEP_WHOLE is the step as it always was.  A ridge / raft step of sz_tile_run is split where timestep_ridging_rafting! stands
+// (simulation.jl:121-136): TILE_STEP_FIRST = unpack, ghosts, collisions -- the list then holds the owned floes, the halo floes and the ghosts of
+// both, with this step's floe.interactions -- and TILE_STEP_SECOND = the forcings of a coupling step (behind the host's possible edits, as
+// timestep_coupling! comes after the ridging) and the integrator.  Nothing between the halves changes what the second reads, and both set the
+// modes their kernels are told, so anything may run between them.
+enum { TILE_STEP_FIRST = 1, TILE_STEP_SECOND = 2, TILE_STEP_WHOLE = 3 };
+static int tile_step_body(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int32_t tstep, int32_t dt, int32_t coupling_dt, int32_t flags, int halves = TILE_STEP_WHOLE) {
   (void)hipSetDevice(c->device);
   State& S = c->S;
+  const bool first = (halves & TILE_STEP_FIRST) != 0, second = (halves & TILE_STEP_SECOND) != 0, whole = first && second;
   const bool coll = (flags & SZ_COLLISIONS_ON) != 0;
   const bool sg = coll && c->grid_ok;
-  if (sg) use_static_grid(c);
-  const bool gl = ghost_list_wanted(c, sg);
-  if (gl) use_ghost_list(c); else c->gl_valid = false;
-  if (d_recv && nranks > 0) {
+  if (sg && first) use_static_grid(c);
+  const bool gl = whole ? ghost_list_wanted(c, sg) : first ? (c->tile_split_gl = ghost_list_wanted(c, sg)) : c->tile_split_gl;
+  if (first) { if (gl) use_ghost_list(c); else c->gl_valid = false; }
+  if (first && d_recv && nranks > 0) {
     // halo floes join the candidate list of THIS step (the owned floes were appended by the last integrator)
     hipLaunchKernelGGL(sz_k_halo_unpack, dim3(1), dim3(1024), 0, c->stream, S, (const double*)d_recv, nranks, cap, sg ? 1 : 0, gl ? c->gl_cur : -1);
   }
   const bool coupling = coupling_at(flags, coupling_dt, tstep);
   const bool periodic = S.any_periodic_ew || S.any_periodic_ns;
   // the forcings of this step: already enqueued by sz_tile_forcing (beside the exchange), else now -- in either
-  // case before the ghost pass, like sz_step
-  if (coupling && c->tile_forcing_tstep != tstep) { int rc = tile_forcing(c); if (rc) return rc; }
-  c->tile_forcing_tstep = -1;
+  // case before the ghost pass, like sz_step (a split step: in its second half)
+  if (whole || second) {
+    if (coupling && c->tile_forcing_tstep != tstep) { int rc = tile_forcing(c); if (rc) return rc; }
+    c->tile_forcing_tstep = -1;
+  }
   // As in sz_step, the ghosts of the previous step are detached by this step's flag kernel and the new ones
   // committed by the flag/scan kernel; the halo of the previous step was overwritten by the unpack kernel.  Nothing
   // between two steps looks past the owned floes, so no clean-up launch is needed per step: the ghosts and halo
   // floes of the LAST step are dropped when the host next looks at the state (tile_cleanup).
   // n_init = every local parent (owned + halo): totals of halo floes are computed and then ignored
-  S.callid = ++c->callid;
+  if (first) S.callid = ++c->callid;
   // (fixed-point totals as in the resident steps of sz_step, so that a tile and the single context give the same bits; the reduce launch stays
   //  inside the step here, assembling rows only)
   const bool facc_on = coll && c->facc_buf != nullptr;
   S.facc = facc_on ? c->facc_buf : nullptr; S.kexp = force_scale_exp(c); c->reduce_mode = facc_on ? 1 : 0; c->acc_mode = facc_on ? 1 : 0;
-  if (coll) stage_ghosts(c, true, sg, gl);
-  if (coll) collisions(c, -1, dt, periodic && !sg, sg);
-  stage_integrate(c, dt, false, coupling, sg, gl ? 1 - c->gl_cur : -1);
+  if (first && coll) stage_ghosts(c, true, sg, gl);
+  if (first && coll) collisions(c, -1, dt, periodic && !sg, sg);
+  if (second) {
+    stage_integrate(c, dt, false, coupling, sg, gl ? 1 - c->gl_cur : -1);
+    if (gl) { c->gl_cur ^= 1; c->gl_est = std::max(c->gl_est, 64); }
+    c->tile_dirty = true;
+  }
   S.facc = nullptr; c->reduce_mode = 0; c->acc_mode = 0;
-  if (gl) { c->gl_cur ^= 1; c->gl_est = std::max(c->gl_est, 64); }
-  c->tile_dirty = true;
   return SZ_OK;
 }
 }  // namespace
@@ -143,7 +154,7 @@ int sz_tile_step(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t cap, int
   if (!c || !c->have_floes) return SZ_E_STATE;
   if (c->frac_kind != SZ_FRAC_OFF) { c->err = "sz_tile_step does not evaluate fracture criteria (the host drives its steps: no library channel to gather the mean height over): sz_tile_run, or sz_set_fracture(SZ_FRAC_OFF)"; return SZ_E_STATE; }
   if (!c->weld_dts.empty()) { c->err = "sz_tile_step does not compute welding overlaps (the host drives its steps: no library channel to gather the candidates over): sz_tile_run, or sz_set_welding(0)"; return SZ_E_STATE; }
-  if (c->rr_on) { c->err = "sz_tile_step has no ridge / raft candidate pass (the ghosts of a tiled list are halo rows): sz_set_ridgeraft(0)"; return SZ_E_STATE; }
+  if (c->rr_on) { c->err = "sz_tile_step has no ridge / raft candidate pass (the host drives its steps: no library channel to gather the ghost keys and the entries over): sz_tile_run, or sz_set_ridgeraft(0)"; return SZ_E_STATE; }
   return tile_step_body(c, d_recv, nranks, cap, tstep, dt, coupling_dt, flags);
 }
 
@@ -663,6 +674,7 @@ int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_ov
 
 int sz_tile_migrate(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_override, int64_t* n_sent, int64_t* n_owned) {
   if (n_sent) *n_sent = 0;
+  if (c && c->rr_pending >= 0) { c->err = "sz_tile_migrate: a ridge / raft step is pending (sz_ridgeraft_pending): sz_tile_step_finish runs its second half first"; return SZ_E_STATE; }
   if (!c || tiled_ready(c, "sz_tile_migrate") || px < 1 || py < 1 || (!owner_override && px * py != c->comm_n)) {
     if (c) c->err = "sz_tile_migrate needs a tiled context after sz_tile_setup, and px * py == the number of ranks";
     return SZ_E_STATE;
@@ -1151,6 +1163,203 @@ int sz_tile_debug_weld_npairs(sz_ctx* c, int64_t* n) {
   return SZ_OK;
 }
 
+// ---------------------------------------------------------------- ridge / raft candidates on a tiled context (sz_ridgeraft_tile.hpp)
+namespace {
+// The candidate table (rr_pass) over the ONE global floe list whose rows live on the ranks' tiles: collective, in the MIDDLE of a step -- behind the
+// first half of a split step (tile_step_body), the local list holding the owned floes, the halo floes and the ghosts of both with this step's
+// rows.  Every rank ends with the single context's whole table in the single context's list numbers and order (c->rrt_i / _j / _k / _f), to the bit,
+// with the draws of all ranks as an exact integer sum, and with the list number of each of its local rows (c->rrt_rownum).  DESIGN.md §9e, "tiled
+// contexts": the owner of a row's root parent evaluates it; i < j is the comparison of the order keys.  The collectives, the same on every rank
+// whatever it holds:
+//   1. the all-gather of {error code, rows this rank found not active, owned floes}: a rank that cannot take part (device error bits) sends its
+//      code and all ranks return it together.  Only where some rank has a row that is not active: the agreement on what each prepared alone, then
+//      the all-gather of those rows' keys (the status of a row behind this step's collisions is its owner's word)
+//   2. the all-gather of {error code, entries, ghost rows of owned root parents, draws}.  All counts zero entries: the table is empty on every
+//      rank and the pass ends here -- two collectives on the path a step runs through
+//   3. the agreement on what each prepared alone (scratch memory)
+//   4. the all-gather of the ghost keys: sorted, they number the single context's ghosts (N_global + place)
+//   5. the all-gather of the entry records, renamed on every rank (sz_k_rrt_rename) and ordered by ascending i, then by the emitting rank's row
+//      order -- the single context's order, as one rank emits all the entries of a list row
+//   6. the agreement on: a device error, a key that could not be renamed
+// The entries are counted before their memory is carved: nothing is truncated, no second round.  Nothing of the floes changes in a pass.
+int tile_rr_pass(sz_ctx* c, int* ntable, long long* draws) {
+  *ntable = 0; *draws = 0;
+  State& S = c->S;
+  const int n = c->comm_n, me = c->comm_rank;
+  constexpr const char* who = "tiled ridge / raft candidates";
+  int h[C_COUNT] = { 0 };
+  int rc = sync_and_check(c, h);
+  if (rc == SZ_E_HIP) return rc;
+  const int M = h[C_M], nown = h[C_NOWN], npar = h[C_N];
+  if (!rc && (M < npar || npar < nown || nown < 0 || M > S.capM)) { c->err = "tiled ridge / raft candidates: bad list counts"; rc = SZ_E_HIP; }
+  Pool& P = c->rrt_allocs;
+  reset_pool(P);
+  // ---- this rank alone: the rows by ascending key, the status of the rows it evaluates
+  RrArgs A{}; RrTiled T{};
+  RrTileDev* d_g = nullptr; long long* skey = nullptr; int *srow = nullptr, *iota = nullptr, *gflag = nullptr, *d_w = nullptr, *d_wall = nullptr;
+  unsigned char* act = nullptr; double *inact = nullptr, *gkeys = nullptr;
+  const size_t Mc = (size_t)std::max(M, 1);
+  if (const int r2 = dalloc(c, &d_w, 4, P)) return r2;          // (the words of gathers 1 and 2: without them there is nothing to agree over)
+  if (const int r2 = dalloc(c, &d_wall, 4 * 64, P)) return r2;
+  if (!rc) (void)((rc = dalloc(c, &A.d, 1, P)) || (rc = dalloc(c, &A.cnt, Mc + 1, P)) || (rc = dalloc(c, &A.off, Mc + 1, P)) || (rc = dalloc(c, &d_g, 1, P)) ||
+                  (rc = dalloc(c, &skey, Mc, P)) || (rc = dalloc(c, &srow, Mc, P)) || (rc = dalloc(c, &iota, Mc, P)) || (rc = dalloc(c, &gflag, Mc, P)) ||
+                  (rc = dalloc(c, &act, Mc, P)) || (rc = dalloc(c, &inact, Mc, P)) || (rc = dalloc(c, &gkeys, Mc, P)));
+  const int nb = grid_for(std::max(M, 1), 256, 2048);
+  c->rrt_hg = RrTileDev{ 0, 0 };
+  if (!rc) {
+    A.m = M; A.cap = 0;
+    A.min_ridge_h = c->rr_h[0]; A.max_floe_ridge_h = c->rr_h[1]; A.max_domain_ridge_h = c->rr_h[2]; A.max_floe_raft_h = c->rr_h[3]; A.max_domain_raft_h = c->rr_h[4];
+    T.skey = skey; T.srow = srow; T.act = act; T.m = M; T.nown = nown; T.npar = npar;
+    HIPCHK(c, hipMemsetAsync(A.d, 0, sizeof(RrDev), c->stream));
+    HIPCHK(c, hipMemsetAsync(d_g, 0, sizeof(RrTileDev), c->stream));
+    if (M > 0) {
+      hipLaunchKernelGGL(sz_k_rrt_iota, dim3(nb), dim3(256), 0, c->stream, iota, M);
+      size_t tmp_bytes = 0;
+      HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const long long*)S.okey, skey, (const int*)iota, srow, (size_t)M, 0u, 43u, c->stream));
+      if (tmp_bytes > c->weld_tmp_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->weld_tmp); c->weld_tmp = nullptr; c->weld_tmp_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->weld_tmp, tmp_bytes + tmp_bytes / 2));
+        c->weld_tmp_bytes = tmp_bytes + tmp_bytes / 2;
+      }
+      HIPCHK(c, rocprim::radix_sort_pairs(c->weld_tmp, tmp_bytes, (const long long*)S.okey, skey, (const int*)iota, srow, (size_t)M, 0u, 43u, c->stream));
+      hipLaunchKernelGGL(sz_k_rrt_active, dim3(nb), dim3(256), 0, c->stream, S, T, (const long long*)c->facc_buf, 1, act, inact, M, d_g, (const long long*)nullptr, 0);
+    }
+    HIPCHK(c, hipMemcpyAsync(&c->rrt_hg, d_g, sizeof(RrTileDev), hipMemcpyDeviceToHost, c->stream));
+    rc = sync_and_check(c);
+    if (rc == SZ_E_HIP) return rc;
+    if (!rc && (c->rrt_hg.ninact < 0 || c->rrt_hg.ninact > M)) { c->err = "tiled ridge / raft candidates: bad count of rows that are not active"; rc = SZ_E_CAPACITY; }
+  }
+  // ---- 1
+  std::vector<int> words((size_t)4 * 64, 0);
+  auto gather_words = [&](int w0, int w1, int w2, int w3) -> int {
+    int* hw = c->rrt_hw; hw[0] = w0; hw[1] = w1; hw[2] = w2; hw[3] = w3;
+    HIPCHK(c, hipMemcpyAsync(d_w, hw, 4 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (const int r2 = comm_allgather(c, d_w, d_wall, 4, NCCL_INT32, sizeof(int))) return r2;
+    HIPCHK(c, hipMemcpyAsync(words.data(), d_wall, (size_t)4 * n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SZ_OK;
+  };
+  if (const int r2 = gather_words(rc, rc ? 0 : c->rrt_hg.ninact, nown, 0)) return r2;
+  auto first_code = [&]() -> int {
+    for (int r = 0; r < n; r++) if (words[(size_t)4 * r] < 0) {
+      if (!rc) c->err = std::string(who) + ": rank " + std::to_string(r) + " reported a device error (this rank is clean; all ranks return together)";
+      return words[(size_t)4 * r];
+    }
+    return 0;
+  };
+  if (const int code = first_code()) return code;
+  long long Ng = 0, nin_all = 0;
+  int icnt[64] = { 0 };
+  for (int r = 0; r < n; r++) { icnt[r] = words[(size_t)4 * r + 1]; nin_all += icnt[r]; Ng += words[(size_t)4 * r + 2]; }
+  int first = 0;
+  long long* d_gin = nullptr;
+  if (nin_all > 0) {
+    ListGather LI(c, icnt, 1, 1);
+    rc = nin_all > 0x3fffffff ? (int)SZ_E_CAPACITY : LI.carve(c, P);
+    if (!rc) rc = dalloc(c, &d_gin, (size_t)nin_all, P);
+    if (const int r2 = comm_agree_rc(c, who, rc, &first)) return r2;
+    if (first) return first;
+    if (icnt[me] > 0) HIPCHK(c, hipMemcpyAsync(LI.d_rec, inact, (size_t)icnt[me] * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = LI.gather(c))) return rc;
+    std::vector<double> hall((size_t)LI.slots * n);
+    HIPCHK(c, hipMemcpyAsync(hall.data(), LI.d_all, hall.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<long long> gin;
+    for (int r = 0; r < n; r++) for (int k = 0; k < icnt[r]; k++) gin.push_back((long long)hall[(size_t)r * LI.slots + k]);
+    std::sort(gin.begin(), gin.end());
+    HIPCHK(c, hipMemcpyAsync(d_gin, gin.data(), gin.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (gin leaves the scope)
+  }
+  // ---- the count pass over the rows this rank evaluates
+  c->rrt_hd = RrDev{ 0ull, 0, 0 };
+  if (M > 0) {
+    hipLaunchKernelGGL(sz_k_rrt_active, dim3(nb), dim3(256), 0, c->stream, S, T, (const long long*)c->facc_buf, 0, act, inact, M, d_g, (const long long*)d_gin, (int)nin_all);
+    hipLaunchKernelGGL(sz_k_rrt_count, dim3(nb), dim3(256), 0, c->stream, S, A, T, gflag);
+    hipLaunchKernelGGL(sz_k_rr_scan, dim3(1), dim3(RR_TPB), 0, c->stream, A);
+    hipLaunchKernelGGL(sz_k_rrt_gscan, dim3(1), dim3(RR_TPB), 0, c->stream, S, (const int*)gflag, M, gkeys, M, d_g);
+    HIPCHK(c, hipMemcpyAsync(&c->rrt_hd, A.d, sizeof(RrDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->rrt_hg, d_g, sizeof(RrTileDev), hipMemcpyDeviceToHost, c->stream));
+  }
+  rc = sync_and_check(c);
+  if (rc == SZ_E_HIP) return rc;
+  const int Tn = c->rrt_hd.total, Gn = c->rrt_hg.nghost;
+  if (!rc && (Tn < 0 || (long long)Tn > (long long)M * S.rowcap || Gn < 0 || Gn > M || c->rrt_hd.draws > 2ull * (unsigned long long)std::max(M, 0))) {
+    c->err = "tiled ridge / raft candidates: bad table count"; rc = SZ_E_CAPACITY;
+  }
+  // ---- 2
+  if (const int r2 = gather_words(rc, rc ? 0 : Tn, rc ? 0 : Gn, rc ? 0 : (int)c->rrt_hd.draws)) return r2;
+  if (const int code = first_code()) return code;
+  c->err.clear();
+  int tcnt[64] = { 0 }, gcnt[64] = { 0 }, tbase[64] = { 0 };
+  long long total = 0, gtotal = 0, dsum = 0;
+  for (int r = 0; r < n; r++) { tcnt[r] = words[(size_t)4 * r + 1]; gcnt[r] = words[(size_t)4 * r + 2]; tbase[r] = (int)std::min(total, (long long)0x3fffffff); total += tcnt[r]; gtotal += gcnt[r]; dsum += words[(size_t)4 * r + 3]; }
+  *draws = dsum;
+  c->rrt_i.clear(); c->rrt_j.clear(); c->rrt_k.clear(); c->rrt_f.clear(); c->rrt_rownum.clear(); c->rrt_rowkey.clear();
+  if (total == 0) { trim_pool(P); return SZ_OK; }
+  // ---- 3
+  ListGather LK(c, gcnt, 1, 1), LE(c, tcnt, RRT_REC, 1);
+  long long *d_gk = nullptr, *d_ti = nullptr, *d_tj = nullptr, *d_rownum = nullptr; int *d_tk = nullptr, *d_base = nullptr, *d_bad = nullptr; double* d_tf = nullptr;
+  rc = total > 0x3fffffff || gtotal > 0x3fffffff || (long long)n * LE.slots > 0x3fffffff ? (int)SZ_E_CAPACITY : (int)SZ_OK;
+  (void)(rc || (rc = LK.carve(c, P)) || (rc = LE.carve(c, P)) || (rc = dalloc(c, &d_gk, (size_t)gtotal + 1, P)) || (rc = dalloc(c, &d_ti, (size_t)total, P)) ||
+         (rc = dalloc(c, &d_tj, (size_t)total, P)) || (rc = dalloc(c, &d_tk, (size_t)total, P)) || (rc = dalloc(c, &d_tf, (size_t)total, P)) ||
+         (rc = dalloc(c, &d_rownum, Mc, P)) || (rc = dalloc(c, &d_base, 64, P)) || (rc = dalloc(c, &d_bad, 1, P)));
+  if (const int r2 = comm_agree_rc(c, who, rc, &first)) return r2;
+  if (first) return first;
+  // ---- 4
+  if (Gn > 0) HIPCHK(c, hipMemcpyAsync(LK.d_rec, gkeys, (size_t)Gn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  if ((rc = LK.gather(c))) return rc;
+  {
+    std::vector<double> hall((size_t)LK.slots * n);
+    HIPCHK(c, hipMemcpyAsync(hall.data(), LK.d_all, hall.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<long long> gk;
+    for (int r = 0; r < n; r++) for (int k = 0; k < gcnt[r]; k++) gk.push_back((long long)hall[(size_t)r * LK.slots + k]);
+    std::sort(gk.begin(), gk.end());
+    gk.erase(std::unique(gk.begin(), gk.end()), gk.end());          // (distinct already: one rank owns a ghost's root parent)
+    gtotal = (long long)gk.size();
+    if (gtotal) HIPCHK(c, hipMemcpyAsync(d_gk, gk.data(), gk.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  // ---- 5
+  if ((rc = LE.upload_counts(c, tcnt))) return rc;
+  HIPCHK(c, hipMemcpyAsync(d_base, tbase, 64 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
+  A.cap = Tn;
+  if (Tn > 0) hipLaunchKernelGGL(sz_k_rrt_write, dim3(nb), dim3(256), 0, c->stream, S, A, T, LE.d_rec);
+  if ((rc = LE.gather(c))) return rc;
+  hipLaunchKernelGGL(sz_k_rrt_rename, dim3(grid_for((long long)n * LE.slots + M, 256, 2048)), dim3(256), 0, c->stream, S, (const double*)LE.d_all, (const int*)LE.d_cnt, (const int*)d_base, n, LE.slots,
+                     (const long long*)d_gk, (int)gtotal, Ng, d_ti, d_tj, d_tk, d_tf, d_rownum, M, d_bad);
+  std::vector<long long> ti((size_t)total), tj((size_t)total); std::vector<int> tk((size_t)total); std::vector<double> tf((size_t)total);
+  c->rrt_rownum.assign((size_t)M, -1); c->rrt_hbad = 0;
+  HIPCHK(c, hipMemcpyAsync(ti.data(), d_ti, (size_t)total * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tj.data(), d_tj, (size_t)total * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tk.data(), d_tk, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tf.data(), d_tf, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (M > 0) HIPCHK(c, hipMemcpyAsync(c->rrt_rownum.data(), d_rownum, (size_t)M * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  c->rrt_rowkey.assign((size_t)M, 0);
+  if (M > 0) HIPCHK(c, hipMemcpyAsync(c->rrt_rowkey.data(), S.okey, (size_t)M * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&c->rrt_hbad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  rc = sync_and_check(c);
+  if (rc == SZ_E_HIP) return rc;
+  // ---- 6
+  int all = 0;
+  if (const int r2 = comm_agree_bits(c, (rc ? 1 : 0) | (c->rrt_hbad ? 2 : 0), &all)) return r2;
+  if (all & 1) { if (!rc) c->err = std::string(who) + ": a rank reported a device error (this rank is clean; all ranks return together)"; return SZ_E_CAPACITY; }
+  if (all & 2) { c->err = std::string(who) + ": an entry names a ghost no rank owns (the ranks do not hold the same floes' bits)"; return SZ_E_STATE; }
+  c->err.clear();
+  // ascending i, then the emitting rank's row order (the gathered order: a stable sort keeps it)
+  std::vector<int> ord((size_t)total);
+  for (int k = 0; k < (int)total; k++) ord[k] = k;
+  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return ti[a] < ti[b]; });
+  c->rrt_i.resize((size_t)total); c->rrt_j.resize((size_t)total); c->rrt_k.resize((size_t)total); c->rrt_f.resize((size_t)total);
+  for (int k = 0; k < (int)total; k++) { c->rrt_i[k] = ti[ord[k]]; c->rrt_j[k] = tj[ord[k]]; c->rrt_k[k] = tk[ord[k]]; c->rrt_f[k] = tf[ord[k]]; }
+  trim_pool(P);
+  *ntable = (int)total;
+  return SZ_OK;
+}
+}  // namespace
+
 // ---------------------------------------------------------------- the batch drivers of sz_tile_run
 namespace {
 // status.fuse_idx of a tiled context, in GLOBAL floe numbers: the order keys of the local rows of the step that ended the batch (owned
@@ -1408,6 +1617,56 @@ static int tile_run_inline(sz_ctx* c, int nsteps, int tstep0, int dt, int coupli
   c->fuse_lists.resize(c->hostM);
   return rc;
 }
+// The second half of a split step (tile_step_body) and what settles it: the integrator, the halo rows and ghosts dropped, and the ranks' agreement
+// on the error word and on "a floe of mine was tagged in this step" (*any_tag: of any rank)
+constexpr int RRS_BIT_TAG = 1 << 30;
+static int tile_rr_second_half(sz_ctx* c, int tstep, int dt, int coupling_dt, int flags, int* any_tag) {
+  State& S = c->S;
+  *any_tag = 0;
+  c->hostN = (int)c->tile_gidx.size();          // (the pass looked at the whole list; the host-side count of a tile is its owned floes)
+  S.stop_on_tags = 1; S.step = 1;
+  if (int rc = tile_step_body(c, nullptr, 0, 0, tstep, dt, coupling_dt, flags, TILE_STEP_SECOND)) return rc;
+  S.step = 0;
+  int hl[C_COUNT] = { 0 };
+  const int rc = sync_and_check(c, hl);
+  if (rc == SZ_E_HIP) return rc;
+  int all = 0;
+  if (const int rc2 = comm_agree_bits(c, (rc ? (c->last_err_bits ? c->last_err_bits & ~RRS_BIT_TAG : 1) : 0) | (hl[C_STOP] > 0 ? RRS_BIT_TAG : 0), &all)) return rc2;
+  if (all & ~RRS_BIT_TAG) return SZ_E_CAPACITY;
+  c->err.clear();
+  *any_tag = (all & RRS_BIT_TAG) != 0;
+  c->fuse_lists.resize(c->hostM);
+  c->inter_any = true; c->inter_lost = false;
+  return SZ_OK;
+}
+// A ridge / raft step of sz_tile_run (tstep % rr_dt == 0), a one-step segment of its own whichever driver runs the segments around it: pack,
+// exchange, the first half of the list-based step, the candidate pass (tile_rr_pass: it starts with the agreement on the error word).  Empty
+// table: the draws go to the batch's counter, the second half runs, *any_tag says whether a floe of any rank was tagged in the step.  Not empty:
+// *pending = 1, the list keeps its halo rows and ghosts, and sz_tile_step_finish runs the second half.
+static int tile_rr_step(sz_ctx* c, int tstep, int dt, int coupling_dt, int flags, int* pending, int* any_tag) {
+  State& S = c->S; const int n = c->comm_n;
+  *pending = 0; *any_tag = 0;
+  BatchModes modes(c);
+  world_rings(c);
+  tile_cleanup(c);          // (halo rows and ghosts a host-driven step may have left attached)
+  S.stop_on_tags = 1;
+  HIPCHK(c, clear_stop_words(c, W_STOP | W_RETRYSTOP));
+  c->tile_dt = dt;
+  S.step = 1;
+  if (int rc = rebox_if_due(c)) return rc;
+  c->tile_since_box++;
+  tile_pack(c);
+  if (int rc = tile_exchange(c, true)) return rc;
+  if (n > 1 && hipStreamWaitEvent(c->stream, c->ev_recv, 0) != hipSuccess) { c->err = "hipStreamWaitEvent (halo exchange)"; return SZ_E_HIP; }
+  if (int rc = tile_step_body(c, c->d_recv, n, c->halo_cap, tstep, dt, coupling_dt, flags, TILE_STEP_FIRST)) return rc;
+  S.step = 0;
+  c->tile_dirty = false;          // (the pass must see the whole list: nothing is dropped before the second half)
+  int nt = 0; long long nd = 0;
+  if (int rc = tile_rr_pass(c, &nt, &nd)) { c->tile_dirty = true; return rc; }
+  if (nt > 0) { *pending = 1; c->inter_any = true; c->inter_lost = false; return SZ_OK; }
+  c->rr_draws += nd;
+  return tile_rr_second_half(c, tstep, dt, coupling_dt, flags, any_tag);
+}
 }  // namespace
 
 // nsteps x timestep_sim! of a tiled run, collectively on every rank (same arguments everywhere)
@@ -1416,12 +1675,17 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   if (c && !c->weld_dts.empty() && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled welding overlaps gather the candidates and rings over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
   if (c && c->frac_kind != SZ_FRAC_OFF && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled fracture criteria gather the mean height over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
   if (!c) return SZ_E_STATE;
-  if (c->rr_on) { c->err = "sz_tile_run has no ridge / raft candidate pass (the ghosts of a tiled list are halo rows): sz_set_ridgeraft(0)"; return SZ_E_STATE; }
+  if (c->rr_pending >= 0) { c->err = "sz_tile_run: a ridge / raft step is pending (sz_ridgeraft_pending): sz_tile_step_finish runs its second half first"; return SZ_E_STATE; }
+  if (c->rr_on && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled ridge / raft candidates gather the ghost keys and the entries over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
   if (int rc = tiled_ready(c, "sz_tile_run")) return rc;
   if (nsteps < 0) return SZ_E_ARG;
+  c->rr_draws = 0;
   const bool frac = c->frac_kind != SZ_FRAC_OFF;
   const bool weld = !c->weld_dts.empty();
-  if ((frac || weld) && c->two_way) { c->err = std::string("tiled two-way coupling with ") + (frac ? "a fracture criterion set: its per-step all-reduce path has no tested stop: sz_set_fracture(SZ_FRAC_OFF)" : "welding set: its per-step all-reduce path has no tested stop: sz_set_welding(0)"); return SZ_E_STATE; }
+  const bool rr = c->rr_on && !(flags & SZ_NO_STOP) && nsteps > 0;
+  if (rr && !(flags & SZ_COLLISIONS_ON)) { c->err = "sz_tile_run with ridge / raft set: the candidates are read from this step's interaction rows (SZ_COLLISIONS_ON)"; return SZ_E_STATE; }
+  if (rr && (flags & SZ_COUPLING_ON) && !c->have_fields) { c->err = "sz_set_fields must be called before coupling"; return SZ_E_STATE; }
+  if ((frac || weld || c->rr_on) && c->two_way) { c->err = std::string("tiled two-way coupling with ") + (frac ? "a fracture criterion set: its per-step all-reduce path has no tested stop: sz_set_fracture(SZ_FRAC_OFF)" : weld ? "welding set: its per-step all-reduce path has no tested stop: sz_set_welding(0)" : "ridge / raft set: its per-step all-reduce path has no tested stop: sz_set_ridgeraft(0)"); return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
   // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
   // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
@@ -1449,27 +1713,50 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   // overlap table (tile_weld_pass), then removal.  A table that is not empty ends the batch on every rank (steps_done counts the welding step), an empty
   // one lets the next segment start.  A tag on a welding step ends the batch there, with removal set too, as in sz_step; where the fracture pass has
   // not agreed it already, the welding pass's last agreement does.
-  // Two-way coupling across tiles has no tag stop of its own to hang a pass on: removal is not engaged there, a criterion or welding refused.
-  // SZ_NO_STOP batches and contexts with none of the three set take the drivers as they are.
-  if ((!c->rm_on && !frac && !weld) || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return segment(nsteps, tstep0, steps_done);
+  // Two-way coupling across tiles has no tag stop of its own to hang a pass on: removal is not engaged there, a criterion, welding or ridge / raft refused.
+  // SZ_NO_STOP batches and contexts with none of the four set take the drivers as they are.
+  // Ridge / raft (sz_set_ridgeraft): the segments also end BEFORE a ridge / raft step (tstep % rr_dt == 0: timestep_ridging_rafting! stands in the middle
+  // of the step), and that step is a one-step segment of its own (tile_rr_step).  A table that is not empty ends the batch on every rank with the
+  // step PENDING: steps_done does not count it, the lists keep their halo rows and ghosts, sz_tile_step_finish runs the rest.  An empty one: the draws
+  // are counted (sz_ridgeraft_draws), the step is finished, and what follows any segment's last step follows it -- a tag any rank raised (agreed behind
+  // the second half), the fracture pass, the welding pass, removal.  A segment cut before a ridge / raft step on no fracture or welding step has no
+  // pass to carry a tag of its last step to the peers: the ranks agree on it there.
+  if ((!c->rm_on && !frac && !weld && !rr) || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return segment(nsteps, tstep0, steps_done);
   int done = 0;
   while (done < nsteps) {
-    int len = nsteps - done, set = -1; bool fstep = false;
-    for (int s = 0; s + 1 < nsteps - done; s++) {
-      const int tstep = tstep0 + done + s;
-      fstep = frac && tstep % c->frac_dt == 0;
-      set = weld ? weld_set_at(c, tstep) : -1;
-      if (fstep || set >= 0) { len = s + 1; break; }
-    }
+    int lim = nsteps - done;
+    if (rr) for (int s = 1; s < lim; s++) if ((tstep0 + done + s) % c->rr_dt == 0) { lim = s; break; }
+    int len = lim, set = -1, rc = SZ_OK; bool fstep = false;
     int32_t more = 0;
+    bool agreed = false;          // the tag of the segment's last step is every rank's knowledge already
     c->tile_stop_raised = 0;
-    const int rc = segment(len, tstep0 + done, &more);
+    if (rr && (tstep0 + done) % c->rr_dt == 0) {
+      const int tstep = tstep0 + done;
+      int pend = 0, tag = 0;
+      if (int rc2 = tile_rr_step(c, tstep, dt, coupling_dt, flags, &pend, &tag)) return rc2;
+      if (pend) { c->rr_pending = tstep; return SZ_OK; }
+      len = more = 1; fstep = frac && tstep % c->frac_dt == 0; set = weld ? weld_set_at(c, tstep) : -1;
+      c->tile_stop_raised = tag ? 1 : 0; agreed = true;
+    } else {
+      for (int s = 0; s < lim && s + 1 < nsteps - done; s++) {
+        const int tstep = tstep0 + done + s;
+        fstep = frac && tstep % c->frac_dt == 0;
+        set = weld ? weld_set_at(c, tstep) : -1;
+        if (fstep || set >= 0) { len = s + 1; break; }
+      }
+      rc = segment(len, tstep0 + done, &more);
+    }
     done += more;
     if (steps_done) *steps_done = done;
     if (rc || done >= nsteps || more < 1) return rc;
-    if (more == len && (fstep || set >= 0)) {          // the segment's last step ran, and the batch goes on behind it: it was cut here, on a fracture or a welding step
+    if (more == len) {          // the segment's last step ran, and the batch goes on behind it: it was cut here, on a fracture or a welding step or before a ridge / raft step
       int tag = 0;
       const bool my_tag = c->tile_stop_raised == len;
+      if (agreed) tag = my_tag;
+      else if (!fstep && set < 0) {          // (cut before a ridge / raft step: no pass carries the tag)
+        if (int rc2 = comm_agree_bits(c, my_tag ? RRS_BIT_TAG : 0, &tag)) return rc2;
+        c->err.clear();
+      }
       if (fstep) {
         int cand = 0, mine = 0;
         if (int rc2 = tile_frac_pass(c, my_tag, false, &cand, &tag, &mine)) return rc2;
@@ -1488,5 +1775,67 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
     if (int rc2 = tile_remove_pass(c, &ok, &nr, &nd)) return rc2;
     if (!ok) return SZ_OK;
   }
+  return SZ_OK;
+}
+
+// ---------------------------------------------------------------- ridge / raft on a tiled context: the entry points of a pending stop
+namespace {
+int tile_rr_pending_ready(sz_ctx* c, const char* who) {
+  if (int rc = tiled_ready(c, who)) return rc;
+  if (!c->rr_on) { c->err = std::string(who) + ": ridge / raft is not set (sz_set_ridgeraft)"; return SZ_E_STATE; }
+  if (c->rr_pending < 0) { c->err = std::string(who) + ": no ridge / raft step is pending (sz_tile_run stops there; sz_ridgeraft_pending)"; return SZ_E_STATE; }
+  return SZ_OK;
+}
+}  // namespace
+// the table of the pending step (collective: it runs the pass again), in the numbering and order of sz_ridgeraft_candidates
+int sz_tile_ridgeraft_candidates(sz_ctx* c, int32_t* n, int32_t cap, int64_t* idx_i, int64_t* idx_j, int32_t* kind, double* frac, int64_t* n_draws) {
+  if (n) *n = 0;
+  if (n_draws) *n_draws = 0;
+  if (!c || !n) return SZ_E_ARG;
+  if (int rc = tile_rr_pending_ready(c, "sz_tile_ridgeraft_candidates")) return rc;
+  (void)hipSetDevice(c->device);
+  int nt = 0; long long nd = 0;
+  if (int rc = tile_rr_pass(c, &nt, &nd)) return rc;
+  *n = nt;
+  if (n_draws) *n_draws = nd;
+  if (!idx_i && !idx_j && !kind && !frac) return SZ_OK;
+  if (cap < nt) { c->err = "sz_tile_ridgeraft_candidates: cap is smaller than the table (*n)"; return SZ_E_ARG; }          // (the same table on every rank: with the same cap, the same answer)
+  for (int k = 0; k < nt; k++) {
+    if (idx_i) idx_i[k] = c->rrt_i[k];
+    if (idx_j) idx_j[k] = c->rrt_j[k];
+    if (kind) kind[k] = c->rrt_k[k];
+    if (frac) frac[k] = c->rrt_f[k];
+  }
+  return SZ_OK;
+}
+// the single context's list number of every local row of the pending step -- owned floes, halo floes, the ghosts of both (-1: a ghost no rank owns)
+int sz_tile_list_numbers(sz_ctx* c, int64_t* out, int64_t cap) {
+  if (!c || !out) return SZ_E_ARG;
+  if (int rc = tile_rr_pending_ready(c, "sz_tile_list_numbers")) return rc;
+  if (cap < (int64_t)c->rrt_rownum.size()) { c->err = "sz_tile_list_numbers: cap is smaller than the local list"; return SZ_E_ARG; }
+  for (size_t k = 0; k < c->rrt_rownum.size(); k++) out[k] = c->rrt_rownum[k];
+  return SZ_OK;
+}
+// ... and its order key (the partner column of a downloaded row holds key + 1)
+int sz_tile_list_keys(sz_ctx* c, int64_t* out, int64_t cap) {
+  if (!c || !out) return SZ_E_ARG;
+  if (int rc = tile_rr_pending_ready(c, "sz_tile_list_keys")) return rc;
+  if (cap < (int64_t)c->rrt_rowkey.size()) { c->err = "sz_tile_list_keys: cap is smaller than the local list"; return SZ_E_ARG; }
+  for (size_t k = 0; k < c->rrt_rowkey.size(); k++) out[k] = c->rrt_rowkey[k];
+  return SZ_OK;
+}
+// the second half of the pending step on what the device holds, collectively
+int sz_tile_step_finish(sz_ctx* c, int32_t tstep, int32_t dt, int32_t coupling_dt, int32_t flags) {
+  if (!c) return SZ_E_ARG;
+  if (c->rr_pending < 0) { c->err = "sz_tile_step_finish: no ridge / raft step is pending"; return SZ_E_STATE; }
+  if (tstep != c->rr_pending) { c->err = "sz_tile_step_finish: tstep is not the pending timestep (sz_ridgeraft_pending)"; return SZ_E_ARG; }
+  if (int rc = tiled_ready(c, "sz_tile_step_finish")) return rc;
+  if ((flags & SZ_COUPLING_ON) && !c->have_fields) { c->err = "sz_set_fields must be called before coupling"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  BatchModes modes(c);
+  int tag = 0;
+  if (int rc = tile_rr_second_half(c, tstep, dt, coupling_dt, flags, &tag)) return rc;
+  c->rr_pending = -1;
+  c->tile_stop_raised = tag ? 1 : 0;
   return SZ_OK;
 }

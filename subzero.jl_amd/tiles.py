@@ -212,6 +212,7 @@ class TiledWorld:
         self.tw_buf = None                                    # per-cell partial sums of the two-way coupling
         self._frac_dt = 0                                     # Δt of the criterion set through set_fracture (0: none): run() asks at its own cuts
         self._weld = None                                     # (dts, nxs, nys, max_weld_area) set through set_welding (None: off): run() asks at its own cuts
+        self._rr_draws = 0                                    # per-floe draws of the ridge / raft steps the last run() ran through (sum over its calls)
 
     def _agree(self, ok, what):
         """collective: raise TileSetupError on every rank when `ok` is false on any of them"""
@@ -595,6 +596,62 @@ class TiledWorld:
         w._chk(w.L.sz_tile_debug_weld_npairs(w.h, C.byref(n)))
         return int(n.value)
 
+    # ---- ridge / raft candidates across tiles (sz_tile_run with ridge / raft set, sz_tile_ridgeraft_candidates: library backends)
+    def set_ridgeraft(self, on=True, dt=150, min_ridge_height=0.2, max_floe_ridge_height=5.0, max_domain_ridge_height=1.25,
+                      max_floe_raft_height=0.25, max_domain_raft_height=0.25):
+        """World.set_ridgeraft for this rank's tile (the same arguments on every rank).  run(..., stop_on_tags=True) then stops on every rank in the
+        middle of the first ridge / raft step (tstep % dt == 0) whose candidate table of the global list is not empty -- the step World.run stops
+        in for the undivided list: that step is not counted, ridgeraft_pending() names it, the lists keep their halo rows and ghosts,
+        ridgeraft_candidates() gives the table and finish_step() runs the rest of the step.  Steps with an empty table are run through."""
+        self._library_only("set_ridgeraft")
+        self.world.set_ridgeraft(on, dt, min_ridge_height, max_floe_ridge_height, max_domain_ridge_height, max_floe_raft_height, max_domain_raft_height)
+
+    def ridgeraft_pending(self):
+        """the timestep whose ridge / raft step is pending, or -1"""
+        return self.world.ridgeraft_pending()
+
+    def ridgeraft_draws(self):
+        """the per-floe draws of the ridge / raft steps the last run() ran through, over the global list: the same number on every rank"""
+        return self._rr_draws
+
+    def ridgeraft_candidates(self):
+        """at a pending stop (collective): (i, j, kind, frac, n_draws) of the global list, the whole table on every rank -- what
+        World.ridgeraft_candidates() returns for the undivided list, in its numbering and order (int64 numbers), kind and frac to the bit"""
+        self._library_only("ridgeraft_candidates")
+        w = self.world
+        n = C.c_int32(0); nd = C.c_int64(0)
+        w._chk(w.L.sz_tile_ridgeraft_candidates(w.h, C.byref(n), 0, None, None, None, None, C.byref(nd)))
+        cap = max(int(n.value), 1)
+        i = np.zeros(cap, np.int64); j = np.zeros(cap, np.int64); k = np.zeros(cap, np.int32); f = np.zeros(cap)
+        w._chk(w.L.sz_tile_ridgeraft_candidates(w.h, C.byref(n), cap, capi.ptr(i, capi._lp), capi.ptr(j, capi._lp), capi.ptr(k, capi._ip), capi.ptr(f), C.byref(nd)))
+        m = int(n.value)
+        return i[:m].copy(), j[:m].copy(), k[:m].copy(), f[:m].copy(), int(nd.value)
+
+    def _list_column(self, fn):
+        w = self.world
+        cap = int(w.stats()["M"])
+        out = np.zeros(max(cap, 1), np.int64)
+        w._chk(fn(w.h, capi.ptr(out, capi._lp), cap))
+        return out[:cap].copy()
+
+    def list_numbers(self):
+        """at a pending stop: the single context's list number of every local row -- owned floes, halo floes, the ghosts of both, in local order"""
+        self._library_only("list_numbers")
+        return self._list_column(self.world.L.sz_tile_list_numbers)
+
+    def list_keys(self):
+        """at a pending stop: the order key of every local row, in local order; the partner column of a downloaded interaction row holds key + 1"""
+        self._library_only("list_keys")
+        return self._list_column(self.world.L.sz_tile_list_keys)
+
+    def finish_step(self, tstep, dt, coupling_dt=10, collisions_on=True, coupling_on=True):
+        """the second half of the pending ridge / raft step on what the device holds (collective): the halo rows and ghosts are dropped behind it"""
+        self._library_only("finish_step")
+        w = self.world
+        flags = (capi.COLLISIONS_ON if collisions_on else 0) | (capi.COUPLING_ON if coupling_on else 0)
+        w._chk(w.L.sz_tile_step_finish(w.h, int(tstep), int(dt), int(coupling_dt), flags))
+        w._host_stale = True
+
     def maybe_repartition(self):
         """Ownership is static between calls of repartition(); floes drift.  Collective: re-tile when more than
         `repartition_fraction` of all floes has left the tile that owns it (cheap test: the owned centroids against the
@@ -622,8 +679,10 @@ class TiledWorld:
         there if it is positive: run(n) returns what World.run(n) returns.  With set_welding() it likewise ends after the first welding step
         whose overlap table of the global list is not empty, and asks for the table itself where a call's last step is a welding step.  A limit that stays: a floe TAGGED on exactly the last step of a
         call is removed behind the first step of the next call, one step later than World.run(n) would; a caller that needs the single
-        context's timing there keeps nsteps within one call or calls remove_floes() itself."""
+        context's timing there keeps nsteps within one call or calls remove_floes() itself.  With set_ridgeraft() it returns at a pending
+        stop (ridgeraft_pending() >= 0) with the steps before that step, and does not repartition there."""
         done = 0
+        self._rr_draws = 0
         while done < nsteps:
             k = min(nsteps - done, self.repartition_every - self._since_check) if self.nranks > 1 else nsteps - done
             if self.backend in ("library", "library-host"):
@@ -632,6 +691,7 @@ class TiledWorld:
                 ran = C.c_int32(0)
                 w._chk(w.L.sz_tile_run(w.h, int(k), int(tstep0 + done), int(dt), int(coupling_dt), flags, C.byref(ran)))
                 w._host_stale = True
+                self._rr_draws += w.ridgeraft_draws()
                 if stop_on_tags and getattr(w, "_removal_on", False):
                     self._after_pass()
                 if ran.value < k:
