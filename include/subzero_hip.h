@@ -20,6 +20,9 @@
  *   sz_remove_ghosts              <- ghost-row deletion in timestep_sim!    src/simulation_components/simulation.jl:138-144
  *   sz_remove_floes               <- remove_floes!(floes, grid, domain, dissolved, floe_settings), where simplify_floes!
  *                                    reduces to it                         src/physical_processes/simplification.jl:279-314
+ *   sz_download_rows /            <- what the host-side topology changes do to the floe list: deleteat!, assignment in place,
+ *   sz_splice_floes                  append! (fracture_floes!, fuse / replace_floe!, ridging and rafting, smoothing), on the rows
+ *                                    they name; the floes themselves are still made by the reference on the host
  *   sz_timestep_coupling          <- timestep_coupling!(model, Δt, consts, coupling_settings,
  *                                    floe_settings), one-way part           src/physical_processes/coupling.jl:1705-1738
  *   sz_timestep_floe_properties   <- timestep_floe_properties!(floes, tstep, Δt, floe_settings)
@@ -322,6 +325,39 @@ int sz_remove_floes(sz_ctx *ctx, int32_t *done, int32_t *n_removed, int32_t *n_d
 int sz_upload_dissolved(sz_ctx *ctx, const double *dissolved);
 int sz_download_dissolved(sz_ctx *ctx, double *dissolved);
 int sz_download_origin(sz_ctx *ctx, int32_t *origin);
+
+/* ---- rows down, rows back (csrc/sz_splice.hpp): the host's side of a stop -- fracture_floes!, the fuse of timestep_welding!, ridging
+   and rafting, smoothing -- changes a few floes; these two calls move those floes alone, and the others do not leave HBM.
+   sz_download_rows: `rows` holds n 0-based parent rows in any order, none twice (SZ_E_ARG: out of range or repeated).  With cols == NULL only
+   sizes3 = {ring points, sub-floe points, interaction rows} of the selection is written, so that the caller can size its buffers.  Otherwise every
+   non-NULL column receives n entries in the order of `rows` (the CSR offsets vert_off / sub_off / inter_off n + 1 entries, starting at 0; ghost_off
+   zeros; ghost_idx is not written), each value with the bits sz_download_floes, sz_download_subpoints or sz_download_interactions give for that
+   row.  One pack kernel writes the selection into one staging buffer, which comes down in one copy.  Works on any context that holds floes.
+   sz_splice_floes: `del` (n_del) and `rep` (n_rep) are ascending 0-based parent rows of the list AS IT IS, without repeats, no row in both.  cols
+   holds n_rep + n_app floes in the layout of sz_upload_floes (vert_off, vx, vy, cx, cy required; NULL columns are read as zeros, a NULL id as
+   row + 1, a NULL status as active; ghost columns are ignored): the first n_rep overwrite the rows `rep`, the other n_app are appended behind the
+   last kept row in the order given.  Deleted rows vanish, kept rows keep their order, as deleteat! / append! do.  inter_off (n_rep + n_app + 1) /
+   inter_rows (k x 7) give floe.interactions of the uploaded floes (NULL: none); kept floes keep theirs, partner numbers untouched, as the removal
+   pass leaves them (a partner that was a ghost of the last resident step is stored as the number sz_download_interactions reports for it).
+   Afterwards the context is the one that sz_upload_floes(N', N', edited list) + sz_upload_interactions(edited lists) would have left in this same
+   context: bit for bit in everything downloadable (columns, rings, sub-floe points, interaction rows, the counts of sz_get_stats, sz_download_origin
+   = the identity), and everything derived is as sz_upload_floes leaves it (made again on demand: collision records, the fp32 copies of mixed
+   precision, the blocked points of the forcing kernel, the static grid and the ghost-candidate list, the stop words, the per-capacity scratch of
+   fracture, welding, removal, ridge / raft and two-way coupling).  Settings, domain, fields, the ocean.dissolved lattice and moving walls are left
+   alone; the neighbour capacity keeps its value (it grows on demand).  An edit the capacities of the last upload cannot take (an eighth more rows or
+   ring points than it held) is not refused: the context is carved anew on the device for the edited list and the rows move there; the sub-floe
+   point pool, which an upload gives no slack, grows by itself.  The result is the same.
+   Refusals leave the state untouched: ghosts in the list (sz_remove_ghosts first) or a pending ridge / raft step (sz_step_finish first) and tiled
+   contexts: SZ_E_STATE; rows unsorted, repeated, out of range or both deleted and replaced, an edit that leaves no floe, an uploaded ring that is
+   open (first point != last, or under 4 points) or longer than 255 points (what the row-moving kernels and the collision record carry): SZ_E_ARG;
+   more interaction rows for a floe than the stride holds: SZ_E_CAPACITY, as sz_upload_interactions.  n_del = n_rep = n_app = 0 changes nothing.
+   The _f32 twins widen and round exactly as sz_upload_floes_f32 / sz_download_floes_f32 / sz_download_interactions_f32 do. */
+int sz_download_rows(sz_ctx *ctx, int32_t n, const int32_t *rows, sz_floe_columns *cols, int32_t *inter_off, double *inter_rows, int64_t *sizes3);
+int sz_splice_floes(sz_ctx *ctx, int32_t n_del, const int32_t *del, int32_t n_rep, const int32_t *rep, int32_t n_app, const sz_floe_columns *cols,
+                    const int32_t *inter_off, const double *inter_rows);
+int sz_download_rows_f32(sz_ctx *ctx, int32_t n, const int32_t *rows, sz_floe_columns_f32 *cols, int32_t *inter_off, float *inter_rows, int64_t *sizes3);
+int sz_splice_floes_f32(sz_ctx *ctx, int32_t n_del, const int32_t *del, int32_t n_rep, const int32_t *rep, int32_t n_app, const sz_floe_columns_f32 *cols,
+                        const int32_t *inter_off, const float *inter_rows);
 
 /* ---- ridge / raft candidates on the device (csrc/sz_ridgeraft.hpp): what tells whether timestep_ridging_rafting!
    (src/physical_processes/ridge_raft.jl:676-837) has anything to do.  The reference calls it on the list WITH its ghosts, between

@@ -705,6 +705,99 @@ function pull_dissolved!(eng::HIPEngine, ocean)
     return
 end
 
+# ------------------------------------------------------------------------------------------------ rows down, rows back
+# floe.interactions of the floes of a list as the CSR pair the C side takes (row-major k x 7)
+function interactions_csr(floes)
+    M = length(floes)
+    off = Vector{Int32}(undef, M + 1); off[1] = 0
+    for i in 1:M
+        off[i+1] = off[i] + floes.num_inters[i]
+    end
+    rows = Matrix{Float64}(undef, 7, max(Int(off[end]), 1))
+    for i in 1:M, k in 1:floes.num_inters[i]
+        rows[:, off[i]+k] .= @view floes.interactions[i][k, :]
+    end
+    return off, rows
+end
+
+"""
+    download_rows!(eng, floes, rows)
+
+The resident state of the parents `rows` (1-based, any order, none twice) into those rows of the host list (`sz_download_rows`): columns,
+geometry, sub-floe points, status and interactions, each value as `pull_state!` would give it -- the other floes are not touched and nothing
+else crosses.  `pack` passes pointers to where the columns lie, so the named rows are packed from a contiguous copy (`floes[rows]`) and
+written back row by row.  The fuse lists (`status.fuse_idx`) live on the host and are not part of this call.
+
+Written, not run: there is no Julia on the machines this engine is built and tested on.  The C call underneath is held to the bits of a full
+download by `tests/test_splice_gpu.py`.
+"""
+function download_rows!(eng::HIPEngine, floes, rows::AbstractVector{<:Integer})
+    n = length(rows)
+    n == 0 && return
+    r0 = Int32.(rows .- 1)
+    sizes = Vector{Int64}(undef, 3)
+    check(eng, @ccall lib.sz_download_rows(eng.ctx::Ptr{Cvoid}, Int32(n)::Int32, r0::Ptr{Int32}, C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Int32},
+                                           C_NULL::Ptr{Float64}, sizes::Ptr{Int64})::Cint)
+    sub = floes[rows]
+    P = pack(sub, n)
+    resize!(P.vx, sizes[1]); resize!(P.vy, sizes[1]); resize!(P.sx, sizes[2]); resize!(P.sy, sizes[2])
+    P.cols.vx = pointer(P.vx); P.cols.vy = pointer(P.vy); P.cols.sx = pointer(P.sx); P.cols.sy = pointer(P.sy)
+    off = Vector{Int32}(undef, n + 1); irows = Matrix{Float64}(undef, 7, max(Int(sizes[3]), 1))
+    GC.@preserve P sub begin
+        check(eng, @ccall lib.sz_download_rows(eng.ctx::Ptr{Cvoid}, Int32(n)::Int32, r0::Ptr{Int32}, P.cols::Ref{SzFloeColumns}, off::Ptr{Int32},
+                                               irows::Ptr{Float64}, C_NULL::Ptr{Int64})::Cint)
+    end
+    unpack_geometry!(sub, P); unpack_status!(sub, P)
+    for k in 1:n
+        s = P.sub_off[k]+1:P.sub_off[k+1]
+        sub.x_subfloe_points[k] = P.sx[s]; sub.y_subfloe_points[k] = P.sy[s]
+        r = off[k]+1:off[k+1]
+        sub.interactions[k] = permutedims(irows[:, r]); sub.num_inters[k] = length(r)
+        sub.collision_force[k][1, 1] = P.coll_fx[k]; sub.collision_force[k][1, 2] = P.coll_fy[k]
+        floes[rows[k]] = sub[k]
+    end
+    return
+end
+
+"""
+    splice!(eng, floes, del, rep, app_range)
+
+The host's edit of a few floes into the resident list (`sz_splice_floes`), the other floes staying on the device.  `floes` is the host list with
+the edit applied EXCEPT the deletion: the rows `rep` changed in place (`replace_floe!`, a fuse, a smoothed ring), the new floes appended at
+`app_range` (pieces of a fracture or a ridge), the rows `del` still there -- so `del` and `rep` number host and device rows alike (1-based,
+ascending, none in both).  Only the rows `rep` and `app_range` are packed (the existing `pack` on a contiguous copy of them) and uploaded with
+their interactions; the rows `del` are then deleted from the host list as `deleteat!` does, and `eng.host_rows` is the identity again, as
+after `upload!`.  Refused (the library's message is thrown, nothing has changed): ghosts in the list, a pending ridge / raft step, a tiled
+context, rows that are unsorted, repeated or out of range.
+
+`run_resident!` does not call this yet: it still makes the full round trip at a stop (`pull_state!`, `upload!`).
+
+Written, not run: there is no Julia on the machines this engine is built and tested on.  The C call underneath is held, bit for bit, to an
+upload of the edited list by `tests/test_splice_gpu.py`.
+"""
+function splice!(eng::HIPEngine, floes, del::AbstractVector{<:Integer}, rep::AbstractVector{<:Integer}, app_range::AbstractUnitRange{<:Integer})
+    staged = vcat(collect(Int, rep), collect(Int, app_range))
+    d0 = Int32.(del .- 1); r0 = Int32.(rep .- 1)
+    if isempty(staged)
+        check(eng, @ccall lib.sz_splice_floes(eng.ctx::Ptr{Cvoid}, Int32(length(d0))::Int32, d0::Ptr{Int32}, Int32(0)::Int32, C_NULL::Ptr{Int32},
+                                              Int32(0)::Int32, C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Int32}, C_NULL::Ptr{Float64})::Cint)
+    else
+        sub = floes[staged]
+        P = pack(sub, length(sub))
+        off, irows = interactions_csr(sub)
+        GC.@preserve P sub begin
+            check(eng, @ccall lib.sz_splice_floes(eng.ctx::Ptr{Cvoid}, Int32(length(d0))::Int32, d0::Ptr{Int32}, Int32(length(r0))::Int32, r0::Ptr{Int32},
+                                                  Int32(length(app_range))::Int32, P.cols::Ref{SzFloeColumns}, off::Ptr{Int32},
+                                                  irows::Ptr{Float64})::Cint)
+        end
+    end
+    for i in reverse(sort(collect(Int, del)))
+        StructArrays.foreachfield(f -> deleteat!(f, i), floes)
+    end
+    eng.host_rows = collect(1:length(floes))
+    return
+end
+
 # ------------------------------------------------------------------------------------------------ ridging and rafting
 """
     set_ridgeraft!(eng, sim)

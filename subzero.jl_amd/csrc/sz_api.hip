@@ -26,6 +26,7 @@
 #include "sz_fracture_tile.hpp"
 #include "sz_weld_tile.hpp"
 #include "sz_ridgeraft_tile.hpp"
+#include "sz_splice.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 #include "sz_ctx.hpp"
 #include "sz_comm.hpp"
@@ -747,7 +748,7 @@ void sz_destroy(sz_ctx* c) {
   (void)hipFree(c->d_stats); (void)hipFree(c->S.acc);
   (void)hipFree(c->frac_d); (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx);
   free_pool(c->weld_allocs); free_pool(c->weldt_allocs); (void)hipFree(c->weld_tmp); free_pool(c->rr_allocs); free_pool(c->rrt_allocs);
-  free_pool(c->rm_allocs);
+  free_pool(c->rm_allocs); free_pool(c->sp_allocs);
   free_pool(c->frac_allocs);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
   (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2);
@@ -2474,6 +2475,348 @@ int sz_download_origin(sz_ctx* c, int32_t* origin) {
   if (int rc = sync_and_check(c)) return rc;
   if (c->hostN > 0) HIPCHK(c, hipMemcpy(origin, c->origin, (size_t)c->hostN * sizeof(int), hipMemcpyDeviceToHost));
   return SZ_OK;
+}
+
+// ---------------------------------------------------------------- rows down, rows back (sz_splice.hpp)
+namespace {
+// the columns the row-moving kernels walk, in the order of a migration record
+void sp_column_table(const State& S, double* out[MIG_NSC + 3]) {
+  double* const t[MIG_NSC + 3] = { S.cx, S.cy, S.rmax, S.area, S.height, S.mass, S.moment, S.alpha, S.u, S.v, S.xi, S.p_dxdt, S.p_dydt, S.p_dalphadt,
+                                   S.p_dudt, S.p_dvdt, S.p_dxidt, S.fxOA, S.fyOA, S.trqOA, S.hflx, S.overarea, S.cfx, S.cfy, S.ctrq, S.sa, S.si, S.strain };
+  for (int k = 0; k < MIG_NSC + 3; k++) out[k] = t[k];
+}
+// rows[0..n): in [0, N), ascending without repeats (sorted) or merely without repeats
+int sp_check_rows(sz_ctx* c, const char* who, const char* what, int n, const int32_t* rows, int N, bool sorted) {
+  std::vector<int> tmp;
+  const int32_t* r = rows;
+  if (!sorted && n > 1) { tmp.assign(rows, rows + n); std::sort(tmp.begin(), tmp.end()); r = tmp.data(); }
+  for (int k = 0; k < n; k++) {
+    if (r[k] < 0 || r[k] >= N) { c->err = std::string(who) + ": " + what + " names row " + std::to_string(r[k]) + ", outside the " + std::to_string(N) + " parents"; return SZ_E_ARG; }
+    if (k && r[k] <= r[k - 1]) { c->err = std::string(who) + ": " + what + (r[k] == r[k - 1] ? " repeats row " + std::to_string(r[k]) : std::string(" is not ascending")); return SZ_E_ARG; }
+  }
+  return SZ_OK;
+}
+// order keys of the last step's inline ghosts, sorted (what an interaction row may name in place of a list number), fetched if pending
+int sp_ghost_keys(sz_ctx* c, std::vector<long long>& sorted) {
+  sorted.clear();
+  if (!c->gi_valid) return SZ_OK;
+  if (int rc = gi_fetch(c)) return rc;
+  if (c->gi_valid) { sorted = c->gi_keys; std::sort(sorted.begin(), sorted.end()); }
+  return SZ_OK;
+}
+}  // namespace
+
+int sz_download_rows(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns* f, int32_t* inter_off, double* inter_rows, int64_t* sizes3) {
+  if (!c || n < 0 || (n > 0 && !rows)) return SZ_E_ARG;
+  if (!c->have_floes) { c->err = "sz_download_rows: no floes uploaded"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  int rc;
+  if ((rc = sync_and_check(c))) return rc;          // hostM / hostN current, nothing pending
+  const int N = c->hostN;
+  if ((rc = sp_check_rows(c, "sz_download_rows", "rows", n, rows, N, false))) return rc;
+  world_rings(c);
+  State& S = c->S;
+  const size_t n1 = (size_t)n + 1;
+  std::vector<int> off(3 * n1, 0);
+  Pool& P = c->sp_allocs;
+  reset_pool(P);
+  int *d_rows = nullptr, *d_len = nullptr, *d_off = nullptr; double** d_cols = nullptr; double* d_out = nullptr;
+  if (n > 0) {
+    if ((rc = dalloc(c, &d_rows, n1, P)) || (rc = dalloc(c, &d_len, 3 * n1, P)) || (rc = dalloc(c, &d_off, 3 * n1, P)) || (rc = dalloc(c, &d_cols, 32, P))) return rc;
+    H2D(d_rows, rows, n, int);
+    hipLaunchKernelGGL(sz_k_sp_sel_len, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, S, (int)n, (const int*)d_rows, c->pts_N > 0 ? 1 : 0, d_len);
+    for (int k = 0; k < 3; k++) scan(c, d_len + k * n1, d_off + k * n1, n, -1, n, -1);
+    HIPCHK(c, hipMemcpyAsync(off.data(), d_off, 3 * n1 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  const size_t V = (size_t)off[n], NS = (size_t)off[n1 + n], R = (size_t)off[2 * n1 + n];
+  if (sizes3) { sizes3[0] = (int64_t)V; sizes3[1] = (int64_t)NS; sizes3[2] = (int64_t)R; }
+  if (!f) return SZ_OK;
+  if (f->vert_off) for (size_t k = 0; k < n1; k++) f->vert_off[k] = off[k];
+  if (f->sub_off) for (size_t k = 0; k < n1; k++) f->sub_off[k] = off[n1 + k];
+  if (f->ghost_off) for (size_t k = 0; k < n1; k++) f->ghost_off[k] = 0;
+  if (inter_off) for (size_t k = 0; k < n1; k++) inter_off[k] = off[2 * n1 + k];
+  if (n == 0) return SZ_OK;
+  const size_t total = (size_t)SP_PACK_NCOL * n + 2 * V + 2 * NS + 7 * R;
+  if ((rc = dalloc(c, &d_out, total, P))) return rc;
+  double* hcols[MIG_NSC + 3];
+  sp_column_table(S, hcols);
+  HIPCHK(c, hipMemcpyAsync(d_cols, hcols, sizeof(hcols), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(sz_k_sp_pack, dim3(grid_for((long long)n * 64, 256, 4096)), dim3(256), 0, c->stream, S, (int)n, (const int*)d_rows, (const int*)d_off, (double* const*)d_cols, d_out);
+  std::vector<double> out(total);
+  HIPCHK(c, hipMemcpyAsync(out.data(), d_out, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  double* const dst[MIG_NSC] = { f->cx, f->cy, f->rmax, f->area, f->height, f->mass, f->moment, f->alpha, f->u, f->v, f->xi, f->p_dxdt, f->p_dydt, f->p_dalphadt,
+                                 f->p_dudt, f->p_dvdt, f->p_dxidt, f->fxOA, f->fyOA, f->trqOA, f->hflx_factor, f->overarea, f->coll_fx, f->coll_fy, f->coll_trq };
+  for (int q = 0; q < MIG_NSC; q++) if (dst[q]) memcpy(dst[q], &out[(size_t)q * n], (size_t)n * sizeof(double));
+  double* const tdst[3] = { f->stress_accum, f->stress_instant, f->strain };
+  for (int t = 0; t < 3; t++) if (tdst[t]) for (int k = 0; k < n; k++) for (int q = 0; q < 4; q++) tdst[t][(size_t)4 * k + q] = out[(size_t)(MIG_NSC + 4 * t + q) * n + k];
+  for (int k = 0; k < n; k++) {
+    long long b;
+    if (f->id) { memcpy(&b, &out[(size_t)37 * n + k], 8); f->id[k] = b; }
+    if (f->status) { memcpy(&b, &out[(size_t)38 * n + k], 8); f->status[k] = (int32_t)b; }
+    if (f->ghost_id) { memcpy(&b, &out[(size_t)39 * n + k], 8); f->ghost_id[k] = b; }
+  }
+  const double* ring = out.data() + (size_t)SP_PACK_NCOL * n;
+  for (size_t k = 0; k < V; k++) { if (f->vx) f->vx[k] = ring[2 * k]; if (f->vy) f->vy[k] = ring[2 * k + 1]; }
+  const double *sx = ring + 2 * V, *sy = sx + NS, *ir = sy + NS;
+  if (f->sx && NS) memcpy(f->sx, sx, NS * sizeof(double));
+  if (f->sy && NS) memcpy(f->sy, sy, NS * sizeof(double));
+  if (inter_rows && R) {
+    memcpy(inter_rows, ir, 7 * R * sizeof(double));
+    std::vector<long long> sorted;
+    if ((rc = sp_ghost_keys(c, sorted))) return rc;
+    if (!sorted.empty()) {            // partners that were inline ghosts: order key -> the reference's floe number (sz_download_interactions)
+      const double lim = (double)((long long)1 << 40);
+      for (size_t r = 0; r < R; r++) {
+        const double idx = inter_rows[r * 7];
+        if (idx <= lim) continue;
+        const long long key = (long long)idx - 1;
+        const auto it = std::lower_bound(sorted.begin(), sorted.end(), key);
+        if (it == sorted.end() || *it != key) { c->err = "interaction row names a ghost that is not among the last step's"; return SZ_E_STATE; }
+        inter_rows[r * 7] = (double)(c->hostN + (int)(it - sorted.begin()) + 1);
+      }
+    }
+  }
+  return SZ_OK;
+}
+
+int sz_splice_floes(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns* f,
+                    const int32_t* ioff, const double* irows) {
+  if (!c || n_del < 0 || n_rep < 0 || n_app < 0 || (n_del && !del) || (n_rep && !rep)) return SZ_E_ARG;
+  const long long ns64 = (long long)n_rep + n_app;
+  if (ns64 > 0x3fffffff) return SZ_E_ARG;
+  const int ns = (int)ns64;
+  if (ns > 0 && (!f || !f->vert_off || !f->vx || !f->vy || !f->cx || !f->cy)) { c->err = "sz_splice_floes: replaced / appended rows need vert_off, vx, vy, cx and cy"; return SZ_E_ARG; }
+  if (!c->have_floes) { c->err = "sz_splice_floes: no floes uploaded"; return SZ_E_STATE; }
+  if (c->S.tiled) { c->err = "sz_splice_floes: the rows of a tiled context carry global numbers and its list is one rank's share: not supported on tiled contexts"; return SZ_E_STATE; }
+  if (c->rr_pending >= 0) { c->err = "sz_splice_floes: a ridge / raft step is pending with its ghosts in the list (sz_step_finish first)"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  int rc;
+  if ((rc = sync_and_check(c))) return rc;          // hostM / hostN current, nothing pending
+  if (c->hostM != c->hostN) { c->err = "sz_splice_floes: ghosts are in the list (sz_remove_ghosts first): the edit is of the parents alone"; return SZ_E_STATE; }
+  State& S = c->S;
+  const int N = c->hostN;
+  // ---- the edit itself: rows, then the uploaded floes
+  if ((rc = sp_check_rows(c, "sz_splice_floes", "del", n_del, del, N, true)) || (rc = sp_check_rows(c, "sz_splice_floes", "rep", n_rep, rep, N, true))) return rc;
+  for (int a = 0, b = 0; a < n_del && b < n_rep;) {
+    if (del[a] == rep[b]) { c->err = "sz_splice_floes: row " + std::to_string(del[a]) + " is both deleted and replaced"; return SZ_E_ARG; }
+    if (del[a] < rep[b]) a++; else b++;
+  }
+  const long long Nn64 = (long long)N - n_del + n_app;
+  if (Nn64 <= 0) { c->err = "sz_splice_floes: the edit leaves no floe"; return SZ_E_ARG; }
+  if (Nn64 > 0x3fffffff) { c->err = "sz_splice_floes: too many floes"; return SZ_E_ARG; }
+  const int Nn = (int)Nn64;
+  const bool with_sub = ns > 0 && f->sub_off != nullptr;
+  if (with_sub && (!f->sx || !f->sy) && f->sub_off[ns] != f->sub_off[0]) { c->err = "sz_splice_floes: sub_off without sx / sy"; return SZ_E_ARG; }
+  size_t stream_len = 0;
+  for (int j = 0; j < ns; j++) {
+    const int o = f->vert_off[j], nv = f->vert_off[j + 1] - o, sp = with_sub ? f->sub_off[j + 1] - f->sub_off[j] : 0, ni = ioff ? ioff[j + 1] - ioff[j] : 0;
+    if (nv < 4 || o < 0 || !(f->vx[o] == f->vx[o + nv - 1] && f->vy[o] == f->vy[o + nv - 1])) { c->err = "sz_splice_floes: uploaded row " + std::to_string(j) + " has an open ring (a ring is closed: its first point repeated, at least 4 points)"; return SZ_E_ARG; }
+    if (nv > SP_MAX_RING) { c->err = "sz_splice_floes: uploaded row " + std::to_string(j) + " has a ring of " + std::to_string(nv) + " points: the row-moving kernels carry " + std::to_string(SP_MAX_RING); return SZ_E_ARG; }
+    if (sp < 0 || ni < 0) { c->err = "sz_splice_floes: offsets of uploaded row " + std::to_string(j) + " descend"; return SZ_E_ARG; }
+    if (sp > 0 && c->pts_N == 0) { c->err = "sz_splice_floes: the list was uploaded without sub-floe points"; return SZ_E_ARG; }
+    if (ni > S.rowcap) { c->err = "more interaction rows per floe than the fixed stride holds"; return SZ_E_CAPACITY; }
+    if (ni > 0 && !irows) { c->err = "sz_splice_floes: inter_off without inter_rows"; return SZ_E_ARG; }
+    stream_len += (size_t)MIG_NCOL + 2 * (size_t)nv + 2 * (size_t)sp;
+  }
+  if (stream_len > 0x7fffffffull) { c->err = "sz_splice_floes: the uploaded rows are too long for one stream"; return SZ_E_ARG; }
+  if (n_del + ns == 0) return SZ_OK;          // nothing to do, nothing touched
+  // ---- from here on the state changes
+  leave_resident(c);
+  std::vector<long long> keys;
+  if ((rc = sp_ghost_keys(c, keys))) return rc;
+  c->gi_pending = false;
+  Pool& P = c->sp_allocs;
+  reset_pool(P);
+  // ---- the uploaded rows as one stream of migration records with its directory (sz_migrate.hpp), their CSR offsets, the marks
+  std::vector<double> stream(std::max<size_t>(stream_len, 1)), dirs((size_t)MIG_DIR * (1 + (size_t)ns), 0.0);
+  std::vector<int> ints(3 * ((size_t)ns + 1) + (size_t)n_del + n_rep + 1, 0);
+  int *h_svoff = ints.data(), *h_ssoff = h_svoff + ns + 1, *h_sioff = h_ssoff + ns + 1, *h_del = h_sioff + ns + 1, *h_rep = h_del + n_del;
+  double staged_rmax = 0.0;
+  {
+    static const sz_floe_columns none{};
+    const sz_floe_columns& F = f ? *f : none;
+    const double* const src[MIG_NSC] = { F.cx, F.cy, F.rmax, F.area, F.height, F.mass, F.moment, F.alpha, F.u, F.v, F.xi, F.p_dxdt, F.p_dydt, F.p_dalphadt,
+                                         F.p_dudt, F.p_dvdt, F.p_dxidt, F.fxOA, F.fyOA, F.trqOA, F.hflx_factor, F.overarea, F.coll_fx, F.coll_fy, F.coll_trq };
+    const double* const tsrc[3] = { F.stress_accum, F.stress_instant, F.strain };
+    dirs[0] = (double)ns;
+    size_t at = 0; int dbelow = 0;
+    for (int j = 0; j < ns; j++) {
+      const int o = f->vert_off[j], nv = f->vert_off[j + 1] - o, so = with_sub ? f->sub_off[j] : 0, sp = with_sub ? f->sub_off[j + 1] - so : 0;
+      // the row this floe takes in the edited list (the id an upload gives a floe without one is its row + 1)
+      int newrow;
+      if (j < n_rep) { while (dbelow < n_del && del[dbelow] < rep[j]) dbelow++; newrow = rep[j] - dbelow; }
+      else newrow = N - n_del + (j - n_rep);
+      double* rec = &stream[at];
+      for (int q = 0; q < MIG_NSC; q++) rec[q] = src[q] ? src[q][j] : 0.0;
+      for (int t = 0; t < 3; t++) for (int q = 0; q < 4; q++) rec[MIG_NSC + 4 * t + q] = tsrc[t] ? tsrc[t][(size_t)4 * j + q] : 0.0;
+      rec[37] = (double)(f->id ? f->id[j] : (long long)newrow + 1); rec[38] = (double)(f->status ? f->status[j] : SZ_ACTIVE); rec[39] = 0.0;
+      rec[40] = (double)nv; rec[41] = (double)sp;
+      for (int k = 0; k < nv; k++) { rec[MIG_NCOL + 2 * k] = f->vx[o + k]; rec[MIG_NCOL + 2 * k + 1] = f->vy[o + k]; }
+      double* sub = rec + MIG_NCOL + 2 * (size_t)nv;
+      for (int k = 0; k < sp; k++) { sub[k] = f->sx[so + k]; sub[sp + k] = f->sy[so + k]; }
+      double* e = &dirs[(size_t)MIG_DIR * (1 + (size_t)j)];
+      e[0] = 0.0; e[1] = (double)nv; e[2] = (double)sp; e[3] = (double)at; e[4] = rec[2]; e[5] = rec[0]; e[6] = rec[1];
+      staged_rmax = std::max(staged_rmax, rec[2]);
+      h_svoff[j + 1] = h_svoff[j] + nv; h_ssoff[j + 1] = h_ssoff[j] + sp; h_sioff[j + 1] = h_sioff[j] + (ioff ? ioff[j + 1] - ioff[j] : 0);
+      at += (size_t)MIG_NCOL + 2 * (size_t)nv + 2 * (size_t)sp;
+    }
+    for (int k = 0; k < n_del; k++) h_del[k] = del[k];
+    for (int k = 0; k < n_rep; k++) h_rep[k] = rep[k];
+  }
+  const int n_irows = h_sioff[ns];
+  double *d_stream = nullptr, *d_dirs = nullptr, *d_irows = nullptr; int* d_ints = nullptr; long long* d_keys = nullptr;
+  SpArgs A{};
+  const size_t o1 = (size_t)N + 2, r1 = (size_t)Nn + 2;
+  if ((rc = dalloc(c, &d_stream, stream.size(), P)) || (rc = dalloc(c, &d_dirs, dirs.size(), P)) || (rc = dalloc(c, &d_ints, ints.size(), P)) ||
+      (rc = dalloc(c, &d_irows, (size_t)std::max(n_irows, 1) * 7, P)) || (rc = dalloc(c, &d_keys, std::max<size_t>(keys.size(), 1), P)) ||
+      (rc = dalloc(c, &A.d, 1, P)) || (rc = dalloc(c, &A.mark, o1, P)) || (rc = dalloc(c, &A.keep, o1, P)) || (rc = dalloc(c, &A.kv, o1, P)) || (rc = dalloc(c, &A.ks, o1, P)) ||
+      (rc = dalloc(c, &A.newrow, o1, P)) || (rc = dalloc(c, &A.ovoff, o1, P)) || (rc = dalloc(c, &A.osoff, o1, P)) ||
+      (rc = dalloc(c, &A.src, r1, P)) || (rc = dalloc(c, &A.nvoff, r1, P)) || (rc = dalloc(c, &A.nsoff, r1, P))) return rc;
+  H2D(d_stream, stream.data(), stream.size(), double); H2D(d_dirs, dirs.data(), dirs.size(), double); H2D(d_ints, ints.data(), ints.size(), int);
+  if (n_irows) H2D(d_irows, irows + (size_t)ioff[0] * 7, (size_t)n_irows * 7, double);
+  if (!keys.empty()) H2D(d_keys, keys.data(), keys.size(), long long);
+  A.n = N; A.n_del = n_del; A.n_rep = n_rep; A.n_app = n_app;
+  A.svoff = d_ints; A.ssoff = d_ints + ns + 1; A.del = d_ints + 3 * ((size_t)ns + 1); A.rep = A.del + n_del;
+  const int* d_sioff = d_ints + 2 * ((size_t)ns + 1);
+  // ---- the plan: marks, flags, removal's scans over old-or-staged lengths, the new rows' sources and offsets, what an upload would find of them
+  HIPCHK(c, hipMemsetAsync(A.mark, 0, o1 * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(A.d, 0, sizeof(SpDev), c->stream));
+  const int nb = grid_for(std::max(N, n_app), 256, 2048);
+  if (n_del + n_rep) hipLaunchKernelGGL(sz_k_sp_marks, dim3(grid_for(n_del + n_rep, 256, 2048)), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL(sz_k_sp_flags, dim3(nb), dim3(256), 0, c->stream, S, A);
+  scan(c, A.keep, A.newrow, N, C_N, 0, -1);
+  scan(c, A.kv, A.ovoff, N, C_N, 0, -1);
+  scan(c, A.ks, A.osoff, N, C_N, 0, -1);
+  hipLaunchKernelGGL(sz_k_sp_rows, dim3(nb), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL(sz_k_sp_limits, dim3(grid_for(Nn, 256, 2048)), dim3(256), 0, c->stream, S, A, Nn, (const double*)d_dirs, (const double*)d_stream);
+  SpDev R{};
+  HIPCHK(c, hipMemcpyAsync(&R, A.d, sizeof(SpDev), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (R.Nn != Nn || R.Vn < 0 || R.NSn < 0) { c->err = "sz_splice_floes: bad counts"; return SZ_E_HIP; }
+  const int Vn = R.Vn, NSn = R.NSn, tcap = S.rowcap;
+  // ---- the rows of the edited list, gathered beside the old ones: kept rows from the list, the others from the stream
+  double** d_cols = nullptr; double *d_tmp = nullptr, *d_tsx = nullptr, *d_tsy = nullptr, *d_trows = nullptr; double2* d_tv = nullptr; int* d_tcnt = nullptr;
+  if ((rc = dalloc(c, &d_cols, 32, P)) || (rc = dalloc(c, &d_tmp, (size_t)SP_NCOL * Nn, P)) || (rc = dalloc(c, &d_tv, (size_t)Vn, P)) || (rc = dalloc(c, &d_tsx, (size_t)NSn, P)) ||
+      (rc = dalloc(c, &d_tsy, (size_t)NSn, P)) || (rc = dalloc(c, &d_tcnt, (size_t)Nn, P)) || (rc = dalloc(c, &d_trows, (size_t)Nn * tcap * 7, P))) return rc;
+  double* hcols[MIG_NSC + 3];
+  sp_column_table(S, hcols);
+  HIPCHK(c, hipMemcpyAsync(d_cols, hcols, sizeof(hcols), hipMemcpyHostToDevice, c->stream));
+  const int nbw = grid_for((long long)Nn * 64, 256, 4096);
+  hipLaunchKernelGGL(sz_k_mig_gather, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, (const double*)d_dirs, (const double*)d_stream,
+                     (double* const*)d_cols, d_tmp);
+  hipLaunchKernelGGL(sz_k_mig_points, dim3(nbw), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, (const double*)d_dirs, (const double*)d_stream,
+                     (const int*)A.nvoff, (const int*)A.nsoff, d_tv, d_tsx, d_tsy);
+  hipLaunchKernelGGL(sz_k_sp_gather_rows, dim3(nbw), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, d_sioff, (const double*)d_irows, (const long long*)d_keys,
+                     (int)keys.size(), N, tcap, d_tcnt, d_trows);
+  // does the edited list fit what the context was carved for?  The rule of a migration's receive path: an eighth more than the upload held is let in.
+  const bool fits = Nn <= c->upload_M + c->upload_M / 8 && Vn <= c->upload_V + c->upload_V / 8 && Nn <= S.capM && Vn <= S.capV;
+  const int pts = c->pts_N ? Nn : 0;
+  int gl_est = std::min(Nn, c->gl_est + ns); double rmax_max = std::max(c->rmax_max, staged_rmax), rmax_hint = c->rmax_hint;
+  Pool old_sub;
+  if (!fits) {
+    // ---- the pools grow: the context is carved anew for the edited list by the upload itself -- given the small host columns its sizing reads (centroids,
+    // rmax, ids, statuses, offsets: fetched from the gathered rows) and rings / points of zeros --, then the gathered rows are placed as below
+    std::vector<double> h3((size_t)3 * Nn), hid((size_t)2 * Nn), zv((size_t)std::max(Vn, 1), 0.0), zs((size_t)std::max(NSn, 1), 0.0);
+    std::vector<int> hvoff((size_t)Nn + 1), hsoff((size_t)Nn + 1), hst((size_t)Nn); std::vector<long long> hidl((size_t)Nn);
+    HIPCHK(c, hipMemcpyAsync(h3.data(), d_tmp, h3.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hid.data(), d_tmp + (size_t)37 * Nn, hid.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hvoff.data(), A.nvoff, hvoff.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hsoff.data(), A.nsoff, hsoff.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int r = 0; r < Nn; r++) { hidl[r] = (long long)hid[r]; hst[r] = (int)hid[(size_t)Nn + r]; }
+    sz_floe_columns d; memset(&d, 0, sizeof(d));
+    d.cx = h3.data(); d.cy = h3.data() + Nn; d.rmax = h3.data() + (size_t)2 * Nn; d.id = (int64_t*)hidl.data(); d.status = hst.data();
+    d.vert_off = hvoff.data(); d.vx = zv.data(); d.vy = zv.data();
+    if (c->pts_N) { d.sub_off = hsoff.data(); d.sx = zs.data(); d.sy = zs.data(); }
+    if ((rc = sz_upload_floes(c, Nn, Nn, &d))) return rc;
+    if (S.rowcap < tcap) { S.rowcap = tcap; if ((rc = carve_interactions(c))) return rc; }      // (a kept floe may hold more rows than a fresh stride)
+    sp_column_table(S, hcols);
+    HIPCHK(c, hipMemcpyAsync(d_cols, hcols, sizeof(hcols), hipMemcpyHostToDevice, c->stream));
+    gl_est = c->gl_est; rmax_max = c->rmax_max; rmax_hint = 0.0;          // (the upload's own, of the edited list)
+  } else if (NSn > S.capS) {          // the sub-floe points have no slack at upload: a new pair, as for a tile that gained points in a migration
+    old_sub = c->sub_allocs; c->sub_allocs = Pool();
+    S.capS = NSn + NSn / 4;
+    if ((rc = dalloc(c, &S.sx, (size_t)S.capS, c->sub_allocs)) || (rc = dalloc(c, &S.sy, (size_t)S.capS, c->sub_allocs))) return rc;
+  }
+  // ---- and into their places, with the links of a freshly placed ghost-free field (as sz_upload_floes leaves them)
+  hipLaunchKernelGGL(sz_k_mig_scatter, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (double* const*)d_cols, (const double*)d_tmp);
+  hipLaunchKernelGGL(sz_k_sp_scatter_rows, dim3(nbw), dim3(256), 0, c->stream, S, Nn, c->origin, tcap, (const int*)d_tcnt, (const double*)d_trows);
+  if (fits && N > Nn) hipLaunchKernelGGL(sz_k_sp_clear_rows, dim3(grid_for(N - Nn, 256, 2048)), dim3(256), 0, c->stream, Nn, N, (double* const*)d_cols);
+  if (std::min(N, S.capM) > Nn) HIPCHK(c, hipMemsetAsync(S.inter_cnt + Nn, 0, (size_t)(std::min(N, S.capM) - Nn) * sizeof(int), c->stream));
+  if (Vn) HIPCHK(c, hipMemcpyAsync(S.vxy, d_tv, (size_t)Vn * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(S.voff, A.nvoff, ((size_t)Nn + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  if (c->pts_N) {
+    if (NSn) {
+      HIPCHK(c, hipMemcpyAsync(S.sx, d_tsx, (size_t)NSn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(S.sy, d_tsy, (size_t)NSn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(S.soff, A.nsoff, ((size_t)Nn + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  }
+  // ---- the field is placed: everything derived as behind the copies of sz_upload_floes; the rows as behind sz_upload_interactions
+  if ((rc = field_placed(c, Nn, 0, Vn, pts, gl_est, rmax_max, rmax_hint))) return rc;
+  free_pool(old_sub);
+  c->inter_any = true; c->inter_lost = false; c->rr_rows = true;
+  c->maybe_tagged = R.n_tagged > 0; c->grid_live = false;
+  c->max_ring = R.max_ring; if (c->pts_N) c->max_sub = R.max_sub;          // (as an upload of the edited list finds them)
+  return SZ_OK;
+}
+
+// ... for Float32 hosts: widened on the way in, rounded on the way out, exactly as sz_upload_floes_f32 / sz_download_floes_f32 do
+int sz_download_rows_f32(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns_f32* f, int32_t* inter_off, float* inter_rows, int64_t* sizes3) {
+  if (!c || n < 0) return SZ_E_ARG;
+  int64_t sz[3] = { 0, 0, 0 };
+  int rc = sz_download_rows(c, n, rows, nullptr, nullptr, nullptr, sz); if (rc) return rc;
+  if (sizes3) { sizes3[0] = sz[0]; sizes3[1] = sz[1]; sizes3[2] = sz[2]; }
+  if (!f) return SZ_OK;
+  const size_t M = (size_t)n, V = (size_t)sz[0], NS = (size_t)sz[1], R = (size_t)sz[2];
+  std::vector<std::vector<double>> keep;
+  struct Back { float* dst; double* src; size_t n; }; std::vector<Back> back;
+  auto room = [&](float* dst, size_t cnt) -> double* {
+    if (!dst) return nullptr;
+    keep.emplace_back(cnt ? cnt : 1);
+    back.push_back({ dst, keep.back().data(), cnt });
+    return keep.back().data();
+  };
+  sz_floe_columns d; memset(&d, 0, sizeof(d));
+#define X(name) d.name = room(f->name, M);
+  SZ_F32_SCALARS(X)
+#undef X
+#define X(name) d.name = room(f->name, 4 * M);
+  SZ_F32_TENSORS(X)
+#undef X
+  d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
+  d.vx = room(f->vx, V); d.vy = room(f->vy, V); d.sx = room(f->sx, NS); d.sy = room(f->sy, NS);
+  double* ir = room(inter_rows, 7 * R);
+  rc = sz_download_rows(c, n, rows, &d, inter_off, ir, nullptr); if (rc) return rc;
+  for (const Back& b : back) for (size_t k = 0; k < b.n; k++) b.dst[k] = (float)b.src[k];
+  return SZ_OK;
+}
+int sz_splice_floes_f32(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns_f32* f,
+                        const int32_t* ioff, const float* irows) {
+  if (!c || n_rep < 0 || n_app < 0) return SZ_E_ARG;
+  const size_t M = (size_t)n_rep + (size_t)n_app;
+  if (M == 0 || !f) return sz_splice_floes(c, n_del, del, n_rep, rep, n_app, nullptr, ioff, nullptr);
+  if (!f->vert_off) { c->err = "sz_splice_floes_f32: vert_off is required"; return SZ_E_ARG; }
+  const size_t V = (size_t)f->vert_off[M], NS = f->sub_off ? (size_t)f->sub_off[M] : 0, R = ioff ? (size_t)ioff[M] : 0;
+  std::vector<std::vector<double>> keep;
+  auto widen = [&](const float* src, size_t cnt) -> double* {
+    if (!src) return nullptr;
+    keep.emplace_back(cnt ? cnt : 1);
+    for (size_t k = 0; k < cnt; k++) keep.back()[k] = (double)src[k];
+    return keep.back().data();
+  };
+  sz_floe_columns d; memset(&d, 0, sizeof(d));
+#define X(name) d.name = widen(f->name, M);
+  SZ_F32_SCALARS(X)
+#undef X
+#define X(name) d.name = widen(f->name, 4 * M);
+  SZ_F32_TENSORS(X)
+#undef X
+  d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
+  d.vx = widen(f->vx, V); d.vy = widen(f->vy, V); d.sx = widen(f->sx, NS); d.sy = widen(f->sy, NS);
+  return sz_splice_floes(c, n_del, del, n_rep, rep, n_app, &d, ioff, widen(irows, 7 * R));
 }
 
 // ---------------------------------------------------------------- ridge / raft candidates (sz_ridgeraft.hpp)

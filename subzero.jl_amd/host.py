@@ -725,6 +725,96 @@ class World:
         self._chk(self.L.sz_download_origin(self.h, capi.ptr(o, capi._ip)))
         return o[:n].copy()
 
+    # ---- rows down, rows back (sz_download_rows / sz_splice_floes): the host's side of a stop edits a few floes, the others stay on the device
+    ROW_INT = {"id": _I64, "ghost_id": _I64, "status": _I32}
+
+    def download_rows(self, rows):
+        """the parents `rows` (0-based, any order, none twice) as a dict in the layout of load_columns: every column with len(rows) entries in
+        that order, the rings (vert_off, vx, vy), the sub-floe points (sub_off, sx, sy) and floe.interactions (inter_off, inter_rows k x 7) as
+        CSR -- each value as a full download gives it"""
+        self._push_interactions()
+        f32 = self._ft == np.float32
+        rows = np.ascontiguousarray(rows, _I32).ravel()
+        n = len(rows)
+        sizes = np.zeros(3, _I64)
+        fn = self.L.sz_download_rows_f32 if f32 else self.L.sz_download_rows
+        self._chk(fn(self.h, n, capi.ptr(rows, capi._ip), None, None, None, capi.ptr(sizes, capi._lp)))
+        V, NS, R = (int(v) for v in sizes)
+        col = {k: np.zeros(n, self._ft) for k in capi.DCOLS}
+        for k in capi.TCOLS:
+            col[k] = np.zeros((n, 4), self._ft)
+        for k, t in self.ROW_INT.items():
+            col[k] = np.zeros(n, t)
+        col["vert_off"] = np.zeros(n + 1, _I32); col["vx"] = np.zeros(V, self._ft); col["vy"] = np.zeros(V, self._ft)
+        col["sub_off"] = np.zeros(n + 1, _I32); col["sx"] = np.zeros(NS, self._ft); col["sy"] = np.zeros(NS, self._ft)
+        ioff = np.zeros(n + 1, _I32); irows = np.zeros((R, 7), self._ft)
+        keep = []
+        f = self._columns_struct(col, keep)
+        self._chk(fn(self.h, n, capi.ptr(rows, capi._ip), C.byref(f), capi.ptr(ioff, capi._ip), capi.ptr(irows, capi._fp if f32 else capi._dp), None))
+        if f32:
+            col = {k: (v.astype(np.float64) if v.dtype == np.float32 else v) for k, v in col.items()}
+            irows = irows.astype(np.float64)
+        col["inter_off"] = ioff; col["inter_rows"] = irows
+        return col
+
+    @staticmethod
+    def _staged(parts):
+        """dicts in the layout of download_rows, one behind the other (missing columns: zeros, as an upload reads a NULL column)"""
+        parts = [p for p in parts if p is not None and len(p["vert_off"]) > 1]
+        if not parts:
+            return None, None, None, 0
+        ns = [len(p["vert_off"]) - 1 for p in parts]
+        col = {}
+        for k in capi.DCOLS + capi.TCOLS + list(World.ROW_INT):
+            if any(k in p for p in parts):
+                shape = (4,) if k in capi.TCOLS else ()
+                t = World.ROW_INT.get(k, np.float64)
+                fill = capi.ACTIVE if k == "status" else 0
+                if k == "id" and not all(k in p for p in parts):
+                    raise SzError("splice: id given for some of the floes only")
+                col[k] = np.concatenate([np.asarray(p[k], t).reshape((m,) + shape) if k in p else np.full((m,) + shape, fill, t) for p, m in zip(parts, ns)])
+
+        def csr(off_name, val_names, width=None):
+            off = [np.zeros(1, _I64)]; vals = {v: [] for v in val_names}
+            for p, m in zip(parts, ns):
+                o = np.asarray(p[off_name], _I64) if off_name in p else np.zeros(m + 1, _I64)
+                off.append(off[-1][-1] + (o[1:] - o[0]))
+                for v in val_names:
+                    a = np.asarray(p[v], np.float64) if off_name in p else np.zeros((0,) if width is None else (0, width))
+                    vals[v].append(a[o[0]:o[-1]])
+            return np.concatenate(off).astype(_I32), {v: np.concatenate(a) for v, a in vals.items()}
+        col["vert_off"], xy = csr("vert_off", ("vx", "vy")); col.update(xy)
+        if any("sub_off" in p for p in parts):
+            col["sub_off"], xy = csr("sub_off", ("sx", "sy")); col.update(xy)
+        ioff, ir = csr("inter_off", ("inter_rows",), 7)
+        return col, ioff, np.ascontiguousarray(ir["inter_rows"].reshape(-1, 7)), sum(ns)
+
+    def splice(self, delete=(), replace=None, append=None):
+        """edits the resident list in place (sz_splice_floes): `delete` -- ascending rows that vanish; replace = (rows, floes) -- ascending rows
+        (of the list as it is, before the deletion) overwritten by the floes of a dict in the layout of download_rows; append = such a dict of
+        floes that go behind the last kept row, in their order.  Afterwards the device holds what an upload of the edited list and its interaction
+        lists would have left; this object's copy of the columns is fetched again when it is next looked at."""
+        self._push_interactions()
+        f32 = self._ft == np.float32
+        dele = np.ascontiguousarray(delete, _I32).ravel()
+        rep_rows, rep_cols = (np.zeros(0, _I32), None) if replace is None else (np.ascontiguousarray(replace[0], _I32).ravel(), replace[1])
+        if rep_cols is not None and len(rep_cols["vert_off"]) - 1 != len(rep_rows):
+            raise SzError("splice: replace names %d rows and gives %d floes" % (len(rep_rows), len(rep_cols["vert_off"]) - 1))
+        col, ioff, irows, ns = self._staged([rep_cols, append])
+        n_app = ns - len(rep_rows)
+        keep = []
+        f = self._columns_struct(col, keep) if col is not None else None
+        if irows is not None:
+            irows = np.ascontiguousarray(irows, self._ft)
+        fn = self.L.sz_splice_floes_f32 if f32 else self.L.sz_splice_floes
+        self._chk(fn(self.h, len(dele), capi.ptr(dele, capi._ip), len(rep_rows), capi.ptr(rep_rows, capi._ip), int(n_app),
+                     C.byref(f) if f is not None else None, capi.ptr(ioff, capi._ip) if ioff is not None else None,
+                     capi.ptr(irows, capi._fp if f32 else capi._dp) if irows is not None and len(irows) else None))
+        if len(dele) + ns:          # the mirror follows: count from the device, columns and sub-floe points fetched on demand
+            self.N = self._M = self.stats()["N"]
+            self._sub_on_device = "sub_off" in self.col or bool(self._sub); self._sub = {}
+            self._host_stale = True
+
     def timestep_sim(self, tstep, dt, coupling_dt=10, collisions_on=True, coupling_on=True):
         self.run(1, tstep, dt, coupling_dt, collisions_on, coupling_on)
 

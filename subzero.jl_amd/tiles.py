@@ -610,6 +610,11 @@ class TiledWorld:
         """the timestep whose ridge / raft step is pending, or -1"""
         return self.world.ridgeraft_pending()
 
+    def splice(self, delete=(), replace=None, append=None):
+        """World.splice on this rank's context: a tiled context refuses it (its rows carry global numbers and its list is one rank's share), and
+        the library's message is raised"""
+        return self.world.splice(delete, replace, append)
+
     def ridgeraft_draws(self):
         """the per-floe draws of the ridge / raft steps the last run() ran through, over the global list: the same number on every rank"""
         return self._rr_draws
