@@ -23,6 +23,9 @@
  *   sz_download_rows /            <- what the host-side topology changes do to the floe list: deleteat!, assignment in place,
  *   sz_splice_floes                  append! (fracture_floes!, fuse / replace_floe!, ridging and rafting, smoothing), on the rows
  *                                    they name; the floes themselves are still made by the reference on the host
+ *   sz_ridgeraft_rows /           <- the rows timestep_ridging_rafting! can touch, and what timestep_sim! does to the list behind it:
+ *   sz_download_list_rows /          deleteat!(floes, n_init_floes + 1 : end), append!(floes, pieces)
+ *   sz_splice_parents                                                       src/simulation_components/simulation.jl:121-147
  *   sz_timestep_coupling          <- timestep_coupling!(model, Δt, consts, coupling_settings,
  *                                    floe_settings), one-way part           src/physical_processes/coupling.jl:1705-1738
  *   sz_timestep_floe_properties   <- timestep_floe_properties!(floes, tstep, Δt, floe_settings)
@@ -401,6 +404,40 @@ int sz_ridgeraft_candidates(sz_ctx *ctx, int32_t *n, int32_t cap, int32_t *idx_i
 int sz_ridgeraft_pending(sz_ctx *ctx, int32_t *tstep);
 int sz_ridgeraft_draws(sz_ctx *ctx, int64_t *n);
 int sz_step_finish(sz_ctx *ctx, int32_t tstep, int32_t dt, int32_t coupling_dt, int32_t flags);
+
+/* ---- a ridge / raft stop as row edits (csrc/sz_ridgeraft.hpp, csrc/sz_splice.hpp).  timestep_ridging_rafting! changes floes in
+   place, parents and ghosts alike, and collects new pieces; timestep_sim! then deletes every row behind n_init_floes and appends the pieces
+   (simulation.jl:137-147).  What goes on is "the parents, some replaced, pieces appended": the ghosts are read by the host and never sent back.
+   sz_ridgeraft_rows: the rows the host's ridging and rafting can touch.  Valid where sz_ridgeraft_candidates is valid, with the same refusals.
+   The candidate pass runs; for every table entry (i, j) row i and, where j > 0, row j - 1 are taken, each with its root parent (the row < N with
+   the same id, found through the device's parent link) and every ghost on that parent's ghost list.  *n rows, ascending 0-based list rows, each
+   once; rows has room for cap entries (cap < *n: SZ_E_ARG), or is NULL to ask for *n only.  An empty table gives *n = 0; two calls on one state
+   give the same bits.
+   sz_download_list_rows: sz_download_rows over the whole list.  `rows` may name any of the M list rows, ghosts included, in any order, none twice
+   (SZ_E_ARG otherwise, the state untouched).  Every value has the bits sz_download_floes, sz_download_subpoints and sz_download_interactions give
+   for that row; ghost_off (n + 1 entries) / ghost_idx are written -- a parent's ghost list in list numbers, as sz_download_floes gives it, an
+   empty list for a ghost row (ghost_idx needs room for 3 entries per selected row).  A ghost row has no sub-floe points: its sub_off span is
+   empty.  The same staging buffer and the same single copy down as sz_download_rows; the ghost lists travel in it.
+   sz_splice_parents: sz_splice_floes on a list that still holds its ghosts.  Arguments and checks are those of sz_splice_floes; rows number the
+   parents as they are; ghost columns of cols are ignored.  With ghosts in the list -- a pending ridge / raft step, or sz_add_ghosts by hand -- the
+   ghosts are dropped as sz_remove_ghosts drops them and the edit is applied as sz_splice_floes applies it, both capacity paths included.  A
+   pending mark stays: sz_step_finish then runs the second half and finds no ghost to remove.  With no ghosts and nothing pending it is
+   sz_splice_floes.  Afterwards the context is, bit for bit in everything downloadable and with everything derived as sz_splice_floes states it,
+   the one that sz_remove_ghosts followed by sz_upload_floes of the edited parents and sz_upload_interactions of their lists leaves in this same
+   context.  Kept rows keep their partner numbers untouched: a kept row may go on naming a ghost's old list number, as in the reference behind
+   simulation.jl:138-147.  Every check comes before the first change, so a refused call leaves the ghosts in the list: tiled contexts SZ_E_STATE;
+   every edit sz_splice_floes refuses, with its code.  n_del = n_rep = n_app = 0 changes nothing and drops no ghost.
+   The _f32 twins widen and round as those of sz_download_rows / sz_splice_floes do; sz_ridgeraft_rows_f32 is sz_ridgeraft_rows (no floating-point
+   value crosses it; a Float32 host finds every call of the stop under one suffix). */
+int sz_ridgeraft_rows(sz_ctx *ctx, int32_t *n, int32_t cap, int32_t *rows);
+int sz_ridgeraft_rows_f32(sz_ctx *ctx, int32_t *n, int32_t cap, int32_t *rows);
+int sz_download_list_rows(sz_ctx *ctx, int32_t n, const int32_t *rows, sz_floe_columns *cols, int32_t *inter_off, double *inter_rows, int64_t *sizes3);
+int sz_splice_parents(sz_ctx *ctx, int32_t n_del, const int32_t *del, int32_t n_rep, const int32_t *rep, int32_t n_app, const sz_floe_columns *cols,
+                      const int32_t *inter_off, const double *inter_rows);
+int sz_download_list_rows_f32(sz_ctx *ctx, int32_t n, const int32_t *rows, sz_floe_columns_f32 *cols, int32_t *inter_off, float *inter_rows,
+                              int64_t *sizes3);
+int sz_splice_parents_f32(sz_ctx *ctx, int32_t n_del, const int32_t *del, int32_t n_rep, const int32_t *rep, int32_t n_app,
+                          const sz_floe_columns_f32 *cols, const int32_t *inter_off, const float *inter_rows);
 
 /* ---- measurement: HIP-event time per kernel class, accumulated since the last reset, on the
    stream the kernels are launched on; launches = number of timed launches of that class.

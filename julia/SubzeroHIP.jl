@@ -848,6 +848,168 @@ function ridgeraft_candidates(eng::HIPEngine)
     return (i = Int.(i[1:m]) .+ 1, j = Int.(j[1:m]), kind = Int.(k[1:m]), frac = f[1:m], n_draws = Int(nd[]))
 end
 
+"""
+    ridgeraft_rows(eng) -> Vector{Int}
+
+The list rows `timestep_ridging_rafting!` can touch (`sz_ridgeraft_rows`; where `ridgeraft_candidates` is valid): for every table entry row `i`
+and, for a floe partner, row `j`, each with its root parent and every ghost on that parent's `ghosts` list -- ascending 1-based list rows, each
+once; empty for an empty table.
+
+Written, not run, as `download_rows!` and `splice!` are; the C call is held to the numpy statement of the rule by
+`tests/test_pending_splice_gpu.py`.
+"""
+function ridgeraft_rows(eng::HIPEngine)
+    n = Ref{Int32}(0)
+    check(eng, @ccall lib.sz_ridgeraft_rows(eng.ctx::Ptr{Cvoid}, n::Ptr{Int32}, Int32(0)::Int32, C_NULL::Ptr{Int32})::Cint)
+    cap = max(Int(n[]), 1)
+    rows = Vector{Int32}(undef, cap)
+    check(eng, @ccall lib.sz_ridgeraft_rows(eng.ctx::Ptr{Cvoid}, n::Ptr{Int32}, Int32(cap)::Int32, rows::Ptr{Int32})::Cint)
+    return Int.(rows[1:Int(n[])]) .+ 1
+end
+
+"""
+    download_list_rows!(eng, floes, rows)
+
+`download_rows!` over the whole list (`sz_download_list_rows`): `floes` is the host list WITH its ghost rows (as `pull_state_with_ghosts!`
+leaves it, one host row per list row) and `rows` may name any of them, 1-based, in any order, none twice.  A parent's `ghosts` come with it in
+list numbers; a ghost row gets an empty list and no sub-floe points, as the reference's ghosts have them (`deepcopy_floe` copies the parent's
+points, which nothing reads -- they are left as they are on the host).  The fuse lists are not part of this call.
+
+Written, not run: there is no Julia on the machines this engine is built and tested on.  The C call underneath is held to the bits of a full
+download by `tests/test_pending_splice_gpu.py`.
+"""
+function download_list_rows!(eng::HIPEngine, floes, rows::AbstractVector{<:Integer})
+    n = length(rows)
+    n == 0 && return
+    r0 = Int32.(rows .- 1)
+    sizes = Vector{Int64}(undef, 3)
+    check(eng, @ccall lib.sz_download_list_rows(eng.ctx::Ptr{Cvoid}, Int32(n)::Int32, r0::Ptr{Int32}, C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Int32},
+                                                C_NULL::Ptr{Float64}, sizes::Ptr{Int64})::Cint)
+    sub = floes[rows]
+    P = pack(sub, n)
+    resize!(P.vx, sizes[1]); resize!(P.vy, sizes[1]); resize!(P.sx, sizes[2]); resize!(P.sy, sizes[2]); resize!(P.ghost_idx, 3n)
+    P.cols.vx = pointer(P.vx); P.cols.vy = pointer(P.vy); P.cols.sx = pointer(P.sx); P.cols.sy = pointer(P.sy)
+    P.cols.ghost_off = pointer(P.ghost_off); P.cols.ghost_idx = pointer(P.ghost_idx)
+    off = Vector{Int32}(undef, n + 1); irows = Matrix{Float64}(undef, 7, max(Int(sizes[3]), 1))
+    GC.@preserve P sub begin
+        check(eng, @ccall lib.sz_download_list_rows(eng.ctx::Ptr{Cvoid}, Int32(n)::Int32, r0::Ptr{Int32}, P.cols::Ref{SzFloeColumns}, off::Ptr{Int32},
+                                                    irows::Ptr{Float64}, C_NULL::Ptr{Int64})::Cint)
+    end
+    unpack_geometry!(sub, P); unpack_status!(sub, P)
+    sub.id .= P.id; sub.ghost_id .= P.ghost_id
+    for k in 1:n
+        if sub.ghost_id[k] == 0          # (a parent: its points and its ghost list are the device's)
+            s = P.sub_off[k]+1:P.sub_off[k+1]
+            sub.x_subfloe_points[k] = P.sx[s]; sub.y_subfloe_points[k] = P.sy[s]
+        end
+        sub.ghosts[k] = Int.(P.ghost_idx[P.ghost_off[k]+1:P.ghost_off[k+1]]) .+ 1
+        r = off[k]+1:off[k+1]
+        sub.interactions[k] = permutedims(irows[:, r]); sub.num_inters[k] = length(r)
+        sub.collision_force[k][1, 1] = P.coll_fx[k]; sub.collision_force[k][1, 2] = P.coll_fy[k]
+        floes[rows[k]] = sub[k]
+    end
+    return
+end
+
+"""
+    splice_parents!(eng, floes, n_parents, del, rep, app_range)
+
+`splice!` at a stop that still has its ghosts in the list (`sz_splice_parents`): a pending ridge / raft step.  `floes` is the host list as
+`timestep_ridging_rafting!` left it -- `n_parents` parents, then the ghosts, then the pieces it collected at `app_range` -- with the rows `rep`
+of the parents changed in place and the rows `del` still there.  The device drops its ghosts as `sz_remove_ghosts` does and applies the edit to
+the parents; the pending step stays pending (`sz_step_finish` runs its second half).  The host list follows `timestep_sim!`
+(simulation.jl:137-147): the ghost rows go, the pieces stay behind the parents, the rows `del` are deleted.
+
+Written, not run.  The C call underneath is held, bit for bit, to `sz_remove_ghosts` + an upload of the edited parents by
+`tests/test_pending_splice_gpu.py`.
+"""
+function splice_parents!(eng::HIPEngine, floes, n_parents::Integer, del::AbstractVector{<:Integer}, rep::AbstractVector{<:Integer},
+                         app_range::AbstractUnitRange{<:Integer})
+    staged = vcat(collect(Int, rep), collect(Int, app_range))
+    d0 = Int32.(del .- 1); r0 = Int32.(rep .- 1)
+    if isempty(staged)
+        check(eng, @ccall lib.sz_splice_parents(eng.ctx::Ptr{Cvoid}, Int32(length(d0))::Int32, d0::Ptr{Int32}, Int32(0)::Int32, C_NULL::Ptr{Int32},
+                                                Int32(0)::Int32, C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Int32}, C_NULL::Ptr{Float64})::Cint)
+    else
+        sub = floes[staged]
+        P = pack(sub, length(sub))
+        off, irows = interactions_csr(sub)
+        GC.@preserve P sub begin
+            check(eng, @ccall lib.sz_splice_parents(eng.ctx::Ptr{Cvoid}, Int32(length(d0))::Int32, d0::Ptr{Int32}, Int32(length(r0))::Int32,
+                                                    r0::Ptr{Int32}, Int32(length(app_range))::Int32, P.cols::Ref{SzFloeColumns}, off::Ptr{Int32},
+                                                    irows::Ptr{Float64})::Cint)
+        end
+    end
+    isempty(d0) && isempty(staged) && return          # (the library changed nothing and dropped no ghost)
+    gone = sort(unique(vcat(collect(Int, del), [i for i in n_parents+1:length(floes) if !(i in app_range)])))
+    for i in reverse(gone)
+        StructArrays.foreachfield(f -> deleteat!(f, i), floes)
+    end
+    for i in eachindex(floes.ghosts)
+        empty!(floes.ghosts[i])
+    end
+    eng.host_rows = collect(1:length(floes))
+    return
+end
+
+# ... for a Floe{Float32} host (see "Float32 hosts" below): the same calls through the _f32 twins on the columns of pack32.  ridgeraft_rows32
+# names the call a Float32 host finds under the suffix; no floating-point value crosses it.
+function ridgeraft_rows32(eng::HIPEngine)
+    n = Ref{Int32}(0)
+    check(eng, @ccall lib.sz_ridgeraft_rows_f32(eng.ctx::Ptr{Cvoid}, n::Ptr{Int32}, Int32(0)::Int32, C_NULL::Ptr{Int32})::Cint)
+    cap = max(Int(n[]), 1)
+    rows = Vector{Int32}(undef, cap)
+    check(eng, @ccall lib.sz_ridgeraft_rows_f32(eng.ctx::Ptr{Cvoid}, n::Ptr{Int32}, Int32(cap)::Int32, rows::Ptr{Int32})::Cint)
+    return Int.(rows[1:Int(n[])]) .+ 1
+end
+
+# the list rows `rows` into a contiguous copy of them: (copy, its Packed32 -- the flattened columns hold the device's values, as after
+# download32! --, ghost_off, ghost_idx, inter_off, inter_rows 7 x k)
+function download_list_rows32(eng::HIPEngine, floes::StructArray{<:Floe{Float32}}, rows::AbstractVector{<:Integer})
+    n = length(rows)
+    r0 = Int32.(rows .- 1)
+    sizes = Vector{Int64}(undef, 3)
+    check(eng, @ccall lib.sz_download_list_rows_f32(eng.ctx::Ptr{Cvoid}, Int32(n)::Int32, r0::Ptr{Int32}, C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Int32},
+                                                    C_NULL::Ptr{Float32}, sizes::Ptr{Int64})::Cint)
+    sub = floes[rows]
+    P = pack32(sub, n)
+    vx = Vector{Float32}(undef, sizes[1]); vy = similar(vx); sx = Vector{Float32}(undef, sizes[2]); sy = similar(sx)
+    goff = Vector{Int32}(undef, n + 1); gidx = Vector{Int32}(undef, max(3n, 1))
+    P.cols.vx = pointer(vx); P.cols.vy = pointer(vy); P.cols.sx = pointer(sx); P.cols.sy = pointer(sy)
+    P.cols.ghost_off = pointer(goff); P.cols.ghost_idx = pointer(gidx)
+    append!(P.keep, Any[vx, vy, sx, sy, goff, gidx])
+    off = Vector{Int32}(undef, n + 1); irows = Matrix{Float32}(undef, 7, max(Int(sizes[3]), 1))
+    GC.@preserve P sub begin
+        check(eng, @ccall lib.sz_download_list_rows_f32(eng.ctx::Ptr{Cvoid}, Int32(n)::Int32, r0::Ptr{Int32}, P.cols::Ref{SzFloeColumnsF32},
+                                                        off::Ptr{Int32}, irows::Ptr{Float32}, C_NULL::Ptr{Int64})::Cint)
+    end
+    return sub, P, goff, gidx[1:goff[end]], off, irows
+end
+
+# sz_splice_parents_f32 with the rows `rep` and `app_range` of the host list packed by pack32; the host list is the caller's to follow
+function splice_parents32!(eng::HIPEngine, floes::StructArray{<:Floe{Float32}}, del::AbstractVector{<:Integer}, rep::AbstractVector{<:Integer},
+                           app_range::AbstractUnitRange{<:Integer})
+    staged = vcat(collect(Int, rep), collect(Int, app_range))
+    isempty(staged) && error("splice_parents32!: nothing replaced or appended (a deletion alone needs no columns: splice_parents!)")
+    d0 = Int32.(del .- 1); r0 = Int32.(rep .- 1)
+    sub = floes[staged]
+    P = pack32(sub, length(sub))
+    off = Vector{Int32}(undef, length(sub) + 1); off[1] = 0
+    for i in 1:length(sub)
+        off[i+1] = off[i] + sub.num_inters[i]
+    end
+    irows = Matrix{Float32}(undef, 7, max(Int(off[end]), 1))
+    for i in 1:length(sub), k in 1:sub.num_inters[i]
+        irows[:, off[i]+k] .= @view sub.interactions[i][k, :]
+    end
+    GC.@preserve P sub begin
+        check(eng, @ccall lib.sz_splice_parents_f32(eng.ctx::Ptr{Cvoid}, Int32(length(d0))::Int32, d0::Ptr{Int32}, Int32(length(r0))::Int32,
+                                                    r0::Ptr{Int32}, Int32(length(app_range))::Int32, P.cols::Ref{SzFloeColumnsF32},
+                                                    off::Ptr{Int32}, irows::Ptr{Float32})::Cint)
+    end
+    return
+end
+
 # At a pending stop the device list holds the ghosts: the host rows follow the parents (pull_state!'s removal bookkeeping), then one row per
 # device ghost is appended -- a copy of its parent, overwritten by the download -- with the ghost lists, ids and ghost ids of the device.
 function pull_state_with_ghosts!(eng::HIPEngine, floes, P::Packed, ocean = nothing)

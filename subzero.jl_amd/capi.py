@@ -91,6 +91,7 @@ EXPORTS = [
     "sz_set_ridgeraft", "sz_ridgeraft_candidates", "sz_ridgeraft_pending", "sz_ridgeraft_draws", "sz_step_finish",
     "sz_tile_ridgeraft_candidates", "sz_tile_list_numbers", "sz_tile_list_keys", "sz_tile_step_finish",
     "sz_download_rows", "sz_splice_floes", "sz_download_rows_f32", "sz_splice_floes_f32",
+    "sz_ridgeraft_rows", "sz_download_list_rows", "sz_splice_parents", "sz_ridgeraft_rows_f32", "sz_download_list_rows_f32", "sz_splice_parents_f32",
 ]
 
 EUL_PARTIAL = 17      # SZ_EUL_PARTIAL: per-cell partial fields of sz_eulerian_partial
@@ -226,6 +227,11 @@ def load(build_if_missing=True):
     L.sz_splice_floes.argtypes = [C.c_void_p, C.c_int32, _ip, C.c_int32, _ip, C.c_int32, C.POINTER(SzFloeColumns), _ip, _dp]
     L.sz_download_rows_f32.argtypes = [C.c_void_p, C.c_int32, _ip, C.POINTER(SzFloeColumnsF32), _ip, _fp, _lp]
     L.sz_splice_floes_f32.argtypes = [C.c_void_p, C.c_int32, _ip, C.c_int32, _ip, C.c_int32, C.POINTER(SzFloeColumnsF32), _ip, _fp]
+    L.sz_ridgeraft_rows.argtypes = L.sz_ridgeraft_rows_f32.argtypes = [C.c_void_p, _ip, C.c_int32, _ip]
+    L.sz_download_list_rows.argtypes = L.sz_download_rows.argtypes
+    L.sz_splice_parents.argtypes = L.sz_splice_floes.argtypes
+    L.sz_download_list_rows_f32.argtypes = L.sz_download_rows_f32.argtypes
+    L.sz_splice_parents_f32.argtypes = L.sz_splice_floes_f32.argtypes
     for n in EXPORTS:
         if n not in ("sz_create", "sz_destroy", "sz_last_error", "sz_version"):
             getattr(L, n).restype = C.c_int

@@ -2486,12 +2486,12 @@ void sp_column_table(const State& S, double* out[MIG_NSC + 3]) {
   for (int k = 0; k < MIG_NSC + 3; k++) out[k] = t[k];
 }
 // rows[0..n): in [0, N), ascending without repeats (sorted) or merely without repeats
-int sp_check_rows(sz_ctx* c, const char* who, const char* what, int n, const int32_t* rows, int N, bool sorted) {
+int sp_check_rows(sz_ctx* c, const char* who, const char* what, int n, const int32_t* rows, int N, bool sorted, const char* of = "parents") {
   std::vector<int> tmp;
   const int32_t* r = rows;
   if (!sorted && n > 1) { tmp.assign(rows, rows + n); std::sort(tmp.begin(), tmp.end()); r = tmp.data(); }
   for (int k = 0; k < n; k++) {
-    if (r[k] < 0 || r[k] >= N) { c->err = std::string(who) + ": " + what + " names row " + std::to_string(r[k]) + ", outside the " + std::to_string(N) + " parents"; return SZ_E_ARG; }
+    if (r[k] < 0 || r[k] >= N) { c->err = std::string(who) + ": " + what + " names row " + std::to_string(r[k]) + ", outside the " + std::to_string(N) + " " + of; return SZ_E_ARG; }
     if (k && r[k] <= r[k - 1]) { c->err = std::string(who) + ": " + what + (r[k] == r[k - 1] ? " repeats row " + std::to_string(r[k]) : std::string(" is not ascending")); return SZ_E_ARG; }
   }
   return SZ_OK;
@@ -2506,38 +2506,40 @@ int sp_ghost_keys(sz_ctx* c, std::vector<long long>& sorted) {
 }
 }  // namespace
 
-int sz_download_rows(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns* f, int32_t* inter_off, double* inter_rows, int64_t* sizes3) {
+namespace {
+// sz_download_rows (list = false: parents, ghost_off zeros) and sz_download_list_rows (list = true: any row of the list, the ghost lists with it)
+int sp_download(sz_ctx* c, const char* who, bool list, int32_t n, const int32_t* rows, sz_floe_columns* f, int32_t* inter_off, double* inter_rows, int64_t* sizes3) {
   if (!c || n < 0 || (n > 0 && !rows)) return SZ_E_ARG;
-  if (!c->have_floes) { c->err = "sz_download_rows: no floes uploaded"; return SZ_E_STATE; }
+  if (!c->have_floes) { c->err = std::string(who) + ": no floes uploaded"; return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
   int rc;
   if ((rc = sync_and_check(c))) return rc;          // hostM / hostN current, nothing pending
-  const int N = c->hostN;
-  if ((rc = sp_check_rows(c, "sz_download_rows", "rows", n, rows, N, false))) return rc;
+  const int N = c->hostN, lim = list ? c->hostM : N;
+  if ((rc = sp_check_rows(c, who, "rows", n, rows, lim, false, list ? "rows of the list" : "parents"))) return rc;
   world_rings(c);
   State& S = c->S;
   const size_t n1 = (size_t)n + 1;
-  std::vector<int> off(3 * n1, 0);
+  std::vector<int> off(4 * n1, 0);
   Pool& P = c->sp_allocs;
   reset_pool(P);
   int *d_rows = nullptr, *d_len = nullptr, *d_off = nullptr; double** d_cols = nullptr; double* d_out = nullptr;
   if (n > 0) {
-    if ((rc = dalloc(c, &d_rows, n1, P)) || (rc = dalloc(c, &d_len, 3 * n1, P)) || (rc = dalloc(c, &d_off, 3 * n1, P)) || (rc = dalloc(c, &d_cols, 32, P))) return rc;
+    if ((rc = dalloc(c, &d_rows, n1, P)) || (rc = dalloc(c, &d_len, 4 * n1, P)) || (rc = dalloc(c, &d_off, 4 * n1, P)) || (rc = dalloc(c, &d_cols, 32, P))) return rc;
     H2D(d_rows, rows, n, int);
-    hipLaunchKernelGGL(sz_k_sp_sel_len, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, S, (int)n, (const int*)d_rows, c->pts_N > 0 ? 1 : 0, d_len);
-    for (int k = 0; k < 3; k++) scan(c, d_len + k * n1, d_off + k * n1, n, -1, n, -1);
-    HIPCHK(c, hipMemcpyAsync(off.data(), d_off, 3 * n1 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(sz_k_sp_sel_len, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, S, (int)n, (const int*)d_rows, c->pts_N > 0 ? N : 0, list ? N : 0, d_len);
+    for (int k = 0; k < 4; k++) scan(c, d_len + k * n1, d_off + k * n1, n, -1, n, -1);
+    HIPCHK(c, hipMemcpyAsync(off.data(), d_off, 4 * n1 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  const size_t V = (size_t)off[n], NS = (size_t)off[n1 + n], R = (size_t)off[2 * n1 + n];
+  const size_t V = (size_t)off[n], NS = (size_t)off[n1 + n], R = (size_t)off[2 * n1 + n], G = (size_t)off[3 * n1 + n];
   if (sizes3) { sizes3[0] = (int64_t)V; sizes3[1] = (int64_t)NS; sizes3[2] = (int64_t)R; }
   if (!f) return SZ_OK;
   if (f->vert_off) for (size_t k = 0; k < n1; k++) f->vert_off[k] = off[k];
   if (f->sub_off) for (size_t k = 0; k < n1; k++) f->sub_off[k] = off[n1 + k];
-  if (f->ghost_off) for (size_t k = 0; k < n1; k++) f->ghost_off[k] = 0;
+  if (f->ghost_off) for (size_t k = 0; k < n1; k++) f->ghost_off[k] = off[3 * n1 + k];          // (zeros where the ghost lists are not asked for)
   if (inter_off) for (size_t k = 0; k < n1; k++) inter_off[k] = off[2 * n1 + k];
   if (n == 0) return SZ_OK;
-  const size_t total = (size_t)SP_PACK_NCOL * n + 2 * V + 2 * NS + 7 * R;
+  const size_t total = (size_t)SP_PACK_NCOL * n + 2 * V + 2 * NS + 7 * R + (G + 1) / 2;
   if ((rc = dalloc(c, &d_out, total, P))) return rc;
   double* hcols[MIG_NSC + 3];
   sp_column_table(S, hcols);
@@ -2562,6 +2564,7 @@ int sz_download_rows(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns*
   const double *sx = ring + 2 * V, *sy = sx + NS, *ir = sy + NS;
   if (f->sx && NS) memcpy(f->sx, sx, NS * sizeof(double));
   if (f->sy && NS) memcpy(f->sy, sy, NS * sizeof(double));
+  if (f->ghost_idx && G) memcpy(f->ghost_idx, ir + 7 * R, G * sizeof(int32_t));
   if (inter_rows && R) {
     memcpy(inter_rows, ir, 7 * R * sizeof(double));
     std::vector<long long> sorted;
@@ -2580,49 +2583,63 @@ int sz_download_rows(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns*
   }
   return SZ_OK;
 }
+}  // namespace
 
-int sz_splice_floes(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns* f,
-                    const int32_t* ioff, const double* irows) {
+int sz_download_rows(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns* f, int32_t* inter_off, double* inter_rows, int64_t* sizes3) {
+  return sp_download(c, "sz_download_rows", false, n, rows, f, inter_off, inter_rows, sizes3);
+}
+int sz_download_list_rows(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns* f, int32_t* inter_off, double* inter_rows, int64_t* sizes3) {
+  return sp_download(c, "sz_download_list_rows", true, n, rows, f, inter_off, inter_rows, sizes3);
+}
+
+namespace {
+// sz_splice_floes (parents = false: a ghost-free list with nothing pending) and sz_splice_parents (parents = true: the ghosts of the list are dropped
+// first, as sz_remove_ghosts drops them, and a pending mark stays) -- every check comes before the first change
+int sp_splice(sz_ctx* c, const char* who_, bool parents, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns* f,
+              const int32_t* ioff, const double* irows) {
+  const std::string who(who_);
   if (!c || n_del < 0 || n_rep < 0 || n_app < 0 || (n_del && !del) || (n_rep && !rep)) return SZ_E_ARG;
   const long long ns64 = (long long)n_rep + n_app;
   if (ns64 > 0x3fffffff) return SZ_E_ARG;
   const int ns = (int)ns64;
-  if (ns > 0 && (!f || !f->vert_off || !f->vx || !f->vy || !f->cx || !f->cy)) { c->err = "sz_splice_floes: replaced / appended rows need vert_off, vx, vy, cx and cy"; return SZ_E_ARG; }
-  if (!c->have_floes) { c->err = "sz_splice_floes: no floes uploaded"; return SZ_E_STATE; }
-  if (c->S.tiled) { c->err = "sz_splice_floes: the rows of a tiled context carry global numbers and its list is one rank's share: not supported on tiled contexts"; return SZ_E_STATE; }
-  if (c->rr_pending >= 0) { c->err = "sz_splice_floes: a ridge / raft step is pending with its ghosts in the list (sz_step_finish first)"; return SZ_E_STATE; }
+  if (ns > 0 && (!f || !f->vert_off || !f->vx || !f->vy || !f->cx || !f->cy)) { c->err = who + ": replaced / appended rows need vert_off, vx, vy, cx and cy"; return SZ_E_ARG; }
+  if (!c->have_floes) { c->err = who + ": no floes uploaded"; return SZ_E_STATE; }
+  if (c->S.tiled) { c->err = who + ": the rows of a tiled context carry global numbers and its list is one rank's share: not supported on tiled contexts"; return SZ_E_STATE; }
+  if (!parents && c->rr_pending >= 0) { c->err = who + ": a ridge / raft step is pending with its ghosts in the list (sz_step_finish first)"; return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
   int rc;
   if ((rc = sync_and_check(c))) return rc;          // hostM / hostN current, nothing pending
-  if (c->hostM != c->hostN) { c->err = "sz_splice_floes: ghosts are in the list (sz_remove_ghosts first): the edit is of the parents alone"; return SZ_E_STATE; }
+  if (!parents && c->hostM != c->hostN) { c->err = who + ": ghosts are in the list (sz_remove_ghosts first): the edit is of the parents alone"; return SZ_E_STATE; }
   State& S = c->S;
   const int N = c->hostN;
   // ---- the edit itself: rows, then the uploaded floes
-  if ((rc = sp_check_rows(c, "sz_splice_floes", "del", n_del, del, N, true)) || (rc = sp_check_rows(c, "sz_splice_floes", "rep", n_rep, rep, N, true))) return rc;
+  if ((rc = sp_check_rows(c, who_, "del", n_del, del, N, true)) || (rc = sp_check_rows(c, who_, "rep", n_rep, rep, N, true))) return rc;
   for (int a = 0, b = 0; a < n_del && b < n_rep;) {
-    if (del[a] == rep[b]) { c->err = "sz_splice_floes: row " + std::to_string(del[a]) + " is both deleted and replaced"; return SZ_E_ARG; }
+    if (del[a] == rep[b]) { c->err = who + ": row " + std::to_string(del[a]) + " is both deleted and replaced"; return SZ_E_ARG; }
     if (del[a] < rep[b]) a++; else b++;
   }
   const long long Nn64 = (long long)N - n_del + n_app;
-  if (Nn64 <= 0) { c->err = "sz_splice_floes: the edit leaves no floe"; return SZ_E_ARG; }
-  if (Nn64 > 0x3fffffff) { c->err = "sz_splice_floes: too many floes"; return SZ_E_ARG; }
+  if (Nn64 <= 0) { c->err = who + ": the edit leaves no floe"; return SZ_E_ARG; }
+  if (Nn64 > 0x3fffffff) { c->err = who + ": too many floes"; return SZ_E_ARG; }
   const int Nn = (int)Nn64;
   const bool with_sub = ns > 0 && f->sub_off != nullptr;
-  if (with_sub && (!f->sx || !f->sy) && f->sub_off[ns] != f->sub_off[0]) { c->err = "sz_splice_floes: sub_off without sx / sy"; return SZ_E_ARG; }
+  if (with_sub && (!f->sx || !f->sy) && f->sub_off[ns] != f->sub_off[0]) { c->err = who + ": sub_off without sx / sy"; return SZ_E_ARG; }
   size_t stream_len = 0;
   for (int j = 0; j < ns; j++) {
     const int o = f->vert_off[j], nv = f->vert_off[j + 1] - o, sp = with_sub ? f->sub_off[j + 1] - f->sub_off[j] : 0, ni = ioff ? ioff[j + 1] - ioff[j] : 0;
-    if (nv < 4 || o < 0 || !(f->vx[o] == f->vx[o + nv - 1] && f->vy[o] == f->vy[o + nv - 1])) { c->err = "sz_splice_floes: uploaded row " + std::to_string(j) + " has an open ring (a ring is closed: its first point repeated, at least 4 points)"; return SZ_E_ARG; }
-    if (nv > SP_MAX_RING) { c->err = "sz_splice_floes: uploaded row " + std::to_string(j) + " has a ring of " + std::to_string(nv) + " points: the row-moving kernels carry " + std::to_string(SP_MAX_RING); return SZ_E_ARG; }
-    if (sp < 0 || ni < 0) { c->err = "sz_splice_floes: offsets of uploaded row " + std::to_string(j) + " descend"; return SZ_E_ARG; }
-    if (sp > 0 && c->pts_N == 0) { c->err = "sz_splice_floes: the list was uploaded without sub-floe points"; return SZ_E_ARG; }
+    if (nv < 4 || o < 0 || !(f->vx[o] == f->vx[o + nv - 1] && f->vy[o] == f->vy[o + nv - 1])) { c->err = who + ": uploaded row " + std::to_string(j) + " has an open ring (a ring is closed: its first point repeated, at least 4 points)"; return SZ_E_ARG; }
+    if (nv > SP_MAX_RING) { c->err = who + ": uploaded row " + std::to_string(j) + " has a ring of " + std::to_string(nv) + " points: the row-moving kernels carry " + std::to_string(SP_MAX_RING); return SZ_E_ARG; }
+    if (sp < 0 || ni < 0) { c->err = who + ": offsets of uploaded row " + std::to_string(j) + " descend"; return SZ_E_ARG; }
+    if (sp > 0 && c->pts_N == 0) { c->err = who + ": the list was uploaded without sub-floe points"; return SZ_E_ARG; }
     if (ni > S.rowcap) { c->err = "more interaction rows per floe than the fixed stride holds"; return SZ_E_CAPACITY; }
-    if (ni > 0 && !irows) { c->err = "sz_splice_floes: inter_off without inter_rows"; return SZ_E_ARG; }
+    if (ni > 0 && !irows) { c->err = who + ": inter_off without inter_rows"; return SZ_E_ARG; }
     stream_len += (size_t)MIG_NCOL + 2 * (size_t)nv + 2 * (size_t)sp;
   }
-  if (stream_len > 0x7fffffffull) { c->err = "sz_splice_floes: the uploaded rows are too long for one stream"; return SZ_E_ARG; }
+  if (stream_len > 0x7fffffffull) { c->err = who + ": the uploaded rows are too long for one stream"; return SZ_E_ARG; }
   if (n_del + ns == 0) return SZ_OK;          // nothing to do, nothing touched
   // ---- from here on the state changes
+  const int Mold = c->hostM;          // (the rows the list's ghosts held are vacated too)
+  if (parents && (Mold != N || c->ghosts_staged)) { if ((rc = sz_remove_ghosts(c))) return rc; }
   leave_resident(c);
   std::vector<long long> keys;
   if ((rc = sp_ghost_keys(c, keys))) return rc;
@@ -2694,7 +2711,7 @@ int sz_splice_floes(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep,
   SpDev R{};
   HIPCHK(c, hipMemcpyAsync(&R, A.d, sizeof(SpDev), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (R.Nn != Nn || R.Vn < 0 || R.NSn < 0) { c->err = "sz_splice_floes: bad counts"; return SZ_E_HIP; }
+  if (R.Nn != Nn || R.Vn < 0 || R.NSn < 0) { c->err = who + ": bad counts"; return SZ_E_HIP; }
   const int Vn = R.Vn, NSn = R.NSn, tcap = S.rowcap;
   // ---- the rows of the edited list, gathered beside the old ones: kept rows from the list, the others from the stream
   double** d_cols = nullptr; double *d_tmp = nullptr, *d_tsx = nullptr, *d_tsy = nullptr, *d_trows = nullptr; double2* d_tv = nullptr; int* d_tcnt = nullptr;
@@ -2743,8 +2760,9 @@ int sz_splice_floes(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep,
   // ---- and into their places, with the links of a freshly placed ghost-free field (as sz_upload_floes leaves them)
   hipLaunchKernelGGL(sz_k_mig_scatter, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (double* const*)d_cols, (const double*)d_tmp);
   hipLaunchKernelGGL(sz_k_sp_scatter_rows, dim3(nbw), dim3(256), 0, c->stream, S, Nn, c->origin, tcap, (const int*)d_tcnt, (const double*)d_trows);
-  if (fits && N > Nn) hipLaunchKernelGGL(sz_k_sp_clear_rows, dim3(grid_for(N - Nn, 256, 2048)), dim3(256), 0, c->stream, Nn, N, (double* const*)d_cols);
-  if (std::min(N, S.capM) > Nn) HIPCHK(c, hipMemsetAsync(S.inter_cnt + Nn, 0, (size_t)(std::min(N, S.capM) - Nn) * sizeof(int), c->stream));
+  const int top = std::min(std::max(N, Mold), S.capM);
+  if (fits && top > Nn) hipLaunchKernelGGL(sz_k_sp_clear_rows, dim3(grid_for(top - Nn, 256, 2048)), dim3(256), 0, c->stream, Nn, top, (double* const*)d_cols);
+  if (top > Nn) HIPCHK(c, hipMemsetAsync(S.inter_cnt + Nn, 0, (size_t)(top - Nn) * sizeof(int), c->stream));
   if (Vn) HIPCHK(c, hipMemcpyAsync(S.vxy, d_tv, (size_t)Vn * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(S.voff, A.nvoff, ((size_t)Nn + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
   if (c->pts_N) {
@@ -2762,12 +2780,25 @@ int sz_splice_floes(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep,
   c->max_ring = R.max_ring; if (c->pts_N) c->max_sub = R.max_sub;          // (as an upload of the edited list finds them)
   return SZ_OK;
 }
+}  // namespace
+
+int sz_splice_floes(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns* f,
+                    const int32_t* ioff, const double* irows) {
+  return sp_splice(c, "sz_splice_floes", false, n_del, del, n_rep, rep, n_app, f, ioff, irows);
+}
+int sz_splice_parents(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns* f,
+                      const int32_t* ioff, const double* irows) {
+  return sp_splice(c, "sz_splice_parents", true, n_del, del, n_rep, rep, n_app, f, ioff, irows);
+}
 
 // ... for Float32 hosts: widened on the way in, rounded on the way out, exactly as sz_upload_floes_f32 / sz_download_floes_f32 do
-int sz_download_rows_f32(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns_f32* f, int32_t* inter_off, float* inter_rows, int64_t* sizes3) {
+namespace {
+using sp_download_fn = int (*)(sz_ctx*, int32_t, const int32_t*, sz_floe_columns*, int32_t*, double*, int64_t*);
+using sp_splice_fn = int (*)(sz_ctx*, int32_t, const int32_t*, int32_t, const int32_t*, int32_t, const sz_floe_columns*, const int32_t*, const double*);
+int sp_download_f32(sp_download_fn down, sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns_f32* f, int32_t* inter_off, float* inter_rows, int64_t* sizes3) {
   if (!c || n < 0) return SZ_E_ARG;
   int64_t sz[3] = { 0, 0, 0 };
-  int rc = sz_download_rows(c, n, rows, nullptr, nullptr, nullptr, sz); if (rc) return rc;
+  int rc = down(c, n, rows, nullptr, nullptr, nullptr, sz); if (rc) return rc;
   if (sizes3) { sizes3[0] = sz[0]; sizes3[1] = sz[1]; sizes3[2] = sz[2]; }
   if (!f) return SZ_OK;
   const size_t M = (size_t)n, V = (size_t)sz[0], NS = (size_t)sz[1], R = (size_t)sz[2];
@@ -2789,16 +2820,16 @@ int sz_download_rows_f32(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_colu
   d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
   d.vx = room(f->vx, V); d.vy = room(f->vy, V); d.sx = room(f->sx, NS); d.sy = room(f->sy, NS);
   double* ir = room(inter_rows, 7 * R);
-  rc = sz_download_rows(c, n, rows, &d, inter_off, ir, nullptr); if (rc) return rc;
+  rc = down(c, n, rows, &d, inter_off, ir, nullptr); if (rc) return rc;
   for (const Back& b : back) for (size_t k = 0; k < b.n; k++) b.dst[k] = (float)b.src[k];
   return SZ_OK;
 }
-int sz_splice_floes_f32(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns_f32* f,
-                        const int32_t* ioff, const float* irows) {
+int sp_splice_f32(sp_splice_fn splice, const char* who, sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app,
+                  const sz_floe_columns_f32* f, const int32_t* ioff, const float* irows) {
   if (!c || n_rep < 0 || n_app < 0) return SZ_E_ARG;
   const size_t M = (size_t)n_rep + (size_t)n_app;
-  if (M == 0 || !f) return sz_splice_floes(c, n_del, del, n_rep, rep, n_app, nullptr, ioff, nullptr);
-  if (!f->vert_off) { c->err = "sz_splice_floes_f32: vert_off is required"; return SZ_E_ARG; }
+  if (M == 0 || !f) return splice(c, n_del, del, n_rep, rep, n_app, nullptr, ioff, nullptr);
+  if (!f->vert_off) { c->err = std::string(who) + ": vert_off is required"; return SZ_E_ARG; }
   const size_t V = (size_t)f->vert_off[M], NS = f->sub_off ? (size_t)f->sub_off[M] : 0, R = ioff ? (size_t)ioff[M] : 0;
   std::vector<std::vector<double>> keep;
   auto widen = [&](const float* src, size_t cnt) -> double* {
@@ -2816,7 +2847,22 @@ int sz_splice_floes_f32(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_
 #undef X
   d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
   d.vx = widen(f->vx, V); d.vy = widen(f->vy, V); d.sx = widen(f->sx, NS); d.sy = widen(f->sy, NS);
-  return sz_splice_floes(c, n_del, del, n_rep, rep, n_app, &d, ioff, widen(irows, 7 * R));
+  return splice(c, n_del, del, n_rep, rep, n_app, &d, ioff, widen(irows, 7 * R));
+}
+}  // namespace
+int sz_download_rows_f32(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns_f32* f, int32_t* inter_off, float* inter_rows, int64_t* sizes3) {
+  return sp_download_f32(sz_download_rows, c, n, rows, f, inter_off, inter_rows, sizes3);
+}
+int sz_download_list_rows_f32(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns_f32* f, int32_t* inter_off, float* inter_rows, int64_t* sizes3) {
+  return sp_download_f32(sz_download_list_rows, c, n, rows, f, inter_off, inter_rows, sizes3);
+}
+int sz_splice_floes_f32(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns_f32* f,
+                        const int32_t* ioff, const float* irows) {
+  return sp_splice_f32(sz_splice_floes, "sz_splice_floes_f32", c, n_del, del, n_rep, rep, n_app, f, ioff, irows);
+}
+int sz_splice_parents_f32(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns_f32* f,
+                          const int32_t* ioff, const float* irows) {
+  return sp_splice_f32(sz_splice_parents, "sz_splice_parents_f32", c, n_del, del, n_rep, rep, n_app, f, ioff, irows);
 }
 
 // ---------------------------------------------------------------- ridge / raft candidates (sz_ridgeraft.hpp)
@@ -2917,6 +2963,38 @@ int sz_ridgeraft_candidates(sz_ctx* c, int32_t* n, int32_t cap, int32_t* idx_i, 
   }
   return SZ_OK;
 }
+// The closure of the table (sz_ridgeraft.hpp): the rows of its entries, their root parents and those parents' ghosts, ascending, each once.
+int sz_ridgeraft_rows(sz_ctx* c, int32_t* n, int32_t cap, int32_t* rows) {
+  if (n) *n = 0;
+  if (!c || !n) return SZ_E_ARG;
+  if (!c->rr_on) { c->err = "sz_ridgeraft_rows: ridge / raft is not set (sz_set_ridgeraft)"; return SZ_E_STATE; }
+  if (int rc = rr_state_checks(c, "sz_ridgeraft_rows")) return rc;
+  (void)hipSetDevice(c->device);
+  if (int rc = sync_and_check(c)) return rc;          // hostM / hostN current
+  int nt = 0; long long nd = 0;
+  if (int rc = rr_pass(c, c->rr_h, &nt, &nd)) return rc;
+  if (nt == 0) return SZ_OK;
+  const int M = c->hostM, N = c->hostN;
+  Pool& P = c->sp_allocs;
+  reset_pool(P);
+  int *flag = nullptr, *off = nullptr, *out = nullptr, rc;
+  if ((rc = dalloc(c, &flag, (size_t)M + 1, P)) || (rc = dalloc(c, &off, (size_t)M + 2, P)) || (rc = dalloc(c, &out, (size_t)M + 1, P))) return rc;
+  HIPCHK(c, hipMemsetAsync(flag, 0, ((size_t)M + 1) * sizeof(int), c->stream));
+  hipLaunchKernelGGL(sz_k_rr_mark, dim3(grid_for(nt, 256, 2048)), dim3(256), 0, c->stream, c->S, (const int*)c->rr.ti, (const int*)c->rr.tj, nt, M, N, flag);
+  scan(c, flag, off, M, -1, M, -1);
+  hipLaunchKernelGGL(sz_k_rr_compact, dim3(grid_for(M, 256, 2048)), dim3(256), 0, c->stream, (const int*)flag, (const int*)off, M, out);
+  int total = 0;
+  HIPCHK(c, hipMemcpyAsync(&total, off + M, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (total < 0 || total > M) { c->err = "sz_ridgeraft_rows: bad row count"; return SZ_E_HIP; }
+  *n = total;
+  if (!rows) return SZ_OK;
+  if (cap < total) { c->err = "sz_ridgeraft_rows: cap is smaller than the closure (*n)"; return SZ_E_ARG; }
+  if (total > 0) HIPCHK(c, hipMemcpy(rows, out, (size_t)total * sizeof(int), hipMemcpyDeviceToHost));
+  return SZ_OK;
+}
+// (a Float32 host's name for the same call: no floating-point value crosses it)
+int sz_ridgeraft_rows_f32(sz_ctx* c, int32_t* n, int32_t cap, int32_t* rows) { return sz_ridgeraft_rows(c, n, cap, rows); }
 int sz_ridgeraft_pending(sz_ctx* c, int32_t* tstep) {
   if (!c || !tstep) return SZ_E_ARG;
   *tstep = c->rr_pending;

@@ -13,6 +13,8 @@
 //   sz_k_rr_scan    ONE workgroup: exclusive offsets of the counts, the total
 //   sz_k_rr_write   the entries at their offsets: ascending i, then first-passing-row order -- columns i, j (the reference's numbering of rows:
 //                   partner index, -1..-4, -(4 + k)), kind, frac.  No atomic decides a position: the same table on every run
+//   sz_k_rr_mark,   sz_ridgeraft_rows: the rows of the table's entries with their root parents and those parents' ghosts, flagged,
+//   sz_k_rr_compact then compacted into ascending list rows (at the end of this file)
 // The gates are stated once, in rr_row, which takes a policy for how a list names its rows: RrSingle here, RrTiled in sz_ridgeraft_tile.hpp.
 // A dependent-load chain over the rows of floe.interactions (ROWCAP rows of 7 doubles per floe), one thread per list row.  fp64 in every precision mode.
 #pragma once
@@ -150,6 +152,35 @@ __global__ void __launch_bounds__(256) sz_k_rr_write(State S, RrArgs A) {
       o++;
     });
   }
+}
+
+// ---- sz_ridgeraft_rows: the list rows the host's ridging and rafting can touch, from the table above.  An entry (i, j) names row
+// i and, where j > 0, row j - 1; each of them stands for its family -- the root parent (the row < n that its parent link leads to: the row the
+// reference's findfirst over floes.id finds) and every ghost on that parent's list.
+//   sz_k_rr_mark      one thread per entry: flag 1 onto the two rows and their families.  Every writer writes the same value: no atomic, no order
+//   (the engine's scan of the flags)
+//   sz_k_rr_compact   flagged row r -> out[off[r]]: ascending list rows, each once
+__device__ __forceinline__ void rr_mark_family(const State& S, int r, int m, int n, int* flag) {
+  if (r < 0 || r >= m) return;
+  flag[r] = 1;
+  int p = r;
+  for (int hop = 0; hop < MAX_GHOSTS && p >= n && p < m; hop++) p = S.parent[p];
+  if (p < 0 || p >= n) return;
+  flag[p] = 1;
+  const int ng = min(S.ngh[p] & 0xff, MAX_GHOSTS);
+  for (int k = 0; k < ng; k++) { const int g = S.gh[p * MAX_GHOSTS + k]; if (g >= 0 && g < m) flag[g] = 1; }
+}
+// ti / tj: nt entries of the table; m list rows of which the first n are parents; flag: m entries, zeroed
+__global__ void __launch_bounds__(256) sz_k_rr_mark(State S, const int* ti, const int* tj, int nt, int m, int n, int* flag) {
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nt; e += gridDim.x * blockDim.x) {
+    rr_mark_family(S, ti[e], m, n, flag);
+    const int j = tj[e];
+    if (j > 0) rr_mark_family(S, j - 1, m, n, flag);
+  }
+}
+__global__ void __launch_bounds__(256) sz_k_rr_compact(const int* flag, const int* off, int m, int* out) {
+  for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < m; r += gridDim.x * blockDim.x)
+    if (flag[r]) { const int o = off[r]; if (o >= 0 && o < m) out[o] = r; }
 }
 
 }  // namespace sz

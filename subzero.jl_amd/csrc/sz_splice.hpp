@@ -1,4 +1,4 @@
-// sz_splice.hpp — device side of sz_download_rows and sz_splice_floes: a few rows of the resident list go down to the host,
+// sz_splice.hpp — device side of sz_download_rows / sz_download_list_rows and sz_splice_floes / sz_splice_parents: a few rows of the resident list go down to the host,
 // the host edits them, and the edit -- rows replaced in place, rows deleted, rows appended -- is spliced back; the other rows stay in HBM.
 //
 // A splice is a migration whose stream comes from the host, combined with removal's compaction.  The host packs the n_rep + n_app uploaded rows
@@ -14,8 +14,8 @@
 //     sz_k_sp_scatter_rows that was an inline ghost is renumbered as a download would), staged ones from the uploaded CSR; and back, with `origin` and
 //                          the order keys as the identity and the tag column equal to the status column, as sz_upload_floes leaves them
 //     sz_k_sp_clear_rows   the rows a shrinking list vacates, zeroed
-//     sz_k_sp_sel_len,     sz_download_rows: the lengths of the selected rows (scanned into the offsets of the staging buffer), then one wavefront
-//     sz_k_sp_pack         per selected row packs columns, ring, sub-floe points and interaction rows into that buffer
+//     sz_k_sp_sel_len,     sz_download_rows / sz_download_list_rows: the lengths of the selected rows (scanned into the offsets of the staging buffer),
+//     sz_k_sp_pack         then one wavefront per selected row packs columns, ring, sub-floe points, interaction rows and ghost list into that buffer
 // Rows move through temporaries (an in-place parallel shift races: sz_remove.hpp); every hand-off between workgroups is a kernel boundary; fp64
 // values move as bits.
 #pragma once
@@ -147,25 +147,30 @@ __global__ void __launch_bounds__(256) sz_k_sp_clear_rows(int from, int to, doub
   }
 }
 
-// ---- sz_download_rows
-// len[k], len[n + 1 + k], len[2 (n + 1) + k]: ring points, sub-floe points and interaction rows of selected row k (three arrays of n + 1 entries)
-__global__ void __launch_bounds__(256) sz_k_sp_sel_len(State S, int n, const int* rows, int with_sub, int* len) {
+// ---- sz_download_rows / sz_download_list_rows
+// len[a (n + 1) + k], a = 0..3: ring points, sub-floe points, interaction rows and ghost-list entries of selected row k (four arrays of n + 1
+// entries).  nsub: the rows below it have sub-floe points (the parents of a list uploaded with points; 0: none) -- the points' offsets are not read
+// at or beyond it, a ghost row has no points; nlist: the rows below it have a ghost list that is reported (0: sz_download_rows, which writes zeros)
+__global__ void __launch_bounds__(256) sz_k_sp_sel_len(State S, int n, const int* rows, int nsub, int nlist, int* len) {
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
     const int i = rows[k];
     len[k] = S.voff[i + 1] - S.voff[i];
-    len[n + 1 + k] = with_sub ? S.soff[i + 1] - S.soff[i] : 0;
+    len[n + 1 + k] = i < nsub ? S.soff[i + 1] - S.soff[i] : 0;
     len[2 * (n + 1) + k] = min(max(S.inter_cnt[i], 0), S.rowcap);
+    len[3 * (n + 1) + k] = i < nlist ? min(S.ngh[i] & 0xff, MAX_GHOSTS) : 0;
   }
 }
 // The staging buffer, in doubles: [0, SP_PACK_NCOL n) the columns (column q of selected row k at q n + k; id, status and ghost_id as bits in a double's place),
-// then the rings as {x, y} pairs, the sub-floe points x.. and y.., the interaction rows; off: the scanned lengths (3 x (n + 1)).
+// then the rings as {x, y} pairs, the sub-floe points x.. and y.., the interaction rows, and last the ghost lists as 32-bit list numbers (two to a
+// double's place); off: the scanned lengths (4 x (n + 1)).
 // cols: the MIG_NSC scalar columns, then stress_accum, stress_instant, strain.
 __global__ void __launch_bounds__(256) sz_k_sp_pack(State S, int n, const int* rows, const int* off, double* const* cols, double* out) {
   const int lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-  const int* voff = off; const int* soff = off + (n + 1); const int* ioff = off + 2 * (n + 1);
-  const size_t V = (size_t)voff[n], NS = (size_t)soff[n];
+  const int* voff = off; const int* soff = off + (n + 1); const int* ioff = off + 2 * (n + 1); const int* goff = off + 3 * (n + 1);
+  const size_t V = (size_t)voff[n], NS = (size_t)soff[n], R = (size_t)ioff[n];
   double* ring = out + (size_t)SP_PACK_NCOL * n;
   double* sx = ring + 2 * V; double* sy = sx + NS; double* irow = sy + NS;
+  int* glist = (int*)(irow + 7 * R);
   for (int k = wave; k < n; k += nw) {
     const int i = rows[k];
     if (lane < MIG_NSC) out[(size_t)lane * n + k] = cols[lane][i];
@@ -173,7 +178,8 @@ __global__ void __launch_bounds__(256) sz_k_sp_pack(State S, int n, const int* r
     else if (lane == 37) out[(size_t)37 * n + k] = __longlong_as_double(S.id[i]);
     else if (lane == 38) out[(size_t)38 * n + k] = __longlong_as_double((long long)S.status[i]);
     else if (lane == 39) out[(size_t)39 * n + k] = __longlong_as_double(S.ghost_id[i]);
-    const int vo = S.voff[i], nv = voff[k + 1] - voff[k], po = S.soff[i], ns = soff[k + 1] - soff[k], ni = (ioff[k + 1] - ioff[k]) * 7;
+    const int vo = S.voff[i], nv = voff[k + 1] - voff[k], ns = soff[k + 1] - soff[k], ni = (ioff[k + 1] - ioff[k]) * 7, ng = goff[k + 1] - goff[k];
+    const int po = ns > 0 ? S.soff[i] : 0;
     const double* from = (const double*)(S.vxy + vo);
     double* to = ring + 2 * (size_t)voff[k];
     for (int q = lane; q < 2 * nv; q += 64) to[q] = from[q];
@@ -181,6 +187,7 @@ __global__ void __launch_bounds__(256) sz_k_sp_pack(State S, int n, const int* r
     const double* rf = S.inter_rows + (size_t)S.rowcap * 7 * i;
     double* rt = irow + (size_t)ioff[k] * 7;
     for (int q = lane; q < ni; q += 64) rt[q] = rf[q];
+    if (lane < ng) glist[goff[k] + lane] = S.gh[i * MAX_GHOSTS + lane];
   }
 }
 

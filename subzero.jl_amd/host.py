@@ -604,6 +604,19 @@ class World:
         m = int(n.value)
         return i[:m].copy(), j[:m].copy(), k[:m].copy(), f[:m].copy(), int(nd.value)
 
+    def ridgeraft_rows(self):
+        """the list rows the host's ridging and rafting can touch (sz_ridgeraft_rows), where ridgeraft_candidates() is valid: for every table
+        entry row i and, for a floe partner, row j - 1, each with its root parent and every ghost on that parent's ghost list -- ascending
+        0-based list rows, each once; empty for an empty table"""
+        self._push_interactions()
+        fn = self.L.sz_ridgeraft_rows_f32 if self._ft == np.float32 else self.L.sz_ridgeraft_rows
+        n = C.c_int32(0)
+        self._chk(fn(self.h, C.byref(n), 0, None))
+        cap = max(int(n.value), 1)
+        rows = np.zeros(cap, _I32)
+        self._chk(fn(self.h, C.byref(n), cap, capi.ptr(rows, capi._ip)))
+        return rows[:int(n.value)].copy()
+
     def ridgeraft_pending(self):
         """the timestep whose ridge / raft step is pending (run() stopped in its middle), or -1"""
         t = C.c_int32(-1)
@@ -732,12 +745,23 @@ class World:
         """the parents `rows` (0-based, any order, none twice) as a dict in the layout of load_columns: every column with len(rows) entries in
         that order, the rings (vert_off, vx, vy), the sub-floe points (sub_off, sx, sy) and floe.interactions (inter_off, inter_rows k x 7) as
         CSR -- each value as a full download gives it"""
+        return self._download_rows(rows, False)
+
+    def download_list_rows(self, rows):
+        """download_rows over the whole list (sz_download_list_rows): `rows` may name any list row, ghosts included; the dict of download_rows
+        plus ghost_off / ghost_idx -- a parent's ghost list in list numbers, an empty one for a ghost row (whose sub_off span is empty too)"""
+        return self._download_rows(rows, True)
+
+    def _download_rows(self, rows, whole_list):
         self._push_interactions()
         f32 = self._ft == np.float32
         rows = np.ascontiguousarray(rows, _I32).ravel()
         n = len(rows)
         sizes = np.zeros(3, _I64)
-        fn = self.L.sz_download_rows_f32 if f32 else self.L.sz_download_rows
+        if whole_list:
+            fn = self.L.sz_download_list_rows_f32 if f32 else self.L.sz_download_list_rows
+        else:
+            fn = self.L.sz_download_rows_f32 if f32 else self.L.sz_download_rows
         self._chk(fn(self.h, n, capi.ptr(rows, capi._ip), None, None, None, capi.ptr(sizes, capi._lp)))
         V, NS, R = (int(v) for v in sizes)
         col = {k: np.zeros(n, self._ft) for k in capi.DCOLS}
@@ -748,9 +772,13 @@ class World:
         col["vert_off"] = np.zeros(n + 1, _I32); col["vx"] = np.zeros(V, self._ft); col["vy"] = np.zeros(V, self._ft)
         col["sub_off"] = np.zeros(n + 1, _I32); col["sx"] = np.zeros(NS, self._ft); col["sy"] = np.zeros(NS, self._ft)
         ioff = np.zeros(n + 1, _I32); irows = np.zeros((R, 7), self._ft)
+        if whole_list:
+            col["ghost_off"] = np.zeros(n + 1, _I32); col["ghost_idx"] = np.zeros(max(3 * n, 1), _I32)
         keep = []
         f = self._columns_struct(col, keep)
         self._chk(fn(self.h, n, capi.ptr(rows, capi._ip), C.byref(f), capi.ptr(ioff, capi._ip), capi.ptr(irows, capi._fp if f32 else capi._dp), None))
+        if whole_list:
+            col["ghost_idx"] = col["ghost_idx"][:col["ghost_off"][n]].copy()
         if f32:
             col = {k: (v.astype(np.float64) if v.dtype == np.float32 else v) for k, v in col.items()}
             irows = irows.astype(np.float64)
@@ -794,6 +822,16 @@ class World:
         (of the list as it is, before the deletion) overwritten by the floes of a dict in the layout of download_rows; append = such a dict of
         floes that go behind the last kept row, in their order.  Afterwards the device holds what an upload of the edited list and its interaction
         lists would have left; this object's copy of the columns is fetched again when it is next looked at."""
+        self._splice(delete, replace, append, False)
+
+    def splice_parents(self, delete=(), replace=None, append=None):
+        """splice on a list that still holds its ghosts (sz_splice_parents) -- a pending ridge / raft stop, or add_ghosts by hand: the ghosts are
+        dropped as remove_ghosts drops them, then the edit is applied to the parents; rows number the parents as they are, ghost columns of the
+        floes are ignored, a pending step stays pending (finish_step runs its second half).  An all-empty edit changes nothing and keeps the
+        ghosts.  With no ghosts and nothing pending it is splice."""
+        self._splice(delete, replace, append, True)
+
+    def _splice(self, delete, replace, append, parents):
         self._push_interactions()
         f32 = self._ft == np.float32
         dele = np.ascontiguousarray(delete, _I32).ravel()
@@ -806,7 +844,10 @@ class World:
         f = self._columns_struct(col, keep) if col is not None else None
         if irows is not None:
             irows = np.ascontiguousarray(irows, self._ft)
-        fn = self.L.sz_splice_floes_f32 if f32 else self.L.sz_splice_floes
+        if parents:
+            fn = self.L.sz_splice_parents_f32 if f32 else self.L.sz_splice_parents
+        else:
+            fn = self.L.sz_splice_floes_f32 if f32 else self.L.sz_splice_floes
         self._chk(fn(self.h, len(dele), capi.ptr(dele, capi._ip), len(rep_rows), capi.ptr(rep_rows, capi._ip), int(n_app),
                      C.byref(f) if f is not None else None, capi.ptr(ioff, capi._ip) if ioff is not None else None,
                      capi.ptr(irows, capi._fp if f32 else capi._dp) if irows is not None and len(irows) else None))
