@@ -724,6 +724,12 @@ int sz_debug_stamps(sz_ctx *ctx, long long *out512);
    DESIGN.md section 3.00) of the owned parents that differ from the columns after the last resident batch -- 0 expected; -1: that batch
    did not run on records */
 int sz_debug_crec_mismatches(sz_ctx *ctx, int64_t *n_bad);
+/* test hook: the cutter of the stop schedule that sz_step and sz_tile_run share (csrc/sz_stops.hpp), with no context and no device call.  The
+   segment that starts at timestep tstep with `remaining` steps of the batch left, for RidgeRaftSettings.Δt rr_dt (0: off), FractureSettings.Δt
+   frac_dt (0: no criterion), the n_weld WeldSettings.Δts and cut_on_fracture (1: segments end on fracture steps too, as on tiled contexts):
+   out4 = { 1 if it is a ridge / raft step, its length, 1 if its last step is a fracture step, that step's welding set or -1 }. */
+int sz_debug_next_segment(int32_t tstep, int32_t remaining, int32_t rr_dt, int32_t frac_dt, int32_t cut_on_fracture, int32_t n_weld,
+                          const int32_t *weld_dts, int32_t *out4);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,7 @@ EXPORTS = [
     "sz_set_ridgeraft", "sz_ridgeraft_candidates", "sz_ridgeraft_pending", "sz_ridgeraft_draws", "sz_step_finish",
     "sz_tile_ridgeraft_candidates", "sz_tile_list_numbers", "sz_tile_list_keys", "sz_tile_step_finish",
     "sz_download_rows", "sz_splice_floes", "sz_download_rows_f32", "sz_splice_floes_f32",
+    "sz_debug_next_segment",
     "sz_ridgeraft_rows", "sz_download_list_rows", "sz_splice_parents", "sz_ridgeraft_rows_f32", "sz_download_list_rows_f32", "sz_splice_parents_f32",
 ]
 
@@ -217,6 +218,7 @@ def load(build_if_missing=True):
     L.sz_set_ridgeraft.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]
     L.sz_ridgeraft_candidates.argtypes = [C.c_void_p, _ip, C.c_int32, _ip, _ip, _ip, _dp, _lp]
     L.sz_ridgeraft_pending.argtypes = [C.c_void_p, _ip]
+    L.sz_debug_next_segment.argtypes = [C.c_int32] * 6 + [_ip, _ip]
     L.sz_ridgeraft_draws.argtypes = [C.c_void_p, _lp]
     L.sz_step_finish.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.sz_tile_ridgeraft_candidates.argtypes = [C.c_void_p, _ip, C.c_int32, _lp, _lp, _ip, _dp, _lp]

@@ -27,6 +27,7 @@
 #include "sz_weld_tile.hpp"
 #include "sz_ridgeraft_tile.hpp"
 #include "sz_splice.hpp"
+#include "sz_stops.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 #include "sz_ctx.hpp"
 #include "sz_comm.hpp"
@@ -2044,7 +2045,7 @@ static int step_batch_three_launch(sz_ctx* c, const BatchPlan& p, int gl0, int n
       // a fracture step (fracture_floes!, simulation.jl:172-183) ends the batch when the criterion finds a candidate -- known only after the
       // update: the step runs as a batch's last one (its ghosts stay, none are made for a next step), and the next step is started behind
       // the test by launches that return at once when it has stopped the batch (sz_fracture.hpp)
-      const bool fstep = frac && (tstep % c->frac_dt) == 0;
+      const bool fstep = is_fracture_step(frac ? c->frac_dt : 0, tstep);
       const bool fcut = fstep && s + 1 < s_end;
       c->acc_mode = integrator_acc_mode(facc_on, rfree, s + 1 == s_end || fcut);
       stage_integrate(c, dt, !coll, coupling, sg, gl && !gi ? 1 - c->gl_cur : -1, gi && s + 1 < s_end && !fcut ? 1 - (s & 1) : -1);
@@ -2190,11 +2191,6 @@ int sz_set_welding(sz_ctx* c, int32_t n, const int32_t* dts, const int32_t* nxs,
 }
 
 namespace {
-// the welding set of timestep tstep: the FIRST k with tstep % dts[k] == 0 (findfirst, simulation.jl:186-189), or -1
-int weld_set_at(const sz_ctx* c, int tstep) {
-  for (size_t k = 0; k < c->weld_dts.size(); k++) if (tstep % c->weld_dts[k] == 0) return (int)k;
-  return -1;
-}
 // the pass's buffers for the parents as they are, `need` pairs and `cells` search cells
 int weld_ensure(sz_ctx* c, int need, int cells) {
   const int N = std::max(c->hostN, 1);
@@ -3015,27 +3011,56 @@ int sz_step_finish(sz_ctx* c, int32_t tstep, int32_t dt, int32_t coupling_dt, in
   return SZ_OK;
 }
 
-// sz_step with ridge / raft set (sz_set_ridgeraft), welding set (sz_set_welding) or removal set (sz_set_removal), in batches that stop.
-// Ridge / raft: the batch is cut into segments that end BEFORE a ridge / raft step (tstep % dt == 0; timestep_ridging_rafting! runs in the middle
-// of the step, simulation.jl:121-136).  That step runs through the process calls: sz_add_ghosts, sz_timestep_collisions, then the candidate pass
-// of sz_ridgeraft.hpp with one host synchronisation.  Empty table = the reference's call would change no floe and draw exactly the per-floe draws,
-// which are added to the batch's counter (sz_ridgeraft_draws); the step is finished as sz_step_finish finishes it and then ends as a segment's
-// last step does: a tag, a fracture candidate, a welding table and the removal pass apply in that order, as below.  Not empty = the batch ends
-// with the step pending (sz_ridgeraft_pending): *steps_done does not count it, the state is the reference's between timestep_collisions! and
-// timestep_ridging_rafting!, and sz_ridgeraft_candidates gives the same table again.
-// Welding: the batch is cut into segments that END on a welding step (tstep % dts[k] == 0,
-// timestep_welding! runs behind timestep_floe_properties!, simulation.jl:184-202).  A segment is an ordinary batch through the drivers above -- its
-// last step keeps its ghosts, the rows come home behind it, segments of pipe_min_steps or more stay pipelined -- then the overlap table of that
-// step's (Nx, Ny): empty = the reference's call would change nothing and draw no random number, and the next segment starts; not empty = the batch
-// ends there (steps_done counts the welding step; sz_weld_overlaps gives the caller the same table again).  A tag or a fracture candidate ends the
-// segment and the batch first, as fracture_floes! runs before the welding.  The batch's own last step is not looked at: the caller sees that the
-// batch ended on a welding step and asks.
-// Removal: a segment that a tag ends before the batch's last step is followed by the pass of sz_remove.hpp (the segment's ghosts are detached by
-// then, as at the start of a new batch); done = the next segment starts at the following step and makes its ghosts from the compacted parents,
-// declined = the batch ends there as without removal.  The reference's order holds (simulation.jl:172-214: fracture, weld, simplify): a fracture
-// step with a candidate, or a welding step of a context with welding set, ends the batch as before -- the caller works through that step and calls
-// sz_remove_floes itself.
-// Batches that run through (SZ_NO_STOP) and contexts with none of the three set take the driver as it is.
+namespace {
+// The passes of the stop schedule (sz_stops.hpp) on the single context.  Every value is this process's own: a tag is always settled.
+struct SingleStops {
+  sz_ctx* c; int dt, coupling_dt, flags;
+  // an ordinary batch: its last step keeps its ghosts, the rows come home behind it, segments of pipe_min_steps or more stay pipelined
+  int segment(int len, int t0, int* ran, int* tag) {
+    const int rc = step_segment(c, len, t0, dt, coupling_dt, flags, ran);
+    *tag = *ran < len || c->last_stopped;
+    return rc;
+  }
+  // through the process calls, with the candidate pass of sz_ridgeraft.hpp (one host synchronisation) in the middle; pending = the state is the
+  // reference's between timestep_collisions! and timestep_ridging_rafting!, and sz_ridgeraft_candidates gives the same table again
+  int rr_step(int tstep, bool last, int* pending, int* tag) {
+    int rc, nt = 0, nc = 0; long long nd = 0; int64_t todo[4] = { 0, 0, 0, 0 };
+    (void)hipSetDevice(c->device);
+    if (c->ghosts_staged && (rc = sz_remove_ghosts(c))) return rc;          // (ghosts a process-mode call left attached: a batch drops them too)
+    if ((rc = sz_add_ghosts(c)) || (rc = sz_timestep_collisions(c, c->hostN, dt)) || (rc = rr_pass(c, c->rr_h, &nt, &nd))) return rc;
+    if (nt > 0) { c->rr_pending = tstep; *pending = 1; return SZ_OK; }
+    c->rr_draws += nd;
+    if ((rc = rr_second_half(c, tstep, dt, coupling_dt, flags))) return rc;
+    // ... which ends as a segment's last step does: a tag, or a fracture candidate on a fracture step, is a stop request
+    if (!last && (rc = sz_simplify_check(c, 0x7fffffff, 0.0, 0.0, todo))) return rc;
+    c->last_stopped = todo[0] + todo[1] > 0;
+    if (!last && !c->last_stopped && is_fracture_step(c->frac_kind != SZ_FRAC_OFF ? c->frac_dt : 0, tstep)) {
+      if ((rc = sz_fracture_candidates(c, &nc, nullptr))) return rc;
+      c->last_stopped = nc > 0;
+    }
+    *tag = c->last_stopped;
+    return SZ_OK;
+  }
+  // only asked behind a stop, which is a tag or a candidate: where a tag alone ends the batch -- no removal, a welding step -- nobody asks which
+  int fracture(int, int weld_set, int* cand, int*) { *cand = 1; return c->rm_on && weld_set < 0 ? sz_fracture_candidates(c, cand, nullptr) : SZ_OK; }
+  // (not empty: sz_weld_overlaps gives the caller the same table again)
+  int weld(int set, int* nt, int*) { return weld_pass(c, c->weld_nxs[set], c->weld_nys[set], c->weld_max_area, nt); }
+  int settle(int*) { return SZ_OK; }
+  // the pass of sz_remove.hpp on the parents alone (the segment's ghosts are detached by then, as at the start of a new batch)
+  int remove(int* ok) {
+    int nr = 0, nd = 0;
+    if (!c->last_stopped || c->hostM != c->hostN) return SZ_OK;
+    leave_resident(c);
+    const int rc = remove_pass(c, ok, &nr, &nd);
+    if (!rc && *ok) c->last_stopped = false;
+    return rc;
+  }
+};
+}  // namespace
+
+// nsteps x timestep_sim!.  With ridge / raft (sz_set_ridgeraft), welding (sz_set_welding) or removal (sz_set_removal) set the batch runs in
+// segments that stop only where the host is needed: the schedule is sz_stops.hpp's, SingleStops its passes.  Batches that run through
+// (SZ_NO_STOP) and contexts with none of the three set take the driver as it is.
 int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
   if (c && c->rr_pending >= 0) {
     if (steps_done) *steps_done = 0;
@@ -3058,68 +3083,15 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   }
   if (rr && !(flags & SZ_COLLISIONS_ON)) { c->err = "sz_step with ridge / raft set: the candidates are read from this step's interaction rows (SZ_COLLISIONS_ON)"; return SZ_E_STATE; }
   if (rr && (flags & SZ_COUPLING_ON) && !c->have_fields) { c->err = "sz_set_fields must be called before coupling"; return SZ_E_STATE; }
-  int done = 0;
-  while (done < nsteps) {
-    int len = nsteps - done, set = -1, more = 0, rc = SZ_OK;
-    if (rr && (tstep0 + done) % c->rr_dt == 0) {
-      // the ridge / raft step, through the process calls
-      const int tstep = tstep0 + done;
-      (void)hipSetDevice(c->device);
-      if (c->ghosts_staged && (rc = sz_remove_ghosts(c))) return rc;          // (ghosts a process-mode call left attached: a batch drops them too)
-      if ((rc = sz_add_ghosts(c)) || (rc = sz_timestep_collisions(c, c->hostN, dt))) return rc;
-      int nt = 0; long long nd = 0;
-      if ((rc = rr_pass(c, c->rr_h, &nt, &nd))) return rc;
-      if (nt > 0) { c->rr_pending = tstep; return SZ_OK; }
-      c->rr_draws += nd;
-      if ((rc = rr_second_half(c, tstep, dt, coupling_dt, flags))) return rc;
-      len = more = 1; set = weld ? weld_set_at(c, tstep) : -1;
-      // ... which ends as a segment's last step does: a tag, or a fracture candidate on a fracture step, is a stop request
-      // (the batch's own last step is not looked at)
-      int64_t todo[4] = { 0, 0, 0, 0 };
-      if (done + 1 < nsteps && (rc = sz_simplify_check(c, 0x7fffffff, 0.0, 0.0, todo))) return rc;
-      c->last_stopped = todo[0] + todo[1] > 0;
-      if (done + 1 < nsteps && !c->last_stopped && c->frac_kind != SZ_FRAC_OFF && c->frac_dt > 0 && (tstep % c->frac_dt) == 0) {
-        int nc = 0;
-        if ((rc = sz_fracture_candidates(c, &nc, nullptr))) return rc;
-        c->last_stopped = nc > 0;
-      }
-    } else {
-      for (int s = 0; s < nsteps - done; s++) {
-        if (rr && s > 0 && (tstep0 + done + s) % c->rr_dt == 0) { len = s; break; }
-        const int k = weld ? weld_set_at(c, tstep0 + done + s) : -1;
-        if (k >= 0) { len = s + 1; set = k; break; }
-      }
-      rc = step_segment(c, len, tstep0 + done, dt, coupling_dt, flags, &more);
-    }
-    done += more;
-    if (steps_done) *steps_done = done;
-    if (rc) return rc;
-    if (more < len || c->last_stopped) {
-      // the segment ended on a stop request: where it is the batch's last step the caller looks; before that, with removal set, and where
-      // neither the fracture nor the welding of that step is the host's, the pass -- and on with the batch
-      if (done == nsteps || !rem || !c->last_stopped || more < 1) return rc;
-      const int tstep = tstep0 + done - 1;
-      if (weld && weld_set_at(c, tstep) >= 0) return SZ_OK;
-      if (c->frac_kind != SZ_FRAC_OFF && c->frac_dt > 0 && (tstep % c->frac_dt) == 0) {
-        int nc = 0;
-        if (int rc2 = sz_fracture_candidates(c, &nc, nullptr)) return rc2;
-        if (nc > 0) return SZ_OK;
-      }
-      if (c->hostM != c->hostN) return SZ_OK;
-      leave_resident(c);
-      int ok = 0, nr = 0, nd = 0;
-      if (int rc2 = remove_pass(c, &ok, &nr, &nd)) return rc2;
-      if (!ok) return SZ_OK;
-      c->last_stopped = false;
-      continue;
-    }
-    if (done == nsteps) return rc;
-    if (set >= 0) {
-      int nt = 0;
-      if (int rc2 = weld_pass(c, c->weld_nxs[set], c->weld_nys[set], c->weld_max_area, &nt)) return rc2;
-      if (nt > 0) break;
-    } else if (!rr) return rc;
-  }
+  SingleStops ops = { c, dt, coupling_dt, flags };
+  return run_with_stops(single_stop_rules(*c), ops, nsteps, tstep0, steps_done);
+}
+int sz_debug_next_segment(int32_t tstep, int32_t remaining, int32_t rr_dt, int32_t frac_dt, int32_t cut_on_fracture, int32_t n_weld, const int32_t* dts, int32_t* out4) {
+  if (!out4 || tstep < 0 || rr_dt < 0 || frac_dt < 0 || n_weld < 0 || (n_weld > 0 && !dts)) return SZ_E_ARG;
+  for (int k = 0; k < n_weld; k++) if (dts[k] <= 0) return SZ_E_ARG;
+  const StopRules r = { rr_dt, frac_dt, dts, n_weld, cut_on_fracture != 0, false };
+  const Segment g = next_segment(r, tstep, remaining);
+  out4[0] = g.rr_step; out4[1] = g.len; out4[2] = g.fstep; out4[3] = g.weld_set;
   return SZ_OK;
 }
 

@@ -122,6 +122,8 @@ int comm_agree_bits(sz_ctx* c, int local, int* all) {
   }
   return SZ_OK;
 }
+// "a floe of mine was tagged in this step", where an agreement carries it beside the error bits or on its own (the stop schedule, sz_stops.hpp)
+constexpr int RRS_BIT_TAG = 1 << 30;
 // The two words that decide how a tiled batch goes on -- the step a tag ended it at (C_STOP) and the step that paused for the largest narrow
 // variant or a list that outgrew its capacity (C_RETRYSTOP) -- as ALL ranks must see them before anyone branches: the smallest non-zero
 // value of each.  A rank's own counters are not enough: a pause on one rank and a tag on another in the SAME step are not heard by either

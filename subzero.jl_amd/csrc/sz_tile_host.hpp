@@ -1619,7 +1619,6 @@ static int tile_run_inline(sz_ctx* c, int nsteps, int tstep0, int dt, int coupli
 }
 // The second half of a split step (tile_step_body) and what settles it: the integrator, the halo rows and ghosts dropped, and the ranks' agreement
 // on the error word and on "a floe of mine was tagged in this step" (*any_tag: of any rank)
-constexpr int RRS_BIT_TAG = 1 << 30;
 static int tile_rr_second_half(sz_ctx* c, int tstep, int dt, int coupling_dt, int flags, int* any_tag) {
   State& S = c->S;
   *any_tag = 0;
@@ -1667,6 +1666,47 @@ static int tile_rr_step(sz_ctx* c, int tstep, int dt, int coupling_dt, int flags
   c->rr_draws += nd;
   return tile_rr_second_half(c, tstep, dt, coupling_dt, flags, any_tag);
 }
+// The passes of the stop schedule (sz_stops.hpp) on a tiled context: collective, each agrees what it returns.  The only reader of tile_stop_raised.
+struct TileStops {
+  sz_ctx* c; int dt, coupling_dt, flags;
+  bool agreed = false;          // the second half of a ridge / raft step has agreed the tag: settle() has nothing left to do
+  // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
+  // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
+  // Needs what the inline ghost maker needs (rings that fit the one-launch integrator, the static grid).  Otherwise: the list-based steps
+  // of sz_tile_step.
+  // Either driver runs under one scope of its own per segment; the ring maxima may shrink behind a removal pass, so each segment asks again.
+  int drive(int len, int t0, int32_t* ran) {
+    const bool inl = (flags & SZ_COLLISIONS_ON) && c->grid_ok && !c->two_way &&
+                     std::max(c->max_ring, c->max_ring_tiled) <= MV_RING && ((flags & SZ_COUPLING_ON) == 0 || c->have_fields);
+    BatchModes modes(c);
+    return inl ? tile_run_inline(c, len, t0, dt, coupling_dt, flags, ran) : tile_run_listed(c, len, t0, dt, coupling_dt, flags, ran);
+  }
+  // a stop before the segment's last step is the same step on every rank; one on it is the driver's own word (sz_ctx.hpp, tile_stop_raised)
+  int segment(int len, int t0, int* ran, int* tag) {
+    c->tile_stop_raised = 0; agreed = false;
+    const int rc = drive(len, t0, ran);
+    *tag = *ran < len || c->tile_stop_raised == len;
+    return rc;
+  }
+  // pending = the lists keep their halo rows and ghosts, sz_tile_step_finish runs the rest
+  int rr_step(int tstep, bool, int* pending, int* tag) {
+    c->tile_stop_raised = 0;
+    if (int rc = tile_rr_step(c, tstep, dt, coupling_dt, flags, pending, tag)) return rc;
+    if (*pending) c->rr_pending = tstep;
+    c->tile_stop_raised = *tag; agreed = true;          // (yet a welding pass of this step still runs: sz_stops.hpp)
+    return SZ_OK;
+  }
+  int fracture(int, int, int* cand, int* tag) { int mine = 0; return tile_frac_pass(c, *tag != 0, false, cand, tag, &mine); }
+  int weld(int set, int* nt, int* tag) { return tile_weld_pass(c, c->weld_nxs[set], c->weld_nys[set], c->weld_max_area, *tag != 0, nt, tag); }
+  int settle(int* tag) {
+    if (agreed) return SZ_OK;
+    const int rc = comm_agree_bits(c, *tag ? RRS_BIT_TAG : 0, tag);
+    if (!rc) c->err.clear();
+    return rc;
+  }
+  // done = the next segment starts from the compacted tiles (boxes, halo capacities and peers are gathered again at its first exchange)
+  int remove(int* ok) { int nr = 0, nd = 0; return tile_remove_pass(c, ok, &nr, &nd); }
+};
 }  // namespace
 
 // nsteps x timestep_sim! of a tiled run, collectively on every rank (same arguments everywhere)
@@ -1687,95 +1727,12 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   if (rr && (flags & SZ_COUPLING_ON) && !c->have_fields) { c->err = "sz_set_fields must be called before coupling"; return SZ_E_STATE; }
   if ((frac || weld || c->rr_on) && c->two_way) { c->err = std::string("tiled two-way coupling with ") + (frac ? "a fracture criterion set: its per-step all-reduce path has no tested stop: sz_set_fracture(SZ_FRAC_OFF)" : weld ? "welding set: its per-step all-reduce path has no tested stop: sz_set_welding(0)" : "ridge / raft set: its per-step all-reduce path has no tested stop: sz_set_ridgeraft(0)"); return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
-  // The steps of a tile are the single context's (sz_step): ghosts made by whoever places the parent (integrator: owned floes, unpack:
-  // halo floes), forcings in the tail of the narrow launch, no ghost launch -- plus the pack and unpack kernels and the exchange.
-  // Needs what the inline ghost maker needs (rings that fit the one-launch integrator, the static grid).  Otherwise: the list-based steps
-  // of sz_tile_step.
-  // Either driver runs under one scope of its own per segment; the ring maxima may shrink behind a removal pass, so each segment asks again.
-  auto segment = [&](int len, int t0, int32_t* ran) {
-    const bool inl = (flags & SZ_COLLISIONS_ON) && c->grid_ok && !c->two_way &&
-                     std::max(c->max_ring, c->max_ring_tiled) <= MV_RING && ((flags & SZ_COUPLING_ON) == 0 || c->have_fields);
-    BatchModes modes(c);
-    return inl ? tile_run_inline(c, len, t0, dt, coupling_dt, flags, ran) : tile_run_listed(c, len, t0, dt, coupling_dt, flags, ran);
-  };
-  // In batches that stop, with a criterion set (sz_set_fracture) or removal set (sz_set_removal): the loop of sz_step.
-  // Fracture: the batch is cut into segments that END on a fracture step (tstep % frac_dt == 0), each an ordinary tiled batch.  Behind a segment
-  // whose last step ran comes the collective criterion pass (tile_frac_pass): a candidate on any rank ends the batch there on every rank
-  // (steps_done counts the fracture step), none = the next segment starts at the following step.  A tag raised on that very step is, behind the
-  // list-based driver, known to its rank alone -- the peers would hear of it in the unpack of a step that does not come; the inline driver has
-  // agreed it already -- so the pass's agreement carries it (tile_stop_raised), and what follows is the single context's order (simulation.jl:172-214: fracture, then simplify): without a candidate the batch ends on the tag as sz_step
-  // does, or -- removal set -- goes into the removal pass.  The batch's own last step is not looked at: the caller asks (sz_tile_fracture_candidates).
-  // Removal: a segment that a tag ends before its last step -- the same step on every rank, and never a fracture step: those end segments -- or
-  // on it (above) is followed by the collective pass; done = the next segment starts at the following step from the compacted tiles (boxes, halo
-  // capacities and peers are gathered again at its first exchange), declined = the batch ends there as without removal, on every rank.
-  // Welding (sz_set_welding): the segments also END on welding steps (weld_set_at: the first k with tstep % dts[k] == 0 gives Nx, Ny).  Behind a segment
-  // whose last step ran the order is the single context's (simulation.jl:172-214, sz_step): the fracture pass on a fracture step, then the collective
-  // overlap table (tile_weld_pass), then removal.  A table that is not empty ends the batch on every rank (steps_done counts the welding step), an empty
-  // one lets the next segment start.  A tag on a welding step ends the batch there, with removal set too, as in sz_step; where the fracture pass has
-  // not agreed it already, the welding pass's last agreement does.
-  // Two-way coupling across tiles has no tag stop of its own to hang a pass on: removal is not engaged there, a criterion, welding or ridge / raft refused.
-  // SZ_NO_STOP batches and contexts with none of the four set take the drivers as they are.
-  // Ridge / raft (sz_set_ridgeraft): the segments also end BEFORE a ridge / raft step (tstep % rr_dt == 0: timestep_ridging_rafting! stands in the middle
-  // of the step), and that step is a one-step segment of its own (tile_rr_step).  A table that is not empty ends the batch on every rank with the
-  // step PENDING: steps_done does not count it, the lists keep their halo rows and ghosts, sz_tile_step_finish runs the rest.  An empty one: the draws
-  // are counted (sz_ridgeraft_draws), the step is finished, and what follows any segment's last step follows it -- a tag any rank raised (agreed behind
-  // the second half), the fracture pass, the welding pass, removal.  A segment cut before a ridge / raft step on no fracture or welding step has no
-  // pass to carry a tag of its last step to the peers: the ranks agree on it there.
-  if ((!c->rm_on && !frac && !weld && !rr) || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return segment(nsteps, tstep0, steps_done);
-  int done = 0;
-  while (done < nsteps) {
-    int lim = nsteps - done;
-    if (rr) for (int s = 1; s < lim; s++) if ((tstep0 + done + s) % c->rr_dt == 0) { lim = s; break; }
-    int len = lim, set = -1, rc = SZ_OK; bool fstep = false;
-    int32_t more = 0;
-    bool agreed = false;          // the tag of the segment's last step is every rank's knowledge already
-    c->tile_stop_raised = 0;
-    if (rr && (tstep0 + done) % c->rr_dt == 0) {
-      const int tstep = tstep0 + done;
-      int pend = 0, tag = 0;
-      if (int rc2 = tile_rr_step(c, tstep, dt, coupling_dt, flags, &pend, &tag)) return rc2;
-      if (pend) { c->rr_pending = tstep; return SZ_OK; }
-      len = more = 1; fstep = frac && tstep % c->frac_dt == 0; set = weld ? weld_set_at(c, tstep) : -1;
-      c->tile_stop_raised = tag ? 1 : 0; agreed = true;
-    } else {
-      for (int s = 0; s < lim && s + 1 < nsteps - done; s++) {
-        const int tstep = tstep0 + done + s;
-        fstep = frac && tstep % c->frac_dt == 0;
-        set = weld ? weld_set_at(c, tstep) : -1;
-        if (fstep || set >= 0) { len = s + 1; break; }
-      }
-      rc = segment(len, tstep0 + done, &more);
-    }
-    done += more;
-    if (steps_done) *steps_done = done;
-    if (rc || done >= nsteps || more < 1) return rc;
-    if (more == len) {          // the segment's last step ran, and the batch goes on behind it: it was cut here, on a fracture or a welding step or before a ridge / raft step
-      int tag = 0;
-      const bool my_tag = c->tile_stop_raised == len;
-      if (agreed) tag = my_tag;
-      else if (!fstep && set < 0) {          // (cut before a ridge / raft step: no pass carries the tag)
-        if (int rc2 = comm_agree_bits(c, my_tag ? RRS_BIT_TAG : 0, &tag)) return rc2;
-        c->err.clear();
-      }
-      if (fstep) {
-        int cand = 0, mine = 0;
-        if (int rc2 = tile_frac_pass(c, my_tag, false, &cand, &tag, &mine)) return rc2;
-        if (cand) return SZ_OK;
-      }
-      if (set >= 0) {          // a tag ends the batch on a welding step, as in sz_step; the fracture pass has agreed it, else the welding pass does
-        if (fstep && tag) return SZ_OK;
-        int nt = 0;
-        if (int rc2 = tile_weld_pass(c, c->weld_nxs[set], c->weld_nys[set], c->weld_max_area, my_tag, &nt, &tag)) return rc2;
-        if (tag || nt > 0) return SZ_OK;
-      }
-      if (!tag) continue;
-    }
-    if (!c->rm_on) return SZ_OK;
-    int ok = 0, nr = 0, nd = 0;
-    if (int rc2 = tile_remove_pass(c, &ok, &nr, &nd)) return rc2;
-    if (!ok) return SZ_OK;
-  }
-  return SZ_OK;
+  // In batches that stop, with a criterion, welding, ridge / raft or removal set: the schedule of sz_stops.hpp over the passes of TileStops.
+  // Two-way coupling across tiles has no tag stop of its own to hang a pass on: removal is not engaged there, the other three
+  // refused above.  SZ_NO_STOP batches and contexts with none of the four set take the drivers as they are.
+  TileStops ops = { c, dt, coupling_dt, flags };
+  if ((!c->rm_on && !frac && !weld && !rr) || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return ops.drive(nsteps, tstep0, steps_done);
+  return run_with_stops(tile_stop_rules(*c), ops, nsteps, tstep0, steps_done);
 }
 
 // ---------------------------------------------------------------- ridge / raft on a tiled context: the entry points of a pending stop
