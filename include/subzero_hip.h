@@ -23,6 +23,8 @@
  *   sz_download_rows /            <- what the host-side topology changes do to the floe list: deleteat!, assignment in place,
  *   sz_splice_floes                  append! (fracture_floes!, fuse / replace_floe!, ridging and rafting, smoothing), on the rows
  *                                    they name; the floes themselves are still made by the reference on the host
+ *   sz_tile_download_rows /       <- the same list edits on a tiled (multi-GPU) context, stated once in global floe numbers
+ *   sz_tile_splice_floes             with the same arguments on every rank
  *   sz_ridgeraft_rows /           <- the rows timestep_ridging_rafting! can touch, and what timestep_sim! does to the list behind it:
  *   sz_download_list_rows /          deleteat!(floes, n_init_floes + 1 : end), append!(floes, pieces)
  *   sz_splice_parents                                                       src/simulation_components/simulation.jl:121-147
@@ -351,7 +353,7 @@ int sz_download_origin(sz_ctx *ctx, int32_t *origin);
    ring points than it held) is not refused: the context is carved anew on the device for the edited list and the rows move there; the sub-floe
    point pool, which an upload gives no slack, grows by itself.  The result is the same.
    Refusals leave the state untouched: ghosts in the list (sz_remove_ghosts first) or a pending ridge / raft step (sz_step_finish first) and tiled
-   contexts: SZ_E_STATE; rows unsorted, repeated, out of range or both deleted and replaced, an edit that leaves no floe, an uploaded ring that is
+   contexts (sz_tile_splice_floes below edits those, by global number): SZ_E_STATE; rows unsorted, repeated, out of range or both deleted and replaced, an edit that leaves no floe, an uploaded ring that is
    open (first point != last, or under 4 points) or longer than 255 points (what the row-moving kernels and the collision record carry): SZ_E_ARG;
    more interaction rows for a floe than the stride holds: SZ_E_CAPACITY, as sz_upload_interactions.  n_del = n_rep = n_app = 0 changes nothing.
    The _f32 twins widen and round exactly as sz_upload_floes_f32 / sz_download_floes_f32 / sz_download_interactions_f32 do. */
@@ -618,6 +620,49 @@ int sz_tile_owned_gidx(sz_ctx *ctx, int64_t *gidx, int64_t n_cap);
    this pass; done = the next segment starts at the following step and *steps_done counts on, declined = the batch ends there as without removal.
    The batch's own last step is not looked at.  Tiled two-way coupling has no tag stop to hang the pass on: removal is not engaged there. */
 int sz_tile_remove_floes(sz_ctx *ctx, int32_t *done, int32_t *n_removed, int32_t *n_dissolved);
+/* Rows down, rows back on a tiled context, by GLOBAL number (csrc/sz_splice_tile.hpp): sz_download_rows / sz_splice_floes over the ONE
+   global floe list whose rows live on the ranks' tiles (library backends; sz_download_rows / sz_splice_floes themselves stay single-context calls).
+   The collective passes give every rank the same table, so every rank's host makes the same decisions: the edit is stated once, in global numbers,
+   and every rank calls with identical arguments and applies the share that concerns the rows it owns.  No floe data crosses between the ranks.
+   Both calls need sz_tile_enable, the parents alone in the list (ghosts: SZ_E_STATE), no pending ridge / raft step (SZ_E_STATE: sz_tile_step_finish
+   first) and the owned global numbers ASCENDING BY ROW (SZ_E_STATE otherwise: the rows are found by binary search in the order keys; sz_tile_migrate
+   and sz_tile_remove_floes leave them so, sz_tile_enable takes any order).
+   sz_tile_download_rows: LOCAL, not collective.  gidx holds n global numbers in any order, none negative, none twice (SZ_E_ARG).  which[0 .. *n_mine)
+   receives the positions in gidx of the floes this rank owns, ascending (which has room for n entries); a name no rank owns is found nowhere.
+   n has no limit of the context's: the names are searched and compacted 2^20 at a time, so a request may be longer than any of its capacities.
+   The rows come back in that order with the layout, the sizes3 / cols == NULL protocol and the bits of sz_download_rows -- the same staging buffer
+   and single copy; partner numbers are as sz_download_interactions reports them on this tiled context.
+   sz_tile_splice_floes: COLLECTIVE, the same arguments on every rank; it also needs sz_tile_setup and the communicator (RCCL, the host transport,
+   or one rank).  del / rep: ascending global numbers of the list AS IT IS, without repeats, none in both.  cols, inter_off, inter_rows: the n_rep
+   replacements, then the n_app appended floes, in the layout of sz_splice_floes; app_owner[k] (required with n_app > 0) is the rank that takes
+   appended floe k.  Afterwards every rank holds what the single context holds after sz_splice_floes with the same edit on the undivided list,
+   restricted to the floes the rank owns:
+     - a kept floe's global number is its old one minus the deleted floes, on ANY rank, with a smaller number; appended floe k gets
+       N_global - n_del + k; a replaced floe stays with its owner (the next sz_tile_migrate moves it if it must); a floe uploaded without an id gets
+       its new global number + 1;
+     - the new numbers are the order keys and what sz_tile_owned_gidx reports; columns, rings, sub-floe points and statuses of owned floes equal the
+       single context's rows of those numbers, bit for bit; everything derived is as sz_splice_floes leaves it, both capacity paths included;
+     - interaction rows of kept floes are what this rank's download reported before the edit, staged floes get the uploaded rows;
+     - the tiling is established again on every rank (one whose rows did not change included: its numbers still move) with the new numbers, the
+       centre kept, and the ring / rmax maxima given to sz_tile_enable raised to cover every staged floe of the whole edit (a maximum of 0 stays 0);
+       owned boxes, halo capacities and peers come with the next exchange, as after sz_tile_remove_floes.
+   *n_global / *n_owned: the new counts (either may be NULL).  The one collective is a small all-gather in front of the change: per rank the error
+   bits, the rows owned, the del and rep names found, the appended floes taken.  From it every rank derives N_global and refuses alike, with the
+   state untouched: names that do not add up to n_del / n_rep -- one out of range or owned twice -- (SZ_E_ARG); an edit that leaves no floe, or
+   leaves ANY rank without a floe, as sz_tile_remove_floes declines (SZ_E_ARG); ghosts, an empty rank or unsorted numbers on any rank (SZ_E_STATE);
+   device error bits on any rank, or more interaction rows for a floe than some rank's stride holds (SZ_E_CAPACITY).  What the arguments alone
+   decide is refused before the collective, on every rank alike: names unsorted, repeated, negative or both deleted and replaced, app_owner out of
+   range, open rings or rings over 255 points (SZ_E_ARG).  A failure of the HIP runtime or of the channel itself (SZ_E_HIP) is returned at once.
+   n_del = n_rep = n_app = 0 changes nothing and issues no collective (*n_global = -1: the global count takes one; *n_owned = the rows owned).
+   The _f32 twins widen and round as those of sz_download_rows / sz_splice_floes do. */
+int sz_tile_download_rows(sz_ctx *ctx, int32_t n, const int64_t *gidx, int32_t *n_mine, int32_t *which, sz_floe_columns *cols, int32_t *inter_off,
+                          double *inter_rows, int64_t *sizes3);
+int sz_tile_splice_floes(sz_ctx *ctx, int32_t n_del, const int64_t *del, int32_t n_rep, const int64_t *rep, int32_t n_app, const int32_t *app_owner,
+                         const sz_floe_columns *cols, const int32_t *inter_off, const double *inter_rows, int64_t *n_global, int64_t *n_owned);
+int sz_tile_download_rows_f32(sz_ctx *ctx, int32_t n, const int64_t *gidx, int32_t *n_mine, int32_t *which, sz_floe_columns_f32 *cols, int32_t *inter_off,
+                              float *inter_rows, int64_t *sizes3);
+int sz_tile_splice_floes_f32(sz_ctx *ctx, int32_t n_del, const int64_t *del, int32_t n_rep, const int64_t *rep, int32_t n_app, const int32_t *app_owner,
+                             const sz_floe_columns_f32 *cols, const int32_t *inter_off, const float *inter_rows, int64_t *n_global, int64_t *n_owned);
 /* Fracture criteria on a tiled context (csrc/sz_fracture_tile.hpp; DESIGN.md §9b, "tiled contexts"): determine_fractures over the ONE global
    floe list whose rows live on the ranks' tiles, on the state as it is.  Collective: it needs sz_tile_enable + sz_tile_setup, the communicator
    (RCCL, the host transport, or one rank), the parents alone in the list and a criterion (sz_set_fracture, the same on every rank).  The heights

@@ -1430,6 +1430,133 @@ function tile_owned(eng::HIPEngine, n_owned::Integer)
     return g[1:n_owned]
 end
 
+"""
+    tile_download_rows!(eng, sub, gidx) -> which
+
+`download_rows!` on a tiled context, by global number (`sz_tile_download_rows`): local, not collective.  `gidx` holds 1-based numbers of the
+undivided list in any order, none twice; `sub` is a list of `length(gidx)` floes to receive them (e.g. copies of any floe).  Returns `which`,
+the ascending 1-based positions in `gidx` of the floes THIS rank owns; `sub[which[k]]` then holds floe `gidx[which[k]]` -- columns, geometry,
+sub-floe points, status and interactions, each value as the rank's full download gives it.  The other entries of `sub` are not touched.  A
+host with its own channel gathers `which` and those floes over the ranks, as `TiledWorld.download_rows` does with `all_gather_object`: every
+name must be found on exactly one rank.
+
+Written, not run, as `download_rows!` and `splice!` are; the C call underneath is held to the single context's `sz_download_rows` by
+`tests/test_splice_tiles_gpu.py`.
+"""
+function tile_download_rows!(eng::HIPEngine, sub, gidx::AbstractVector{<:Integer})
+    n = length(gidx)
+    n == 0 && return Int[]
+    g0 = Int64.(gidx .- 1)
+    which = Vector{Int32}(undef, n); nm = Ref{Int32}(0)
+    sizes = Vector{Int64}(undef, 3)
+    check(eng, @ccall lib.sz_tile_download_rows(eng.ctx::Ptr{Cvoid}, Int32(n)::Int32, g0::Ptr{Int64}, nm::Ptr{Int32}, which::Ptr{Int32}, C_NULL::Ptr{Cvoid},
+                                                C_NULL::Ptr{Int32}, C_NULL::Ptr{Float64}, sizes::Ptr{Int64})::Cint)
+    m = Int(nm[])
+    m == 0 && return Int[]
+    mine = Int.(which[1:m]) .+ 1
+    got = sub[mine]
+    P = pack(got, m)
+    resize!(P.vx, sizes[1]); resize!(P.vy, sizes[1]); resize!(P.sx, sizes[2]); resize!(P.sy, sizes[2])
+    P.cols.vx = pointer(P.vx); P.cols.vy = pointer(P.vy); P.cols.sx = pointer(P.sx); P.cols.sy = pointer(P.sy)
+    off = Vector{Int32}(undef, m + 1); irows = Matrix{Float64}(undef, 7, max(Int(sizes[3]), 1))
+    GC.@preserve P got begin
+        check(eng, @ccall lib.sz_tile_download_rows(eng.ctx::Ptr{Cvoid}, Int32(n)::Int32, g0::Ptr{Int64}, nm::Ptr{Int32}, which::Ptr{Int32}, P.cols::Ref{SzFloeColumns},
+                                                    off::Ptr{Int32}, irows::Ptr{Float64}, C_NULL::Ptr{Int64})::Cint)
+    end
+    unpack_geometry!(got, P); unpack_status!(got, P)
+    for k in 1:m
+        s = P.sub_off[k]+1:P.sub_off[k+1]
+        got.x_subfloe_points[k] = P.sx[s]; got.y_subfloe_points[k] = P.sy[s]
+        r = off[k]+1:off[k+1]
+        got.interactions[k] = permutedims(irows[:, r]); got.num_inters[k] = length(r)
+        got.collision_force[k][1, 1] = P.coll_fx[k]; got.collision_force[k][1, 2] = P.coll_fy[k]
+        sub[mine[k]] = got[k]
+    end
+    return mine
+end
+
+"""
+    tile_splice!(eng, staged, del, rep, app_owner) -> (N_global, N_owned)
+
+`splice!` on a tiled context, by global number (`sz_tile_splice_floes`): collective, the same arguments on every rank.  `del` and `rep` are
+ascending 1-based numbers of the undivided list as it is, none in both; `staged` holds the `length(rep)` replacements, then the appended
+floes -- the whole edit, on every rank --, and `app_owner[k]` is the 0-based rank that takes appended floe `k`.  Every rank applies the share
+that concerns the floes it owns: no floe data crosses between the ranks.  Afterwards `tile_owned(eng, N_owned)` gives the new numbers of this
+rank's floes -- a kept floe's old number minus the deleted floes with a smaller one, appended floe `k` at `N_global_before - length(del) + k`.
+Refused on every rank alike, nothing changed (the library's message is thrown): ghosts in the list, a pending ridge / raft step, names that
+are unsorted, repeated, out of range or owned twice, an edit that leaves a rank without a floe.
+
+`run_resident!` does not call this.  Written, not run, as `download_rows!` and `splice!` are; the C call underneath is held, bit for bit, to
+`sz_splice_floes` of the same edit on the undivided list by `tests/test_splice_tiles_gpu.py`.
+"""
+function tile_splice!(eng::HIPEngine, staged, del::AbstractVector{<:Integer}, rep::AbstractVector{<:Integer}, app_owner::AbstractVector{<:Integer})
+    d0 = Int64.(del .- 1); r0 = Int64.(rep .- 1); own = Int32.(app_owner)
+    ng = Ref{Int64}(0); no = Ref{Int64}(0)
+    ns = length(staged)
+    ns == length(r0) + length(own) || error("tile_splice!: $(ns) staged floes for $(length(r0)) replaced and $(length(own)) appended")
+    if ns == 0
+        check(eng, @ccall lib.sz_tile_splice_floes(eng.ctx::Ptr{Cvoid}, Int32(length(d0))::Int32, d0::Ptr{Int64}, Int32(0)::Int32, C_NULL::Ptr{Int64}, Int32(0)::Int32,
+                                                   C_NULL::Ptr{Int32}, C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Int32}, C_NULL::Ptr{Float64}, ng::Ptr{Int64}, no::Ptr{Int64})::Cint)
+    else
+        P = pack(staged, ns)
+        off, irows = interactions_csr(staged)
+        GC.@preserve P staged begin
+            check(eng, @ccall lib.sz_tile_splice_floes(eng.ctx::Ptr{Cvoid}, Int32(length(d0))::Int32, d0::Ptr{Int64}, Int32(length(r0))::Int32, r0::Ptr{Int64},
+                                                       Int32(length(own))::Int32, own::Ptr{Int32}, P.cols::Ref{SzFloeColumns}, off::Ptr{Int32}, irows::Ptr{Float64},
+                                                       ng::Ptr{Int64}, no::Ptr{Int64})::Cint)
+        end
+    end
+    return Int(ng[]), Int(no[])
+end
+
+# ... for a Floe{Float32} host, through the _f32 twins on the columns of pack32 (as download_list_rows32 / splice_parents32! above).
+# tile_download_rows32: (which, a contiguous copy of sub[which], its Packed32 holding the device's values, inter_off, inter_rows 7 x k)
+function tile_download_rows32(eng::HIPEngine, sub::StructArray{<:Floe{Float32}}, gidx::AbstractVector{<:Integer})
+    n = length(gidx)
+    g0 = Int64.(gidx .- 1)
+    which = Vector{Int32}(undef, max(n, 1)); nm = Ref{Int32}(0)
+    sizes = Vector{Int64}(undef, 3)
+    check(eng, @ccall lib.sz_tile_download_rows_f32(eng.ctx::Ptr{Cvoid}, Int32(n)::Int32, g0::Ptr{Int64}, nm::Ptr{Int32}, which::Ptr{Int32}, C_NULL::Ptr{Cvoid},
+                                                    C_NULL::Ptr{Int32}, C_NULL::Ptr{Float32}, sizes::Ptr{Int64})::Cint)
+    m = Int(nm[])
+    mine = Int.(which[1:m]) .+ 1
+    got = sub[mine]
+    P = pack32(got, m)
+    vx = Vector{Float32}(undef, sizes[1]); vy = similar(vx); sx = Vector{Float32}(undef, sizes[2]); sy = similar(sx)
+    P.cols.vx = pointer(vx); P.cols.vy = pointer(vy); P.cols.sx = pointer(sx); P.cols.sy = pointer(sy)
+    append!(P.keep, Any[vx, vy, sx, sy])
+    off = Vector{Int32}(undef, m + 1); irows = Matrix{Float32}(undef, 7, max(Int(sizes[3]), 1))
+    GC.@preserve P got begin
+        check(eng, @ccall lib.sz_tile_download_rows_f32(eng.ctx::Ptr{Cvoid}, Int32(n)::Int32, g0::Ptr{Int64}, nm::Ptr{Int32}, which::Ptr{Int32},
+                                                        P.cols::Ref{SzFloeColumnsF32}, off::Ptr{Int32}, irows::Ptr{Float32}, C_NULL::Ptr{Int64})::Cint)
+    end
+    return mine, got, P, off, irows
+end
+
+# sz_tile_splice_floes_f32 with the whole edit's staged floes packed by pack32; -> (N_global, N_owned)
+function tile_splice32!(eng::HIPEngine, staged::StructArray{<:Floe{Float32}}, del::AbstractVector{<:Integer}, rep::AbstractVector{<:Integer},
+                        app_owner::AbstractVector{<:Integer})
+    isempty(staged) && error("tile_splice32!: nothing replaced or appended (a deletion alone needs no columns: tile_splice!)")
+    d0 = Int64.(del .- 1); r0 = Int64.(rep .- 1); own = Int32.(app_owner)
+    ng = Ref{Int64}(0); no = Ref{Int64}(0)
+    ns = length(staged)
+    P = pack32(staged, ns)
+    off = Vector{Int32}(undef, ns + 1); off[1] = 0
+    for i in 1:ns
+        off[i+1] = off[i] + staged.num_inters[i]
+    end
+    irows = Matrix{Float32}(undef, 7, max(Int(off[end]), 1))
+    for i in 1:ns, k in 1:staged.num_inters[i]
+        irows[:, off[i]+k] .= @view staged.interactions[i][k, :]
+    end
+    GC.@preserve P staged begin
+        check(eng, @ccall lib.sz_tile_splice_floes_f32(eng.ctx::Ptr{Cvoid}, Int32(length(d0))::Int32, d0::Ptr{Int64}, Int32(length(r0))::Int32, r0::Ptr{Int64},
+                                                       Int32(length(own))::Int32, own::Ptr{Int32}, P.cols::Ref{SzFloeColumnsF32}, off::Ptr{Int32},
+                                                       irows::Ptr{Float32}, ng::Ptr{Int64}, no::Ptr{Int64})::Cint)
+    end
+    return Int(ng[]), Int(no[])
+end
+
 writer_periods(w) = Int[x.Δtout for ws in (w.floewriters, w.gridwriters, w.checkpointwriters) for x in ws]
 output_due(w, tstep, start) = tstep == start || any(p -> mod(tstep, p) == 0, writer_periods(w))
 function steps_to_next_output(w, tstep, start)

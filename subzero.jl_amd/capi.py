@@ -93,6 +93,7 @@ EXPORTS = [
     "sz_download_rows", "sz_splice_floes", "sz_download_rows_f32", "sz_splice_floes_f32",
     "sz_debug_next_segment",
     "sz_ridgeraft_rows", "sz_download_list_rows", "sz_splice_parents", "sz_ridgeraft_rows_f32", "sz_download_list_rows_f32", "sz_splice_parents_f32",
+    "sz_tile_download_rows", "sz_tile_splice_floes", "sz_tile_download_rows_f32", "sz_tile_splice_floes_f32",
 ]
 
 EUL_PARTIAL = 17      # SZ_EUL_PARTIAL: per-cell partial fields of sz_eulerian_partial
@@ -234,6 +235,10 @@ def load(build_if_missing=True):
     L.sz_splice_parents.argtypes = L.sz_splice_floes.argtypes
     L.sz_download_list_rows_f32.argtypes = L.sz_download_rows_f32.argtypes
     L.sz_splice_parents_f32.argtypes = L.sz_splice_floes_f32.argtypes
+    L.sz_tile_download_rows.argtypes = [C.c_void_p, C.c_int32, _lp, _ip, _ip, C.POINTER(SzFloeColumns), _ip, _dp, _lp]
+    L.sz_tile_splice_floes.argtypes = [C.c_void_p, C.c_int32, _lp, C.c_int32, _lp, C.c_int32, _ip, C.POINTER(SzFloeColumns), _ip, _dp, _lp, _lp]
+    L.sz_tile_download_rows_f32.argtypes = [C.c_void_p, C.c_int32, _lp, _ip, _ip, C.POINTER(SzFloeColumnsF32), _ip, _fp, _lp]
+    L.sz_tile_splice_floes_f32.argtypes = [C.c_void_p, C.c_int32, _lp, C.c_int32, _lp, C.c_int32, _ip, C.POINTER(SzFloeColumnsF32), _ip, _fp, _lp, _lp]
     for n in EXPORTS:
         if n not in ("sz_create", "sz_destroy", "sz_last_error", "sz_version"):
             getattr(L, n).restype = C.c_int

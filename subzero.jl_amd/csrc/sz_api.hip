@@ -27,6 +27,7 @@
 #include "sz_weld_tile.hpp"
 #include "sz_ridgeraft_tile.hpp"
 #include "sz_splice.hpp"
+#include "sz_splice_tile.hpp"
 #include "sz_stops.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 #include "sz_ctx.hpp"
@@ -749,7 +750,7 @@ void sz_destroy(sz_ctx* c) {
   (void)hipFree(c->d_stats); (void)hipFree(c->S.acc);
   (void)hipFree(c->frac_d); (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx);
   free_pool(c->weld_allocs); free_pool(c->weldt_allocs); (void)hipFree(c->weld_tmp); free_pool(c->rr_allocs); free_pool(c->rrt_allocs);
-  free_pool(c->rm_allocs); free_pool(c->sp_allocs);
+  free_pool(c->rm_allocs); free_pool(c->sp_allocs); free_pool(c->spt_allocs);
   free_pool(c->frac_allocs);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
   (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2);
@@ -2589,6 +2590,39 @@ int sz_download_list_rows(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_col
 }
 
 namespace {
+// The uploaded floes of a row edit, checked before anything changes: closed rings the row-moving kernels carry, offsets that ascend, interaction rows
+// that fit the stride; *stream_len: the doubles of their migration records.  bits == null: the first fault is returned.  A tiled context's share
+// (sz_tile_splice_floes) gives `bits`: what depends on this rank's context alone -- SPT_BIT_ROWCAP, SPT_BIT_POINTS -- is then noted there for the
+// ranks' agreement and the walk goes on; what the arguments alone decide is returned as ever, the same on every rank.
+constexpr int SPT_BIT_ERR = 1, SPT_BIT_GHOSTS = 2, SPT_BIT_ORDER = 4, SPT_BIT_ROWCAP = 8, SPT_BIT_POINTS = 16, SPT_BIT_NONE = 32, SPT_BIT_MEM = 64;
+int sp_check_staged(sz_ctx* c, const std::string& who, int ns, const sz_floe_columns* f, const int32_t* ioff, const double* irows, bool* with_sub_out, size_t* stream_len_out,
+                    int* bits = nullptr) {
+  const State& S = c->S;
+  const bool with_sub = ns > 0 && f->sub_off != nullptr;
+  if (with_sub && (!f->sx || !f->sy) && f->sub_off[ns] != f->sub_off[0]) { c->err = who + ": sub_off without sx / sy"; return SZ_E_ARG; }
+  size_t stream_len = 0;
+  for (int j = 0; j < ns; j++) {
+    const int o = f->vert_off[j], nv = f->vert_off[j + 1] - o, sp = with_sub ? f->sub_off[j + 1] - f->sub_off[j] : 0, ni = ioff ? ioff[j + 1] - ioff[j] : 0;
+    if (nv < 4 || o < 0 || !(f->vx[o] == f->vx[o + nv - 1] && f->vy[o] == f->vy[o + nv - 1])) { c->err = who + ": uploaded row " + std::to_string(j) + " has an open ring (a ring is closed: its first point repeated, at least 4 points)"; return SZ_E_ARG; }
+    if (nv > SP_MAX_RING) { c->err = who + ": uploaded row " + std::to_string(j) + " has a ring of " + std::to_string(nv) + " points: the row-moving kernels carry " + std::to_string(SP_MAX_RING); return SZ_E_ARG; }
+    if (sp < 0 || ni < 0) { c->err = who + ": offsets of uploaded row " + std::to_string(j) + " descend"; return SZ_E_ARG; }
+    if (sp > 0 && c->pts_N == 0) { if (bits) *bits |= SPT_BIT_POINTS; else { c->err = who + ": the list was uploaded without sub-floe points"; return SZ_E_ARG; } }
+    if (ni > S.rowcap) { if (bits) *bits |= SPT_BIT_ROWCAP; else { c->err = "more interaction rows per floe than the fixed stride holds"; return SZ_E_CAPACITY; } }
+    if (ni > 0 && !irows) { c->err = who + ": inter_off without inter_rows"; return SZ_E_ARG; }
+    stream_len += (size_t)MIG_NCOL + 2 * (size_t)nv + 2 * (size_t)sp;
+  }
+  if (stream_len > 0x7fffffffull) { c->err = who + ": the uploaded rows are too long for one stream"; return SZ_E_ARG; }
+  *with_sub_out = with_sub; *stream_len_out = stream_len;
+  return SZ_OK;
+}
+
+// What a tiled context's share of a global edit gives the body of a splice: how sz_k_spt_renumber numbers the new rows, the new global number of
+// every staged floe (a floe uploaded without an id gets it + 1), and where the new numbers of all new rows go on the host.
+struct SpTile { SptKeys keys; const long long* staged_num; std::vector<long long>* newkey; };
+
+int sp_splice_rows(sz_ctx* c, const std::string& who, bool parents, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns* f,
+                   const int32_t* ioff, const double* irows, bool with_sub, size_t stream_len, const SpTile* tile);
+
 // sz_splice_floes (parents = false: a ghost-free list with nothing pending) and sz_splice_parents (parents = true: the ghosts of the list are dropped
 // first, as sz_remove_ghosts drops them, and a pending mark stays) -- every check comes before the first change
 int sp_splice(sz_ctx* c, const char* who_, bool parents, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns* f,
@@ -2600,13 +2634,12 @@ int sp_splice(sz_ctx* c, const char* who_, bool parents, int32_t n_del, const in
   const int ns = (int)ns64;
   if (ns > 0 && (!f || !f->vert_off || !f->vx || !f->vy || !f->cx || !f->cy)) { c->err = who + ": replaced / appended rows need vert_off, vx, vy, cx and cy"; return SZ_E_ARG; }
   if (!c->have_floes) { c->err = who + ": no floes uploaded"; return SZ_E_STATE; }
-  if (c->S.tiled) { c->err = who + ": the rows of a tiled context carry global numbers and its list is one rank's share: not supported on tiled contexts"; return SZ_E_STATE; }
+  if (c->S.tiled) { c->err = who + ": the rows of a tiled context carry global numbers and its list is one rank's share: not supported on tiled contexts (sz_tile_splice_floes edits them by global number)"; return SZ_E_STATE; }
   if (!parents && c->rr_pending >= 0) { c->err = who + ": a ridge / raft step is pending with its ghosts in the list (sz_step_finish first)"; return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
   int rc;
   if ((rc = sync_and_check(c))) return rc;          // hostM / hostN current, nothing pending
   if (!parents && c->hostM != c->hostN) { c->err = who + ": ghosts are in the list (sz_remove_ghosts first): the edit is of the parents alone"; return SZ_E_STATE; }
-  State& S = c->S;
   const int N = c->hostN;
   // ---- the edit itself: rows, then the uploaded floes
   if ((rc = sp_check_rows(c, who_, "del", n_del, del, N, true)) || (rc = sp_check_rows(c, who_, "rep", n_rep, rep, N, true))) return rc;
@@ -2617,22 +2650,20 @@ int sp_splice(sz_ctx* c, const char* who_, bool parents, int32_t n_del, const in
   const long long Nn64 = (long long)N - n_del + n_app;
   if (Nn64 <= 0) { c->err = who + ": the edit leaves no floe"; return SZ_E_ARG; }
   if (Nn64 > 0x3fffffff) { c->err = who + ": too many floes"; return SZ_E_ARG; }
-  const int Nn = (int)Nn64;
-  const bool with_sub = ns > 0 && f->sub_off != nullptr;
-  if (with_sub && (!f->sx || !f->sy) && f->sub_off[ns] != f->sub_off[0]) { c->err = who + ": sub_off without sx / sy"; return SZ_E_ARG; }
-  size_t stream_len = 0;
-  for (int j = 0; j < ns; j++) {
-    const int o = f->vert_off[j], nv = f->vert_off[j + 1] - o, sp = with_sub ? f->sub_off[j + 1] - f->sub_off[j] : 0, ni = ioff ? ioff[j + 1] - ioff[j] : 0;
-    if (nv < 4 || o < 0 || !(f->vx[o] == f->vx[o + nv - 1] && f->vy[o] == f->vy[o + nv - 1])) { c->err = who + ": uploaded row " + std::to_string(j) + " has an open ring (a ring is closed: its first point repeated, at least 4 points)"; return SZ_E_ARG; }
-    if (nv > SP_MAX_RING) { c->err = who + ": uploaded row " + std::to_string(j) + " has a ring of " + std::to_string(nv) + " points: the row-moving kernels carry " + std::to_string(SP_MAX_RING); return SZ_E_ARG; }
-    if (sp < 0 || ni < 0) { c->err = who + ": offsets of uploaded row " + std::to_string(j) + " descend"; return SZ_E_ARG; }
-    if (sp > 0 && c->pts_N == 0) { c->err = who + ": the list was uploaded without sub-floe points"; return SZ_E_ARG; }
-    if (ni > S.rowcap) { c->err = "more interaction rows per floe than the fixed stride holds"; return SZ_E_CAPACITY; }
-    if (ni > 0 && !irows) { c->err = who + ": inter_off without inter_rows"; return SZ_E_ARG; }
-    stream_len += (size_t)MIG_NCOL + 2 * (size_t)nv + 2 * (size_t)sp;
-  }
-  if (stream_len > 0x7fffffffull) { c->err = who + ": the uploaded rows are too long for one stream"; return SZ_E_ARG; }
+  bool with_sub = false; size_t stream_len = 0;
+  if ((rc = sp_check_staged(c, who, ns, f, ioff, irows, &with_sub, &stream_len))) return rc;
   if (n_del + ns == 0) return SZ_OK;          // nothing to do, nothing touched
+  return sp_splice_rows(c, who, parents, n_del, del, n_rep, rep, n_app, f, ioff, irows, with_sub, stream_len, nullptr);
+}
+
+// The body of a splice, behind the checks: rows del / rep of this context's list, the ns = n_rep + n_app uploaded floes.  tile: this context's share of
+// a global edit (sz_tile_splice_floes, which has agreed it with the other ranks and establishes the tiling again behind it) -- the new rows then take
+// the global numbers of sz_k_spt_renumber as order keys and origin instead of the identity.
+int sp_splice_rows(sz_ctx* c, const std::string& who, bool parents, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app, const sz_floe_columns* f,
+                   const int32_t* ioff, const double* irows, bool with_sub, size_t stream_len, const SpTile* tile) {
+  int rc;
+  State& S = c->S;
+  const int N = c->hostN, ns = n_rep + n_app, Nn = N - n_del + n_app;
   // ---- from here on the state changes
   const int Mold = c->hostM;          // (the rows the list's ghosts held are vacated too)
   if (parents && (Mold != N || c->ghosts_staged)) { if ((rc = sz_remove_ghosts(c))) return rc; }
@@ -2664,7 +2695,7 @@ int sp_splice(sz_ctx* c, const char* who_, bool parents, int32_t n_del, const in
       double* rec = &stream[at];
       for (int q = 0; q < MIG_NSC; q++) rec[q] = src[q] ? src[q][j] : 0.0;
       for (int t = 0; t < 3; t++) for (int q = 0; q < 4; q++) rec[MIG_NSC + 4 * t + q] = tsrc[t] ? tsrc[t][(size_t)4 * j + q] : 0.0;
-      rec[37] = (double)(f->id ? f->id[j] : (long long)newrow + 1); rec[38] = (double)(f->status ? f->status[j] : SZ_ACTIVE); rec[39] = 0.0;
+      rec[37] = (double)(f->id ? f->id[j] : (tile ? tile->staged_num[j] : (long long)newrow) + 1); rec[38] = (double)(f->status ? f->status[j] : SZ_ACTIVE); rec[39] = 0.0;
       rec[40] = (double)nv; rec[41] = (double)sp;
       for (int k = 0; k < nv; k++) { rec[MIG_NCOL + 2 * k] = f->vx[o + k]; rec[MIG_NCOL + 2 * k + 1] = f->vy[o + k]; }
       double* sub = rec + MIG_NCOL + 2 * (size_t)nv;
@@ -2703,6 +2734,13 @@ int sp_splice(sz_ctx* c, const char* who_, bool parents, int32_t n_del, const in
   scan(c, A.kv, A.ovoff, N, C_N, 0, -1);
   scan(c, A.ks, A.osoff, N, C_N, 0, -1);
   hipLaunchKernelGGL(sz_k_sp_rows, dim3(nb), dim3(256), 0, c->stream, A);
+  long long* d_newkey = nullptr;
+  if (tile) {
+    if ((rc = dalloc(c, &d_newkey, (size_t)Nn + 1, P))) return rc;
+    hipLaunchKernelGGL(sz_k_spt_renumber, dim3(grid_for(Nn, 256, 2048)), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, tile->keys, d_newkey);
+    tile->newkey->assign((size_t)Nn, 0);
+    HIPCHK(c, hipMemcpyAsync(tile->newkey->data(), d_newkey, (size_t)Nn * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  }
   hipLaunchKernelGGL(sz_k_sp_limits, dim3(grid_for(Nn, 256, 2048)), dim3(256), 0, c->stream, S, A, Nn, (const double*)d_dirs, (const double*)d_stream);
   SpDev R{};
   HIPCHK(c, hipMemcpyAsync(&R, A.d, sizeof(SpDev), hipMemcpyDeviceToHost, c->stream));
@@ -2755,7 +2793,7 @@ int sp_splice(sz_ctx* c, const char* who_, bool parents, int32_t n_del, const in
   }
   // ---- and into their places, with the links of a freshly placed ghost-free field (as sz_upload_floes leaves them)
   hipLaunchKernelGGL(sz_k_mig_scatter, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (double* const*)d_cols, (const double*)d_tmp);
-  hipLaunchKernelGGL(sz_k_sp_scatter_rows, dim3(nbw), dim3(256), 0, c->stream, S, Nn, c->origin, tcap, (const int*)d_tcnt, (const double*)d_trows);
+  hipLaunchKernelGGL(sz_k_sp_scatter_rows, dim3(nbw), dim3(256), 0, c->stream, S, Nn, c->origin, (const long long*)d_newkey, tcap, (const int*)d_tcnt, (const double*)d_trows);
   const int top = std::min(std::max(N, Mold), S.capM);
   if (fits && top > Nn) hipLaunchKernelGGL(sz_k_sp_clear_rows, dim3(grid_for(top - Nn, 256, 2048)), dim3(256), 0, c->stream, Nn, top, (double* const*)d_cols);
   if (top > Nn) HIPCHK(c, hipMemsetAsync(S.inter_cnt + Nn, 0, (size_t)(top - Nn) * sizeof(int), c->stream));
@@ -2791,33 +2829,65 @@ int sz_splice_parents(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_re
 namespace {
 using sp_download_fn = int (*)(sz_ctx*, int32_t, const int32_t*, sz_floe_columns*, int32_t*, double*, int64_t*);
 using sp_splice_fn = int (*)(sz_ctx*, int32_t, const int32_t*, int32_t, const int32_t*, int32_t, const sz_floe_columns*, const int32_t*, const double*);
+// Float64 room for the n rows a download brings (sz: the sizes its sizing call gave): d and ir go to the Float64 call, back() rounds into f
+struct SpF32Down {
+  std::vector<std::vector<double>> keep;
+  struct Back { float* dst; double* src; size_t n; }; std::vector<Back> todo;
+  sz_floe_columns d; double* ir;
+  SpF32Down(size_t M, const int64_t* sz, sz_floe_columns_f32* f, float* inter_rows) {
+    const size_t V = (size_t)sz[0], NS = (size_t)sz[1], R = (size_t)sz[2];
+    memset(&d, 0, sizeof(d));
+#define X(name) d.name = room(f->name, M);
+    SZ_F32_SCALARS(X)
+#undef X
+#define X(name) d.name = room(f->name, 4 * M);
+    SZ_F32_TENSORS(X)
+#undef X
+    d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
+    d.vx = room(f->vx, V); d.vy = room(f->vy, V); d.sx = room(f->sx, NS); d.sy = room(f->sy, NS);
+    ir = room(inter_rows, 7 * R);
+  }
+  double* room(float* dst, size_t cnt) {
+    if (!dst) return nullptr;
+    keep.emplace_back(cnt ? cnt : 1);
+    todo.push_back({ dst, keep.back().data(), cnt });
+    return keep.back().data();
+  }
+  void back() const { for (const Back& b : todo) for (size_t k = 0; k < b.n; k++) b.dst[k] = (float)b.src[k]; }
+};
+// the M = n_rep + n_app uploaded floes of a splice, widened: d and ir go to the Float64 call
+struct SpF32Up {
+  std::vector<std::vector<double>> keep;
+  sz_floe_columns d; const double* ir;
+  SpF32Up(size_t M, const sz_floe_columns_f32* f, const int32_t* ioff, const float* irows) {
+    const size_t V = (size_t)f->vert_off[M], NS = f->sub_off ? (size_t)f->sub_off[M] : 0, R = ioff ? (size_t)ioff[M] : 0;
+    memset(&d, 0, sizeof(d));
+#define X(name) d.name = widen(f->name, M);
+    SZ_F32_SCALARS(X)
+#undef X
+#define X(name) d.name = widen(f->name, 4 * M);
+    SZ_F32_TENSORS(X)
+#undef X
+    d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
+    d.vx = widen(f->vx, V); d.vy = widen(f->vy, V); d.sx = widen(f->sx, NS); d.sy = widen(f->sy, NS);
+    ir = widen(irows, 7 * R);
+  }
+  double* widen(const float* src, size_t cnt) {
+    if (!src) return nullptr;
+    keep.emplace_back(cnt ? cnt : 1);
+    for (size_t k = 0; k < cnt; k++) keep.back()[k] = (double)src[k];
+    return keep.back().data();
+  }
+};
 int sp_download_f32(sp_download_fn down, sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns_f32* f, int32_t* inter_off, float* inter_rows, int64_t* sizes3) {
   if (!c || n < 0) return SZ_E_ARG;
   int64_t sz[3] = { 0, 0, 0 };
   int rc = down(c, n, rows, nullptr, nullptr, nullptr, sz); if (rc) return rc;
   if (sizes3) { sizes3[0] = sz[0]; sizes3[1] = sz[1]; sizes3[2] = sz[2]; }
   if (!f) return SZ_OK;
-  const size_t M = (size_t)n, V = (size_t)sz[0], NS = (size_t)sz[1], R = (size_t)sz[2];
-  std::vector<std::vector<double>> keep;
-  struct Back { float* dst; double* src; size_t n; }; std::vector<Back> back;
-  auto room = [&](float* dst, size_t cnt) -> double* {
-    if (!dst) return nullptr;
-    keep.emplace_back(cnt ? cnt : 1);
-    back.push_back({ dst, keep.back().data(), cnt });
-    return keep.back().data();
-  };
-  sz_floe_columns d; memset(&d, 0, sizeof(d));
-#define X(name) d.name = room(f->name, M);
-  SZ_F32_SCALARS(X)
-#undef X
-#define X(name) d.name = room(f->name, 4 * M);
-  SZ_F32_TENSORS(X)
-#undef X
-  d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
-  d.vx = room(f->vx, V); d.vy = room(f->vy, V); d.sx = room(f->sx, NS); d.sy = room(f->sy, NS);
-  double* ir = room(inter_rows, 7 * R);
-  rc = down(c, n, rows, &d, inter_off, ir, nullptr); if (rc) return rc;
-  for (const Back& b : back) for (size_t k = 0; k < b.n; k++) b.dst[k] = (float)b.src[k];
+  SpF32Down W((size_t)n, sz, f, inter_rows);
+  rc = down(c, n, rows, &W.d, inter_off, W.ir, nullptr); if (rc) return rc;
+  W.back();
   return SZ_OK;
 }
 int sp_splice_f32(sp_splice_fn splice, const char* who, sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_rep, const int32_t* rep, int32_t n_app,
@@ -2826,24 +2896,8 @@ int sp_splice_f32(sp_splice_fn splice, const char* who, sz_ctx* c, int32_t n_del
   const size_t M = (size_t)n_rep + (size_t)n_app;
   if (M == 0 || !f) return splice(c, n_del, del, n_rep, rep, n_app, nullptr, ioff, nullptr);
   if (!f->vert_off) { c->err = std::string(who) + ": vert_off is required"; return SZ_E_ARG; }
-  const size_t V = (size_t)f->vert_off[M], NS = f->sub_off ? (size_t)f->sub_off[M] : 0, R = ioff ? (size_t)ioff[M] : 0;
-  std::vector<std::vector<double>> keep;
-  auto widen = [&](const float* src, size_t cnt) -> double* {
-    if (!src) return nullptr;
-    keep.emplace_back(cnt ? cnt : 1);
-    for (size_t k = 0; k < cnt; k++) keep.back()[k] = (double)src[k];
-    return keep.back().data();
-  };
-  sz_floe_columns d; memset(&d, 0, sizeof(d));
-#define X(name) d.name = widen(f->name, M);
-  SZ_F32_SCALARS(X)
-#undef X
-#define X(name) d.name = widen(f->name, 4 * M);
-  SZ_F32_TENSORS(X)
-#undef X
-  d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
-  d.vx = widen(f->vx, V); d.vy = widen(f->vy, V); d.sx = widen(f->sx, NS); d.sy = widen(f->sy, NS);
-  return splice(c, n_del, del, n_rep, rep, n_app, &d, ioff, widen(irows, 7 * R));
+  const SpF32Up W(M, f, ioff, irows);
+  return splice(c, n_del, del, n_rep, rep, n_app, &W.d, ioff, W.ir);
 }
 }  // namespace
 int sz_download_rows_f32(sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns_f32* f, int32_t* inter_off, float* inter_rows, int64_t* sizes3) {

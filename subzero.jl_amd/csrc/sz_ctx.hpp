@@ -170,6 +170,7 @@ struct sz_ctx {
   bool rm_on = false; int rm_max_vertices = 0x7fffffff; double rm_min_area = 0, rm_min_height = 0;
   double* dissolved = nullptr; int* origin = nullptr; Pool rm_allocs;
   Pool sp_allocs;                   // scratch of sz_download_rows / sz_download_list_rows / sz_splice_floes / sz_splice_parents (sz_splice.hpp) and of sz_ridgeraft_rows: the staged rows, the plan, the gathered rows, the closure's flags; kept between calls
+  Pool spt_allocs;                  // scratch of sz_tile_download_rows / sz_tile_splice_floes in front of that (sz_splice_tile.hpp): the names, their rows, the ranks' records; kept between calls
   // ridge / raft (sz_set_ridgeraft; sz_ridgeraft.hpp): RidgeRaftSettings' Δt and the five heights the gates read; the buffers of the candidate pass,
   // carved for rr_capM list rows and rr_cap entries.  rr_pending: the timestep whose ridge / raft step stopped between timestep_collisions! and
   // timestep_ridging_rafting! (-1: none; sz_step_finish runs its second half); rr_draws: the per-floe draws of the ridge / raft steps the last

@@ -12,7 +12,8 @@
 //     sz_k_sp_limits       over the new rows: longest ring, most sub-floe points, rows whose status is not `active` (what an upload finds on the host)
 //     sz_k_sp_gather_rows  what a migration does not carry, one wavefront per new row: the interaction rows, kept ones from the old rows (a partner
 //     sz_k_sp_scatter_rows that was an inline ghost is renumbered as a download would), staged ones from the uploaded CSR; and back, with `origin` and
-//                          the order keys as the identity and the tag column equal to the status column, as sz_upload_floes leaves them
+//                          the order keys as the identity (a tiled context's share of a global edit, sz_splice_tile.hpp: as the new global numbers)
+//                          and the tag column equal to the status column, as sz_upload_floes leaves them
 //     sz_k_sp_clear_rows   the rows a shrinking list vacates, zeroed
 //     sz_k_sp_sel_len,     sz_download_rows / sz_download_list_rows: the lengths of the selected rows (scanned into the offsets of the staging buffer),
 //     sz_k_sp_pack         then one wavefront per selected row packs columns, ring, sub-floe points, interaction rows and ghost list into that buffer
@@ -127,11 +128,12 @@ __global__ void __launch_bounds__(256) sz_k_sp_gather_rows(State S, int Nn, cons
     }
   }
 }
-__global__ void __launch_bounds__(256) sz_k_sp_scatter_rows(State S, int Nn, int* origin, int tcap, const int* t_cnt, const double* t_rows) {
+// newkey: the order keys of the new rows (a tiled context's share of a global edit: their global numbers) or null: the identity
+__global__ void __launch_bounds__(256) sz_k_sp_scatter_rows(State S, int Nn, int* origin, const long long* newkey, int tcap, const int* t_cnt, const double* t_rows) {
   const int lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
   for (int r = wave; r < Nn; r += nw) {
     const int cnt = t_cnt[r], n = min(min(max(cnt, 0), S.rowcap), tcap) * 7;
-    if (lane == 0) { origin[r] = r; S.okey[r] = r; S.inter_cnt[r] = cnt; S.tagA[r] = S.status[r]; }      // (an appended floe lies in a row that held a ghost, with the ghost's order key)
+    if (lane == 0) { const long long key = newkey ? newkey[r] : r; origin[r] = (int)key; S.okey[r] = key; S.inter_cnt[r] = cnt; S.tagA[r] = S.status[r]; }      // (an appended floe lies in a row that held a ghost, with the ghost's order key)
     const double* from = t_rows + (size_t)tcap * 7 * r;
     double* to = S.inter_rows + (size_t)S.rowcap * 7 * r;
     for (int k = lane; k < n; k += 64) to[k] = from[k];

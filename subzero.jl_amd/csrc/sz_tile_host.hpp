@@ -1,5 +1,5 @@
 // sz_tile_host.hpp — the host code of tiled (multi-GPU) contexts: set-up, the steps a host drives itself (sz_halo_* / sz_tile_step), the box
-// gather and the halo exchange, migration, the collective removal, fracture, welding and ridge / raft passes, and the batch drivers of sz_tile_run.  Host code of
+// gather and the halo exchange, migration, the collective removal, row edits by global number, the fracture, welding and ridge / raft passes, and the batch drivers of sz_tile_run.  Host code of
 // the one translation unit sz_api.hip, which includes it behind the single context's batch drivers and passes: a tile's steps are theirs.
 #pragma once
 #include "sz_comm.hpp"
@@ -817,6 +817,260 @@ int sz_tile_remove_floes(sz_ctx* c, int32_t* done, int32_t* n_removed, int32_t* 
   if (n_removed) *n_removed = nr;
   if (n_dissolved) *n_dissolved = nd;
   return SZ_OK;
+}
+
+// ---------------------------------------------------------------- row edits by global number (sz_splice_tile.hpp)
+namespace {
+// names[0 .. n): no negative one, none twice; sorted: ascending as given
+int spt_check_names(sz_ctx* c, const std::string& who, const char* what, int n, const int64_t* names, bool sorted) {
+  std::vector<int64_t> tmp;
+  const int64_t* g = names;
+  if (!sorted && n > 1) { tmp.assign(names, names + n); std::sort(tmp.begin(), tmp.end()); g = tmp.data(); }
+  for (int k = 0; k < n; k++) {
+    if (g[k] < 0) { c->err = who + ": " + what + " names floe " + std::to_string((long long)g[k]) + ": global numbers start at 0"; return SZ_E_ARG; }
+    if (k && g[k] <= g[k - 1]) { c->err = who + ": " + what + (g[k] == g[k - 1] ? " repeats floe " + std::to_string((long long)g[k]) : std::string(" is not ascending")); return SZ_E_ARG; }
+  }
+  return SZ_OK;
+}
+// the binary searches of sz_k_spt_* need the owned numbers ascending by row: TiledWorld, sz_tile_migrate and sz_tile_remove_floes leave them so,
+// sz_tile_enable takes any order
+bool spt_ascending(const sz_ctx* c) {
+  const std::vector<long long>& g = c->tile_gidx;
+  for (size_t i = 1; i < g.size(); i++) if (g[i] <= g[i - 1]) return false;
+  return true;
+}
+// names per find and scan of sz_tile_download_rows.  The engine's three-launch scan notes one total per SCAN_B elements in S.blk, which is sized by the
+// context's capacities and holds at least 1024 of them whatever those are: a request of any length stays inside it in rounds of this size
+constexpr int SPT_CHUNK = 1024 * SCAN_B;
+constexpr const char* SPT_ORDER_MSG = ": the global numbers of the owned floes are not ascending by row (sz_tile_enable takes any order; rows are found by binary search)";
+
+// the staged floes `sel` (ascending positions among the ns = n_rep + n_app uploaded floes) as a list of their own: this rank's share
+struct SptSubset {
+  std::vector<std::vector<double>> keep; std::vector<int64_t> id; std::vector<int32_t> status, voff, soff, ioff;
+  std::vector<double> vx, vy, sx, sy, irows;
+  sz_floe_columns f;
+  SptSubset(const sz_floe_columns* a, const int32_t* a_ioff, const double* a_irows, const std::vector<int>& sel) {
+    memset(&f, 0, sizeof(f));
+    const size_t m = sel.size();
+    if (!a || m == 0) return;
+    auto pick = [&](const double* src, int w) -> double* {
+      if (!src) return nullptr;
+      keep.emplace_back(m * w);
+      for (size_t k = 0; k < m; k++) for (int q = 0; q < w; q++) keep.back()[k * w + q] = src[(size_t)sel[k] * w + q];
+      return keep.back().data();
+    };
+#define X(name) f.name = pick(a->name, 1);
+    SZ_F32_SCALARS(X)
+#undef X
+#define X(name) f.name = pick(a->name, 4);
+    SZ_F32_TENSORS(X)
+#undef X
+    if (a->id) { for (int j : sel) id.push_back(a->id[j]); f.id = id.data(); }
+    if (a->status) { for (int j : sel) status.push_back(a->status[j]); f.status = status.data(); }
+    voff.assign(1, 0); soff.assign(1, 0); ioff.assign(1, 0);
+    for (int j : sel) {
+      for (int q = a->vert_off[j]; q < a->vert_off[j + 1]; q++) { vx.push_back(a->vx[q]); vy.push_back(a->vy[q]); }
+      voff.push_back((int32_t)vx.size());
+      if (a->sub_off) { for (int q = a->sub_off[j]; q < a->sub_off[j + 1]; q++) { sx.push_back(a->sx[q]); sy.push_back(a->sy[q]); } soff.push_back((int32_t)sx.size()); }
+      if (a_ioff) { for (size_t q = (size_t)a_ioff[j] * 7; q < (size_t)a_ioff[j + 1] * 7; q++) irows.push_back(a_irows[q]); ioff.push_back((int32_t)(irows.size() / 7)); }
+    }
+    vx.push_back(0.0); vy.push_back(0.0); sx.push_back(0.0); sy.push_back(0.0); irows.push_back(0.0);          // (never NULL where the offsets are given)
+    f.vert_off = voff.data(); f.vx = vx.data(); f.vy = vy.data();
+    if (a->sub_off) { f.sub_off = soff.data(); f.sx = sx.data(); f.sy = sy.data(); }
+  }
+};
+}  // namespace
+
+// The rows `gidx` of the global list that this rank owns: local, not collective.  sz_k_spt_find and the engine's scan name them; the rows come through
+// sp_download, the path of sz_download_rows (one staging buffer, one copy).
+int sz_tile_download_rows(sz_ctx* c, int32_t n, const int64_t* gidx, int32_t* n_mine, int32_t* which, sz_floe_columns* f, int32_t* inter_off, double* inter_rows, int64_t* sizes3) {
+  const std::string who = "sz_tile_download_rows";
+  if (n_mine) *n_mine = 0;
+  if (!c || n < 0 || !n_mine || (n > 0 && (!gidx || !which))) return SZ_E_ARG;
+  if (!c->have_floes || !c->S.tiled) { c->err = who + " needs sz_tile_enable after the last sz_upload_floes: on a single context sz_download_rows names the rows"; return SZ_E_STATE; }
+  if (c->rr_pending >= 0) { c->err = who + ": a ridge / raft step is pending with halo rows and ghosts in the list (sz_tile_step_finish first)"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  int rc;
+  if ((rc = sync_and_check(c))) return rc;          // hostM / hostN current; the halo rows and ghosts of the last step are dropped
+  if (c->hostM != c->hostN) { c->err = who + ": ghosts are in the list (sz_remove_ghosts first): the rows are the parents'"; return SZ_E_STATE; }
+  if (!spt_ascending(c)) { c->err = who + SPT_ORDER_MSG; return SZ_E_STATE; }
+  if ((rc = spt_check_names(c, who, "gidx", n, gidx, false))) return rc;
+  const int N = c->hostN;
+  std::vector<int> hw((size_t)n + 1, 0), hr((size_t)n + 1, 0);
+  int cnt = 0;
+  if (n > 0) {
+    Pool& P = c->spt_allocs;
+    reset_pool(P);
+    long long* d_names = nullptr; int *d_loc = nullptr, *d_flag = nullptr, *d_pos = nullptr, *d_which = nullptr, *d_rows = nullptr;
+    const size_t n1 = (size_t)n + 1, c1 = (size_t)std::min((int)n, SPT_CHUNK) + 1;
+    if ((rc = dalloc(c, &d_names, n1, P)) || (rc = dalloc(c, &d_loc, c1, P)) || (rc = dalloc(c, &d_flag, c1, P)) || (rc = dalloc(c, &d_pos, c1 + 1, P)) ||
+        (rc = dalloc(c, &d_which, n1, P)) || (rc = dalloc(c, &d_rows, n1, P))) return rc;
+    H2D(d_names, gidx, n, long long);
+    // n is the caller's, not one of the context's capacities: the names go through the find and the scan SPT_CHUNK at a time (one round for any
+    // request a run makes), and every round appends what it found behind the rounds before it
+    for (int k0 = 0; k0 < n; k0 += SPT_CHUNK) {
+      const int m = std::min(SPT_CHUNK, (int)n - k0), nb = grid_for(m, 256, 2048);
+      int got = -1;
+      hipLaunchKernelGGL(sz_k_spt_find, dim3(nb), dim3(256), 0, c->stream, c->S, N, m, k0, (const long long*)d_names + k0, d_loc, d_flag, (const int*)nullptr, d_which + cnt, d_rows + cnt);
+      scan(c, d_flag, d_pos, m, -1, m, -1);
+      hipLaunchKernelGGL(sz_k_spt_find, dim3(nb), dim3(256), 0, c->stream, c->S, N, m, k0, (const long long*)d_names + k0, d_loc, d_flag, (const int*)d_pos, d_which + cnt, d_rows + cnt);
+      HIPCHK(c, hipMemcpyAsync(&got, d_pos + m, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(hw.data() + cnt, d_which + cnt, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));          // (cnt <= k0: the m entries lie inside the n)
+      HIPCHK(c, hipMemcpyAsync(hr.data() + cnt, d_rows + cnt, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      if (got < 0 || got > m) { c->err = who + ": bad counts"; return SZ_E_HIP; }
+      cnt += got;
+    }
+    for (int k = 0; k < cnt; k++) if (hr[k] < 0 || hr[k] >= N || hw[k] < 0 || hw[k] >= n) { c->err = who + ": bad rows"; return SZ_E_HIP; }
+  }
+  for (int k = 0; k < cnt; k++) which[k] = hw[k];
+  *n_mine = cnt;
+  return sp_download(c, who.c_str(), false, cnt, hr.data(), f, inter_off, inter_rows, sizes3);
+}
+
+// One edit of the global list, stated in global numbers with the same arguments on every rank: collective.  Every rank applies the share that
+// concerns the rows it owns -- no floe data crosses between the ranks; the one collective is the all-gather of a per-rank record {error bits, rows
+// owned, `del` names found, `rep` names found, appended floes taken} in front of the change, from which every rank derives N_global and the same
+// verdict.  Behind it the rows move through the body of sz_splice_floes (sp_splice_rows) with local rows, the staged floes this rank takes and the
+// new global numbers (sz_k_spt_renumber), and the tiling is established again as behind tile_remove_pass.
+int sz_tile_splice_floes(sz_ctx* c, int32_t n_del, const int64_t* del, int32_t n_rep, const int64_t* rep, int32_t n_app, const int32_t* app_owner, const sz_floe_columns* f,
+                         const int32_t* ioff, const double* irows, int64_t* n_global, int64_t* n_owned) {
+  const std::string who = "sz_tile_splice_floes";
+  if (n_global) *n_global = -1;
+  if (n_owned) *n_owned = -1;
+  if (!c || n_del < 0 || n_rep < 0 || n_app < 0 || (n_del && !del) || (n_rep && !rep)) return SZ_E_ARG;
+  const long long ns64 = (long long)n_rep + n_app;
+  if (ns64 > 0x3fffffff || (long long)n_del + n_rep > 0x3fffffff) return SZ_E_ARG;
+  const int ns = (int)ns64, nn = n_del + n_rep;
+  if (n_app > 0 && !app_owner) { c->err = who + ": appended floes need app_owner, the rank that takes each"; return SZ_E_ARG; }
+  if (ns > 0 && (!f || !f->vert_off || !f->vx || !f->vy || !f->cx || !f->cy)) { c->err = who + ": replaced / appended rows need vert_off, vx, vy, cx and cy"; return SZ_E_ARG; }
+  int rc;
+  if ((rc = tiled_ready(c, who.c_str()))) return rc;
+  if (c->rr_pending >= 0) { c->err = who + ": a ridge / raft step is pending with halo rows and ghosts in the list (sz_tile_step_finish first)"; return SZ_E_STATE; }
+  const int n = c->comm_n, me = c->comm_rank;
+  // ---- what the arguments alone decide: the same verdict on every rank, no collective needed
+  if ((rc = spt_check_names(c, who, "del", n_del, del, true)) || (rc = spt_check_names(c, who, "rep", n_rep, rep, true))) return rc;
+  for (int a = 0, b = 0; a < n_del && b < n_rep;) {
+    if (del[a] == rep[b]) { c->err = who + ": floe " + std::to_string((long long)del[a]) + " is both deleted and replaced"; return SZ_E_ARG; }
+    if (del[a] < rep[b]) a++; else b++;
+  }
+  int app_mine = 0;
+  for (int k = 0; k < n_app; k++) {
+    if (app_owner[k] < 0 || app_owner[k] >= n) { c->err = who + ": app_owner[" + std::to_string(k) + "] = " + std::to_string(app_owner[k]) + ", outside the " + std::to_string(n) + " ranks"; return SZ_E_ARG; }
+    app_mine += app_owner[k] == me;
+  }
+  int bits = 0; bool with_sub = false; size_t stream_len = 0;
+  if ((rc = sp_check_staged(c, who, ns, f, ioff, irows, &with_sub, &stream_len, &bits))) return rc;
+  if (n_del + ns == 0) { if (n_owned) *n_owned = (int64_t)c->tile_gidx.size(); return SZ_OK; }          // nothing to do, nothing touched, no collective (*n_global stays -1: it takes one)
+  // ---- this rank's state and its share of the names
+  (void)hipSetDevice(c->device);
+  rc = sync_and_check(c);
+  if (rc == SZ_E_HIP) return rc;
+  if (rc) bits |= SPT_BIT_ERR;
+  const int N = c->hostN;
+  if (!rc) bits |= c->hostM != N ? SPT_BIT_GHOSTS : N <= 0 ? SPT_BIT_NONE : !spt_ascending(c) ? SPT_BIT_ORDER : 0;
+  Pool& P = c->spt_allocs;
+  reset_pool(P);
+  constexpr int RW = 5;          // the record: error bits, rows owned, `del` names found, `rep` names found, appended floes taken
+  int *d_rec = nullptr, *d_all = nullptr, *d_loc = nullptr, *d_found = nullptr, *d_lrep = nullptr, *d_appk = nullptr; long long* d_names = nullptr;
+  if ((rc = dalloc(c, &d_rec, 8, P)) || (rc = dalloc(c, &d_all, (size_t)RW * Gather::RANKS, P))) return rc;          // (the record's own two words: without them there is no gathering, as with a failed channel)
+  // the scratch of the names: a rank that cannot have it says so in its record and goes into the gather, instead of leaving the others there
+  // (tile_remove_pass agrees such a code with comm_agree_rc; here the record is the agreement)
+  if (dalloc(c, &d_loc, (size_t)nn + 1, P) || dalloc(c, &d_found, 2, P) || dalloc(c, &d_names, (size_t)nn + 1, P) || dalloc(c, &d_lrep, (size_t)n_rep + 1, P) ||
+      dalloc(c, &d_appk, (size_t)n_app + 1, P)) bits |= SPT_BIT_MEM;
+  std::vector<int> loc((size_t)nn + 1, -1);
+  int found[2] = { 0, 0 };
+  if (!bits && nn > 0) {
+    if (n_del) H2D(d_names, del, n_del, long long);
+    if (n_rep) H2D(d_names + n_del, rep, n_rep, long long);
+    HIPCHK(c, hipMemsetAsync(d_found, 0, 2 * sizeof(int), c->stream));
+    hipLaunchKernelGGL(sz_k_spt_marks, dim3(grid_for(nn, 256, 2048)), dim3(256), 0, c->stream, c->S, N, (int)n_del, (int)n_rep, (const long long*)d_names, d_loc, d_found);
+    HIPCHK(c, hipMemcpyAsync(loc.data(), d_loc, (size_t)nn * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(found, d_found, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  // ---- the agreement, before anything changes
+  const int rec[RW] = { bits, N, found[0], found[1], app_mine };
+  std::vector<int> all((size_t)RW * n, 0);
+  H2D(d_rec, rec, RW, int);
+  if ((rc = comm_allgather(c, d_rec, d_all, RW, NCCL_INT32, sizeof(int)))) return rc;
+  HIPCHK(c, hipMemcpyAsync(all.data(), d_all, all.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  long long Ng = 0; int allbits = 0, fdel = 0, frep = 0, empty_rank = -1;
+  for (int r = 0; r < n; r++) {
+    const int* a = &all[(size_t)RW * r];
+    allbits |= a[0]; Ng += a[1]; fdel += a[2]; frep += a[3];
+    if (empty_rank < 0 && (long long)a[1] - a[2] + a[4] <= 0) empty_rank = r;
+  }
+  const std::string some = bits ? " (this rank among them)" : " (not this one; all ranks return together)";
+  if (allbits & SPT_BIT_MEM) { if (!(bits & SPT_BIT_MEM)) c->err = who + ": a rank of the tiled run could not allocate the scratch of the names" + some; return SZ_E_HIP; }
+  if (allbits & SPT_BIT_ERR) { if (!(bits & SPT_BIT_ERR)) c->err = who + ": a rank of the tiled run reported device error bits" + some; return SZ_E_CAPACITY; }
+  if (allbits & SPT_BIT_GHOSTS) { c->err = who + ": ghosts are in the list on some rank" + some + ": the edit is of the parents alone (sz_remove_ghosts first)"; return SZ_E_STATE; }
+  if (allbits & SPT_BIT_NONE) { c->err = who + ": some rank holds no floe" + some; return SZ_E_STATE; }
+  if (allbits & SPT_BIT_ORDER) { c->err = who + SPT_ORDER_MSG + ", on some rank" + some; return SZ_E_STATE; }
+  if (allbits & SPT_BIT_POINTS) { c->err = who + ": an uploaded floe has sub-floe points, and some rank's list was uploaded without" + some; return SZ_E_ARG; }
+  if (allbits & SPT_BIT_ROWCAP) { c->err = "more interaction rows per floe than the fixed stride holds on some rank" + some; return SZ_E_CAPACITY; }
+  if (fdel != n_del || frep != n_rep) {
+    c->err = who + ": the ranks own " + std::to_string(fdel) + " of the " + std::to_string(n_del) + " del names and " + std::to_string(frep) + " of the " + std::to_string(n_rep) +
+             " rep names: a name outside the " + std::to_string(Ng) + " floes of the global list, or owned twice";
+    return SZ_E_ARG;
+  }
+  const long long Nng = Ng - n_del + n_app;
+  if (Nng <= 0) { c->err = who + ": the edit leaves no floe"; return SZ_E_ARG; }
+  if (Nng > 0x3fffffff) { c->err = who + ": too many floes"; return SZ_E_ARG; }
+  if (empty_rank >= 0) { c->err = who + ": the edit leaves no floe on rank " + std::to_string(empty_rank) + " (an empty tile is not a state the tile drivers run in)"; return SZ_E_ARG; }
+  c->err.clear();
+  // ---- the share: local rows, the staged floes this rank takes, their new global numbers
+  std::vector<int32_t> ldel, lrep; std::vector<int> sel, appk; std::vector<long long> num;
+  for (int t = 0; t < n_del; t++) if (loc[t] >= 0) ldel.push_back(loc[t]);
+  for (int j = 0, below = 0; j < n_rep; j++) {
+    while (below < n_del && del[below] < rep[j]) below++;
+    if (loc[n_del + j] >= 0) { lrep.push_back(loc[n_del + j]); sel.push_back(j); num.push_back((long long)rep[j] - below); }
+  }
+  for (int k = 0; k < n_app; k++) if (app_owner[k] == me) { sel.push_back(n_rep + k); appk.push_back(k); num.push_back(Ng - n_del + k); }
+  if ((int)ldel.size() != found[0] || (int)lrep.size() != found[1]) { c->err = who + ": bad counts"; return SZ_E_HIP; }
+  const SptSubset mine(f, ioff, irows, sel);
+  bool sub2 = false; size_t len2 = 0;
+  if ((rc = sp_check_staged(c, who, (int)sel.size(), &mine.f, ioff ? mine.ioff.data() : nullptr, mine.irows.data(), &sub2, &len2))) return rc;          // (its sizes; the verdict is known)
+  if (!lrep.empty()) H2D(d_lrep, lrep.data(), lrep.size(), int);
+  if (!appk.empty()) H2D(d_appk, appk.data(), appk.size(), int);
+  std::vector<long long> newkey;
+  SpTile T{ SptKeys{ d_names, (int)n_del, d_lrep, (int)lrep.size(), d_appk, Ng - n_del }, num.data(), &newkey };
+  // ---- the tiling before, with hints that cover every staged floe of the whole edit (every rank sees the same edit: the same maxima, no exchange)
+  Retile tiling(c);
+  for (int j = 0; j < ns; j++) {
+    if (tiling.ring_hint > 0) tiling.ring_hint = std::max(tiling.ring_hint, (double)(f->vert_off[j + 1] - f->vert_off[j]));
+    if (tiling.rmax_hint > 0 && f->rmax) tiling.rmax_hint = std::max(tiling.rmax_hint, f->rmax[j]);
+  }
+  const bool ctr_valid = c->tile_box_valid; const double ctr[2] = { c->tile_box_ctr[0], c->tile_box_ctr[1] };
+  if ((rc = sp_splice_rows(c, who, false, (int32_t)ldel.size(), ldel.data(), (int32_t)lrep.size(), lrep.data(), (int32_t)appk.size(), sel.empty() ? nullptr : &mine.f,
+                           ioff && !sel.empty() ? mine.ioff.data() : nullptr, mine.irows.data(), sub2, len2, &T))) return rc;
+  if ((rc = tiling.again(c, newkey.data(), 0, 0))) return rc;
+  if (ctr_valid) (void)sz_tile_set_center(c, ctr[0], ctr[1]);
+  if (n_global) *n_global = Nng;
+  if (n_owned) *n_owned = c->hostN;
+  return SZ_OK;
+}
+
+int sz_tile_download_rows_f32(sz_ctx* c, int32_t n, const int64_t* gidx, int32_t* n_mine, int32_t* which, sz_floe_columns_f32* f, int32_t* inter_off, float* inter_rows, int64_t* sizes3) {
+  if (!c || !n_mine) return SZ_E_ARG;
+  int64_t sz[3] = { 0, 0, 0 };
+  if (int rc = sz_tile_download_rows(c, n, gidx, n_mine, which, nullptr, nullptr, nullptr, sz)) return rc;          // (*n_mine and the sizes: the room the rows need)
+  if (sizes3) { sizes3[0] = sz[0]; sizes3[1] = sz[1]; sizes3[2] = sz[2]; }
+  if (!f) return SZ_OK;
+  SpF32Down W((size_t)*n_mine, sz, f, inter_rows);
+  if (int rc = sz_tile_download_rows(c, n, gidx, n_mine, which, &W.d, inter_off, W.ir, nullptr)) return rc;
+  W.back();
+  return SZ_OK;
+}
+int sz_tile_splice_floes_f32(sz_ctx* c, int32_t n_del, const int64_t* del, int32_t n_rep, const int64_t* rep, int32_t n_app, const int32_t* app_owner, const sz_floe_columns_f32* f,
+                             const int32_t* ioff, const float* irows, int64_t* n_global, int64_t* n_owned) {
+  if (!c || n_rep < 0 || n_app < 0) return SZ_E_ARG;
+  const size_t M = (size_t)n_rep + (size_t)n_app;
+  if (M == 0 || !f) return sz_tile_splice_floes(c, n_del, del, n_rep, rep, n_app, app_owner, nullptr, ioff, nullptr, n_global, n_owned);
+  if (!f->vert_off) { c->err = "sz_tile_splice_floes_f32: vert_off is required"; return SZ_E_ARG; }
+  const SpF32Up W(M, f, ioff, irows);
+  return sz_tile_splice_floes(c, n_del, del, n_rep, rep, n_app, app_owner, &W.d, ioff, W.ir, n_global, n_owned);
 }
 
 // ---------------------------------------------------------------- fracture criteria on a tiled context (sz_fracture_tile.hpp)

@@ -757,12 +757,19 @@ class World:
         f32 = self._ft == np.float32
         rows = np.ascontiguousarray(rows, _I32).ravel()
         n = len(rows)
-        sizes = np.zeros(3, _I64)
         if whole_list:
             fn = self.L.sz_download_list_rows_f32 if f32 else self.L.sz_download_list_rows
         else:
             fn = self.L.sz_download_rows_f32 if f32 else self.L.sz_download_rows
-        self._chk(fn(self.h, n, capi.ptr(rows, capi._ip), None, None, None, capi.ptr(sizes, capi._lp)))
+        return self._rows_down(lambda f, ioff, irows, sizes: fn(self.h, n, capi.ptr(rows, capi._ip), f, ioff, irows, sizes), lambda: n, whole_list)
+
+    def _rows_down(self, call, count, whole_list=False):
+        """the two calls of a row download through call(cols, inter_off, inter_rows, sizes3) -- the sizes, then the columns; count(): the rows
+        that come back, asked behind the first call (tiles.TiledWorld.download_rows learns it there)"""
+        f32 = self._ft == np.float32
+        sizes = np.zeros(3, _I64)
+        self._chk(call(None, None, None, capi.ptr(sizes, capi._lp)))
+        n = count()
         V, NS, R = (int(v) for v in sizes)
         col = {k: np.zeros(n, self._ft) for k in capi.DCOLS}
         for k in capi.TCOLS:
@@ -776,7 +783,7 @@ class World:
             col["ghost_off"] = np.zeros(n + 1, _I32); col["ghost_idx"] = np.zeros(max(3 * n, 1), _I32)
         keep = []
         f = self._columns_struct(col, keep)
-        self._chk(fn(self.h, n, capi.ptr(rows, capi._ip), C.byref(f), capi.ptr(ioff, capi._ip), capi.ptr(irows, capi._fp if f32 else capi._dp), None))
+        self._chk(call(C.byref(f), capi.ptr(ioff, capi._ip), capi.ptr(irows, capi._fp if f32 else capi._dp), None))
         if whole_list:
             col["ghost_idx"] = col["ghost_idx"][:col["ghost_off"][n]].copy()
         if f32:

@@ -76,6 +76,35 @@ def subset_config(cfg, idx):
     return cols, soff, cfg["sx"][ssel], cfg["sy"][ssel]
 
 
+_ROW_CSR = (("vert_off", ("vx", "vy")), ("sub_off", ("sx", "sy")), ("inter_off", ("inter_rows",)))
+_ROW_CSR_NAMES = {n for off, vals in _ROW_CSR for n in (off,) + vals}
+
+
+def _concat_rows(parts):
+    """floe lists in the layout of World.download_rows (the same keys in each), one behind the other"""
+    out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0] if k not in _ROW_CSR_NAMES}
+    for off, vals in _ROW_CSR:
+        n = np.concatenate([np.diff(np.asarray(p[off], np.int64)) for p in parts])
+        out[off] = np.concatenate([[0], np.cumsum(n)]).astype(parts[0][off].dtype)
+        for v in vals:
+            out[v] = np.concatenate([p[v] for p in parts])
+    return out
+
+
+def _take_rows(col, idx):
+    """the floes idx of such a list, in that order, as a list of their own"""
+    idx = np.asarray(idx, np.int64)
+    out = {k: v[idx] for k, v in col.items() if k not in _ROW_CSR_NAMES}
+    for off, vals in _ROW_CSR:
+        o = np.asarray(col[off], np.int64)
+        n = np.diff(o)[idx]
+        out[off] = np.concatenate([[0], np.cumsum(n)]).astype(col[off].dtype)
+        sel = np.concatenate([np.arange(o[i], o[i + 1]) for i in idx]).astype(np.int64) if len(idx) else np.zeros(0, np.int64)
+        for v in vals:
+            out[v] = col[v][sel]
+    return out
+
+
 def host_transport(dist, rank, world):
     """sz_host_transport over torch.distributed collectives on HOST tensors (gloo, or any backend that takes CPU tensors):
     the three collectives the library calls when the tiled run was set up with sz_comm_init_host."""
@@ -130,13 +159,14 @@ class TiledWorld:
     """One rank of a tiled run.  `dist` is torch.distributed (initialised) or None for world == 1."""
 
     def __init__(self, cfg, rank, world, device, dist, drift_margin=None, rebox_every=50, host_staging=False,
-                 always_exchange=False, backend="torch"):
+                 always_exchange=False, backend="torch", ftype=np.float64):
         """backend: "library" -- the exchange runs inside libsubzero_hip.so (sz_comm_init / sz_tile_setup / sz_tile_run: RCCL
         bound by the library, grouped send / receive with the neighbouring tiles only; `dist` is then only used to hand the
         communicator id to the ranks); "torch" -- one torch.distributed all_to_all_single per step on buffers the library
         packs and unpacks (and, with host_staging, through the host: the gloo tests); "library-host" -- sz_tile_run as
         with "library", but over the host's channel (sz_comm_init_host: `dist` collectives on host buffers, e.g. gloo) --
-        the library's multi-rank exchange without an RCCL communicator, which ranks sharing one GPU cannot open."""
+        the library's multi-rank exchange without an RCCL communicator, which ranks sharing one GPU cannot open.
+        ftype: World's -- numpy.float32 for a Floe{Float32} host (the columns cross the boundary through the _f32 twins)."""
         import torch
         self.torch = torch
         self.cfg, self.rank, self.nranks, self.dist = cfg, rank, world, dist
@@ -150,7 +180,7 @@ class TiledWorld:
         self.gidx = np.nonzero(owner == rank)[0]
         cols, soff, sx, sy = subset_config(cfg, self.gidx)
         from . import fields
-        w = World(device)
+        w = World(device, ftype=ftype)
         w.set_consts(E=cfg["E"]); w.set_settings()
         w.set_domain([fields.KIND[k] for k in cfg["kinds"]], 0.0, self.L, 0.0, self.L)
         if cfg["topography"]:
@@ -614,6 +644,88 @@ class TiledWorld:
         """World.splice on this rank's context: a tiled context refuses it (its rows carry global numbers and its list is one rank's share), and
         the library's message is raised"""
         return self.world.splice(delete, replace, append)
+
+    # ---- rows down, rows back by global number (sz_tile_download_rows / sz_tile_splice_floes: library backends)
+    def download_rows_local(self, gidx):
+        """the floes of `gidx` (global numbers, any order, none twice) that THIS rank owns: (which, floes) -- their positions in gidx, ascending,
+        and a dict in the layout of World.download_rows with the floes in that order.  Local: no rank waits for another."""
+        self._library_only("download_rows_local")
+        w = self.world
+        w._push_interactions()
+        f32 = w._ft == np.float32
+        g = np.ascontiguousarray(gidx, np.int64).ravel()
+        n = len(g)
+        which = np.zeros(max(n, 1), np.int32); nm = C.c_int32(0)
+        fn = w.L.sz_tile_download_rows_f32 if f32 else w.L.sz_tile_download_rows
+        col = w._rows_down(lambda f, ioff, irows, sizes: fn(w.h, n, capi.ptr(g, capi._lp), C.byref(nm), capi.ptr(which, capi._ip), f, ioff, irows, sizes),
+                           lambda: int(nm.value))
+        return which[:nm.value].copy(), col
+
+    def download_rows(self, gidx):
+        """World.download_rows over the global floe list: the floes `gidx` (global numbers, any order, none twice) in that order, on every rank.
+        Collective in Python only -- the local call, then one all_gather_object of what each rank found: the template for a host with its own
+        channel (MPI).  Raises when a name was found on no rank."""
+        g = np.ascontiguousarray(gidx, np.int64).ravel()
+        which, col = self.download_rows_local(g)
+        parts = [(which, col)]
+        if self.dist is not None and self.nranks > 1:
+            parts = [None] * self.nranks
+            self.dist.all_gather_object(parts, (which, col))
+        pos = np.concatenate([p[0] for p in parts]).astype(np.int64)
+        missing = np.setdiff1d(np.arange(len(g)), pos)
+        if len(missing) or len(pos) != len(g):
+            raise capi.SzError("TiledWorld.download_rows: no rank owns the floes %s (or a floe is owned twice)" % list(g[missing][:8]))
+        return _take_rows(_concat_rows([p[1] for p in parts]), np.argsort(pos, kind="stable"))
+
+    def splice_global(self, delete=(), replace=None, append=None, owner=None):
+        """World.splice over the global floe list (sz_tile_splice_floes; collective, the same arguments on every rank): `delete` and the rows of
+        replace = (rows, floes) are ascending GLOBAL numbers of the list as it is, `append` goes behind the last kept floe of the global list;
+        owner[k]: the rank that takes appended floe k (default: the tile that holds its centroid, assign_tiles).  Every rank applies its share;
+        afterwards self.gidx holds the single context's new numbers of the floes this rank owns.  Returns (N_global, N_owned)."""
+        self._library_only("splice_global")
+        w = self.world
+        w._push_interactions()
+        f32 = w._ft == np.float32
+        dele = np.ascontiguousarray(delete, np.int64).ravel()
+        rep_rows, rep_cols = (np.zeros(0, np.int64), None) if replace is None else (np.ascontiguousarray(replace[0], np.int64).ravel(), replace[1])
+        if rep_cols is not None and len(rep_cols["vert_off"]) - 1 != len(rep_rows):
+            raise capi.SzError("splice_global: replace names %d rows and gives %d floes" % (len(rep_rows), len(rep_cols["vert_off"]) - 1))
+        col, ioff, irows, ns = World._staged([rep_cols, append])
+        n_app = ns - len(rep_rows)
+        if n_app and owner is None:
+            cx, cy = np.array(col["cx"][len(rep_rows):], float), np.array(col["cy"][len(rep_rows):], float)
+            if self.per_x: cx %= self.L
+            if self.per_y: cy %= self.L
+            owner = assign_tiles(cx, cy, self.L, self.nranks)
+        own = np.ascontiguousarray(owner if n_app else np.zeros(0), np.int32).ravel()
+        if len(own) != n_app:
+            raise capi.SzError("splice_global: %d appended floes and %d owners" % (n_app, len(own)))
+        keep = []
+        f = w._columns_struct(col, keep) if col is not None else None
+        if irows is not None:
+            irows = np.ascontiguousarray(irows, w._ft)
+        fn = w.L.sz_tile_splice_floes_f32 if f32 else w.L.sz_tile_splice_floes
+        ng, no = C.c_int64(0), C.c_int64(0)
+        w._chk(fn(w.h, len(dele), capi.ptr(dele, capi._lp), len(rep_rows), capi.ptr(rep_rows, capi._lp), int(n_app), capi.ptr(own, capi._ip) if n_app else None,
+                  C.byref(f) if f is not None else None, capi.ptr(ioff, capi._ip) if ioff is not None else None,
+                  capi.ptr(irows, capi._fp if f32 else capi._dp) if irows is not None and len(irows) else None, C.byref(ng), C.byref(no)))
+        if len(dele) + ns == 0:
+            return None, len(self.gidx)
+        # the mirror follows, as in _after_pass: count and numbers from the library, columns and sub-floe points fetched on demand; the maxima
+        # given to sz_tile_enable cover the staged floes of the whole edit, as the library raised them
+        n = int(no.value)
+        w.N = n; w._M = n; w._dirty = False; w._host_stale = True; w._sub = {}; w._sub_on_device = True
+        g = np.zeros(max(n, 1), np.int64)
+        w._chk(w.L.sz_tile_owned_gidx(w.h, capi.ptr(g, capi._lp), int(g.size)))
+        self.gidx = g[:n].copy()
+        self.boxes = None; self._ref = None
+        self.REC = w.L.sz_halo_record_doubles_ctx(w.h)
+        if ns:
+            if self._max_ring > 0:
+                self._max_ring = max(self._max_ring, float(np.diff(col["vert_off"]).max()))
+            if self._max_rmax > 0 and "rmax" in col:
+                self._max_rmax = max(self._max_rmax, float(np.max(col["rmax"])))
+        return int(ng.value), n
 
     def ridgeraft_draws(self):
         """the per-floe draws of the ridge / raft steps the last run() ran through, over the global list: the same number on every rank"""
