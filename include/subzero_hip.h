@@ -775,6 +775,9 @@ int sz_debug_crec_mismatches(sz_ctx *ctx, int64_t *n_bad);
    out4 = { 1 if it is a ridge / raft step, its length, 1 if its last step is a fracture step, that step's welding set or -1 }. */
 int sz_debug_next_segment(int32_t tstep, int32_t remaining, int32_t rr_dt, int32_t frac_dt, int32_t cut_on_fracture, int32_t n_weld,
                           const int32_t *weld_dts, int32_t *out4);
+/* test hook: the columns of sz_floe_columns in the order the engine's tables hold them (csrc/sz_columns.hpp) -- the scalar columns, then the
+   tensors, as the member names of the struct above, space-separated; no context and no device call */
+const char *sz_debug_column_names(void);
 
 #ifdef __cplusplus
 }

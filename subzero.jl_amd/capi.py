@@ -91,7 +91,7 @@ EXPORTS = [
     "sz_set_ridgeraft", "sz_ridgeraft_candidates", "sz_ridgeraft_pending", "sz_ridgeraft_draws", "sz_step_finish",
     "sz_tile_ridgeraft_candidates", "sz_tile_list_numbers", "sz_tile_list_keys", "sz_tile_step_finish",
     "sz_download_rows", "sz_splice_floes", "sz_download_rows_f32", "sz_splice_floes_f32",
-    "sz_debug_next_segment",
+    "sz_debug_next_segment", "sz_debug_column_names",
     "sz_ridgeraft_rows", "sz_download_list_rows", "sz_splice_parents", "sz_ridgeraft_rows_f32", "sz_download_list_rows_f32", "sz_splice_parents_f32",
     "sz_tile_download_rows", "sz_tile_splice_floes", "sz_tile_download_rows_f32", "sz_tile_splice_floes_f32",
 ]
@@ -220,6 +220,8 @@ def load(build_if_missing=True):
     L.sz_ridgeraft_candidates.argtypes = [C.c_void_p, _ip, C.c_int32, _ip, _ip, _ip, _dp, _lp]
     L.sz_ridgeraft_pending.argtypes = [C.c_void_p, _ip]
     L.sz_debug_next_segment.argtypes = [C.c_int32] * 6 + [_ip, _ip]
+    L.sz_debug_column_names.restype = C.c_char_p
+    L.sz_debug_column_names.argtypes = []
     L.sz_ridgeraft_draws.argtypes = [C.c_void_p, _lp]
     L.sz_step_finish.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.sz_tile_ridgeraft_candidates.argtypes = [C.c_void_p, _ip, C.c_int32, _lp, _lp, _ip, _dp, _lp]
@@ -240,7 +242,7 @@ def load(build_if_missing=True):
     L.sz_tile_download_rows_f32.argtypes = [C.c_void_p, C.c_int32, _lp, _ip, _ip, C.POINTER(SzFloeColumnsF32), _ip, _fp, _lp]
     L.sz_tile_splice_floes_f32.argtypes = [C.c_void_p, C.c_int32, _lp, C.c_int32, _lp, C.c_int32, _ip, C.POINTER(SzFloeColumnsF32), _ip, _fp, _lp, _lp]
     for n in EXPORTS:
-        if n not in ("sz_create", "sz_destroy", "sz_last_error", "sz_version"):
+        if n not in ("sz_create", "sz_destroy", "sz_last_error", "sz_version", "sz_debug_column_names"):
             getattr(L, n).restype = C.c_int
     _LIB = L
     return L

@@ -949,20 +949,15 @@ int sz_upload_floes(sz_ctx* c, int64_t M64, int64_t N64, const sz_floe_columns* 
   int rc;
 #define DA(field, n) if ((rc = dalloc(c, &S.field, (size_t)(n), c->allocs))) return rc
   DA(cnt, C_COUNT + 64 + 72); DA(warn, WARN_SLOTS * 32);      // counters | 64 per-rank counts of the pack kernel | its 66 scratch words
-  double** dcols[] = { &S.cx, &S.cy, &S.rmax, &S.area, &S.height, &S.mass, &S.moment, &S.alpha, &S.u, &S.v, &S.xi,
-                       &S.p_dxdt, &S.p_dydt, &S.p_dalphadt, &S.p_dudt, &S.p_dvdt, &S.p_dxidt, &S.fxOA, &S.fyOA, &S.trqOA,
-                       &S.hflx, &S.overarea, &S.cfx, &S.cfy, &S.ctrq };
-  double* const hcols[] = { f->cx, f->cy, f->rmax, f->area, f->height, f->mass, f->moment, f->alpha, f->u, f->v, f->xi,
-                            f->p_dxdt, f->p_dydt, f->p_dalphadt, f->p_dudt, f->p_dvdt, f->p_dxidt, f->fxOA, f->fyOA, f->trqOA,
-                            f->hflx_factor, f->overarea, f->coll_fx, f->coll_fy, f->coll_trq };
-  for (size_t k = 0; k < sizeof(dcols) / sizeof(dcols[0]); k++) {
-    if ((rc = dalloc(c, dcols[k], S.capM, c->allocs))) return rc;
-    if (hcols[k]) H2D(*dcols[k], hcols[k], M, double);
+  const ColTable<double**> dcols = state_column_slots(S);
+  const ColTable<const double*> hcols = host_columns(*f);
+  for (int k = 0; k < MIG_NSC; k++) {
+    if ((rc = dalloc(c, dcols.p[k], S.capM, c->allocs))) return rc;
+    if (hcols.p[k]) H2D(*dcols.p[k], hcols.p[k], M, double);
   }
-  DA(sa, 4 * S.capM); DA(si, 4 * S.capM); DA(strain, 4 * S.capM); DA(mot, 4 * S.capM); DA(mot2, 2 * S.capM); DA(trig, 2 * S.capM);
-  if (f->stress_accum) H2D(S.sa, f->stress_accum, 4 * M, double);
-  if (f->stress_instant) H2D(S.si, f->stress_instant, 4 * M, double);
-  if (f->strain) H2D(S.strain, f->strain, 4 * M, double);
+  for (int k = MIG_NSC; k < MIG_NTAB; k++) if ((rc = dalloc(c, dcols.p[k], (size_t)4 * S.capM, c->allocs))) return rc;
+  DA(mot, 4 * S.capM); DA(mot2, 2 * S.capM); DA(trig, 2 * S.capM);
+  for (int k = MIG_NSC; k < MIG_NTAB; k++) if (hcols.p[k]) H2D(*dcols.p[k], hcols.p[k], 4 * M, double);
   DA(id, S.capM); DA(ghost_id, S.capM); DA(okey, S.capM); DA(status, S.capM); DA(parent, S.capM); DA(gh, MAX_GHOSTS * S.capM); DA(ngh, S.capM);
   DA(gh_save, MAX_GHOSTS * S.capM); DA(ngh_save, S.capM);
   std::vector<int> tag0;          // (tagA starts as the status column: the integrator of a resident step only rewrites it where a tag was raised)
@@ -1096,15 +1091,8 @@ int sz_download_floes(sz_ctx* c, sz_floe_columns* f) {
   HIPCHK(c, hipMemcpy(h, S.cnt, sizeof(h), hipMemcpyDeviceToHost));
   int M = h[C_M], N = h[C_N], V = h[C_NV];
 #define D2H(dst, src, n, T) if (dst) HIPCHK(c, hipMemcpy(dst, src, (size_t)(n) * sizeof(T), hipMemcpyDeviceToHost))
-  D2H(f->cx, S.cx, M, double); D2H(f->cy, S.cy, M, double); D2H(f->rmax, S.rmax, M, double); D2H(f->area, S.area, M, double);
-  D2H(f->height, S.height, M, double); D2H(f->mass, S.mass, M, double); D2H(f->moment, S.moment, M, double);
-  D2H(f->alpha, S.alpha, M, double); D2H(f->u, S.u, M, double); D2H(f->v, S.v, M, double); D2H(f->xi, S.xi, M, double);
-  D2H(f->p_dxdt, S.p_dxdt, M, double); D2H(f->p_dydt, S.p_dydt, M, double); D2H(f->p_dalphadt, S.p_dalphadt, M, double);
-  D2H(f->p_dudt, S.p_dudt, M, double); D2H(f->p_dvdt, S.p_dvdt, M, double); D2H(f->p_dxidt, S.p_dxidt, M, double);
-  D2H(f->fxOA, S.fxOA, M, double); D2H(f->fyOA, S.fyOA, M, double); D2H(f->trqOA, S.trqOA, M, double);
-  D2H(f->hflx_factor, S.hflx, M, double); D2H(f->overarea, S.overarea, M, double);
-  D2H(f->coll_fx, S.cfx, M, double); D2H(f->coll_fy, S.cfy, M, double); D2H(f->coll_trq, S.ctrq, M, double);
-  D2H(f->stress_accum, S.sa, 4 * M, double); D2H(f->stress_instant, S.si, 4 * M, double); D2H(f->strain, S.strain, 4 * M, double);
+  const ColTable<double*> dst = host_columns(*f), src = state_columns(S);
+  for (int k = 0; k < MIG_NTAB; k++) D2H(dst.p[k], src.p[k], col_width(k) * M, double);
   D2H(f->id, S.id, M, long long); D2H(f->ghost_id, S.ghost_id, M, long long); D2H(f->status, S.status, M, int);
   D2H(f->vert_off, S.voff, M + 1, int);
   if ((f->vx || f->vy) && V > 0) {
@@ -1127,57 +1115,21 @@ int sz_download_floes(sz_ctx* c, sz_floe_columns* f) {
 }
 
 // ---------------------------------------------------------------- Float32 hosts (include/subzero_hip.h: sz_floe_columns_f32)
-#define SZ_F32_SCALARS(X) X(cx) X(cy) X(rmax) X(area) X(height) X(mass) X(moment) X(alpha) X(u) X(v) X(xi) X(p_dxdt) X(p_dydt) X(p_dalphadt) \
-  X(p_dudt) X(p_dvdt) X(p_dxidt) X(fxOA) X(fyOA) X(trqOA) X(hflx_factor) X(overarea) X(coll_fx) X(coll_fy) X(coll_trq)
-#define SZ_F32_TENSORS(X) X(stress_accum) X(stress_instant) X(strain)
+// (widened on the way in, rounded on the way out: F32Up / F32Down, sz_columns.hpp)
 int sz_upload_floes_f32(sz_ctx* c, int64_t M, int64_t N, const sz_floe_columns_f32* f) {
   if (!c || !f || M < 0 || N < 0 || N > M) return SZ_E_ARG;
   if (M > 0 && !f->vert_off) { c->err = "sz_upload_floes_f32: vert_off is required"; return SZ_E_ARG; }
   const size_t V = M > 0 ? (size_t)f->vert_off[M] : 0, NS = (f->sub_off && N > 0) ? (size_t)f->sub_off[N] : 0;
-  std::vector<std::vector<double>> keep;
-  auto widen = [&](const float* src, size_t n) -> double* {
-    if (!src) return nullptr;
-    keep.emplace_back(n ? n : 1);
-    for (size_t k = 0; k < n; k++) keep.back()[k] = (double)src[k];
-    return keep.back().data();
-  };
-  sz_floe_columns d; memset(&d, 0, sizeof(d));
-#define X(name) d.name = widen(f->name, (size_t)M);
-  SZ_F32_SCALARS(X)
-#undef X
-#define X(name) d.name = widen(f->name, (size_t)4 * M);
-  SZ_F32_TENSORS(X)
-#undef X
-  d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
-  d.vx = widen(f->vx, V); d.vy = widen(f->vy, V); d.sx = widen(f->sx, NS); d.sy = widen(f->sy, NS);
-  return sz_upload_floes(c, M, N, &d);
+  const F32Up W(f, (size_t)M, V, NS);
+  return sz_upload_floes(c, M, N, &W.d);
 }
 int sz_download_floes_f32(sz_ctx* c, sz_floe_columns_f32* f) {
   if (!c || !f) return SZ_E_ARG;
   sz_stats st;
   int rc = sz_get_stats(c, &st); if (rc) return rc;
-  const size_t M = (size_t)st.M, V = (size_t)st.n_ring_points, NS = (size_t)st.n_sub_points;
-  std::vector<std::vector<double>> keep;
-  struct Back { float* dst; double* src; size_t n; }; std::vector<Back> back;
-  auto room = [&](float* dst, size_t n) -> double* {
-    if (!dst) return nullptr;
-    keep.emplace_back(n ? n : 1);
-    back.push_back({ dst, keep.back().data(), n });
-    return keep.back().data();
-  };
-  sz_floe_columns d; memset(&d, 0, sizeof(d));
-#define X(name) d.name = room(f->name, M);
-  SZ_F32_SCALARS(X)
-#undef X
-#define X(name) d.name = room(f->name, 4 * M);
-  SZ_F32_TENSORS(X)
-#undef X
-  d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
-  // (sx / sy are not written by a download -- sz_download_subpoints is their way back --, so the caller's buffers are left alone: staging them
-  //  here used to hand zeros back)
-  d.vx = room(f->vx, V); d.vy = room(f->vy, V); d.sx = nullptr; d.sy = nullptr; (void)NS;
-  rc = sz_download_floes(c, &d); if (rc) return rc;
-  for (const Back& b : back) for (size_t k = 0; k < b.n; k++) b.dst[k] = (float)b.src[k];
+  F32Down W(f, (size_t)st.M, (size_t)st.n_ring_points, (size_t)st.n_sub_points, F32_LEAVE_SUB);
+  rc = sz_download_floes(c, &W.d); if (rc) return rc;
+  W.back();
   return SZ_OK;
 }
 int sz_set_fields_f32(sz_ctx* c, int32_t Nx, int32_t Ny, double x0, double xf, double y0, double yf, const float* uocn, const float* vocn,
@@ -2373,12 +2325,11 @@ int rm_move_rows(sz_ctx* c, int N, const RmArgs& A, const RmDev& R) {
   c->gi_pending = false;
   // ---- the rows into their new places, gathered beside the old ones first
   double** d_cols = nullptr; double *d_tmp = nullptr, *d_tsx = nullptr, *d_tsy = nullptr, *d_trows = nullptr; double2* d_tv = nullptr; int *d_torigin = nullptr, *d_tcnt = nullptr;
-  if ((rc = dalloc(c, &d_cols, 32, P)) || (rc = dalloc(c, &d_tmp, (size_t)39 * Nn, P)) || (rc = dalloc(c, &d_tv, (size_t)Vn, P)) || (rc = dalloc(c, &d_tsx, (size_t)NSn, P)) ||
+  if ((rc = dalloc(c, &d_cols, MIG_TAB_CAP, P)) || (rc = dalloc(c, &d_tmp, (size_t)MIG_NGATHER * Nn, P)) || (rc = dalloc(c, &d_tv, (size_t)Vn, P)) || (rc = dalloc(c, &d_tsx, (size_t)NSn, P)) ||
       (rc = dalloc(c, &d_tsy, (size_t)NSn, P)) || (rc = dalloc(c, &d_torigin, (size_t)Nn, P)) || (rc = dalloc(c, &d_tcnt, (size_t)Nn, P)) ||
       (rc = dalloc(c, &d_trows, (size_t)Nn * S.rowcap * 7, P))) return rc;
-  double* const hcols[MIG_NSC + 3] = { S.cx, S.cy, S.rmax, S.area, S.height, S.mass, S.moment, S.alpha, S.u, S.v, S.xi, S.p_dxdt, S.p_dydt, S.p_dalphadt,
-                                       S.p_dudt, S.p_dvdt, S.p_dxidt, S.fxOA, S.fyOA, S.trqOA, S.hflx, S.overarea, S.cfx, S.cfy, S.ctrq, S.sa, S.si, S.strain };
-  HIPCHK(c, hipMemcpyAsync(d_cols, hcols, sizeof(hcols), hipMemcpyHostToDevice, c->stream));
+  const ColTable<double*> hcols = state_columns(S);
+  HIPCHK(c, hipMemcpyAsync(d_cols, hcols.p, sizeof(hcols.p), hipMemcpyHostToDevice, c->stream));
   const int nbw = grid_for((long long)Nn * 64, 256, 4096);
   hipLaunchKernelGGL(sz_k_mig_gather, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, (const double*)nullptr, (const double*)nullptr,
                      (double* const*)d_cols, d_tmp);
@@ -2476,12 +2427,6 @@ int sz_download_origin(sz_ctx* c, int32_t* origin) {
 
 // ---------------------------------------------------------------- rows down, rows back (sz_splice.hpp)
 namespace {
-// the columns the row-moving kernels walk, in the order of a migration record
-void sp_column_table(const State& S, double* out[MIG_NSC + 3]) {
-  double* const t[MIG_NSC + 3] = { S.cx, S.cy, S.rmax, S.area, S.height, S.mass, S.moment, S.alpha, S.u, S.v, S.xi, S.p_dxdt, S.p_dydt, S.p_dalphadt,
-                                   S.p_dudt, S.p_dvdt, S.p_dxidt, S.fxOA, S.fyOA, S.trqOA, S.hflx, S.overarea, S.cfx, S.cfy, S.ctrq, S.sa, S.si, S.strain };
-  for (int k = 0; k < MIG_NSC + 3; k++) out[k] = t[k];
-}
 // rows[0..n): in [0, N), ascending without repeats (sorted) or merely without repeats
 int sp_check_rows(sz_ctx* c, const char* who, const char* what, int n, const int32_t* rows, int N, bool sorted, const char* of = "parents") {
   std::vector<int> tmp;
@@ -2521,7 +2466,7 @@ int sp_download(sz_ctx* c, const char* who, bool list, int32_t n, const int32_t*
   reset_pool(P);
   int *d_rows = nullptr, *d_len = nullptr, *d_off = nullptr; double** d_cols = nullptr; double* d_out = nullptr;
   if (n > 0) {
-    if ((rc = dalloc(c, &d_rows, n1, P)) || (rc = dalloc(c, &d_len, 4 * n1, P)) || (rc = dalloc(c, &d_off, 4 * n1, P)) || (rc = dalloc(c, &d_cols, 32, P))) return rc;
+    if ((rc = dalloc(c, &d_rows, n1, P)) || (rc = dalloc(c, &d_len, 4 * n1, P)) || (rc = dalloc(c, &d_off, 4 * n1, P)) || (rc = dalloc(c, &d_cols, MIG_TAB_CAP, P))) return rc;
     H2D(d_rows, rows, n, int);
     hipLaunchKernelGGL(sz_k_sp_sel_len, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, S, (int)n, (const int*)d_rows, c->pts_N > 0 ? N : 0, list ? N : 0, d_len);
     for (int k = 0; k < 4; k++) scan(c, d_len + k * n1, d_off + k * n1, n, -1, n, -1);
@@ -2538,23 +2483,20 @@ int sp_download(sz_ctx* c, const char* who, bool list, int32_t n, const int32_t*
   if (n == 0) return SZ_OK;
   const size_t total = (size_t)SP_PACK_NCOL * n + 2 * V + 2 * NS + 7 * R + (G + 1) / 2;
   if ((rc = dalloc(c, &d_out, total, P))) return rc;
-  double* hcols[MIG_NSC + 3];
-  sp_column_table(S, hcols);
-  HIPCHK(c, hipMemcpyAsync(d_cols, hcols, sizeof(hcols), hipMemcpyHostToDevice, c->stream));
+  const ColTable<double*> hcols = state_columns(S);
+  HIPCHK(c, hipMemcpyAsync(d_cols, hcols.p, sizeof(hcols.p), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(sz_k_sp_pack, dim3(grid_for((long long)n * 64, 256, 4096)), dim3(256), 0, c->stream, S, (int)n, (const int*)d_rows, (const int*)d_off, (double* const*)d_cols, d_out);
   std::vector<double> out(total);
   HIPCHK(c, hipMemcpyAsync(out.data(), d_out, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  double* const dst[MIG_NSC] = { f->cx, f->cy, f->rmax, f->area, f->height, f->mass, f->moment, f->alpha, f->u, f->v, f->xi, f->p_dxdt, f->p_dydt, f->p_dalphadt,
-                                 f->p_dudt, f->p_dvdt, f->p_dxidt, f->fxOA, f->fyOA, f->trqOA, f->hflx_factor, f->overarea, f->coll_fx, f->coll_fy, f->coll_trq };
-  for (int q = 0; q < MIG_NSC; q++) if (dst[q]) memcpy(dst[q], &out[(size_t)q * n], (size_t)n * sizeof(double));
-  double* const tdst[3] = { f->stress_accum, f->stress_instant, f->strain };
-  for (int t = 0; t < 3; t++) if (tdst[t]) for (int k = 0; k < n; k++) for (int q = 0; q < 4; q++) tdst[t][(size_t)4 * k + q] = out[(size_t)(MIG_NSC + 4 * t + q) * n + k];
+  const ColTable<double*> dst = host_columns(*f);
+  for (int q = 0; q < MIG_NSC; q++) if (dst.p[q]) memcpy(dst.p[q], &out[(size_t)q * n], (size_t)n * sizeof(double));
+  for (int t = 0; t < MIG_NTEN; t++) if (double* td = dst.p[MIG_NSC + t]) for (int k = 0; k < n; k++) for (int q = 0; q < 4; q++) td[(size_t)4 * k + q] = out[(size_t)(MIG_TEN + 4 * t + q) * n + k];
   for (int k = 0; k < n; k++) {
     long long b;
-    if (f->id) { memcpy(&b, &out[(size_t)37 * n + k], 8); f->id[k] = b; }
-    if (f->status) { memcpy(&b, &out[(size_t)38 * n + k], 8); f->status[k] = (int32_t)b; }
-    if (f->ghost_id) { memcpy(&b, &out[(size_t)39 * n + k], 8); f->ghost_id[k] = b; }
+    if (f->id) { memcpy(&b, &out[(size_t)MIG_ID * n + k], 8); f->id[k] = b; }
+    if (f->status) { memcpy(&b, &out[(size_t)MIG_STATUS * n + k], 8); f->status[k] = (int32_t)b; }
+    if (f->ghost_id) { memcpy(&b, &out[(size_t)SP_GHOST_ID * n + k], 8); f->ghost_id[k] = b; }
   }
   const double* ring = out.data() + (size_t)SP_PACK_NCOL * n;
   for (size_t k = 0; k < V; k++) { if (f->vx) f->vx[k] = ring[2 * k]; if (f->vy) f->vy[k] = ring[2 * k + 1]; }
@@ -2680,10 +2622,7 @@ int sp_splice_rows(sz_ctx* c, const std::string& who, bool parents, int32_t n_de
   double staged_rmax = 0.0;
   {
     static const sz_floe_columns none{};
-    const sz_floe_columns& F = f ? *f : none;
-    const double* const src[MIG_NSC] = { F.cx, F.cy, F.rmax, F.area, F.height, F.mass, F.moment, F.alpha, F.u, F.v, F.xi, F.p_dxdt, F.p_dydt, F.p_dalphadt,
-                                         F.p_dudt, F.p_dvdt, F.p_dxidt, F.fxOA, F.fyOA, F.trqOA, F.hflx_factor, F.overarea, F.coll_fx, F.coll_fy, F.coll_trq };
-    const double* const tsrc[3] = { F.stress_accum, F.stress_instant, F.strain };
+    const ColTable<const double*> src = host_columns(f ? *f : none);
     dirs[0] = (double)ns;
     size_t at = 0; int dbelow = 0;
     for (int j = 0; j < ns; j++) {
@@ -2693,16 +2632,16 @@ int sp_splice_rows(sz_ctx* c, const std::string& who, bool parents, int32_t n_de
       if (j < n_rep) { while (dbelow < n_del && del[dbelow] < rep[j]) dbelow++; newrow = rep[j] - dbelow; }
       else newrow = N - n_del + (j - n_rep);
       double* rec = &stream[at];
-      for (int q = 0; q < MIG_NSC; q++) rec[q] = src[q] ? src[q][j] : 0.0;
-      for (int t = 0; t < 3; t++) for (int q = 0; q < 4; q++) rec[MIG_NSC + 4 * t + q] = tsrc[t] ? tsrc[t][(size_t)4 * j + q] : 0.0;
-      rec[37] = (double)(f->id ? f->id[j] : (tile ? tile->staged_num[j] : (long long)newrow) + 1); rec[38] = (double)(f->status ? f->status[j] : SZ_ACTIVE); rec[39] = 0.0;
-      rec[40] = (double)nv; rec[41] = (double)sp;
+      for (int q = 0; q < MIG_NSC; q++) rec[q] = src.p[q] ? src.p[q][j] : 0.0;
+      for (int t = 0; t < MIG_NTEN; t++) for (int q = 0; q < 4; q++) rec[MIG_TEN + 4 * t + q] = src.p[MIG_NSC + t] ? src.p[MIG_NSC + t][(size_t)4 * j + q] : 0.0;
+      rec[MIG_ID] = (double)(f->id ? f->id[j] : (tile ? tile->staged_num[j] : (long long)newrow) + 1); rec[MIG_STATUS] = (double)(f->status ? f->status[j] : SZ_ACTIVE); rec[MIG_GIDX] = 0.0;
+      rec[MIG_NV] = (double)nv; rec[MIG_NS] = (double)sp;
       for (int k = 0; k < nv; k++) { rec[MIG_NCOL + 2 * k] = f->vx[o + k]; rec[MIG_NCOL + 2 * k + 1] = f->vy[o + k]; }
       double* sub = rec + MIG_NCOL + 2 * (size_t)nv;
       for (int k = 0; k < sp; k++) { sub[k] = f->sx[so + k]; sub[sp + k] = f->sy[so + k]; }
       double* e = &dirs[(size_t)MIG_DIR * (1 + (size_t)j)];
-      e[0] = 0.0; e[1] = (double)nv; e[2] = (double)sp; e[3] = (double)at; e[4] = rec[2]; e[5] = rec[0]; e[6] = rec[1];
-      staged_rmax = std::max(staged_rmax, rec[2]);
+      e[0] = 0.0; e[1] = (double)nv; e[2] = (double)sp; e[3] = (double)at; e[4] = rec[COL_rmax]; e[5] = rec[COL_cx]; e[6] = rec[COL_cy];
+      staged_rmax = std::max(staged_rmax, rec[COL_rmax]);
       h_svoff[j + 1] = h_svoff[j] + nv; h_ssoff[j + 1] = h_ssoff[j] + sp; h_sioff[j + 1] = h_sioff[j] + (ioff ? ioff[j + 1] - ioff[j] : 0);
       at += (size_t)MIG_NCOL + 2 * (size_t)nv + 2 * (size_t)sp;
     }
@@ -2749,11 +2688,10 @@ int sp_splice_rows(sz_ctx* c, const std::string& who, bool parents, int32_t n_de
   const int Vn = R.Vn, NSn = R.NSn, tcap = S.rowcap;
   // ---- the rows of the edited list, gathered beside the old ones: kept rows from the list, the others from the stream
   double** d_cols = nullptr; double *d_tmp = nullptr, *d_tsx = nullptr, *d_tsy = nullptr, *d_trows = nullptr; double2* d_tv = nullptr; int* d_tcnt = nullptr;
-  if ((rc = dalloc(c, &d_cols, 32, P)) || (rc = dalloc(c, &d_tmp, (size_t)SP_NCOL * Nn, P)) || (rc = dalloc(c, &d_tv, (size_t)Vn, P)) || (rc = dalloc(c, &d_tsx, (size_t)NSn, P)) ||
+  if ((rc = dalloc(c, &d_cols, MIG_TAB_CAP, P)) || (rc = dalloc(c, &d_tmp, (size_t)SP_NCOL * Nn, P)) || (rc = dalloc(c, &d_tv, (size_t)Vn, P)) || (rc = dalloc(c, &d_tsx, (size_t)NSn, P)) ||
       (rc = dalloc(c, &d_tsy, (size_t)NSn, P)) || (rc = dalloc(c, &d_tcnt, (size_t)Nn, P)) || (rc = dalloc(c, &d_trows, (size_t)Nn * tcap * 7, P))) return rc;
-  double* hcols[MIG_NSC + 3];
-  sp_column_table(S, hcols);
-  HIPCHK(c, hipMemcpyAsync(d_cols, hcols, sizeof(hcols), hipMemcpyHostToDevice, c->stream));
+  ColTable<double*> hcols = state_columns(S);
+  HIPCHK(c, hipMemcpyAsync(d_cols, hcols.p, sizeof(hcols.p), hipMemcpyHostToDevice, c->stream));
   const int nbw = grid_for((long long)Nn * 64, 256, 4096);
   hipLaunchKernelGGL(sz_k_mig_gather, dim3(grid_for(Nn, 256)), dim3(256), 0, c->stream, S, Nn, (const int*)A.src, (const double*)d_dirs, (const double*)d_stream,
                      (double* const*)d_cols, d_tmp);
@@ -2771,8 +2709,9 @@ int sp_splice_rows(sz_ctx* c, const std::string& who, bool parents, int32_t n_de
     // rmax, ids, statuses, offsets: fetched from the gathered rows) and rings / points of zeros --, then the gathered rows are placed as below
     std::vector<double> h3((size_t)3 * Nn), hid((size_t)2 * Nn), zv((size_t)std::max(Vn, 1), 0.0), zs((size_t)std::max(NSn, 1), 0.0);
     std::vector<int> hvoff((size_t)Nn + 1), hsoff((size_t)Nn + 1), hst((size_t)Nn); std::vector<long long> hidl((size_t)Nn);
+    static_assert(COL_cx == 0 && COL_cy == 1 && COL_rmax == 2 && MIG_STATUS == MIG_ID + 1, "fetched as two runs of the gathered columns: cx, cy, rmax and id, status");
     HIPCHK(c, hipMemcpyAsync(h3.data(), d_tmp, h3.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hid.data(), d_tmp + (size_t)37 * Nn, hid.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hid.data(), d_tmp + (size_t)MIG_ID * Nn, hid.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(hvoff.data(), A.nvoff, hvoff.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(hsoff.data(), A.nsoff, hsoff.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2783,8 +2722,8 @@ int sp_splice_rows(sz_ctx* c, const std::string& who, bool parents, int32_t n_de
     if (c->pts_N) { d.sub_off = hsoff.data(); d.sx = zs.data(); d.sy = zs.data(); }
     if ((rc = sz_upload_floes(c, Nn, Nn, &d))) return rc;
     if (S.rowcap < tcap) { S.rowcap = tcap; if ((rc = carve_interactions(c))) return rc; }      // (a kept floe may hold more rows than a fresh stride)
-    sp_column_table(S, hcols);
-    HIPCHK(c, hipMemcpyAsync(d_cols, hcols, sizeof(hcols), hipMemcpyHostToDevice, c->stream));
+    hcols = state_columns(S);
+    HIPCHK(c, hipMemcpyAsync(d_cols, hcols.p, sizeof(hcols.p), hipMemcpyHostToDevice, c->stream));
     gl_est = c->gl_est; rmax_max = c->rmax_max; rmax_hint = 0.0;          // (the upload's own, of the edited list)
   } else if (NSn > S.capS) {          // the sub-floe points have no slack at upload: a new pair, as for a tile that gained points in a migration
     old_sub = c->sub_allocs; c->sub_allocs = Pool();
@@ -2829,55 +2768,13 @@ int sz_splice_parents(sz_ctx* c, int32_t n_del, const int32_t* del, int32_t n_re
 namespace {
 using sp_download_fn = int (*)(sz_ctx*, int32_t, const int32_t*, sz_floe_columns*, int32_t*, double*, int64_t*);
 using sp_splice_fn = int (*)(sz_ctx*, int32_t, const int32_t*, int32_t, const int32_t*, int32_t, const sz_floe_columns*, const int32_t*, const double*);
-// Float64 room for the n rows a download brings (sz: the sizes its sizing call gave): d and ir go to the Float64 call, back() rounds into f
-struct SpF32Down {
-  std::vector<std::vector<double>> keep;
-  struct Back { float* dst; double* src; size_t n; }; std::vector<Back> todo;
-  sz_floe_columns d; double* ir;
-  SpF32Down(size_t M, const int64_t* sz, sz_floe_columns_f32* f, float* inter_rows) {
-    const size_t V = (size_t)sz[0], NS = (size_t)sz[1], R = (size_t)sz[2];
-    memset(&d, 0, sizeof(d));
-#define X(name) d.name = room(f->name, M);
-    SZ_F32_SCALARS(X)
-#undef X
-#define X(name) d.name = room(f->name, 4 * M);
-    SZ_F32_TENSORS(X)
-#undef X
-    d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
-    d.vx = room(f->vx, V); d.vy = room(f->vy, V); d.sx = room(f->sx, NS); d.sy = room(f->sy, NS);
-    ir = room(inter_rows, 7 * R);
-  }
-  double* room(float* dst, size_t cnt) {
-    if (!dst) return nullptr;
-    keep.emplace_back(cnt ? cnt : 1);
-    todo.push_back({ dst, keep.back().data(), cnt });
-    return keep.back().data();
-  }
-  void back() const { for (const Back& b : todo) for (size_t k = 0; k < b.n; k++) b.dst[k] = (float)b.src[k]; }
+// Float64 room for the n rows a download brings (sz: the sizes its sizing call gave -- ring points, sub-floe points, interaction rows)
+struct SpF32Down : F32Down {
+  SpF32Down(size_t n, const int64_t* sz, sz_floe_columns_f32* f, float* inter_rows) : F32Down(f, n, (size_t)sz[0], (size_t)sz[1], F32_STAGE_SUB, inter_rows, 7 * (size_t)sz[2]) {}
 };
-// the M = n_rep + n_app uploaded floes of a splice, widened: d and ir go to the Float64 call
-struct SpF32Up {
-  std::vector<std::vector<double>> keep;
-  sz_floe_columns d; const double* ir;
-  SpF32Up(size_t M, const sz_floe_columns_f32* f, const int32_t* ioff, const float* irows) {
-    const size_t V = (size_t)f->vert_off[M], NS = f->sub_off ? (size_t)f->sub_off[M] : 0, R = ioff ? (size_t)ioff[M] : 0;
-    memset(&d, 0, sizeof(d));
-#define X(name) d.name = widen(f->name, M);
-    SZ_F32_SCALARS(X)
-#undef X
-#define X(name) d.name = widen(f->name, 4 * M);
-    SZ_F32_TENSORS(X)
-#undef X
-    d.id = f->id; d.ghost_id = f->ghost_id; d.status = f->status; d.vert_off = f->vert_off; d.sub_off = f->sub_off; d.ghost_off = f->ghost_off; d.ghost_idx = f->ghost_idx;
-    d.vx = widen(f->vx, V); d.vy = widen(f->vy, V); d.sx = widen(f->sx, NS); d.sy = widen(f->sy, NS);
-    ir = widen(irows, 7 * R);
-  }
-  double* widen(const float* src, size_t cnt) {
-    if (!src) return nullptr;
-    keep.emplace_back(cnt ? cnt : 1);
-    for (size_t k = 0; k < cnt; k++) keep.back()[k] = (double)src[k];
-    return keep.back().data();
-  }
+// the M = n_rep + n_app uploaded floes of a splice, widened
+struct SpF32Up : F32Up {
+  SpF32Up(size_t M, const sz_floe_columns_f32* f, const int32_t* ioff, const float* irows) : F32Up(f, M, (size_t)f->vert_off[M], f->sub_off ? (size_t)f->sub_off[M] : 0, irows, ioff ? 7 * (size_t)ioff[M] : 0) {}
 };
 int sp_download_f32(sp_download_fn down, sz_ctx* c, int32_t n, const int32_t* rows, sz_floe_columns_f32* f, int32_t* inter_off, float* inter_rows, int64_t* sizes3) {
   if (!c || n < 0) return SZ_E_ARG;
@@ -3148,7 +3045,7 @@ int sz_debug_next_segment(int32_t tstep, int32_t remaining, int32_t rr_dt, int32
   out4[0] = g.rr_step; out4[1] = g.len; out4[2] = g.fstep; out4[3] = g.weld_set;
   return SZ_OK;
 }
-
+const char* sz_debug_column_names(void) { return COLUMN_NAMES + 1; }
 
 int sz_profile_enable(sz_ctx* c, int32_t on) {
   if (!c) return SZ_E_ARG;

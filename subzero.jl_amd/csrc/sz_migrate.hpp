@@ -6,19 +6,18 @@
 //     [0]                    number of records R
 //     [1 .. 1 + MIG_DIR R)   directory: per record {global index, ring points, sub-floe points, offset of the record in the stream,
 //                                                   rmax, cx, cy, -}
-//     records                MIG_NCOL doubles (25 scalar columns, stress_accum / stress_instant / strain, id, status, global index,
-//                            ring points, sub-floe points), the ring as {x, y} pairs, the sub-floe points x.. then y..
+//     records                MIG_NCOL doubles (sz_columns.hpp: the MIG_NSC scalar columns, the tensors from MIG_TEN, then the slots MIG_ID,
+//                            MIG_STATUS, MIG_GIDX, MIG_NV, MIG_NS), the ring as {x, y} pairs, the sub-floe points x.. then y..
 // The receiver merges the directories of all streams (sz_k_mig_dirs) -- the only part the host reads -- builds the new row order
 // (kept and received floes by global index, as the single context holds them), and the rows are gathered on the device into
 // that order (sz_k_mig_gather, sz_k_mig_points), kept floes from the old rows and received ones from the streams.
 #pragma once
+#include "sz_columns.hpp"
 #include "sz_kernels.hpp"
 
 namespace sz {
 
-constexpr int MIG_NSC = 25;                 // scalar columns of a record, in the order of mig_column_table()
-constexpr int MIG_NCOL = MIG_NSC + 12 + 5;  // + three 2 x 2 tensors, id, status, global index, ring points, sub-floe points
-constexpr int MIG_DIR = 8;
+constexpr int MIG_DIR = 8;                  // doubles of a directory entry (the record itself: sz_columns.hpp)
 
 // who owns floe i now: the tile that holds the centroid (periodic: of its image inside the domain), px x py tiles over the domain.
 // tally[2 d], tally[2 d + 1]: movers to rank d and the doubles of their records
@@ -47,7 +46,7 @@ __global__ void sz_k_mig_owner(State S, int N, const int* owner_override, double
 
 // one wavefront per mover: its record into the stream of its destination.  base[d]: start of stream d in `send`; cntd[d]: records of
 // stream d (the directory's length); cur[2 d], cur[2 d + 1]: next directory entry, next record offset behind the directory.
-// cols: the MIG_NSC scalar columns, then stress_accum, stress_instant, strain.
+// cols: the device copy of state_columns(S).
 __global__ void sz_k_mig_pack(State S, int N, const int* owner, int me, double* send, const long long* base, const int* cntd, unsigned long long* cur,
                               double* const* cols) {
   const int lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
@@ -66,12 +65,12 @@ __global__ void sz_k_mig_pack(State S, int N, const int* owner, int me, double* 
     const size_t off = 1 + (size_t)MIG_DIR * cntd[d] + (((size_t)ohi << 32) | olo);
     double* rec = st + off;
     if (lane < MIG_NSC) rec[lane] = cols[lane][i];
-    else if (lane < MIG_NSC + 12) { const int t = (lane - MIG_NSC) >> 2, q = (lane - MIG_NSC) & 3; rec[lane] = cols[MIG_NSC + t][(size_t)4 * i + q]; }
-    else if (lane == 37) rec[37] = (double)S.id[i];
-    else if (lane == 38) rec[38] = (double)S.status[i];
-    else if (lane == 39) rec[39] = (double)S.okey[i];
-    else if (lane == 40) rec[40] = (double)nv;
-    else if (lane == 41) rec[41] = (double)ns;
+    else if (lane < MIG_ID) { const int t = (lane - MIG_TEN) >> 2, q = (lane - MIG_TEN) & 3; rec[lane] = cols[MIG_NSC + t][(size_t)4 * i + q]; }
+    else if (lane == MIG_ID) rec[MIG_ID] = (double)S.id[i];
+    else if (lane == MIG_STATUS) rec[MIG_STATUS] = (double)S.status[i];
+    else if (lane == MIG_GIDX) rec[MIG_GIDX] = (double)S.okey[i];
+    else if (lane == MIG_NV) rec[MIG_NV] = (double)nv;
+    else if (lane == MIG_NS) rec[MIG_NS] = (double)ns;
     const double* ring = (const double*)(S.vxy + vo);
     for (int k = lane; k < 2 * nv; k += 64) rec[MIG_NCOL + k] = ring[k];
     double* sub = rec + MIG_NCOL + 2 * nv;
@@ -118,17 +117,17 @@ __global__ void __launch_bounds__(256) sz_k_mig_dirs(const double* recv, const l
 }
 
 // new row r <- old row src[r] (>= 0) or received record -src[r] - 1 of the directory table: the columns into tmp[k * Nn + r]
-// (k < 39: the record's first 39 doubles)
+// (k < MIG_NGATHER: the record up to its status)
 __global__ void sz_k_mig_gather(State S, int Nn, const int* src, const double* dirs, const double* recv, double* const* cols, double* tmp) {
   for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < Nn; r += gridDim.x * blockDim.x) {
     const int s = src[r];
     if (s >= 0) {
       for (int k = 0; k < MIG_NSC; k++) tmp[(size_t)k * Nn + r] = cols[k][s];
-      for (int t = 0; t < 3; t++) for (int q = 0; q < 4; q++) tmp[(size_t)(MIG_NSC + 4 * t + q) * Nn + r] = cols[MIG_NSC + t][(size_t)4 * s + q];
-      tmp[(size_t)37 * Nn + r] = (double)S.id[s]; tmp[(size_t)38 * Nn + r] = (double)S.status[s];
+      for (int t = 0; t < MIG_NTEN; t++) for (int q = 0; q < 4; q++) tmp[(size_t)(MIG_TEN + 4 * t + q) * Nn + r] = cols[MIG_NSC + t][(size_t)4 * s + q];
+      tmp[(size_t)MIG_ID * Nn + r] = (double)S.id[s]; tmp[(size_t)MIG_STATUS * Nn + r] = (double)S.status[s];
     } else {
       const double* b = recv + (size_t)dirs[(size_t)MIG_DIR * (size_t)(-s) + 3];         // entry e = -s - 1 lives at MIG_DIR (1 + e)
-      for (int k = 0; k < 39; k++) tmp[(size_t)k * Nn + r] = b[k];
+      for (int k = 0; k < MIG_NGATHER; k++) tmp[(size_t)k * Nn + r] = b[k];
     }
   }
 }
@@ -136,8 +135,8 @@ __global__ void sz_k_mig_gather(State S, int Nn, const int* src, const double* d
 __global__ void sz_k_mig_scatter(State S, int Nn, double* const* cols, const double* tmp) {
   for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < Nn; r += gridDim.x * blockDim.x) {
     for (int k = 0; k < MIG_NSC; k++) cols[k][r] = tmp[(size_t)k * Nn + r];
-    for (int t = 0; t < 3; t++) for (int q = 0; q < 4; q++) cols[MIG_NSC + t][(size_t)4 * r + q] = tmp[(size_t)(MIG_NSC + 4 * t + q) * Nn + r];
-    S.id[r] = (long long)tmp[(size_t)37 * Nn + r]; S.status[r] = (int)tmp[(size_t)38 * Nn + r];
+    for (int t = 0; t < MIG_NTEN; t++) for (int q = 0; q < 4; q++) cols[MIG_NSC + t][(size_t)4 * r + q] = tmp[(size_t)(MIG_TEN + 4 * t + q) * Nn + r];
+    S.id[r] = (long long)tmp[(size_t)MIG_ID * Nn + r]; S.status[r] = (int)tmp[(size_t)MIG_STATUS * Nn + r];
     S.ghost_id[r] = 0; S.parent[r] = r; S.ngh[r] = 0; S.frc_remove[r] = 0;
     for (int q = 0; q < MAX_GHOSTS; q++) S.gh[r * MAX_GHOSTS + q] = -1;
   }

@@ -25,8 +25,7 @@
 namespace sz {
 
 constexpr int SP_MAX_RING = 255;      // ring points of a spliced floe: what the collision record (State::crec, 8 bits) and a halo record carry
-constexpr int SP_NCOL = 39;           // doubles per row the column gather moves (the first 39 of a migration record: 25 scalars, 3 tensors, id, status)
-constexpr int SP_PACK_NCOL = 40;      // doubles per row of sz_download_rows' staging buffer: those, and ghost_id
+// (SP_NCOL, the doubles per row the column gather moves, and SP_PACK_NCOL, those of sz_download_rows' staging buffer -- ghost_id at SP_GHOST_ID --: sz_columns.hpp)
 
 struct SpDev {
   int Nn, Vn, NSn;                    // sz_k_sp_rows: rows, ring points and sub-floe points of the edited list
@@ -76,7 +75,7 @@ __global__ void __launch_bounds__(256) sz_k_sp_rows(SpArgs A) {
   }
 }
 
-// dirs / recv: the staged stream as sz_k_mig_gather reads it (record -s - 1 of the directory; its status is double 38)
+// dirs / recv: the staged stream as sz_k_mig_gather reads it (record -s - 1 of the directory; its status is double MIG_STATUS)
 __global__ void __launch_bounds__(256) sz_k_sp_limits(State S, SpArgs A, int Nn, const double* dirs, const double* recv) {
   const int lane = threadIdx.x & 63;
   for (int r0 = blockIdx.x * blockDim.x; r0 < Nn; r0 += gridDim.x * blockDim.x) {
@@ -85,7 +84,7 @@ __global__ void __launch_bounds__(256) sz_k_sp_limits(State S, SpArgs A, int Nn,
     if (r < Nn) {
       const int s = A.src[r];
       nv = A.nvoff[r + 1] - A.nvoff[r]; ns = A.nsoff[r + 1] - A.nsoff[r];
-      const int st = s >= 0 ? S.status[s] : (int)recv[(size_t)dirs[(size_t)MIG_DIR * (size_t)(-s) + 3] + 38];
+      const int st = s >= 0 ? S.status[s] : (int)recv[(size_t)dirs[(size_t)MIG_DIR * (size_t)(-s) + 3] + MIG_STATUS];
       tagged = st != SZ_ACTIVE;
     }
     for (int d = 32; d >= 1; d >>= 1) { nv = max(nv, __shfl_xor(nv, d)); ns = max(ns, __shfl_xor(ns, d)); }
@@ -145,7 +144,7 @@ __global__ void __launch_bounds__(256) sz_k_sp_scatter_rows(State S, int Nn, int
 __global__ void __launch_bounds__(256) sz_k_sp_clear_rows(int from, int to, double* const* cols) {
   for (int r = from + blockIdx.x * blockDim.x + threadIdx.x; r < to; r += gridDim.x * blockDim.x) {
     for (int k = 0; k < MIG_NSC; k++) cols[k][r] = 0.0;
-    for (int t = 0; t < 3; t++) for (int q = 0; q < 4; q++) cols[MIG_NSC + t][(size_t)4 * r + q] = 0.0;
+    for (int t = 0; t < MIG_NTEN; t++) for (int q = 0; q < 4; q++) cols[MIG_NSC + t][(size_t)4 * r + q] = 0.0;
   }
 }
 
@@ -165,7 +164,7 @@ __global__ void __launch_bounds__(256) sz_k_sp_sel_len(State S, int n, const int
 // The staging buffer, in doubles: [0, SP_PACK_NCOL n) the columns (column q of selected row k at q n + k; id, status and ghost_id as bits in a double's place),
 // then the rings as {x, y} pairs, the sub-floe points x.. and y.., the interaction rows, and last the ghost lists as 32-bit list numbers (two to a
 // double's place); off: the scanned lengths (4 x (n + 1)).
-// cols: the MIG_NSC scalar columns, then stress_accum, stress_instant, strain.
+// cols: the device copy of state_columns(S).
 __global__ void __launch_bounds__(256) sz_k_sp_pack(State S, int n, const int* rows, const int* off, double* const* cols, double* out) {
   const int lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
   const int* voff = off; const int* soff = off + (n + 1); const int* ioff = off + 2 * (n + 1); const int* goff = off + 3 * (n + 1);
@@ -176,10 +175,10 @@ __global__ void __launch_bounds__(256) sz_k_sp_pack(State S, int n, const int* r
   for (int k = wave; k < n; k += nw) {
     const int i = rows[k];
     if (lane < MIG_NSC) out[(size_t)lane * n + k] = cols[lane][i];
-    else if (lane < MIG_NSC + 12) { const int t = (lane - MIG_NSC) >> 2, q = (lane - MIG_NSC) & 3; out[(size_t)lane * n + k] = cols[MIG_NSC + t][(size_t)4 * i + q]; }
-    else if (lane == 37) out[(size_t)37 * n + k] = __longlong_as_double(S.id[i]);
-    else if (lane == 38) out[(size_t)38 * n + k] = __longlong_as_double((long long)S.status[i]);
-    else if (lane == 39) out[(size_t)39 * n + k] = __longlong_as_double(S.ghost_id[i]);
+    else if (lane < MIG_ID) { const int t = (lane - MIG_TEN) >> 2, q = (lane - MIG_TEN) & 3; out[(size_t)lane * n + k] = cols[MIG_NSC + t][(size_t)4 * i + q]; }
+    else if (lane == MIG_ID) out[(size_t)MIG_ID * n + k] = __longlong_as_double(S.id[i]);
+    else if (lane == MIG_STATUS) out[(size_t)MIG_STATUS * n + k] = __longlong_as_double((long long)S.status[i]);
+    else if (lane == SP_GHOST_ID) out[(size_t)SP_GHOST_ID * n + k] = __longlong_as_double(S.ghost_id[i]);
     const int vo = S.voff[i], nv = voff[k + 1] - voff[k], ns = soff[k + 1] - soff[k], ni = (ioff[k + 1] - ioff[k]) * 7, ng = goff[k + 1] - goff[k];
     const int po = ns > 0 ? S.soff[i] : 0;
     const double* from = (const double*)(S.vxy + vo);

@@ -407,7 +407,7 @@ int tile_migrate_device(sz_ctx* c, int px, int py, const int32_t* owner_override
   unsigned long long *d_tally = nullptr, *d_cur = nullptr; long long *d_base = nullptr, *d_rbase = nullptr, *d_rsize = nullptr; double** d_cols = nullptr;
   if ((rc = dalloc(c, &d_owner, (size_t)N + 1, pool.v)) || (rc = dalloc(c, &d_tally, 128, pool.v)) || (rc = dalloc(c, &d_cur, 128, pool.v)) ||
       (rc = dalloc(c, &d_base, 64, pool.v)) || (rc = dalloc(c, &d_rbase, 64, pool.v)) || (rc = dalloc(c, &d_rsize, 64, pool.v)) ||
-      (rc = dalloc(c, &d_cntd, 64, pool.v)) || (rc = dalloc(c, &d_bad, 1, pool.v)) || (rc = dalloc(c, &d_cols, 32, pool.v))) return rc;
+      (rc = dalloc(c, &d_cntd, 64, pool.v)) || (rc = dalloc(c, &d_bad, 1, pool.v)) || (rc = dalloc(c, &d_cols, MIG_TAB_CAP, pool.v))) return rc;
   if (owner_override) {
     if ((rc = dalloc(c, &d_override, (size_t)N + 1, pool.v))) return rc;
     if (N) HIPCHK(c, hipMemcpyAsync(d_override, owner_override, (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -439,9 +439,8 @@ int tile_migrate_device(sz_ctx* c, int px, int py, const int32_t* owner_override
   if (too_long) { for (int d = 0; d < n; d++) { mine[d] = 0; cntd[d] = 0; } ts = 0; }      // (says so in the agreement below; nothing is sent)
   double* d_sendb = nullptr;
   if ((rc = dalloc(c, &d_sendb, ts, pool.v))) return rc;
-  double* const hcols[MIG_NSC + 3] = { S.cx, S.cy, S.rmax, S.area, S.height, S.mass, S.moment, S.alpha, S.u, S.v, S.xi, S.p_dxdt, S.p_dydt, S.p_dalphadt,
-                                       S.p_dudt, S.p_dvdt, S.p_dxidt, S.fxOA, S.fyOA, S.trqOA, S.hflx, S.overarea, S.cfx, S.cfy, S.ctrq, S.sa, S.si, S.strain };
-  HIPCHK(c, hipMemcpyAsync(d_cols, hcols, sizeof(hcols), hipMemcpyHostToDevice, c->stream));
+  const ColTable<double*> hcols = state_columns(S);
+  HIPCHK(c, hipMemcpyAsync(d_cols, hcols.p, sizeof(hcols.p), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_base, base.data(), 64 * sizeof(long long), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_cntd, cntd.data(), 64 * sizeof(int), hipMemcpyHostToDevice, c->stream));
   if (ts) hipLaunchKernelGGL(sz_k_mig_pack, dim3(grid_for((long long)N * 64, 256, 2048)), dim3(256), 0, c->stream, S, N, (const int*)d_owner, me, d_sendb,
@@ -516,7 +515,7 @@ int tile_migrate_device(sz_ctx* c, int px, int py, const int32_t* owner_override
   // ---- the rows into their new order: gathered beside the old ones first (a row's source may lie on either side of it)
   int *d_src = nullptr, *d_nvoff = nullptr, *d_nsoff = nullptr; double *d_tmp = nullptr, *d_tsx = nullptr, *d_tsy = nullptr; double2* d_tv = nullptr;
   if ((rc = dalloc(c, &d_src, (size_t)Nn + 1, pool.v)) || (rc = dalloc(c, &d_nvoff, (size_t)Nn + 1, pool.v)) || (rc = dalloc(c, &d_nsoff, (size_t)Nn + 1, pool.v)) ||
-      (rc = dalloc(c, &d_tmp, (size_t)39 * Nn, pool.v)) || (rc = dalloc(c, &d_tv, (size_t)Vn, pool.v)) ||
+      (rc = dalloc(c, &d_tmp, (size_t)MIG_NGATHER * Nn, pool.v)) || (rc = dalloc(c, &d_tv, (size_t)Vn, pool.v)) ||
       (rc = dalloc(c, &d_tsx, (size_t)NSn, pool.v)) || (rc = dalloc(c, &d_tsy, (size_t)NSn, pool.v))) return rc;
   HIPCHK(c, hipMemcpyAsync(d_src, hsrc.data(), (size_t)Nn * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_nvoff, nvoff.data(), ((size_t)Nn + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -559,14 +558,13 @@ int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_ov
   int rc;
   const int N = c->hostN;
   // ---- the tile's state on the host
-  double* const dcol[25] = { S.cx, S.cy, S.rmax, S.area, S.height, S.mass, S.moment, S.alpha, S.u, S.v, S.xi, S.p_dxdt, S.p_dydt, S.p_dalphadt, S.p_dudt, S.p_dvdt, S.p_dxidt,
-                             S.fxOA, S.fyOA, S.trqOA, S.hflx, S.overarea, S.cfx, S.cfy, S.ctrq };
-  std::vector<std::vector<double>> col(25, std::vector<double>((size_t)N));
-  std::vector<double> ten[3] = { std::vector<double>((size_t)4 * N), std::vector<double>((size_t)4 * N), std::vector<double>((size_t)4 * N) };
+  const ColTable<double*> dcol = state_columns(S);
+  std::vector<std::vector<double>> col(MIG_NTAB);
   std::vector<long long> id((size_t)N); std::vector<int> status((size_t)N), voff((size_t)N + 1), soff((size_t)N + 1);
-  for (int k = 0; k < 25; k++) if (N) HIPCHK(c, hipMemcpy(col[k].data(), dcol[k], (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-  double* const dten[3] = { S.sa, S.si, S.strain };
-  for (int k = 0; k < 3; k++) if (N) HIPCHK(c, hipMemcpy(ten[k].data(), dten[k], (size_t)4 * N * sizeof(double), hipMemcpyDeviceToHost));
+  for (int k = 0; k < MIG_NTAB; k++) {
+    col[k].resize(col_width(k) * N);
+    if (N) HIPCHK(c, hipMemcpy(col[k].data(), dcol.p[k], col[k].size() * sizeof(double), hipMemcpyDeviceToHost));
+  }
   if (N) { HIPCHK(c, hipMemcpy(id.data(), S.id, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost)); HIPCHK(c, hipMemcpy(status.data(), S.status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost)); }
   HIPCHK(c, hipMemcpy(voff.data(), S.voff, ((size_t)N + 1) * sizeof(int), hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(soff.data(), S.soff, ((size_t)N + 1) * sizeof(int), hipMemcpyDeviceToHost));
@@ -583,23 +581,26 @@ int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_ov
   std::vector<int> owner((size_t)N);
   for (int i = 0; i < N; i++) {
     if (owner_override) { owner[i] = owner_override[i]; if (owner[i] < 0 || owner[i] >= n) { c->err = "sz_tile_migrate: owner out of range"; return SZ_E_ARG; } continue; }
-    double x = col[0][i] - x0, y = col[1][i] - y0;
+    double x = col[COL_cx][i] - x0, y = col[COL_cy][i] - y0;
     if (c->tile_per_x) { x = std::fmod(x, Lx); if (x < 0) x += Lx; }
     if (c->tile_per_y) { y = std::fmod(y, Ly); if (y < 0) y += Ly; }
     const int ix = std::max(0, std::min(px - 1, (int)(x / Lx * px))), iy = std::max(0, std::min(py - 1, (int)(y / Ly * py)));
     owner[i] = iy * px + ix;
   }
-  // ---- movers, one stream of doubles per destination: MIG_NCOL scalars, then ring x / y, then sub-floe points x / y of every floe
+  // ---- movers, one stream of doubles per destination: the MIG_NCOL doubles of a record (sz_columns.hpp), then ring x.. / y.., then sub-floe points
+  // x.. / y.. of every floe
   std::vector<std::vector<double>> sendv(n), recvv;
   int nmove = 0;
   for (int i = 0; i < N; i++) {
     if (owner[i] == me) continue;
     nmove++;
     std::vector<double>& b = sendv[owner[i]];
-    for (int k = 0; k < 25; k++) b.push_back(col[k][i]);
-    for (int k = 0; k < 3; k++) for (int q = 0; q < 4; q++) b.push_back(ten[k][(size_t)4 * i + q]);
     const int nv = voff[i + 1] - voff[i], ns = soff[i + 1] - soff[i];
-    b.push_back((double)id[i]); b.push_back((double)status[i]); b.push_back((double)c->tile_gidx[i]); b.push_back((double)nv); b.push_back((double)ns);
+    double rec[MIG_NCOL];
+    for (int k = 0; k < MIG_NSC; k++) rec[k] = col[k][i];
+    for (int t = 0; t < MIG_NTEN; t++) for (int q = 0; q < 4; q++) rec[MIG_TEN + 4 * t + q] = col[MIG_NSC + t][(size_t)4 * i + q];
+    rec[MIG_ID] = (double)id[i]; rec[MIG_STATUS] = (double)status[i]; rec[MIG_GIDX] = (double)c->tile_gidx[i]; rec[MIG_NV] = (double)nv; rec[MIG_NS] = (double)ns;
+    b.insert(b.end(), rec, rec + MIG_NCOL);
     b.insert(b.end(), vx.begin() + voff[i], vx.begin() + voff[i + 1]); b.insert(b.end(), vy.begin() + voff[i], vy.begin() + voff[i + 1]);
     b.insert(b.end(), sx.begin() + soff[i], sx.begin() + soff[i + 1]); b.insert(b.end(), sy.begin() + soff[i], sy.begin() + soff[i + 1]);
   }
@@ -617,16 +618,16 @@ int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_ov
     const std::vector<double>& b = recvv[s2];
     for (size_t at = 0; at < b.size();) {
       if (at + MIG_NCOL > b.size()) { c->err = "sz_tile_migrate: truncated record"; return SZ_E_STATE; }
-      const int nv = (int)b[at + 40], ns = (int)b[at + 41];
-      src.push_back({ (long long)b[at + 39], s2, at });
+      const int nv = (int)b[at + MIG_NV], ns = (int)b[at + MIG_NS];
+      src.push_back({ (long long)b[at + MIG_GIDX], s2, at });
       at += (size_t)MIG_NCOL + 2 * (size_t)nv + 2 * (size_t)ns;
     }
   }
   std::sort(src.begin(), src.end(), [](const Src& a, const Src& b2) { return a.g < b2.g; });
   const int Nn = (int)src.size();
   if (Nn == 0) { c->err = "sz_tile_migrate: a tile without floes (every rank must own at least one)"; return SZ_E_STATE; }
-  std::vector<std::vector<double>> ncol(25, std::vector<double>((size_t)Nn));
-  std::vector<double> nten[3] = { std::vector<double>((size_t)4 * Nn), std::vector<double>((size_t)4 * Nn), std::vector<double>((size_t)4 * Nn) };
+  std::vector<std::vector<double>> ncol(MIG_NTAB);
+  for (int k = 0; k < MIG_NTAB; k++) ncol[k].resize(col_width(k) * Nn);
   std::vector<long long> nid((size_t)Nn), ngid((size_t)Nn); std::vector<int> nstatus((size_t)Nn), nvoff((size_t)Nn + 1, 0), nsoff((size_t)Nn + 1, 0);
   std::vector<double> nvx, nvy, nsx, nsy;
   for (int r = 0; r < Nn; r++) {
@@ -634,17 +635,16 @@ int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_ov
     ngid[r] = q.g;
     if (q.from < 0) {
       const size_t i = q.at;
-      for (int k = 0; k < 25; k++) ncol[k][r] = col[k][i];
-      for (int k = 0; k < 3; k++) for (int t = 0; t < 4; t++) nten[k][(size_t)4 * r + t] = ten[k][4 * i + t];
+      for (int k = 0; k < MIG_NTAB; k++) std::copy_n(&col[k][col_width(k) * i], col_width(k), &ncol[k][col_width(k) * r]);
       nid[r] = id[i]; nstatus[r] = status[i];
       nvx.insert(nvx.end(), vx.begin() + voff[i], vx.begin() + voff[i + 1]); nvy.insert(nvy.end(), vy.begin() + voff[i], vy.begin() + voff[i + 1]);
       nsx.insert(nsx.end(), sx.begin() + soff[i], sx.begin() + soff[i + 1]); nsy.insert(nsy.end(), sy.begin() + soff[i], sy.begin() + soff[i + 1]);
     } else {
       const double* b = recvv[q.from].data() + q.at;
-      for (int k = 0; k < 25; k++) ncol[k][r] = b[k];
-      for (int k = 0; k < 3; k++) for (int t = 0; t < 4; t++) nten[k][(size_t)4 * r + t] = b[25 + 4 * k + t];
-      nid[r] = (long long)b[37]; nstatus[r] = (int)b[38];
-      const int nv = (int)b[40], ns = (int)b[41];
+      for (int k = 0; k < MIG_NSC; k++) ncol[k][r] = b[k];
+      for (int t = 0; t < MIG_NTEN; t++) std::copy_n(b + MIG_TEN + 4 * t, 4, &ncol[MIG_NSC + t][(size_t)4 * r]);
+      nid[r] = (long long)b[MIG_ID]; nstatus[r] = (int)b[MIG_STATUS];
+      const int nv = (int)b[MIG_NV], ns = (int)b[MIG_NS];
       const double* p = b + MIG_NCOL;
       nvx.insert(nvx.end(), p, p + nv); nvy.insert(nvy.end(), p + nv, p + 2 * nv);
       p += 2 * (size_t)nv;
@@ -657,11 +657,8 @@ int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_ov
   // ---- rebuild through the upload path, then the tile set-up again
   const Retile tiling(c);
   sz_floe_columns f; memset(&f, 0, sizeof(f));
-  f.cx = ncol[0].data(); f.cy = ncol[1].data(); f.rmax = ncol[2].data(); f.area = ncol[3].data(); f.height = ncol[4].data(); f.mass = ncol[5].data(); f.moment = ncol[6].data();
-  f.alpha = ncol[7].data(); f.u = ncol[8].data(); f.v = ncol[9].data(); f.xi = ncol[10].data(); f.p_dxdt = ncol[11].data(); f.p_dydt = ncol[12].data(); f.p_dalphadt = ncol[13].data();
-  f.p_dudt = ncol[14].data(); f.p_dvdt = ncol[15].data(); f.p_dxidt = ncol[16].data(); f.fxOA = ncol[17].data(); f.fyOA = ncol[18].data(); f.trqOA = ncol[19].data();
-  f.hflx_factor = ncol[20].data(); f.overarea = ncol[21].data(); f.coll_fx = ncol[22].data(); f.coll_fy = ncol[23].data(); f.coll_trq = ncol[24].data();
-  f.stress_accum = nten[0].data(); f.stress_instant = nten[1].data(); f.strain = nten[2].data();
+  const ColTable<double**> fcol = host_column_slots(f);
+  for (int k = 0; k < MIG_NTAB; k++) *fcol.p[k] = ncol[k].data();
   f.id = (int64_t*)nid.data(); f.status = nstatus.data(); f.vert_off = nvoff.data(); f.vx = nvx.data(); f.vy = nvy.data(); f.sub_off = nsoff.data(); f.sx = nsx.data(); f.sy = nsy.data();
   if ((rc = sz_upload_floes(c, Nn, Nn, &f))) return rc;
   c->inter_lost = false; c->inter_any = true;
@@ -859,11 +856,8 @@ struct SptSubset {
       for (size_t k = 0; k < m; k++) for (int q = 0; q < w; q++) keep.back()[k * w + q] = src[(size_t)sel[k] * w + q];
       return keep.back().data();
     };
-#define X(name) f.name = pick(a->name, 1);
-    SZ_F32_SCALARS(X)
-#undef X
-#define X(name) f.name = pick(a->name, 4);
-    SZ_F32_TENSORS(X)
+#define X(host, state) f.host = pick(a->host, (int)col_width(COL_##host));
+    SZ_ALL_COLUMNS(X)
 #undef X
     if (a->id) { for (int j : sel) id.push_back(a->id[j]); f.id = id.data(); }
     if (a->status) { for (int j : sel) status.push_back(a->status[j]); f.status = status.data(); }
