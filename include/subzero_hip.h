@@ -749,6 +749,48 @@ int sz_eulerian_finish(sz_ctx *ctx, int32_t nx, int32_t ny, const double *xg, co
                        int32_t nout, const int32_t *outputs, double *data);
 int sz_simplify_check(sz_ctx *ctx, int32_t max_vertices, double min_floe_area, double min_floe_height, int64_t *out4);
 
+/* ---- output frames on the device (csrc/sz_record.hpp): write_data! runs at the start of every output step, right behind
+   add_ghosts! (simulation.jl:102-105).  With a writer registered sz_step cuts its batch BEFORE each output step of that writer and records, at
+   the cut, what the writer would take -- and goes on: ghosts a process call left attached are detached, sz_add_ghosts, one pack launch per due
+   floe writer, the averages per due grid writer, sz_remove_ghosts.  The frames stay in device memory until the host drains them; nothing else
+   crosses to the host at an output step.  The schedule is taken whenever a writer is set, also with nothing else set and with SZ_NO_STOP (the
+   batch is then only cut and recorded: no pass runs, no tag is looked at); segments long enough stay pipelined.
+   THE RULE: every output step at which a batch BEGINS A STEP has exactly one frame per due writer, taken before the step -- the batch's first
+   step included, and a ridge / raft step that is left pending (*steps_done does not count it; the next sz_step starts behind it, so no step
+   gets two frames).  The batch's end step, tstep0 + *steps_done, has none: the next call records it.
+   Up to 4 floe writers and 4 grid writers, each with its own dt_out (FloeOutputWriter / GridOutputWriter Δtout; tstep % dt_out == 0 is an
+   output step).  dt_out == 0 turns that writer off, which is the default: not a launch more, and no allocation.  dt_out < 0 or a writer
+   index outside 0..3: SZ_E_ARG.  Setting a writer again frees its frames.  Single contexts only: both setters return SZ_E_STATE on a tiled
+   context, sz_tile_enable returns SZ_E_STATE on a context with a writer set.
+   sz_set_floe_output: columns_mask has one bit per column group of sz_floe_columns, in struct order (sz_debug_frame_bits): bits 0..27 the 28
+     double columns cx .. strain (tensors 4 per floe), 28 id, 29 ghost_id, 30 status, 31 the rings (vert_off + vx + vy), 32 the ghost links
+     (ghost_off + ghost_idx).  NOT recorded: the sub-floe points, floe.interactions and status.fuse_idx -- a host writer that wants them keeps
+     cutting its own batches.  Frames are appended to one arena of arena_bytes in device memory.
+     A FLOE FRAME is what sz_add_ghosts followed by sz_download_floes of the selected columns gives at the start of the step, with one rule made
+     explicit: a ghost is a deep copy of its parent (collisions.jl:881-901, floe_utils.jl:138), so a ghost row carries the parent's bits in
+     every recorded column except cx, cy, the ring and ghost_id (the device keeps only the collision columns on ghost rows; the pack reads the
+     others from the parent row).  vert_off is frame-relative; a ghost row's ghost_off span is empty.
+   sz_set_grid_output: the arguments of sz_eulerian_data (evenly spaced grid lines, nout >= 1 of the SZ_EUL_* codes) and room for max_frames
+     frames.  A GRID FRAME is the nout * nx * ny doubles sz_eulerian_data gives on the same list, bit for bit, and its timestep.  The averages run
+     in a workspace the recorder keeps (sized when the writer is set, grown on demand): a recorded output step allocates nothing once warm.
+   A frame that finds no room -- the arena, the max_frames + 1-th grid frame -- is not taken and no writer gets a frame of that step: the batch
+   ends in front of it with SZ_OK, *steps_done not counting it, and `full` set until the next sz_step or sz_clear_frames.
+   Draining: sz_output_frames: frames held per writer (n_floe, n_grid: 4 entries each, may be NULL) and full.  sz_floe_frame_info: the header of
+   floe frame k {tstep, M, N, n_ring_points, n_ghost_links}.  sz_download_floe_frame: every non-NULL member of cols that was recorded is filled
+   (sized from sz_floe_frame_info; ghost_idx n_ghost_links entries); a non-NULL member that was not recorded -- sub_off, sx, sy always --
+   returns SZ_E_ARG and nothing is written.  sz_download_grid_frame: tstep and data[nout][nx][ny] (either may be NULL).  A frame or writer
+   that does not exist: SZ_E_ARG.  Frames survive sz_upload_floes, sz_splice_floes and sz_remove_floes, so a host that edits at a stop drains
+   whenever it likes; they are freed by sz_clear_frames (all writers, the writers stay set), by setting that writer again and by sz_destroy. */
+int sz_set_floe_output(sz_ctx *ctx, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes);
+int sz_set_grid_output(sz_ctx *ctx, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double *xg, const double *yg,
+                       int32_t nout, const int32_t *outputs, int32_t max_frames);
+int sz_output_frames(sz_ctx *ctx, int32_t *n_floe, int32_t *n_grid, int32_t *full);
+int sz_floe_frame_info(sz_ctx *ctx, int32_t writer, int32_t k, int64_t *tstep, int64_t *M, int64_t *N, int64_t *n_ring_points,
+                       int64_t *n_ghost_links);
+int sz_download_floe_frame(sz_ctx *ctx, int32_t writer, int32_t k, sz_floe_columns *cols);
+int sz_download_grid_frame(sz_ctx *ctx, int32_t writer, int32_t k, int32_t *tstep, double *data);
+int sz_clear_frames(sz_ctx *ctx);
+
 /* test hook: which_vertices_match_points(points, region) (floe_utils.jl:331-352) as the narrow phase evaluates it, on
    given points (<= 64) and a given closed region ring; idx = sorted 0-based vertex indices */
 int sz_debug_match_vertices(sz_ctx *ctx, int32_t npts, const double *px, const double *py, int32_t nr, const double *rx,
@@ -760,7 +802,8 @@ int sz_debug_match_vertices(sz_ctx *ctx, int32_t npts, const double *px, const d
    blend reads, its weights tx, ty.  Needs sz_set_domain and sz_set_fields. */
 int sz_debug_sample_fields(sz_ctx *ctx, int32_t n, const double *x, const double *y, double *out12);
 
-/* test hook: 1 when the last sz_step batch ran as pipelined steps (two launches per timestep: csrc/sz_pipeline.hpp), 0 otherwise */
+/* test hook: 1 when the last sz_step batch ran as pipelined steps (two launches per timestep: csrc/sz_pipeline.hpp), 0 otherwise; with an
+   output writer set (sz_set_floe_output / sz_set_grid_output): 1 when any of the segments between its cuts did */
 int sz_debug_pipelined(sz_ctx *ctx);
 /* diagnostic build (-DSZ_STAMPS) only: stamp log of one lane group of the narrow phase
    (out512[0] = entries, then (stage << 48) | cycles since the wave started) */
@@ -775,9 +818,16 @@ int sz_debug_crec_mismatches(sz_ctx *ctx, int64_t *n_bad);
    out4 = { 1 if it is a ridge / raft step, its length, 1 if its last step is a fracture step, that step's welding set or -1 }. */
 int sz_debug_next_segment(int32_t tstep, int32_t remaining, int32_t rr_dt, int32_t frac_dt, int32_t cut_on_fracture, int32_t n_weld,
                           const int32_t *weld_dts, int32_t *out4);
+/* ... the same cutter with the output intervals of registered writers: n_out entries out_dts (0: that writer is off), a segment also ends
+   BEFORE every step that is an output step of one of them.  With n_out = 0 every answer is sz_debug_next_segment's. */
+int sz_debug_next_segment_out(int32_t tstep, int32_t remaining, int32_t rr_dt, int32_t frac_dt, int32_t cut_on_fracture, int32_t n_weld,
+                              const int32_t *weld_dts, int32_t n_out, const int32_t *out_dts, int32_t *out4);
 /* test hook: the columns of sz_floe_columns in the order the engine's tables hold them (csrc/sz_columns.hpp) -- the scalar columns, then the
    tensors, as the member names of the struct above, space-separated; no context and no device call */
 const char *sz_debug_column_names(void);
+/* test hook: the bits of sz_set_floe_output's columns_mask in order, bit 0 first, space-separated: the names above, then id, ghost_id, status,
+   rings (vert_off + vx + vy) and ghost_links (ghost_off + ghost_idx); no context and no device call */
+const char *sz_debug_frame_bits(void);
 
 #ifdef __cplusplus
 }

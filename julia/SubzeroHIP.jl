@@ -204,6 +204,8 @@ mutable struct HIPEngine
     min_floe_area::Float64       # (sz_simplify_check)
     min_floe_height::Float64
     host_rows::Vector{Int}       # per host row the row it had at the last upload! (the device removes floes: origin, pull_state!)
+    rec_floe::Vector{Tuple{Int, UInt64}}   # device floe writer k + 1 -> (index in sim.writers.floewriters, its column mask); set_floe_output!
+    rec_grid::Vector{Int}        # device grid writer k + 1 -> index in sim.writers.gridwriters; set_grid_output!
 end
 
 const ENGINE = Ref{Union{Nothing, HIPEngine}}(nothing)
@@ -231,7 +233,7 @@ function enable!(sim; device::Integer = 0)
     model, c, cs, fs, cp = sim.model, sim.consts, sim.collision_settings, sim.floe_settings, sim.coupling_settings
     grid = model.grid
     eng = HIPEngine(ctx, cp.two_way_coupling_on, grid.Nx, grid.Ny, Int32(sim.simp_settings.max_vertices),
-                    Float64(fs.min_floe_area), Float64(fs.min_floe_height), Int[])
+                    Float64(fs.min_floe_area), Float64(fs.min_floe_height), Int[], Tuple{Int, UInt64}[], Int[])
     λ = hasproperty(fs.stress_calculator, :λ) ? Float64(fs.stress_calculator.λ) :
         error("SubzeroHIP implements DecayAreaScaledCalculator (stress_calculators.jl:82) only")
     p = Ref(SzParams(c.E, c.ν, c.μ, c.ρo, c.ρa, c.Cd_io, c.Cd_ia, c.f, c.turnθ, cs.floe_floe_max_overlap,
@@ -1097,8 +1099,14 @@ and the step ends like any other (fracture, weld, simplify).
 Removal (`set_removal!`): where `simplify_floes!` reduces to `remove_floes!` -- nothing to fuse, no ring to smooth -- the device deletes the
 rows and adds the dissolved mass to its copy of `ocean.dissolved`, inside a batch (which then runs on) or, behind a batch's last step, through
 `remove_floes!(eng)`.  The host's rows follow at the next `pull_state!`, which deletes the rows `origin(eng)` no longer names.
+
+Output (`device_output = true`; off by default, this file has not been run): every GridOutputWriter and every FloeOutputWriter whose outputs a
+device frame holds (`FRAME_OUTPUTS`) is registered with the recorder (`set_floe_output!`, `set_grid_output!`; four of each at most).  Batches
+then run past those writers' output steps -- `sz_step` cuts before the step, records the frames on the device and goes on -- and
+`drain_frames!` writes them through the writers' own files after each batch.  Every other writer (checkpoint, initial state, a floe writer that
+asks for `interactions` and the like, a fifth writer) keeps the cut on the host, where only those writers write.
 """
-function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Integer = 500)
+function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Integer = 500, device_output::Bool = false)
     # (the candidates are read from the step's own interaction rows: sz_step refuses ridge / raft without SZ_COLLISIONS_ON)
     sim.ridgeraft_settings.ridge_raft_on && !sim.collision_settings.collisions_on &&
         error("run_resident!: ridging / rafting with collisions off works on rows no step refreshes: use run!(sim)")
@@ -1106,6 +1114,15 @@ function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Int
     set_fracture!(eng, sim)
     set_welding!(eng, sim)
     set_removal!(eng, sim)
+    if device_output
+        for i in eachindex(sim.writers.floewriters)
+            set_floe_output!(eng, sim, i)
+        end
+        for i in eachindex(sim.writers.gridwriters)
+            set_grid_output!(eng, sim, i)
+        end
+    end
+    rec = device_output ? eng : nothing
     fractures = sim.fracture_settings.fractures_on
     ws = sim.weld_settings
     Subzero.startup_sim(sim, nothing, 1)
@@ -1120,17 +1137,20 @@ function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Int
     tstep, last = start_tstep, start_tstep + sim.nΔt
     dirty = false                                    # the device state is ahead of the host's
     while tstep <= last
-        if output_due(sim.writers, tstep, start_tstep)
+        if output_due(sim.writers, tstep, start_tstep, rec)
             dirty && (P = pull_state!(eng, floes, P, ocean); dirty = false)
             Subzero.add_ghosts!(floes, sim.model.domain)           # write_data! sees the ghosts (simulation.jl:102-105)
-            Subzero.write_data!(sim, tstep, start_tstep)
+            device_output ? write_host_data!(sim, eng, tstep, start_tstep) : Subzero.write_data!(sim, tstep, start_tstep)
             remove_ghosts!(floes)
         end
-        n = min(batch, last - tstep + 1, steps_to_next_output(sim.writers, tstep, start_tstep))
+        n = min(batch, last - tstep + 1, steps_to_next_output(sim.writers, tstep, start_tstep, rec))
         done = Ref{Int32}(0)
         check(eng, @ccall lib.sz_step(eng.ctx::Ptr{Cvoid}, n::Int32, tstep::Int32, sim.Δt::Int32,
                                       sim.coupling_settings.Δt::Int32, flags::Int32, done::Ptr{Int32})::Cint)
         tstep += done[]; dirty = true
+        # the frames of the output steps the batch began: through the writers' files.  A batch that ended on a frame without room goes on
+        # from that step with the frames cleared
+        device_output && drain_frames!(eng, sim)
         # ridge / raft steps the batch ran through with an empty table: their per-floe draws, before anything below uses sim.rng
         if sim.ridgeraft_settings.ridge_raft_on
             for _ in 1:ridgeraft_draws(eng)
@@ -1557,10 +1577,156 @@ function tile_splice32!(eng::HIPEngine, staged::StructArray{<:Floe{Float32}}, de
     return Int(ng[]), Int(no[])
 end
 
-writer_periods(w) = Int[x.Δtout for ws in (w.floewriters, w.gridwriters, w.checkpointwriters) for x in ws]
-output_due(w, tstep, start) = tstep == start || any(p -> mod(tstep, p) == 0, writer_periods(w))
-function steps_to_next_output(w, tstep, start)
-    ps = writer_periods(w)
+# ------------------------------------------------------------------------------------------------ output frames on the device
+# include/subzero_hip.h, "output frames on the device": sz_step cuts before the output steps of registered writers and records what they
+# would take into device memory; drain_frames! writes the frames through the writers' own files afterwards.
+# The bits of sz_set_floe_output's mask, bit 0 first (sz_debug_frame_bits)
+const FRAME_BITS = (:cx, :cy, :rmax, :area, :height, :mass, :moment, :alpha, :u, :v, :xi, :p_dxdt, :p_dydt, :p_dalphadt, :p_dudt, :p_dvdt,
+                    :p_dxidt, :fxOA, :fyOA, :trqOA, :hflx_factor, :overarea, :coll_fx, :coll_fy, :coll_trq, :stress_accum, :stress_instant,
+                    :strain, :id, :ghost_id, :status, :rings, :ghost_links)
+frame_mask(groups) = reduce(|, (UInt64(1) << (findfirst(==(g), FRAME_BITS) - 1) for g in groups); init = UInt64(0))
+# FloeOutputWriter outputs a frame can give, and the column groups each needs.  Not recorded, so not here: :status (its fuse_idx), :poly and
+# :angles (derived on the host), the sub-floe points, :parent_ids, :interactions, :num_inters, :damage -- a writer that asks for one of those
+# keeps the host's cut
+const FRAME_OUTPUTS = Dict{Symbol, Vector{Symbol}}(
+    :centroid => [:cx, :cy], :coords => [:rings], :height => [:height], :area => [:area], :mass => [:mass], :rmax => [:rmax],
+    :moment => [:moment], :α => [:alpha], :u => [:u], :v => [:v], :ξ => [:xi], :id => [:id], :ghost_id => [:ghost_id],
+    :ghosts => [:ghost_links], :fxOA => [:fxOA], :fyOA => [:fyOA], :trqOA => [:trqOA], :hflx_factor => [:hflx_factor],
+    :overarea => [:overarea], :collision_force => [:coll_fx, :coll_fy], :collision_trq => [:coll_trq], :stress_accum => [:stress_accum],
+    :stress_instant => [:stress_instant], :strain => [:strain], :p_dxdt => [:p_dxdt], :p_dydt => [:p_dydt], :p_dudt => [:p_dudt],
+    :p_dvdt => [:p_dvdt], :p_dξdt => [:p_dxidt], :p_dαdt => [:p_dalphadt])
+frame_covers(w) = all(o -> haskey(FRAME_OUTPUTS, o), w.outputs)
+const EUL_CODES = Dict(name => Int32(k - 1) for (k, name) in enumerate(
+    (:u_grid, :v_grid, :dudt_grid, :dvdt_grid, :overarea_grid, :mass_grid, :area_grid, :height_grid, :si_frac_grid, :stress_xx_grid,
+     :stress_yx_grid, :stress_xy_grid, :stress_yy_grid, :stress_eig_grid, :strain_ux_grid, :strain_vx_grid, :strain_uy_grid, :strain_vy_grid)))
+
+"""
+    set_floe_output!(eng, sim, i; arena_bytes = 1 << 28) -> Bool
+
+Register `sim.writers.floewriters[i]` with the device recorder (at most 4): its Δtout and the column groups its outputs need.  `false`, and
+nothing registered, when the writer asks for an output a frame does not hold.
+"""
+function set_floe_output!(eng::HIPEngine, sim, i::Integer; arena_bytes::Integer = 1 << 28)
+    w = sim.writers.floewriters[i]
+    (frame_covers(w) && length(eng.rec_floe) < 4) || return false
+    mask = frame_mask(g for o in w.outputs for g in FRAME_OUTPUTS[o])
+    check(eng, @ccall lib.sz_set_floe_output(eng.ctx::Ptr{Cvoid}, Int32(length(eng.rec_floe))::Int32, Int32(w.Δtout)::Int32, mask::UInt64,
+                                             Int64(arena_bytes)::Int64)::Cint)
+    push!(eng.rec_floe, (Int(i), mask))
+    return true
+end
+
+"""
+    set_grid_output!(eng, sim, i; max_frames = 64) -> Bool
+
+Register `sim.writers.gridwriters[i]` with the device recorder (at most 4): Δtout, grid lines and outputs.
+"""
+function set_grid_output!(eng::HIPEngine, sim, i::Integer; max_frames::Integer = 64)
+    w = sim.writers.gridwriters[i]
+    length(eng.rec_grid) < 4 || return false
+    xg, yg = collect(Float64, w.xg), collect(Float64, w.yg)
+    codes = Int32[EUL_CODES[o] for o in w.outputs]
+    check(eng, @ccall lib.sz_set_grid_output(eng.ctx::Ptr{Cvoid}, Int32(length(eng.rec_grid))::Int32, Int32(w.Δtout)::Int32,
+                                             Int32(length(xg) - 1)::Int32, Int32(length(yg) - 1)::Int32, xg::Ptr{Float64}, yg::Ptr{Float64},
+                                             Int32(length(codes))::Int32, codes::Ptr{Int32}, Int32(max_frames)::Int32)::Cint)
+    push!(eng.rec_grid, Int(i))
+    return true
+end
+
+tensor(t, i) = [t[4i-3] t[4i-2]; t[4i-1] t[4i]]          # 11, 12, 21, 22
+# one output of a FloeOutputWriter from the columns of a frame, as StructArrays.component(floes, output) would give it
+function frame_component(o::Symbol, c::Dict{Symbol, Vector}, M::Int)
+    o === :centroid && return [[c[:cx][i], c[:cy][i]] for i in 1:M]
+    o === :coords && return [[[[c[:vx][k], c[:vy][k]] for k in c[:vert_off][i]+1:c[:vert_off][i+1]]] for i in 1:M]
+    o === :ghosts && return [Int[c[:ghost_idx][k] + 1 for k in c[:ghost_off][i]+1:c[:ghost_off][i+1]] for i in 1:M]
+    o === :collision_force && return [[c[:coll_fx][i] c[:coll_fy][i]] for i in 1:M]
+    o in (:stress_accum, :stress_instant, :strain) && return [tensor(c[o], i) for i in 1:M]
+    o in (:id, :ghost_id) && return Int.(c[o])
+    return c[FRAME_OUTPUTS[o][1]]
+end
+
+"""
+    drain_frames!(eng, sim)
+
+Write every frame the device holds through the writers' own files -- `write_field` under `output/tstep` for a FloeOutputWriter, the NetCDF
+slice `istep = div(tstep, Δtout) + 1` for a GridOutputWriter (output.jl:558-605) -- and clear them.  Returns whether the last batch ended on
+a frame that found no room.
+"""
+function drain_frames!(eng::HIPEngine, sim)
+    nf, ng, full = zeros(Int32, 4), zeros(Int32, 4), Ref{Int32}(0)
+    check(eng, @ccall lib.sz_output_frames(eng.ctx::Ptr{Cvoid}, nf::Ptr{Int32}, ng::Ptr{Int32}, full::Ptr{Int32})::Cint)
+    for (slot, (i, mask)) in enumerate(eng.rec_floe), k in 0:nf[slot]-1
+        w = sim.writers.floewriters[i]
+        info = [Ref{Int64}(0) for _ in 1:5]
+        check(eng, @ccall lib.sz_floe_frame_info(eng.ctx::Ptr{Cvoid}, Int32(slot - 1)::Int32, Int32(k)::Int32, info[1]::Ptr{Int64},
+                                                 info[2]::Ptr{Int64}, info[3]::Ptr{Int64}, info[4]::Ptr{Int64}, info[5]::Ptr{Int64})::Cint)
+        tstep, M, _, V, G = (Int(r[]) for r in info)
+        cols, c = SzFloeColumns(), Dict{Symbol, Vector}()
+        for (b, g) in enumerate(FRAME_BITS)
+            (mask >> (b - 1)) & 1 == 1 || continue
+            if g === :rings
+                c[:vert_off], c[:vx], c[:vy] = zeros(Int32, M + 1), zeros(Float64, max(V, 1)), zeros(Float64, max(V, 1))
+            elseif g === :ghost_links
+                c[:ghost_off], c[:ghost_idx] = zeros(Int32, M + 1), zeros(Int32, max(G, 1))
+            elseif g === :status
+                c[g] = zeros(Int32, M)
+            elseif g in (:id, :ghost_id)
+                c[g] = zeros(Int64, M)
+            else
+                c[g] = zeros(Float64, (b > 25 ? 4 : 1) * M)
+            end
+        end
+        GC.@preserve c begin
+            for (name, v) in c
+                setfield!(cols, name, pointer(v))
+            end
+            check(eng, @ccall lib.sz_download_floe_frame(eng.ctx::Ptr{Cvoid}, Int32(slot - 1)::Int32, Int32(k)::Int32,
+                                                         cols::Ref{SzFloeColumns})::Cint)
+        end
+        Subzero.jldopen(w.filepath, "a+") do file
+            for o in w.outputs
+                Subzero.write_field(file, string(o, "/", tstep), frame_component(o, c, M))
+            end
+        end
+    end
+    for (slot, i) in enumerate(eng.rec_grid), k in 0:ng[slot]-1
+        w = sim.writers.gridwriters[i]
+        nx, ny, nout = length(w.xg) - 1, length(w.yg) - 1, length(w.outputs)
+        tstep, data = Ref{Int32}(0), Vector{Float64}(undef, nout * nx * ny)
+        check(eng, @ccall lib.sz_download_grid_frame(eng.ctx::Ptr{Cvoid}, Int32(slot - 1)::Int32, Int32(k)::Int32, tstep::Ptr{Int32},
+                                                     data::Ptr{Float64})::Cint)
+        d = permutedims(reshape(data, ny, nx, nout), (2, 1, 3))          # data[k][ix][iy], row-major -> [ix, iy, k]
+        istep = div(Int(tstep[]), w.Δtout) + 1
+        ds = Subzero.NCDataset(w.filepath, "a")
+        for j in eachindex(w.outputs)
+            ds[string(w.outputs[j])][istep, :, :] = d[:, :, j]
+        end
+        close(ds)
+    end
+    check(eng, @ccall lib.sz_clear_frames(eng.ctx::Ptr{Cvoid})::Cint)
+    return full[] != 0
+end
+
+# write_data! (output.jl:478-499) for the writers the recorder does not serve: the registered ones get that step's frame from the device
+function write_host_data!(sim, eng::HIPEngine, tstep, start_tstep)
+    tstep == start_tstep && Subzero.write_init_state_data!(sim)
+    Subzero.write_checkpoint_data!(sim, tstep)
+    fw, gw = sim.writers.floewriters, sim.writers.gridwriters
+    Subzero.write_floe_data!(fw[[k for k in eachindex(fw) if !(k in first.(eng.rec_floe))]], sim.model.floes, tstep)
+    Subzero.write_grid_data!(gw[[k for k in eachindex(gw) if !(k in eng.rec_grid)]], sim.model.floes, sim.model.domain.topography, tstep)
+    return
+end
+
+# the writers the host still serves: with device_output the registered ones leave the list
+function writer_periods(w, eng = nothing)
+    on_device(ws, idx) = eng === nothing ? ws : [x for (k, x) in enumerate(ws) if !(k in idx)]
+    fl = on_device(w.floewriters, eng === nothing ? () : first.(eng.rec_floe))
+    gr = on_device(w.gridwriters, eng === nothing ? () : eng.rec_grid)
+    return Int[x.Δtout for ws in (fl, gr, w.checkpointwriters) for x in ws]
+end
+output_due(w, tstep, start, eng = nothing) = tstep == start || any(p -> mod(tstep, p) == 0, writer_periods(w, eng))
+function steps_to_next_output(w, tstep, start, eng = nothing)
+    ps = writer_periods(w, eng)
     isempty(ps) && return typemax(Int32) ÷ 2
     return minimum(p - mod(tstep, p) for p in ps)
 end

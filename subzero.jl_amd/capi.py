@@ -94,7 +94,14 @@ EXPORTS = [
     "sz_debug_next_segment", "sz_debug_column_names",
     "sz_ridgeraft_rows", "sz_download_list_rows", "sz_splice_parents", "sz_ridgeraft_rows_f32", "sz_download_list_rows_f32", "sz_splice_parents_f32",
     "sz_tile_download_rows", "sz_tile_splice_floes", "sz_tile_download_rows_f32", "sz_tile_splice_floes_f32",
+    "sz_set_floe_output", "sz_set_grid_output", "sz_output_frames", "sz_floe_frame_info", "sz_download_floe_frame", "sz_download_grid_frame",
+    "sz_clear_frames", "sz_debug_next_segment_out", "sz_debug_frame_bits",
 ]
+
+# the column groups of sz_set_floe_output's mask, bit 0 first (sz_debug_frame_bits; tests/test_output_stops_cpu.py holds the list to the library's)
+FRAME_BITS = DCOLS + TCOLS + ["id", "ghost_id", "status", "rings", "ghost_links"]
+FRAME_MEMBERS = {"rings": ["vert_off", "vx", "vy"], "ghost_links": ["ghost_off", "ghost_idx"]}      # groups of more than one struct member
+REC_WRITERS = 4
 
 EUL_PARTIAL = 17      # SZ_EUL_PARTIAL: per-cell partial fields of sz_eulerian_partial
 
@@ -241,8 +248,18 @@ def load(build_if_missing=True):
     L.sz_tile_splice_floes.argtypes = [C.c_void_p, C.c_int32, _lp, C.c_int32, _lp, C.c_int32, _ip, C.POINTER(SzFloeColumns), _ip, _dp, _lp, _lp]
     L.sz_tile_download_rows_f32.argtypes = [C.c_void_p, C.c_int32, _lp, _ip, _ip, C.POINTER(SzFloeColumnsF32), _ip, _fp, _lp]
     L.sz_tile_splice_floes_f32.argtypes = [C.c_void_p, C.c_int32, _lp, C.c_int32, _lp, C.c_int32, _ip, C.POINTER(SzFloeColumnsF32), _ip, _fp, _lp, _lp]
+    L.sz_set_floe_output.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64]
+    L.sz_set_grid_output.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, _ip, C.c_int32]
+    L.sz_output_frames.argtypes = [C.c_void_p, _ip, _ip, _ip]
+    L.sz_floe_frame_info.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _lp, _lp, _lp, _lp, _lp]
+    L.sz_download_floe_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SzFloeColumns)]
+    L.sz_download_grid_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp]
+    L.sz_clear_frames.argtypes = [C.c_void_p]
+    L.sz_debug_next_segment_out.argtypes = [C.c_int32] * 6 + [_ip, C.c_int32, _ip, _ip]
+    L.sz_debug_frame_bits.restype = C.c_char_p
+    L.sz_debug_frame_bits.argtypes = []
     for n in EXPORTS:
-        if n not in ("sz_create", "sz_destroy", "sz_last_error", "sz_version", "sz_debug_column_names"):
+        if n not in ("sz_create", "sz_destroy", "sz_last_error", "sz_version", "sz_debug_column_names", "sz_debug_frame_bits"):
             getattr(L, n).restype = C.c_int
     _LIB = L
     return L

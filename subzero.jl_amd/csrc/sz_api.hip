@@ -29,6 +29,7 @@
 #include "sz_splice.hpp"
 #include "sz_splice_tile.hpp"
 #include "sz_stops.hpp"
+#include "sz_record.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 #include "sz_ctx.hpp"
 #include "sz_comm.hpp"
@@ -739,10 +740,12 @@ sz_ctx* sz_create(int device_id) {
   return c;
 }
 
+static void rec_free_all(sz_ctx* c);          // (the output recorder's frames and workspace, below)
 void sz_destroy(sz_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
+  rec_free_all(c);
   free_pool(c->allocs); free_pool(c->list_allocs); free_pool(c->inter_allocs); free_pool(c->static_allocs); free_pool(c->field_allocs); free_pool(c->tw_allocs); free_pool(c->tw_field_allocs);
   free_pool(c->blk_pt_allocs); free_pool(c->mixed_pt_allocs); free_pool(c->mixed_node_allocs); free_pool(c->mixed_geom_allocs); free_pool(c->comm_allocs); free_pool(c->tw_part_allocs); free_pool(c->sub_allocs); free_pool(c->mig_allocs);
   (void)sz_comm_destroy(c);
@@ -2962,14 +2965,18 @@ int sz_step_finish(sz_ctx* c, int32_t tstep, int32_t dt, int32_t coupling_dt, in
   return SZ_OK;
 }
 
+static int rec_record(sz_ctx* c, int tstep, int* full);          // (the recorder: behind the output path, below)
 namespace {
 // The passes of the stop schedule (sz_stops.hpp) on the single context.  Every value is this process's own: a tag is always settled.
 struct SingleStops {
-  sz_ctx* c; int dt, coupling_dt, flags;
+  sz_ctx* c; int dt, coupling_dt, flags; int pipelined = 0;
+  // write_data! of an output step (sz_record.hpp): the frames of the list as add_ghosts! leaves it, the ghosts detached again
+  int record(int tstep, int* full) { return rec_record(c, tstep, full); }
   // an ordinary batch: its last step keeps its ghosts, the rows come home behind it, segments of pipe_min_steps or more stay pipelined
   int segment(int len, int t0, int* ran, int* tag) {
     const int rc = step_segment(c, len, t0, dt, coupling_dt, flags, ran);
-    *tag = *ran < len || c->last_stopped;
+    *tag = !(flags & SZ_NO_STOP) && (*ran < len || c->last_stopped);          // (a batch that runs through is only cut and recorded: no tag is looked at)
+    pipelined |= c->last_pipelined;
     return rc;
   }
   // through the process calls, with the candidate pass of sz_ridgeraft.hpp (one host synchronisation) in the middle; pending = the state is the
@@ -3012,6 +3019,9 @@ struct SingleStops {
 // nsteps x timestep_sim!.  With ridge / raft (sz_set_ridgeraft), welding (sz_set_welding) or removal (sz_set_removal) set the batch runs in
 // segments that stop only where the host is needed: the schedule is sz_stops.hpp's, SingleStops its passes.  Batches that run through
 // (SZ_NO_STOP) and contexts with none of the three set take the driver as it is.
+// With an output writer registered (sz_set_floe_output, sz_set_grid_output) every batch takes the schedule, which then also cuts before the
+// output steps and records their frames; a batch that runs through (SZ_NO_STOP) carries the output intervals alone in its rules -- no pass
+// runs, no tag is looked at.  sz_debug_pipelined then says whether ANY segment ran pipelined: the cuts leave short segments between long ones.
 int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupling_dt, int32_t flags, int32_t* steps_done) {
   if (c && c->rr_pending >= 0) {
     if (steps_done) *steps_done = 0;
@@ -3024,8 +3034,11 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
     c->err = "sz_step on a tiled context has no ridge / raft candidate pass (a tile's rows are named by order keys, its ghosts' partners live on other ranks): sz_tile_run, or sz_set_ridgeraft(0)";
     return SZ_E_STATE;
   }
-  const bool weld = c && !c->weld_dts.empty(), rem = c && c->rm_on && !c->S.tiled, rr = c && c->rr_on;
-  if (!c || (!weld && !rem && !rr) || (flags & SZ_NO_STOP) || nsteps <= 0) return step_segment(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done);
+  const bool rec = c && c->rec.any && !c->S.tiled;
+  const bool through = (flags & SZ_NO_STOP) != 0;
+  const bool weld = c && !through && !c->weld_dts.empty(), rem = c && !through && c->rm_on && !c->S.tiled, rr = c && !through && c->rr_on;
+  if (c) c->rec.full = false;
+  if (!c || (!weld && !rem && !rr && !rec) || nsteps <= 0) return step_segment(c, nsteps, tstep0, dt, coupling_dt, flags, steps_done);
   if (steps_done) *steps_done = 0;
   if (!c->have_floes) return SZ_E_STATE;
   if (weld) {
@@ -3035,7 +3048,11 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
   if (rr && !(flags & SZ_COLLISIONS_ON)) { c->err = "sz_step with ridge / raft set: the candidates are read from this step's interaction rows (SZ_COLLISIONS_ON)"; return SZ_E_STATE; }
   if (rr && (flags & SZ_COUPLING_ON) && !c->have_fields) { c->err = "sz_set_fields must be called before coupling"; return SZ_E_STATE; }
   SingleStops ops = { c, dt, coupling_dt, flags };
-  return run_with_stops(single_stop_rules(*c), ops, nsteps, tstep0, steps_done);
+  StopRules rules = through ? StopRules{ 0, 0, nullptr, 0, false, false } : single_stop_rules(*c);
+  if (rec) { rules.out_dts = c->rec.dts; rules.n_out = 2 * REC_WRITERS; }
+  const int rc = run_with_stops(rules, ops, nsteps, tstep0, steps_done);
+  if (rec) c->last_pipelined = ops.pipelined;
+  return rc;
 }
 int sz_debug_next_segment(int32_t tstep, int32_t remaining, int32_t rr_dt, int32_t frac_dt, int32_t cut_on_fracture, int32_t n_weld, const int32_t* dts, int32_t* out4) {
   if (!out4 || tstep < 0 || rr_dt < 0 || frac_dt < 0 || n_weld < 0 || (n_weld > 0 && !dts)) return SZ_E_ARG;
@@ -3044,6 +3061,21 @@ int sz_debug_next_segment(int32_t tstep, int32_t remaining, int32_t rr_dt, int32
   const Segment g = next_segment(r, tstep, remaining);
   out4[0] = g.rr_step; out4[1] = g.len; out4[2] = g.fstep; out4[3] = g.weld_set;
   return SZ_OK;
+}
+int sz_debug_next_segment_out(int32_t tstep, int32_t remaining, int32_t rr_dt, int32_t frac_dt, int32_t cut_on_fracture, int32_t n_weld, const int32_t* dts,
+                              int32_t n_out, const int32_t* out_dts, int32_t* out4) {
+  if (!out4 || tstep < 0 || rr_dt < 0 || frac_dt < 0 || n_weld < 0 || (n_weld > 0 && !dts) || n_out < 0 || (n_out > 0 && !out_dts)) return SZ_E_ARG;
+  for (int k = 0; k < n_weld; k++) if (dts[k] <= 0) return SZ_E_ARG;
+  for (int k = 0; k < n_out; k++) if (out_dts[k] < 0) return SZ_E_ARG;
+  StopRules r = { rr_dt, frac_dt, dts, n_weld, cut_on_fracture != 0, false };
+  r.out_dts = out_dts; r.n_out = n_out;
+  const Segment g = next_segment(r, tstep, remaining);
+  out4[0] = g.rr_step; out4[1] = g.len; out4[2] = g.fstep; out4[3] = g.weld_set;
+  return SZ_OK;
+}
+const char* sz_debug_frame_bits(void) {
+  static const std::string names = std::string(COLUMN_NAMES + 1) + FRAME_BIT_TAIL;
+  return names.c_str();
 }
 const char* sz_debug_column_names(void) { return COLUMN_NAMES + 1; }
 
@@ -3148,12 +3180,23 @@ int sz_debug_stamps(sz_ctx* c, long long* out16) {
 // ---------------------------------------------------------------- output path
 
 // shared front of the grid-output calls: argument checks, grid lines to the device, cell areas
-int eul_grid(sz_ctx* c, int32_t nx, int32_t ny, const double* xg, const double* yg, PoolGuard& pool, EulGrid& E) {
+// (the memory comes from `pool`: a call's own, freed behind it, or the recorder's workspace, which stays -- eul_grid_bytes / eul_fill_bytes say how
+//  much a pool of one chunk must hold)
+int eul_check_lines(sz_ctx* c, int32_t nx, int32_t ny, const double* xg, const double* yg) {
   if (nx < 1 || ny < 1 || !xg || !yg) return SZ_E_ARG;
   const double dx = xg[1] - xg[0], dy = yg[1] - yg[0];
   if (!(dx > 0) || !(dy > 0)) { c->err = "grid lines must ascend"; return SZ_E_ARG; }
   for (int k = 0; k <= nx; k++) if (fabs(xg[k] - (xg[0] + k * dx)) > 1e-6 * dx) { c->err = "x grid lines must be evenly spaced"; return SZ_E_ARG; }
   for (int k = 0; k <= ny; k++) if (fabs(yg[k] - (yg[0] + k * dy)) > 1e-6 * dy) { c->err = "y grid lines must be evenly spaced"; return SZ_E_ARG; }
+  return SZ_OK;
+}
+static size_t pool_bytes(size_t n, size_t size) { return ((n ? n : 1) * size + 255) & ~(size_t)255; }          // (what dalloc carves for n elements)
+size_t eul_grid_bytes(int nx, int ny) {
+  const size_t ncell = (size_t)nx * ny;
+  return pool_bytes(nx + 1, 8) + pool_bytes(ny + 1, 8) + pool_bytes(1, sizeof(int)) + pool_bytes(ncell, 8) + pool_bytes((size_t)EUL_COUNT * ncell, 8);
+}
+int eul_grid(sz_ctx* c, int32_t nx, int32_t ny, const double* xg, const double* yg, Pool& pool, EulGrid& E) {
+  if (int rc = eul_check_lines(c, nx, ny, xg, yg)) return rc;
   (void)hipSetDevice(c->device);
   world_rings(c);
   int rc = sync_and_check(c);          // hostM current, nothing pending
@@ -3162,39 +3205,57 @@ int eul_grid(sz_ctx* c, int32_t nx, int32_t ny, const double* xg, const double* 
   E = EulGrid{};
   E.nx = nx; E.ny = ny; E.M = c->hostM > 0 ? c->hostM : 1;
   double *d_xg, *d_yg;
-  if ((rc = dalloc(c, &d_xg, nx + 1, pool.v)) || (rc = dalloc(c, &d_yg, ny + 1, pool.v)) || (rc = dalloc(c, &E.count, 1, pool.v)) ||
-      (rc = dalloc(c, &E.cell_area, ncell, pool.v)) || (rc = dalloc(c, &E.data, (size_t)EUL_COUNT * ncell, pool.v))) return rc;
+  if ((rc = dalloc(c, &d_xg, nx + 1, pool)) || (rc = dalloc(c, &d_yg, ny + 1, pool)) || (rc = dalloc(c, &E.count, 1, pool)) ||
+      (rc = dalloc(c, &E.cell_area, ncell, pool)) || (rc = dalloc(c, &E.data, (size_t)EUL_COUNT * ncell, pool))) return rc;
   H2D(d_xg, xg, nx + 1, double); H2D(d_yg, yg, ny + 1, double);
   E.xg = d_xg; E.yg = d_yg;
   hipLaunchKernelGGL(sz_k_eul_cell_area, dim3(grid_for(ncell, 64 / EU_G, 8192)), dim3(64), 0, c->stream, c->S, E);
   return SZ_OK;
 }
-// entries (count, size, fill, sort) and the area of every entry
-int eul_entries(sz_ctx* c, PoolGuard& pool, EulGrid& E, int& nent) {
-  State& S = c->S;
-  int rc;
-  hipLaunchKernelGGL(sz_k_eul_entries, dim3(grid_for(S.capM, 256)), dim3(256), 0, c->stream, S, E, 0);
+// entries: counted ...
+int eul_count(sz_ctx* c, EulGrid& E, int& nent) {
+  hipLaunchKernelGGL(sz_k_eul_entries, dim3(grid_for(c->S.capM, 256)), dim3(256), 0, c->stream, c->S, E, 0);
   nent = 0;
   HIPCHK(c, hipMemcpyAsync(&nent, E.count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (nent < 0) { c->err = "output grid: entry count overflow"; return SZ_E_CAPACITY; }
+  return SZ_OK;
+}
+static unsigned eul_key_bits(const EulGrid& E) {
+  unsigned long long top = (unsigned long long)E.nx * E.ny * (unsigned long long)E.M;
+  unsigned bits = 1; while (bits < 64 && (top >> bits)) bits++;
+  return bits;
+}
+int eul_fill_bytes(sz_ctx* c, const EulGrid& E, int nent, size_t* bytes) {
+  size_t tmp_bytes = 0;
+  if (nent > 0) HIPCHK(c, rocprim::radix_sort_keys(nullptr, tmp_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (size_t)nent, 0u, eul_key_bits(E), c->stream));
+  *bytes = 3 * pool_bytes(nent, 8) + pool_bytes(tmp_bytes, 1);
+  return SZ_OK;
+}
+// ... then sized, filled and sorted, and the area of every entry
+int eul_fill(sz_ctx* c, Pool& pool, EulGrid& E, int nent) {
+  State& S = c->S;
+  int rc;
   unsigned long long* keys_in = nullptr;
   E.cap = nent;
-  if ((rc = dalloc(c, &keys_in, nent, pool.v)) || (rc = dalloc(c, &E.keys, nent, pool.v)) || (rc = dalloc(c, &E.pic, nent, pool.v))) return rc;
+  if ((rc = dalloc(c, &keys_in, nent, pool)) || (rc = dalloc(c, &E.keys, nent, pool)) || (rc = dalloc(c, &E.pic, nent, pool))) return rc;
   if (nent == 0) return SZ_OK;
   HIPCHK(c, hipMemsetAsync(E.count, 0, sizeof(int), c->stream));
   EulGrid Ein = E; Ein.keys = keys_in;
   hipLaunchKernelGGL(sz_k_eul_entries, dim3(grid_for(S.capM, 256)), dim3(256), 0, c->stream, S, Ein, 1);
-  unsigned long long top = (unsigned long long)E.nx * E.ny * (unsigned long long)E.M;
-  unsigned bits = 1; while (bits < 64 && (top >> bits)) bits++;
+  const unsigned bits = eul_key_bits(E);
   size_t tmp_bytes = 0;
   HIPCHK(c, rocprim::radix_sort_keys(nullptr, tmp_bytes, keys_in, E.keys, (size_t)nent, 0u, bits, c->stream));
   char* tmp = nullptr;
-  if ((rc = dalloc(c, &tmp, tmp_bytes, pool.v))) return rc;
+  if ((rc = dalloc(c, &tmp, tmp_bytes, pool))) return rc;
   HIPCHK(c, rocprim::radix_sort_keys((void*)tmp, tmp_bytes, keys_in, E.keys, (size_t)nent, 0u, bits, c->stream));
   if (S.nelem > 4) hipLaunchKernelGGL(sz_k_eul_area, dim3(grid_for(nent, 64 / EU_G, 1 << 16)), dim3(64), 0, c->stream, S, E, nent);
   else hipLaunchKernelGGL(sz_k_eul_area_rect, dim3(grid_for(nent, 256, 1 << 16)), dim3(256), 0, c->stream, S, E, nent);
   return SZ_OK;
+}
+int eul_entries(sz_ctx* c, Pool& pool, EulGrid& E, int& nent) {
+  if (int rc = eul_count(c, E, nent)) return rc;
+  return eul_fill(c, pool, E, nent);
 }
 int eul_check_outputs(sz_ctx* c, int32_t nout, const int32_t* outputs, const double* data) {
   if (nout < 0 || (nout > 0 && (!outputs || !data))) return SZ_E_ARG;
@@ -3217,7 +3278,7 @@ int sz_eulerian_data(sz_ctx* c, int32_t nx, int32_t ny, const double* xg, const 
   if (rc) return rc;
   if (c->S.tiled) { c->err = "tiled contexts: sz_eulerian_partial, all-reduce, sz_eulerian_finish"; return SZ_E_STATE; }
   PoolGuard pool; EulGrid E; int nent = 0;
-  if ((rc = eul_grid(c, nx, ny, xg, yg, pool, E)) || (rc = eul_entries(c, pool, E, nent))) return rc;
+  if ((rc = eul_grid(c, nx, ny, xg, yg, pool.v, E)) || (rc = eul_entries(c, pool.v, E, nent))) return rc;
   hipLaunchKernelGGL(sz_k_eul_reduce, dim3(grid_for(nx * ny, 64)), dim3(64), 0, c->stream, c->S, E, nent);
   return eul_copy_out(c, E, nout, outputs, data);
 }
@@ -3226,7 +3287,7 @@ int sz_eulerian_partial(sz_ctx* c, int32_t nx, int32_t ny, const double* xg, con
   if (!c || !c->have_floes) return SZ_E_STATE;
   if (!d_partial) return SZ_E_ARG;
   PoolGuard pool; EulGrid E; int nent = 0, rc;
-  if ((rc = eul_grid(c, nx, ny, xg, yg, pool, E)) || (rc = eul_entries(c, pool, E, nent))) return rc;
+  if ((rc = eul_grid(c, nx, ny, xg, yg, pool.v, E)) || (rc = eul_entries(c, pool.v, E, nent))) return rc;
   hipLaunchKernelGGL(sz_k_eul_partial, dim3(grid_for(nx * ny, 64)), dim3(64), 0, c->stream, c->S, E, nent, (double*)d_partial);
   return sync_and_check(c);
 }
@@ -3238,9 +3299,196 @@ int sz_eulerian_finish(sz_ctx* c, int32_t nx, int32_t ny, const double* xg, cons
   int rc = eul_check_outputs(c, nout, outputs, data);
   if (rc) return rc;
   PoolGuard pool; EulGrid E;
-  if ((rc = eul_grid(c, nx, ny, xg, yg, pool, E))) return rc;
+  if ((rc = eul_grid(c, nx, ny, xg, yg, pool.v, E))) return rc;
   hipLaunchKernelGGL(sz_k_eul_finish, dim3(grid_for(nx * ny, 64)), dim3(64), 0, c->stream, E, (const double*)d_partial);
   return eul_copy_out(c, E, nout, outputs, data);
+}
+
+// ---------------------------------------------------------------- output recorder (sz_record.hpp)
+// a workspace chunk as a pool of one chunk for the eul_* helpers; work_keep() takes back whatever the round left (the same chunk, when it was
+// reserved large enough)
+static int work_reserve(sz_ctx* c, RecWork& w, size_t need) {
+  if (w.bytes >= need) return SZ_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  (void)hipFree(w.p); w.p = nullptr; w.bytes = 0;
+  need = (need + need / 4 + 255) & ~(size_t)255;          // (a quarter to spare: the entry count wanders from frame to frame)
+  HIPCHK(c, hipMalloc((void**)&w.p, need));
+  w.bytes = need;
+  return SZ_OK;
+}
+static Pool work_pool(const RecWork& w) { Pool p; p.chunks.push_back(w.p); p.sizes.push_back(w.bytes); return p; }
+static void work_keep(RecWork& w, Pool& p) {
+  for (size_t k = 1; k < p.chunks.size(); k++) (void)hipFree(p.chunks[k]);
+  w.p = p.chunks.empty() ? nullptr : (char*)p.chunks[0]; w.bytes = p.chunks.empty() ? 0 : p.sizes[0];
+  p.chunks.clear(); p.sizes.clear();
+}
+static void rec_free_floe(FloeWriter& w) { (void)hipFree(w.arena); w = FloeWriter{}; }
+static void rec_free_grid(GridWriter& g) { (void)hipFree(g.store); g = GridWriter{}; }
+static void rec_free_all(sz_ctx* c) {
+  for (int w = 0; w < REC_WRITERS; w++) { rec_free_floe(c->rec.floe[w]); rec_free_grid(c->rec.grid[w]); }
+  (void)hipFree(c->rec.grid_work.p); (void)hipFree(c->rec.entry_work.p);
+  c->rec = Recorder{};
+}
+static int rec_setter_checks(sz_ctx* c, int32_t writer, int32_t dt_out) {
+  if (!c) return SZ_E_ARG;
+  if (writer < 0 || writer >= REC_WRITERS) { c->err = "output writer index out of range (0..3)"; return SZ_E_ARG; }
+  if (dt_out < 0) { c->err = "output interval must not be negative (0 turns the writer off)"; return SZ_E_ARG; }
+  if (c->S.tiled) { c->err = "the output recorder serves single contexts only"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SZ_OK;
+}
+int sz_set_floe_output(sz_ctx* c, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes) {
+  if (int rc = rec_setter_checks(c, writer, dt_out)) return rc;
+  if (dt_out > 0 && (columns_mask == 0 || (columns_mask >> FR_NBITS) != 0)) { c->err = "sz_set_floe_output: the mask selects no column group, or one that does not exist (sz_debug_frame_bits)"; return SZ_E_ARG; }
+  if (dt_out > 0 && arena_bytes < (int64_t)FR_HEADER) { c->err = "sz_set_floe_output: the arena holds no frame"; return SZ_E_ARG; }
+  FloeWriter& w = c->rec.floe[writer];
+  rec_free_floe(w);
+  if (dt_out > 0) {
+    HIPCHK(c, hipMalloc((void**)&w.arena, (size_t)arena_bytes));
+    w.dt = dt_out; w.mask = columns_mask; w.bytes = (size_t)arena_bytes;
+  }
+  c->rec.refresh();
+  return SZ_OK;
+}
+int sz_set_grid_output(sz_ctx* c, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double* xg, const double* yg, int32_t nout,
+                       const int32_t* outputs, int32_t max_frames) {
+  if (int rc = rec_setter_checks(c, writer, dt_out)) return rc;
+  if (dt_out > 0) {
+    if (int rc = eul_check_lines(c, nx, ny, xg, yg)) return rc;
+    if (nout < 1 || !outputs || max_frames < 1) return SZ_E_ARG;
+    for (int k = 0; k < nout; k++) if (outputs[k] < 0 || outputs[k] >= EUL_COUNT) { c->err = "unknown grid output"; return SZ_E_ARG; }
+  }
+  GridWriter& g = c->rec.grid[writer];
+  rec_free_grid(g);
+  if (dt_out > 0) {
+    HIPCHK(c, hipMalloc((void**)&g.store, (size_t)max_frames * nout * nx * ny * sizeof(double)));
+    g.dt = dt_out; g.nx = nx; g.ny = ny; g.max_frames = max_frames;
+    g.xg.assign(xg, xg + nx + 1); g.yg.assign(yg, yg + ny + 1); g.outputs.assign(outputs, outputs + nout);
+    if (int rc = work_reserve(c, c->rec.grid_work, eul_grid_bytes(nx, ny))) return rc;
+  }
+  c->rec.refresh();
+  return SZ_OK;
+}
+// one floe frame: the layout from the host's counts, one launch
+static int rec_pack(sz_ctx* c, FloeWriter& w, int tstep, int V) {
+  const int M = c->hostM, N = c->hostN;
+  const FrameLayout L(w.mask, M, N, V);
+  FramePack F;
+  const ColTable<double*> src = state_columns(c->S);
+  for (int k = 0; k < MIG_NTAB; k++) F.col[k] = src.p[k];
+  for (int k = 0; k < FR_NSEC; k++) F.off[k] = L.off[k];
+  F.dst = w.arena + w.used; F.tstep = tstep; F.M = M; F.N = N; F.V = V;
+  const long long widest = std::max<long long>(4ll * M, V);
+  hipLaunchKernelGGL(sz_k_frame_pack, dim3(grid_for(widest, FP_TPB, 256), FP_SLICES), dim3(FP_TPB), 0, c->stream, c->S, F);
+  w.frames.push_back({ w.used, tstep, M, N, V });
+  w.used += (size_t)L.total;
+  return SZ_OK;
+}
+// one grid frame: the averages of sz_eulerian_data in the recorder's workspace, the wanted outputs copied into the store on the device
+static int rec_grid(sz_ctx* c, GridWriter& g, int tstep) {
+  Recorder& R = c->rec;
+  EulGrid E; int nent = 0, rc;
+  if ((rc = work_reserve(c, R.grid_work, eul_grid_bytes(g.nx, g.ny)))) return rc;
+  Pool gp = work_pool(R.grid_work);
+  rc = eul_grid(c, g.nx, g.ny, g.xg.data(), g.yg.data(), gp, E);
+  work_keep(R.grid_work, gp);
+  size_t need = 0;
+  if (rc || (rc = eul_count(c, E, nent)) || (rc = eul_fill_bytes(c, E, nent, &need)) || (rc = work_reserve(c, R.entry_work, need))) return rc;
+  Pool ep = work_pool(R.entry_work);
+  rc = eul_fill(c, ep, E, nent);
+  work_keep(R.entry_work, ep);
+  if (rc) return rc;
+  const size_t ncell = (size_t)g.nx * g.ny, nout = g.outputs.size();
+  hipLaunchKernelGGL(sz_k_eul_reduce, dim3(grid_for((long long)ncell, 64)), dim3(64), 0, c->stream, c->S, E, nent);
+  double* dst = g.store + g.tsteps.size() * nout * ncell;
+  for (size_t k = 0; k < nout; k++)
+    HIPCHK(c, hipMemcpyAsync(dst + k * ncell, E.data + (size_t)g.outputs[k] * ncell, ncell * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  g.tsteps.push_back(tstep);
+  return SZ_OK;
+}
+// write_data! of output step tstep, in front of the segment that starts there (run_with_stops).  *full: a due writer has no room for its
+// frame -- nothing is recorded for this step, the batch ends in front of it.
+static int rec_record(sz_ctx* c, int tstep, int* full) {
+  Recorder& R = c->rec;
+  *full = 0;
+  bool fdue[REC_WRITERS], gdue[REC_WRITERS], any = false;
+  for (int w = 0; w < REC_WRITERS; w++) { fdue[w] = step_due(R.floe[w].dt, tstep); gdue[w] = step_due(R.grid[w].dt, tstep); any = any || fdue[w] || gdue[w]; }
+  if (!any) return SZ_OK;
+  for (int w = 0; w < REC_WRITERS; w++) if (gdue[w] && (int)R.grid[w].tsteps.size() >= R.grid[w].max_frames) { *full = 1; R.full = true; return SZ_OK; }
+  int rc, h[C_COUNT];
+  (void)hipSetDevice(c->device);
+  if ((c->ghosts_staged || c->hostM != c->hostN) && (rc = sz_remove_ghosts(c))) return rc;          // (ghosts a process-mode call left attached: a batch drops them too)
+  if ((rc = sz_add_ghosts(c)) || (rc = fetch_counters(c, h))) return rc;
+  const int V = h[C_NV];
+  for (int w = 0; w < REC_WRITERS; w++)
+    if (fdue[w] && R.floe[w].used + (size_t)FrameLayout(R.floe[w].mask, c->hostM, c->hostN, V).total > R.floe[w].bytes) { *full = 1; R.full = true; }
+  for (int w = 0; w < REC_WRITERS && !*full; w++) if (fdue[w] && (rc = rec_pack(c, R.floe[w], tstep, V))) return rc;
+  for (int w = 0; w < REC_WRITERS && !*full; w++) if (gdue[w] && (rc = rec_grid(c, R.grid[w], tstep))) return rc;
+  return sz_remove_ghosts(c);
+}
+int sz_output_frames(sz_ctx* c, int32_t* n_floe, int32_t* n_grid, int32_t* full) {
+  if (!c) return SZ_E_ARG;
+  for (int w = 0; w < REC_WRITERS; w++) { if (n_floe) n_floe[w] = (int32_t)c->rec.floe[w].frames.size(); if (n_grid) n_grid[w] = (int32_t)c->rec.grid[w].tsteps.size(); }
+  if (full) *full = c->rec.full;
+  return SZ_OK;
+}
+static const FloeFrame* rec_floe_frame(sz_ctx* c, int32_t writer, int32_t k) {
+  if (!c) return nullptr;
+  if (writer < 0 || writer >= REC_WRITERS || k < 0 || k >= (int)c->rec.floe[writer].frames.size()) { c->err = "no such floe frame (sz_output_frames)"; return nullptr; }
+  return &c->rec.floe[writer].frames[k];
+}
+int sz_floe_frame_info(sz_ctx* c, int32_t writer, int32_t k, int64_t* tstep, int64_t* M, int64_t* N, int64_t* n_ring_points, int64_t* n_ghost_links) {
+  const FloeFrame* f = rec_floe_frame(c, writer, k);
+  if (!f) return SZ_E_ARG;
+  if (tstep) *tstep = f->tstep;
+  if (M) *M = f->M;
+  if (N) *N = f->N;
+  if (n_ring_points) *n_ring_points = f->V;
+  if (n_ghost_links) *n_ghost_links = f->M - f->N;
+  return SZ_OK;
+}
+int sz_download_floe_frame(sz_ctx* c, int32_t writer, int32_t k, sz_floe_columns* f) {
+  const FloeFrame* fr = rec_floe_frame(c, writer, k);
+  if (!fr || !f) return SZ_E_ARG;
+  const FloeWriter& w = c->rec.floe[writer];
+  const FrameLayout L(w.mask, fr->M, fr->N, fr->V);
+  const long long M = fr->M, V = fr->V, G = fr->M - fr->N;
+  struct Part { void* dst; int sec; long long bytes; };
+  std::vector<Part> parts;
+  const ColTable<double*> dst = host_columns(*f);
+  for (int q = 0; q < MIG_NTAB; q++) parts.push_back({ dst.p[q], q, (long long)col_width(q) * M * 8 });
+  parts.push_back({ f->id, FR_ID, M * 8 }); parts.push_back({ f->ghost_id, FR_GHOST_ID, M * 8 }); parts.push_back({ f->status, FR_STATUS, M * 4 });
+  parts.push_back({ f->vert_off, FR_VOFF, (M + 1) * 4 }); parts.push_back({ f->vx, FR_VX, V * 8 }); parts.push_back({ f->vy, FR_VY, V * 8 });
+  parts.push_back({ f->ghost_off, FR_GOFF, (M + 1) * 4 }); parts.push_back({ f->ghost_idx, FR_GIDX, G * 4 });
+  for (const Part& p : parts) if (p.dst && L.off[p.sec] < 0) { c->err = "sz_download_floe_frame: a member is asked for that the writer's mask did not record"; return SZ_E_ARG; }
+  if (f->sub_off || f->sx || f->sy) { c->err = "sz_download_floe_frame: sub-floe points are not recorded"; return SZ_E_ARG; }
+  (void)hipSetDevice(c->device);
+  // the frame comes down in one copy
+  std::vector<char>& host = c->rec.host;
+  host.resize((size_t)L.total);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(host.data(), w.arena + fr->at, (size_t)L.total, hipMemcpyDeviceToHost));
+  for (const Part& p : parts) if (p.dst && p.bytes > 0) memcpy(p.dst, host.data() + L.off[p.sec], (size_t)p.bytes);
+  return SZ_OK;
+}
+int sz_download_grid_frame(sz_ctx* c, int32_t writer, int32_t k, int32_t* tstep, double* data) {
+  if (!c) return SZ_E_ARG;
+  if (writer < 0 || writer >= REC_WRITERS || k < 0 || k >= (int)c->rec.grid[writer].tsteps.size()) { c->err = "no such grid frame (sz_output_frames)"; return SZ_E_ARG; }
+  const GridWriter& g = c->rec.grid[writer];
+  const size_t n = g.outputs.size() * g.nx * g.ny;
+  if (tstep) *tstep = g.tsteps[k];
+  if (!data) return SZ_OK;
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(data, g.store + (size_t)k * n, n * sizeof(double), hipMemcpyDeviceToHost));
+  return SZ_OK;
+}
+int sz_clear_frames(sz_ctx* c) {
+  if (!c) return SZ_E_ARG;
+  for (int w = 0; w < REC_WRITERS; w++) { c->rec.floe[w].frames.clear(); c->rec.floe[w].used = 0; c->rec.grid[w].tsteps.clear(); }
+  c->rec.full = false;
+  return SZ_OK;
 }
 
 // what simplify_floes! (simplification.jl:339-378) would find to do, without downloading a floe

@@ -18,6 +18,7 @@
 #include "sz_ridgeraft.hpp"
 #include "sz_ridgeraft_tile.hpp"
 #include "sz_splice.hpp"
+#include "sz_record.hpp"
 
 using namespace sz;
 
@@ -185,6 +186,8 @@ struct sz_ctx {
   Pool rrt_allocs; RrDev rrt_hd{}; RrTileDev rrt_hg{}; int rrt_hw[4] = { 0, 0, 0, 0 }, rrt_hbad = 0; std::vector<int> rrt_cnt;
   std::vector<long long> rrt_i, rrt_j, rrt_rownum, rrt_rowkey; std::vector<int> rrt_k; std::vector<double> rrt_f;
   bool tile_split_gl = false;
+  // output recorder (sz_set_floe_output / sz_set_grid_output; sz_record.hpp): the writers, their frames in HBM, the workspace of the averages
+  Recorder rec;
   bool last_stopped = false;        // the last batch of resident steps ended on a stop request (tag, fracture candidate), not at its last step
   bool maybe_tagged = false;        // a parent may be non-active on the device (an upload said so, a batch ended on a tag, a process-mode call ran):
                                     // the next batch then runs its first step on its own (see sz_step)

@@ -1,0 +1,157 @@
+// sz_record.hpp — the output recorder: what the reference's writers take at an output step, kept in HBM until the host asks for it.
+// write_data! runs at the start of a step, right behind add_ghosts! (simulation.jl:102-105).  With a writer registered (sz_set_floe_output,
+// sz_set_grid_output) sz_step cuts its batch BEFORE every output step (sz_stops.hpp: StopRules::out_dts, the hook record()) and, at the cut:
+// detaches ghosts a process call left attached, sz_add_ghosts, one sz_k_frame_pack launch per due floe writer, the averages of
+// calc_eulerian_data! per due grid writer, sz_remove_ghosts -- and goes on.  Nothing crosses to the host but the counters.  Single contexts only.
+//
+// A FLOE FRAME is the list as add_ghosts! leaves it, in the columns the writer's mask selects.  The mask has one bit per column group of
+// sz_floe_columns, in struct order (frame_bit_names below): bits 0..27 the double columns (the three tensors 4 doubles per floe), 28 id,
+// 29 ghost_id, 30 status, 31 the rings (vert_off + vx + vy), 32 the ghost links (ghost_off + ghost_idx).  Not recorded: the sub-floe points,
+// floe.interactions and status.fuse_idx -- a writer that wants those keeps cutting its own batches.
+// A ghost is a deep copy of its parent (collisions.jl:881-901, floe_utils.jl:138), translated: the device keeps only the collision columns on a
+// ghost row, so the pack reads every column of a ghost row from the row State::parent names -- cx, cy, the ring and ghost_id apart, which are
+// the ghost's own.  A ghost row has no ghost links of its own (its ghost_off span is empty), as sz_download_floes reports it.
+// Layout of a frame in the writer's arena (FrameLayout): a header of 8 x int64 {tstep, M, N, n_ring_points, n_ghost_links, 0, 0, 0}, then the
+// selected sections in bit order, each padded to 8 bytes: doubles [M] or [M][4]; id, ghost_id int64 [M]; status int32 [M]; vert_off int32
+// [M + 1], frame-relative (vert_off[0] == 0), vx [V], vy [V] de-interleaved; ghost_off int32 [M + 1], ghost_idx int32 [M - N] in list numbers.
+// A GRID FRAME is nout * nx * ny doubles in the layout of sz_eulerian_data, in a store of max_frames frames; its timestep is kept on the host.
+// Limits: 4 floe and 4 grid writers; a frame that finds no room (the arena, max_frames) is not taken: the batch ends in front of that step with
+// `full` set (sz_output_frames), and no writer gets a frame of a step that not all due writers have room for.
+#pragma once
+#include "sz_kernels.hpp"
+#include "sz_columns.hpp"
+
+namespace sz {
+
+constexpr int REC_WRITERS = 4;
+// mask bits behind the double columns
+constexpr int FR_BIT_ID = MIG_NTAB, FR_BIT_GHOST_ID = FR_BIT_ID + 1, FR_BIT_STATUS = FR_BIT_ID + 2, FR_BIT_RINGS = FR_BIT_ID + 3, FR_BIT_LINKS = FR_BIT_ID + 4,
+              FR_NBITS = FR_BIT_ID + 5;
+// sections of a frame: the double columns, then
+constexpr int FR_ID = MIG_NTAB, FR_GHOST_ID = FR_ID + 1, FR_STATUS = FR_ID + 2, FR_VOFF = FR_ID + 3, FR_VX = FR_ID + 4, FR_VY = FR_ID + 5, FR_GOFF = FR_ID + 6,
+              FR_GIDX = FR_ID + 7, FR_NSEC = FR_ID + 8;
+constexpr size_t FR_HEADER = 8 * sizeof(long long);
+static_assert(FR_NBITS == 33, "frame mask: 28 double columns, id, ghost_id, status, rings, ghost links");
+// the mask bits by name, space-separated, each with a space in front (sz_debug_frame_bits)
+constexpr char FRAME_BIT_TAIL[] = " id ghost_id status rings ghost_links";
+
+// where the sections of a frame of M rows (N parents), V ring points lie: byte offsets from the frame's start, -1 = not recorded
+struct FrameLayout {
+  long long off[FR_NSEC]; long long total;
+  FrameLayout(unsigned long long mask, long long M, long long N, long long V) {
+    long long at = (long long)FR_HEADER;
+    auto take = [&](int sec, bool on, long long bytes) { off[sec] = on ? at : -1; if (on) at += (bytes + 7) & ~7ll; };
+    for (int k = 0; k < MIG_NTAB; k++) take(k, mask >> k & 1, (long long)col_width(k) * M * 8);
+    take(FR_ID, mask >> FR_BIT_ID & 1, M * 8); take(FR_GHOST_ID, mask >> FR_BIT_GHOST_ID & 1, M * 8); take(FR_STATUS, mask >> FR_BIT_STATUS & 1, M * 4);
+    const bool rings = mask >> FR_BIT_RINGS & 1, links = mask >> FR_BIT_LINKS & 1;
+    take(FR_VOFF, rings, (M + 1) * 4); take(FR_VX, rings, V * 8); take(FR_VY, rings, V * 8);
+    take(FR_GOFF, links, (M + 1) * 4); take(FR_GIDX, links, (M - N) * 4);
+    total = at;
+  }
+};
+
+// what one launch of sz_k_frame_pack is told
+struct FramePack {
+  const double* col[MIG_NTAB];
+  long long off[FR_NSEC];
+  char* dst;                      // the frame's start in the arena
+  int tstep, M, N, V;             // the host's counts behind sz_add_ghosts: every store lies inside the layout made from them
+};
+
+constexpr int FP_TPB = 256;
+constexpr int FP_SLICES = MIG_NTAB + 5;      // blockIdx.y: one slice per mask bit
+
+// One launch gathers a frame: slice y < MIG_NTAB double column y over all rows; then id, ghost_id, status; the rings (offsets made
+// frame-relative, vxy de-interleaved); the header and the ghost links (one workgroup: the offsets are a prefix sum over the parents' counts).
+__global__ void __launch_bounds__(FP_TPB) sz_k_frame_pack(State S, FramePack F) {
+  const int y = blockIdx.y, M = F.M, N = F.N;
+  const long long t0 = (long long)blockIdx.x * FP_TPB + threadIdx.x, stride = (long long)gridDim.x * FP_TPB;
+  auto src_row = [&](int r) { if (r < N) return r; const int p = S.parent[r]; return p >= 0 && p < N ? p : r; };
+  if (y < MIG_NTAB) {
+    if (F.off[y] < 0) return;
+    double* out = (double*)(F.dst + F.off[y]);
+    const bool own = y == COL_cx || y == COL_cy;
+    if (y < MIG_NSC) for (long long r = t0; r < M; r += stride) out[r] = F.col[y][own ? (int)r : src_row((int)r)];
+    else for (long long e = t0; e < 4ll * M; e += stride) out[e] = F.col[y][4ll * src_row((int)(e >> 2)) + (e & 3)];
+  } else if (y == FR_BIT_ID) {
+    if (F.off[FR_ID] < 0) return;
+    long long* out = (long long*)(F.dst + F.off[FR_ID]);
+    for (long long r = t0; r < M; r += stride) out[r] = S.id[src_row((int)r)];
+  } else if (y == FR_BIT_GHOST_ID) {
+    if (F.off[FR_GHOST_ID] < 0) return;
+    long long* out = (long long*)(F.dst + F.off[FR_GHOST_ID]);
+    for (long long r = t0; r < M; r += stride) out[r] = S.ghost_id[r];
+  } else if (y == FR_BIT_STATUS) {
+    if (F.off[FR_STATUS] < 0) return;
+    int* out = (int*)(F.dst + F.off[FR_STATUS]);
+    for (long long r = t0; r < M; r += stride) out[r] = S.status[src_row((int)r)];
+  } else if (y == FR_BIT_RINGS) {
+    if (F.off[FR_VOFF] < 0) return;
+    int* voff = (int*)(F.dst + F.off[FR_VOFF]);
+    double *vx = (double*)(F.dst + F.off[FR_VX]), *vy = (double*)(F.dst + F.off[FR_VY]);
+    const int v0 = S.voff[0];
+    for (long long r = t0; r <= M; r += stride) voff[r] = S.voff[r] - v0;
+    for (long long p = t0; p < F.V; p += stride) { const double2 q = S.vxy[v0 + p]; vx[p] = q.x; vy[p] = q.y; }
+  } else if (blockIdx.x == 0) {
+    const int G = M - N, t = threadIdx.x;
+    if (t == 0) {
+      long long* h = (long long*)F.dst;
+      h[0] = F.tstep; h[1] = M; h[2] = N; h[3] = F.V; h[4] = G; h[5] = h[6] = h[7] = 0;
+    }
+    if (F.off[FR_GOFF] < 0) return;
+    int *goff = (int*)(F.dst + F.off[FR_GOFF]), *gidx = (int*)(F.dst + F.off[FR_GIDX]);
+    // thread t owns the parents [lo, hi): their counts summed, the sums scanned over the workgroup, the offsets and links written
+    __shared__ int part[FP_TPB];
+    const int per = (N + FP_TPB - 1) / FP_TPB, lo = min(t * per, N), hi = min(lo + per, N);
+    auto count = [&](int i) { const int n = S.ngh[i]; return n < 0 ? 0 : n > MAX_GHOSTS ? MAX_GHOSTS : n; };
+    int sum = 0;
+    for (int i = lo; i < hi; i++) sum += count(i);
+    part[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < FP_TPB; d <<= 1) {
+      const int v = t >= d ? part[t - d] : 0;
+      __syncthreads();
+      part[t] += v;
+      __syncthreads();
+    }
+    int at = part[t] - sum;
+    for (int i = lo; i < hi; i++) {
+      goff[i] = at;
+      const int n = count(i);
+      for (int k = 0; k < n; k++, at++) if (at < G) gidx[at] = S.gh[i * MAX_GHOSTS + k];
+    }
+    const int tot = min(part[FP_TPB - 1], G);
+    for (int r = N + t; r <= M; r += FP_TPB) goff[r] = tot;          // (a ghost row has no links; entry M closes the list)
+    if (t == 0 && N == 0) goff[0] = 0;
+  }
+}
+
+// host side of one writer each; the device memory is the recorder's own (hipMalloc / hipFree when a writer is set, re-set or cleared away),
+// so frames outlive uploads and row edits
+struct FloeFrame { size_t at; int tstep, M, N, V; };
+struct FloeWriter {
+  int dt = 0; unsigned long long mask = 0;
+  char* arena = nullptr; size_t bytes = 0, used = 0;
+  std::vector<FloeFrame> frames;
+};
+struct GridWriter {
+  int dt = 0, nx = 0, ny = 0, max_frames = 0;
+  std::vector<double> xg, yg; std::vector<int> outputs;
+  double* store = nullptr;        // [max_frames][nout][nx][ny]
+  std::vector<int> tsteps;
+};
+// one device chunk that is kept and grows on demand: the persistent workspace of the recorded averages
+struct RecWork { char* p = nullptr; size_t bytes = 0; };
+struct Recorder {
+  FloeWriter floe[REC_WRITERS]; GridWriter grid[REC_WRITERS];
+  int dts[2 * REC_WRITERS] = { 0 };          // StopRules::out_dts: floe writers, then grid writers
+  bool any = false, full = false;
+  RecWork grid_work, entry_work;             // EulGrid's per-cell arrays; its entries and the sort's scratch
+  std::vector<char> host;                    // a frame on its way down
+  void refresh() {
+    any = false;
+    for (int w = 0; w < REC_WRITERS; w++) { dts[w] = floe[w].dt; dts[REC_WRITERS + w] = grid[w].dt; any = any || floe[w].dt > 0 || grid[w].dt > 0; }
+  }
+};
+
+}  // namespace sz

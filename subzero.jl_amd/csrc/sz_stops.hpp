@@ -12,7 +12,14 @@
 //   - behind a segment whose last step t ran, in that order: a fracture candidate ends the batch (steps_done counts t); on a welding step a tag
 //     ends it, removal set or not (the caller works through the step and removes the floes itself), and so does an overlap table that is not
 //     empty; elsewhere a tag goes to the removal pass, and ends the batch where removal is not set or the pass declines; else on at t + 1;
-//   - the batch's own last step is never looked at: the caller sees what kind of step the batch ended on and asks.
+//   - the batch's own last step is never looked at: the caller sees what kind of step the batch ended on and asks;
+//   - an output step of a registered writer (StopRules::out_dts, the recorder of sz_record.hpp) is a cut BEFORE the step, as in front of a
+//     ridge / raft step: write_data! runs at the start of a step, right behind add_ghosts! (simulation.jl:102-105).  record() takes the frames
+//     in front of the segment that starts there; the passes behind the segment that ends there run as behind any other cut.
+// Output frames: every output step at which a batch BEGINS A STEP has exactly one frame per due writer, taken before the step -- the batch's
+// first step and a ridge / raft step that is left pending included (its frame belongs to the start of the step; the next batch starts behind
+// it).  The batch's end step, tstep0 + steps_done, has none: the next call records it.  A frame that finds no room ends the batch there with
+// SZ_OK, the step not begun.
 // What differs between the two contexts is in the rules and the ops, nowhere else:
 //   - the single context's three-launch driver evaluates the criterion inside the batch, and a candidate arrives as a stop, as a tag does
 //     (SingleStops::fracture asks which only where a tag alone would let the batch go on).  On tiles the pass is collective, behind a cut;
@@ -35,6 +42,7 @@ struct StopRules {
   const int* weld_dts; int n_weld;      // WeldSettings.Δts, in the reference's order
   bool cut_on_fracture;                 // tiles: the passes are collective, the criterion's runs behind a segment, not inside the batch
   bool removal;                         // a tag goes to the removal pass
+  const int* out_dts = nullptr; int n_out = 0;      // the Δtout of the registered output writers (an entry <= 0: that writer is off); none by default
 };
 // the two call sites (sz_step on a tiled context has no pass for any of the four: removal is not engaged there, the others are refused)
 template <class Ctx> StopRules single_stop_rules(const Ctx& c) {
@@ -44,6 +52,11 @@ template <class Ctx> StopRules tile_stop_rules(const Ctx& c) { StopRules r = sin
 
 inline bool step_due(int dt, int tstep) { return dt > 0 && tstep % dt == 0; }
 inline bool is_fracture_step(int frac_dt, int tstep) { return step_due(frac_dt, tstep); }
+// an output step of any registered writer
+inline bool is_output_step(const StopRules& r, int tstep) {
+  for (int k = 0; k < r.n_out; k++) if (step_due(r.out_dts[k], tstep)) return true;
+  return false;
+}
 // the welding set of timestep tstep: the FIRST k with tstep % dts[k] == 0 (findfirst, simulation.jl:186-189), or -1
 inline int weld_set_at(const StopRules& r, int tstep) {
   for (int k = 0; k < r.n_weld; k++) if (tstep % r.weld_dts[k] == 0) return k;
@@ -57,19 +70,22 @@ inline Segment next_segment(const StopRules& r, int tstep, int remaining) {
   if (g.len == 0) return g;
   if (step_due(r.rr_dt, tstep)) { g.rr_step = true; g.len = 1; }
   else for (int s = 0; s + 1 < remaining; s++)
-    if (weld_set_at(r, tstep + s) >= 0 || (r.cut_on_fracture && is_fracture_step(r.frac_dt, tstep + s)) || step_due(r.rr_dt, tstep + s + 1)) { g.len = s + 1; break; }
+    if (weld_set_at(r, tstep + s) >= 0 || (r.cut_on_fracture && is_fracture_step(r.frac_dt, tstep + s)) || step_due(r.rr_dt, tstep + s + 1) ||
+        is_output_step(r, tstep + s + 1)) { g.len = s + 1; break; }
   g.fstep = is_fracture_step(r.frac_dt, tstep + g.len - 1); g.weld_set = weld_set_at(r, tstep + g.len - 1);
   return g;
 }
 
 // The batch [tstep0, tstep0 + nsteps) in segments.  Every hook of ops returns an SZ_* code, which ends the batch; flags are 0 / 1.  tag: a stop
 // request ended the segment early or was raised on its last step; fracture() and weld() take this rank's and return the settled one; last: the
-// batch's last step, nothing behind it is looked at; ok: the removal pass is done, the batch may go on.
+// batch's last step, nothing behind it is looked at; ok: the removal pass is done, the batch may go on; full: a frame of the output step found
+// no room, the batch ends in front of that step.
 template <class Ops>
 int run_with_stops(const StopRules& r, Ops& ops, int nsteps, int tstep0, int32_t* steps_done) {
   for (int done = 0; done < nsteps;) {
+    int ran = 0, rc = SZ_OK, pending = 0, tag = 0, full = 0;
+    if (is_output_step(r, tstep0 + done) && ((rc = ops.record(tstep0 + done, &full)) || full)) return rc;          // write_data!
     Segment g = next_segment(r, tstep0 + done, nsteps - done);
-    int ran = 0, rc = SZ_OK, pending = 0, tag = 0;
     if (g.rr_step) {
       if ((rc = ops.rr_step(tstep0 + done, done + 1 == nsteps, &pending, &tag)) || pending) return rc;
       ran = 1;

@@ -89,6 +89,7 @@ int sz_tile_enable(sz_ctx* c, const int64_t* gidx, double halo_capacity_factor, 
   leave_resident(c);
   State& S = c->S;
   if (c->hostM != c->hostN) { c->err = "sz_tile_enable needs a ghost-free upload"; return SZ_E_STATE; }
+  if (c->rec.any) { c->err = "sz_tile_enable: an output writer is set, and the recorder serves single contexts only (sz_set_floe_output / sz_set_grid_output with dt_out = 0)"; return SZ_E_STATE; }
   std::vector<long long>& ok = c->tile_gidx;
   ok.assign(c->hostN, 0);
   for (int i = 0; i < c->hostN; i++) ok[i] = gidx[i];
@@ -1954,6 +1955,8 @@ struct TileStops {
   }
   // done = the next segment starts from the compacted tiles (boxes, halo capacities and peers are gathered again at its first exchange)
   int remove(int* ok) { int nr = 0, nd = 0; return tile_remove_pass(c, ok, &nr, &nd); }
+  // (never asked: a tiled context has no output recorder, its rules carry no output interval)
+  int record(int, int* full) { *full = 0; return SZ_OK; }
 };
 }  // namespace
 

@@ -484,6 +484,121 @@ class World:
         finally:
             self.remove_ghosts()
 
+    # ---- output frames on the device (sz_set_floe_output / sz_set_grid_output): run() cuts before the writers' output steps, records what they
+    # would take -- the list as add_ghosts! leaves it -- into device memory and goes on; the frames are drained afterwards
+    @staticmethod
+    def frame_mask(columns=None):
+        """the columns_mask of set_floe_output for group names out of capi.FRAME_BITS (None: all)"""
+        names = capi.FRAME_BITS if columns is None else list(columns)
+        for n in names:
+            if n not in capi.FRAME_BITS:
+                raise SzError(f"{n} is not a column group of a floe frame")
+        return sum(1 << capi.FRAME_BITS.index(n) for n in set(names))
+
+    @staticmethod
+    def frame_bytes(mask, M, N, V):
+        """what a floe frame of M rows (N parents) and V ring points takes of its writer's arena (FrameLayout, csrc/sz_record.hpp): a header of
+        64 bytes, then the selected sections, each padded to 8 bytes"""
+        def pad(b):
+            return (b + 7) // 8 * 8
+        total = 64
+        for b, n in enumerate(capi.FRAME_BITS):
+            if not mask >> b & 1:
+                continue
+            if n in capi.DCOLS or n in ("id", "ghost_id"):
+                total += 8 * M
+            elif n in capi.TCOLS:
+                total += 32 * M
+            elif n == "status":
+                total += pad(4 * M)
+            elif n == "rings":
+                total += pad(4 * (M + 1)) + 16 * V
+            else:
+                total += pad(4 * (M + 1)) + pad(4 * (M - N))
+        return total
+
+    def set_floe_output(self, writer, dt_out, columns=None, arena_bytes=1 << 26):
+        """a FloeOutputWriter with Δtout = dt_out (0: off) that records the column groups `columns` (names out of capi.FRAME_BITS, or a ready
+        mask; None: all) into an arena of arena_bytes on the device"""
+        mask = columns if isinstance(columns, int) else self.frame_mask(columns)
+        self._chk(self.L.sz_set_floe_output(self.h, int(writer), int(dt_out), int(mask), int(arena_bytes)))
+        self._floe_masks = getattr(self, "_floe_masks", {})
+        self._floe_masks[int(writer)] = int(mask)
+
+    def set_grid_output(self, writer, dt_out, xg=None, yg=None, outputs=None, max_frames=64):
+        """a GridOutputWriter with Δtout = dt_out (0: off) on the grid lines xg, yg for the outputs named (EUL_OUTPUTS, default all), with room
+        for max_frames frames on the device"""
+        names = list(self.EUL_OUTPUTS if outputs is None else outputs)
+        for n in names:
+            if n not in self.EUL_OUTPUTS:
+                raise SzError(f"{n} is not a known grid output")
+        codes = np.array([self.EUL_OUTPUTS.index(n) for n in names], _I32)
+        xg = np.ascontiguousarray(xg if xg is not None else [0.0, 1.0], np.float64); yg = np.ascontiguousarray(yg if yg is not None else [0.0, 1.0], np.float64)
+        self._chk(self.L.sz_set_grid_output(self.h, int(writer), int(dt_out), len(xg) - 1, len(yg) - 1, capi.ptr(xg), capi.ptr(yg), len(names),
+                                            capi.ptr(codes, capi._ip), int(max_frames)))
+        self._grid_writers = getattr(self, "_grid_writers", {})
+        self._grid_writers[int(writer)] = (len(names), len(xg) - 1, len(yg) - 1)
+
+    def output_frames(self):
+        """(frames held per floe writer, frames held per grid writer, full): full = the last run() ended in front of an output step whose
+        frame found no room"""
+        nf = np.zeros(capi.REC_WRITERS, _I32); ng = np.zeros(capi.REC_WRITERS, _I32); full = C.c_int32(0)
+        self._chk(self.L.sz_output_frames(self.h, capi.ptr(nf, capi._ip), capi.ptr(ng, capi._ip), C.byref(full)))
+        return [int(v) for v in nf], [int(v) for v in ng], bool(full.value)
+
+    def floe_frame(self, writer, k, members=None):
+        """floe frame k of a writer: a dict with tstep, M, N and the recorded columns as arrays in the layout of load_columns (the rings as
+        vert_off, vx, vy; the ghost links as ghost_off, ghost_idx).  members: struct members to ask for instead of everything recorded."""
+        info = [C.c_int64(0) for _ in range(5)]
+        self._chk(self.L.sz_floe_frame_info(self.h, int(writer), int(k), *(C.byref(v) for v in info)))
+        tstep, M, N, V, G = (int(v.value) for v in info)
+        if members is None:
+            members = []
+            for b, n in enumerate(capi.FRAME_BITS):
+                if self._floe_masks[int(writer)] >> b & 1:
+                    members += capi.FRAME_MEMBERS.get(n, [n])
+        col = {}
+        for n in members:
+            if n in capi.DCOLS:
+                col[n] = np.zeros(M)
+            elif n in capi.TCOLS:
+                col[n] = np.zeros((M, 4))
+            elif n in ("id", "ghost_id"):
+                col[n] = np.zeros(M, _I64)
+            elif n == "status":
+                col[n] = np.zeros(M, _I32)
+            elif n in ("vert_off", "ghost_off", "sub_off"):
+                col[n] = np.zeros(M + 1, _I32)
+            elif n in ("vx", "vy", "sx", "sy"):
+                col[n] = np.zeros(max(V, 1))
+            elif n == "ghost_idx":
+                col[n] = np.zeros(max(G, 1), _I32)
+            else:
+                raise SzError(f"{n} is not a member of sz_floe_columns")
+        keep = []
+        f = capi.SzFloeColumns()
+        for n, a in col.items():
+            keep.append(a)
+            setattr(f, n, capi.ptr(a.reshape(-1), capi._lp if a.dtype == _I64 else capi._ip if a.dtype == _I32 else capi._dp))
+        self._chk(self.L.sz_download_floe_frame(self.h, int(writer), int(k), C.byref(f)))
+        for n in ("vx", "vy"):
+            if n in col:
+                col[n] = col[n][:V]
+        if "ghost_idx" in col:
+            col["ghost_idx"] = col["ghost_idx"][:G]
+        col.update(tstep=tstep, M=M, N=N)
+        return col
+
+    def grid_frame(self, writer, k):
+        """grid frame k of a writer: (tstep, array [nout, nx, ny])"""
+        nout, nx, ny = self._grid_writers[int(writer)]
+        t = C.c_int32(0); out = np.zeros((nout, nx, ny))
+        self._chk(self.L.sz_download_grid_frame(self.h, int(writer), int(k), C.byref(t), capi.ptr(out)))
+        return int(t.value), out
+
+    def clear_frames(self):
+        self._chk(self.L.sz_clear_frames(self.h))
+
     def simplify_check(self, max_vertices=30, min_floe_area=1e6, min_floe_height=0.1):
         """counts of what simplify_floes! (simplification.jl:339-378) would act on: remove, fuse, rings over
         max_vertices, floes under the minimum area / height; all zero = the pass is a no-op"""
@@ -565,7 +680,10 @@ class World:
         and timestep_ridging_rafting! (ghosts in the list), ridgeraft_candidates() gives the table, and finish_step() runs the rest of the step
         after the host's ridging and rafting; ridge / raft steps with an empty table are run through, and ridgeraft_draws() says by how many
         rand(rng, FT) calls the host's rng has to advance for them;
-        stop_on_tags=False runs on regardless (measurement / soak runs)."""
+        stop_on_tags=False runs on regardless (measurement / soak runs).
+        With an output writer set (set_floe_output, set_grid_output) the batch is also cut BEFORE each of its output steps, the frames are
+        recorded on the device and the batch goes on: every output step at which the batch begins a step has one frame per due writer, its end
+        step has none (the next run() records it); a frame that finds no room ends the batch in front of that step (output_frames()[2])."""
         self._push()
         flags = self._flags(collisions_on, coupling_on)
         if not stop_on_tags:
