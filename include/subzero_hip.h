@@ -805,6 +805,24 @@ int sz_debug_sample_fields(sz_ctx *ctx, int32_t n, const double *x, const double
 /* test hook: 1 when the last sz_step batch ran as pipelined steps (two launches per timestep: csrc/sz_pipeline.hpp), 0 otherwise; with an
    output writer set (sz_set_floe_output / sz_set_grid_output): 1 when any of the segments between its cuts did */
 int sz_debug_pipelined(sz_ctx *ctx);
+/* test hook: where the last sz_step batch took collision_force, collision_trq, overarea and the stress sums from: 0 the serial double sums of
+   the row assembly (process mode's; batches with collisions off), 1 the fixed-point totals with the rows assembled inside every step, 2 the
+   fixed-point totals with the rows of the batch's last step assembled once behind it */
+int sz_debug_totals_mode(sz_ctx *ctx);
+/* test hook: the arithmetic of the fixed-point totals (csrc/sz_geom.hpp: fx_force_exp, fx_lever_exp, fx_area_exp, fx_split, fx_join) on given
+   numbers, by the device functions the step kernels call; no floe is needed.  Thread t of nthreads (1..1024) splits the values
+   v[perm[t]], v[perm[t + nthreads]], ... (n <= 4096, perm a permutation of 0..n-1) at exponent E, sums its words and adds them to ONE pair of
+   words with the narrow phase's atomics.  E by mode & 7: 0 the argument e; 1 fx_force_exp(kexp = e, area, height); 2 that + fx_lever_exp(rmax);
+   3 fx_area_exp(area); 4 fx_lever_exp(rmax); with mode & 8 kexp is the context's own (from the E and mu of sz_set_params) instead of e.
+   words2 = { sum of the high words, sum of the low words }, flags2 = { 1 if a value was out of range (it adds nothing), E },
+   joined = fx_join(words2, E). */
+int sz_debug_fx_totals(sz_ctx *ctx, int32_t n, const double *v, const int32_t *perm, int32_t nthreads, int32_t mode, int32_t e, double area,
+                       double height, double rmax, int64_t *words2, int32_t *flags2, double *joined);
+/* test hook: what one interaction row row5 = { xforce, yforce, xpoint, ypoint, overlap } adds to the totals of a floe with centroid (cx, cy)
+   (fx_word; sign +1: the pair's first floe, -1: its second) at force, area and lever exponents eF, eA, eL: words14 = the high words
+   0 xforce, 1 yforce, 2 (x-cx) fx, 3 (y-cy) fx, 4 (x-cx) fy, 5 (y-cy) fy, 6 overlap, then their seven low words; bad: 1 if one was out of range */
+int sz_debug_fx_word(sz_ctx *ctx, const double *row5, double sign, double cx, double cy, int32_t eF, int32_t eA, int32_t eL, int64_t *words14,
+                     int32_t *bad);
 /* diagnostic build (-DSZ_STAMPS) only: stamp log of one lane group of the narrow phase
    (out512[0] = entries, then (stage << 48) | cycles since the wave started) */
 int sz_debug_stamps(sz_ctx *ctx, long long *out512);

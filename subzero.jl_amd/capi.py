@@ -96,6 +96,7 @@ EXPORTS = [
     "sz_tile_download_rows", "sz_tile_splice_floes", "sz_tile_download_rows_f32", "sz_tile_splice_floes_f32",
     "sz_set_floe_output", "sz_set_grid_output", "sz_output_frames", "sz_floe_frame_info", "sz_download_floe_frame", "sz_download_grid_frame",
     "sz_clear_frames", "sz_debug_next_segment_out", "sz_debug_frame_bits",
+    "sz_debug_totals_mode", "sz_debug_fx_totals", "sz_debug_fx_word",
 ]
 
 # the column groups of sz_set_floe_output's mask, bit 0 first (sz_debug_frame_bits; tests/test_output_stops_cpu.py holds the list to the library's)
@@ -258,6 +259,9 @@ def load(build_if_missing=True):
     L.sz_debug_next_segment_out.argtypes = [C.c_int32] * 6 + [_ip, C.c_int32, _ip, _ip]
     L.sz_debug_frame_bits.restype = C.c_char_p
     L.sz_debug_frame_bits.argtypes = []
+    L.sz_debug_totals_mode.argtypes = [C.c_void_p]
+    L.sz_debug_fx_totals.argtypes = [C.c_void_p, C.c_int32, _dp, _ip, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _lp, _ip, _dp]
+    L.sz_debug_fx_word.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _lp, _ip]
     for n in EXPORTS:
         if n not in ("sz_create", "sz_destroy", "sz_last_error", "sz_version", "sz_debug_column_names", "sz_debug_frame_bits"):
             getattr(L, n).restype = C.c_int

@@ -30,6 +30,7 @@
 #include "sz_splice_tile.hpp"
 #include "sz_stops.hpp"
 #include "sz_record.hpp"
+#include "sz_fxdebug.hpp"
 #include <rocprim/rocprim.hpp>      // device radix sort of the output-grid entries (sz_eulerian_data)
 #include "sz_ctx.hpp"
 #include "sz_comm.hpp"
@@ -1307,6 +1308,52 @@ int sz_debug_sample_fields(sz_ctx* c, int32_t n, const double* x, const double* 
   return SZ_OK;
 }
 
+// the fixed-point totals' own arithmetic on given numbers (sz_fxdebug.hpp): no floe, no step kernel
+int sz_debug_fx_totals(sz_ctx* c, int32_t n, const double* v, const int32_t* perm, int32_t nthreads, int32_t mode, int32_t e, double area, double height,
+                       double rmax, int64_t* words2, int32_t* flags2, double* joined) {
+  const int how = mode & 7;
+  if (!c || n < 0 || n > 4096 || nthreads < 1 || nthreads > 1024 || (n > 0 && (!v || !perm)) || (mode & ~15) || how > FXD_LEVER || !words2 || !flags2 || !joined) return SZ_E_ARG;
+  for (int k = 0; k < n; k++) if (perm[k] < 0 || perm[k] >= n) return SZ_E_ARG;
+  if (mode & FXD_CTX_KEXP) e = force_scale_exp(c);
+  (void)hipSetDevice(c->device);
+  PoolGuard pool;
+  double *dv, *dj; int *dp, *df; long long* dw;
+  int rc;
+  if ((rc = dalloc(c, &dv, n, pool.v)) || (rc = dalloc(c, &dp, n, pool.v)) || (rc = dalloc(c, &dw, 2, pool.v)) || (rc = dalloc(c, &df, 2, pool.v)) ||
+      (rc = dalloc(c, &dj, 1, pool.v))) return rc;
+  if (n > 0) { H2D(dv, v, n, double); H2D(dp, perm, n, int); }
+  HIPCHK(c, hipMemsetAsync(dw, 0, 2 * sizeof(long long), c->stream));
+  HIPCHK(c, hipMemsetAsync(df, 0, 2 * sizeof(int), c->stream));
+  hipLaunchKernelGGL(sz_k_debug_fx_add, dim3(grid_for(nthreads, 256)), dim3(256), 0, c->stream, n, dv, dp, nthreads, how, e, area, height, rmax, dw, df);
+  hipLaunchKernelGGL(sz_k_debug_fx_read, dim3(1), dim3(64), 0, c->stream, how, e, area, height, rmax, dw, df, dj);
+  long long hw[2]; int hf[2];
+  HIPCHK(c, hipMemcpyAsync(hw, dw, sizeof(hw), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hf, df, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(joined, dj, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  words2[0] = hw[0]; words2[1] = hw[1]; flags2[0] = hf[0]; flags2[1] = hf[1];
+  return SZ_OK;
+}
+
+int sz_debug_fx_word(sz_ctx* c, const double* row5, double sign, double cx, double cy, int32_t eF, int32_t eA, int32_t eL, int64_t* words14, int32_t* bad) {
+  if (!c || !row5 || !words14 || !bad) return SZ_E_ARG;
+  (void)hipSetDevice(c->device);
+  PoolGuard pool;
+  double* dr; long long* dw; int* df;
+  int rc;
+  if ((rc = dalloc(c, &dr, 5, pool.v)) || (rc = dalloc(c, &dw, 14, pool.v)) || (rc = dalloc(c, &df, 1, pool.v))) return rc;
+  H2D(dr, row5, 5, double);
+  HIPCHK(c, hipMemsetAsync(df, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(sz_k_debug_fx_word, dim3(1), dim3(64), 0, c->stream, dr, sign, cx, cy, eF, eA, eL, dw, df);
+  long long hw[14]; int hb = 0;
+  HIPCHK(c, hipMemcpyAsync(hw, dw, sizeof(hw), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&hb, df, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 14; k++) words14[k] = hw[k];
+  *bad = hb;
+  return SZ_OK;
+}
+
 // ---------------------------------------------------------------- processes
 int sz_add_ghosts(sz_ctx* c) {
   if (!c || !c->have_floes) return SZ_E_STATE;
@@ -1929,6 +1976,7 @@ int sz_debug_fracture_mean(sz_ctx* c, double* mean_h, double* p) {
 }
 
 int sz_debug_pipelined(sz_ctx* c) { return c ? c->last_pipelined : 0; }
+int sz_debug_totals_mode(sz_ctx* c) { return c ? c->last_totals_mode : 0; }
 
 // The side effects of a batch's start, from the plan: the stop words, the cells, the ghosts' form, the buffers and rings the steps read, the
 // records and totals.  The per-batch modes it sets are put back by the caller's BatchModes scope.  *gl0: the candidate list the batch starts on.
@@ -1954,7 +2002,7 @@ static int batch_enter(sz_ctx* c, const BatchPlan& p, int* gl0) {
   if (p.cr && !p.pipe) seed_records(c, c->S, c->hostN);
   // the ghosts of the first step, from the parents as they lie (after the rings are in the batch's form)
   if (p.gi && !p.pipe && !p.own_first_ghosts) { if (int rc = reseed_inline_ghosts(c, 0)) return rc; }
-  c->S.facc = p.facc_on ? c->facc_buf : nullptr; c->S.kexp = force_scale_exp(c); c->reduce_mode = p.reduce_mode;
+  c->S.facc = p.facc_on ? c->facc_buf : nullptr; c->S.kexp = force_scale_exp(c); c->reduce_mode = p.reduce_mode; c->last_totals_mode = p.reduce_mode;
   if (p.facc_on && !p.pipe) { if (int rc = clear_totals(c)) return rc; }          // (a pipelined batch clears them with the rest of its prologue: one launch)
   if (p.frac) { if (int rc = frac_ensure(c)) return rc; }
   return SZ_OK;

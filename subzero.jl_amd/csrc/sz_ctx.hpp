@@ -135,6 +135,7 @@ struct sz_ctx {
   // bit 1: the batch's last step); reduce_mode: 0 sz_k_inter_fill does everything inside the step (process mode), 1 it only assembles rows inside
   // the step, 2 it is left out of the steps and runs once behind the batch (the reduce-free steps)
   long long* facc_buf = nullptr; int acc_mode = 0, reduce_mode = 0;
+  int last_totals_mode = 0;         // reduce_mode of the last sz_step batch (sz_debug_totals_mode)
   // pipelined resident steps (sz_pipeline.hpp): the second set of what is double-buffered by step parity.  pb[0] is what the upload carved
   // (State::vxy, crec_buf, the cell lists, the work list, the ghost links), pb[1] its twin; gpar: the set that holds the context's state -- c->S
   // points at pb[gpar]'s buffers, the records apart: State::crec is a batch mode, the set's records are crec_buf (own_set_carved, pipe_adopt).

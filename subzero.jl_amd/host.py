@@ -448,6 +448,28 @@ class World:
         """the last run() batch ran as pipelined steps (two launches per timestep)"""
         return bool(self.L.sz_debug_pipelined(self.h))
 
+    def totals_mode(self):
+        """where the last run() batch took the collision totals from: 0 serial double sums, 1 / 2 the fixed-point totals (sz_debug_totals_mode)"""
+        return int(self.L.sz_debug_totals_mode(self.h))
+
+    def fx_totals(self, v, e=0, mode=0, area=1.0, height=1.0, rmax=1.0, perm=None, nthreads=1):
+        """test hook (sz_debug_fx_totals): the values v split and added to one pair of fixed-point words by nthreads threads in the order perm;
+        mode 0: at exponent e, 1: fx_force_exp(kexp=e, area, height), 2: + fx_lever_exp(rmax), 3: fx_area_exp(area), 4: fx_lever_exp(rmax);
+        + 8: kexp from this world's E and mu.  Returns (hi, lo, bad, exponent, joined value)."""
+        v = np.ascontiguousarray(v, np.float64)
+        perm = np.ascontiguousarray(np.arange(len(v)) if perm is None else perm, _I32)
+        words = np.zeros(2, _I64); flags = np.zeros(2, _I32); joined = np.zeros(1)
+        self._chk(self.L.sz_debug_fx_totals(self.h, len(v), capi.ptr(v), capi.ptr(perm, capi._ip), int(nthreads), int(mode), int(e), float(area),
+                                            float(height), float(rmax), capi.ptr(words, capi._lp), capi.ptr(flags, capi._ip), capi.ptr(joined)))
+        return int(words[0]), int(words[1]), int(flags[0]), int(flags[1]), float(joined[0])
+
+    def fx_word(self, row5, sign, cx, cy, eF, eA, eL):
+        """test hook (sz_debug_fx_word): the seven high and seven low words one row {fx, fy, px, py, overlap} adds to a floe's totals, and the range flag"""
+        row = np.ascontiguousarray(row5, np.float64); assert row.shape == (5,)
+        words = np.zeros(14, _I64); bad = C.c_int32(0)
+        self._chk(self.L.sz_debug_fx_word(self.h, capi.ptr(row), float(sign), float(cx), float(cy), int(eF), int(eA), int(eL), capi.ptr(words, capi._lp), C.byref(bad)))
+        return [int(w) for w in words[:7]], [int(w) for w in words[7:]], int(bad.value)
+
     def warn_counts(self):
         s = self.stats()
         return np.array([s["warn_height"], s["warn_force"], s["warn_vel"], s["warn_xi"]], _I64)
