@@ -761,7 +761,7 @@ int sz_simplify_check(sz_ctx *ctx, int32_t max_vertices, double min_floe_area, d
    Up to 4 floe writers and 4 grid writers, each with its own dt_out (FloeOutputWriter / GridOutputWriter Δtout; tstep % dt_out == 0 is an
    output step).  dt_out == 0 turns that writer off, which is the default: not a launch more, and no allocation.  dt_out < 0 or a writer
    index outside 0..3: SZ_E_ARG.  Setting a writer again frees its frames.  Single contexts only: both setters return SZ_E_STATE on a tiled
-   context, sz_tile_enable returns SZ_E_STATE on a context with a writer set.
+   context, sz_tile_enable returns SZ_E_STATE on a context with a writer set through them (a tiled context has setters of its own, below).
    sz_set_floe_output: columns_mask has one bit per column group of sz_floe_columns, in struct order (sz_debug_frame_bits): bits 0..27 the 28
      double columns cx .. strain (tensors 4 per floe), 28 id, 29 ghost_id, 30 status, 31 the rings (vert_off + vx + vy), 32 the ghost links
      (ghost_off + ghost_idx).  NOT recorded: the sub-floe points, floe.interactions and status.fuse_idx -- a host writer that wants them keeps
@@ -790,6 +790,39 @@ int sz_floe_frame_info(sz_ctx *ctx, int32_t writer, int32_t k, int64_t *tstep, i
 int sz_download_floe_frame(sz_ctx *ctx, int32_t writer, int32_t k, sz_floe_columns *cols);
 int sz_download_grid_frame(sz_ctx *ctx, int32_t writer, int32_t k, int32_t *tstep, double *data);
 int sz_clear_frames(sz_ctx *ctx);
+
+/* ---- output frames of a tiled run (csrc/sz_record_tile.hpp; DESIGN.md §9i, "Tiled contexts"): with a writer set through the two setters below
+   sz_tile_run cuts its batch before every output step and records there, collectively, and goes on -- the rule at the ends, `full`, the limits
+   and the draining calls are the single context's, above.  The setters take the single setters' arguments and checks, are local, are to be
+   called alike on every rank, and need a tiled context (sz_tile_enable; SZ_E_STATE otherwise: a single context takes sz_set_floe_output).
+   Writers set through them do not stop sz_tile_enable, so they and their frames survive a re-tile, sz_tile_migrate, sz_tile_splice_floes and
+   sz_tile_remove_floes; they are cleared and freed as on the single context.
+   At a record point: halo rows and ghosts are dropped, sz_add_ghosts makes the ghosts of the OWNED parents (which ghosts a parent gets depends
+   on that parent alone), ONE all-gather of {error / full bits, M, N, n_ring_points} per rank, one pack launch per due floe writer; with a grid
+   writer due, ONE all-reduce over the per-cell sums of all grid writers due at that step; sz_remove_ghosts.  An error of one rank is every
+   rank's.  If any rank has no room for any due frame no rank records that step: every rank ends in front of it with SZ_OK and `full` set.
+   A TILE FLOE FRAME is the floe frame above over the rank's own rows -- its owned parents, then their ghosts; ghost_idx in local row numbers --
+   with every row's ORDER KEY kept beside it: a parent's key is its global number, a ghost's (pass << 40) + 4 * parent key + k.  The rows of all
+   ranks sorted by key are the single context's frame of that step, bit for bit in every section.  A GRID FRAME is held by every rank: the sums
+   over the ranks differ from the single context's serial sums by round-off (two ranks: by the order of one addition, i.e. not at all).
+   The single context's calls work on a tiled context as they are, locally: sz_output_frames, sz_floe_frame_info (local counts),
+   sz_download_floe_frame (the tile frame: local rows), sz_download_grid_frame, sz_clear_frames.
+   sz_tile_floe_frame_keys: the M order keys of tile frame k (local).  sz_tile_floe_frame_info: the header of the MERGED frame -- global counts,
+   from the ranks' counts kept with the frame at the record point; local, no rank waits for another.  sz_tile_download_floe_frame: the merged
+   frame, in the members of cols as sz_download_floe_frame fills them, sized from sz_tile_floe_frame_info.  COLLECTIVE: every rank calls it for
+   the same writer and k; cols may be NULL on a rank that only takes part.  What a rank prepares alone (the frame exists, the members were
+   recorded, its scratch) is agreed before the gather: an error of one rank is returned by every rank, nobody is left waiting.  The frames
+   travel between device buffers (RCCL) and are merged on the device; the merged frame comes down in one copy.
+   sz_tile_run refuses, with SZ_E_STATE and no step run: writers whose settings differ between the ranks (one gather of a digest, before any
+   other collective: the message names the writer); two-way coupling with a tile writer set; a context without sz_tile_setup and a
+   communicator.  sz_step on a context with tile writers set returns SZ_E_STATE: sz_tile_run records. */
+int sz_tile_set_floe_output(sz_ctx *ctx, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes);
+int sz_tile_set_grid_output(sz_ctx *ctx, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double *xg, const double *yg,
+                            int32_t nout, const int32_t *outputs, int32_t max_frames);
+int sz_tile_floe_frame_keys(sz_ctx *ctx, int32_t writer, int32_t k, int64_t *keys);
+int sz_tile_floe_frame_info(sz_ctx *ctx, int32_t writer, int32_t k, int64_t *tstep, int64_t *M, int64_t *N, int64_t *n_ring_points,
+                            int64_t *n_ghost_links);
+int sz_tile_download_floe_frame(sz_ctx *ctx, int32_t writer, int32_t k, sz_floe_columns *cols);
 
 /* test hook: which_vertices_match_points(points, region) (floe_utils.jl:331-352) as the narrow phase evaluates it, on
    given points (<= 64) and a given closed region ring; idx = sorted 0-based vertex indices */

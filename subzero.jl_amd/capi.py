@@ -96,6 +96,7 @@ EXPORTS = [
     "sz_tile_download_rows", "sz_tile_splice_floes", "sz_tile_download_rows_f32", "sz_tile_splice_floes_f32",
     "sz_set_floe_output", "sz_set_grid_output", "sz_output_frames", "sz_floe_frame_info", "sz_download_floe_frame", "sz_download_grid_frame",
     "sz_clear_frames", "sz_debug_next_segment_out", "sz_debug_frame_bits",
+    "sz_tile_set_floe_output", "sz_tile_set_grid_output", "sz_tile_floe_frame_keys", "sz_tile_floe_frame_info", "sz_tile_download_floe_frame",
     "sz_debug_totals_mode", "sz_debug_fx_totals", "sz_debug_fx_word",
 ]
 
@@ -256,6 +257,11 @@ def load(build_if_missing=True):
     L.sz_download_floe_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SzFloeColumns)]
     L.sz_download_grid_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp]
     L.sz_clear_frames.argtypes = [C.c_void_p]
+    L.sz_tile_set_floe_output.argtypes = L.sz_set_floe_output.argtypes
+    L.sz_tile_set_grid_output.argtypes = L.sz_set_grid_output.argtypes
+    L.sz_tile_floe_frame_keys.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _lp]
+    L.sz_tile_floe_frame_info.argtypes = L.sz_floe_frame_info.argtypes
+    L.sz_tile_download_floe_frame.argtypes = L.sz_download_floe_frame.argtypes
     L.sz_debug_next_segment_out.argtypes = [C.c_int32] * 6 + [_ip, C.c_int32, _ip, _ip]
     L.sz_debug_frame_bits.restype = C.c_char_p
     L.sz_debug_frame_bits.argtypes = []

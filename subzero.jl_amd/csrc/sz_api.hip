@@ -754,7 +754,7 @@ void sz_destroy(sz_ctx* c) {
   (void)hipFree(c->d_stats); (void)hipFree(c->S.acc);
   (void)hipFree(c->frac_d); (void)hipFree(c->frac_flag); (void)hipFree(c->frac_idx);
   free_pool(c->weld_allocs); free_pool(c->weldt_allocs); (void)hipFree(c->weld_tmp); free_pool(c->rr_allocs); free_pool(c->rrt_allocs);
-  free_pool(c->rm_allocs); free_pool(c->sp_allocs); free_pool(c->spt_allocs);
+  free_pool(c->rm_allocs); free_pool(c->sp_allocs); free_pool(c->spt_allocs); free_pool(c->rect_allocs);
   free_pool(c->frac_allocs);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
   (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2);
@@ -3082,6 +3082,11 @@ int sz_step(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t coupl
     c->err = "sz_step on a tiled context has no ridge / raft candidate pass (a tile's rows are named by order keys, its ghosts' partners live on other ranks): sz_tile_run, or sz_set_ridgeraft(0)";
     return SZ_E_STATE;
   }
+  if (c && c->rec.any_tile) {
+    if (steps_done) *steps_done = 0;
+    c->err = "sz_step: an output writer of a tiled context is set (sz_tile_set_floe_output / sz_tile_set_grid_output): its record point is collective, sz_tile_run takes it";
+    return SZ_E_STATE;
+  }
   const bool rec = c && c->rec.any && !c->S.tiled;
   const bool through = (flags & SZ_NO_STOP) != 0;
   const bool weld = c && !through && !c->weld_dts.empty(), rem = c && !through && c->rm_on && !c->S.tiled, rr = c && !through && c->rr_on;
@@ -3374,34 +3379,44 @@ static void rec_free_floe(FloeWriter& w) { (void)hipFree(w.arena); w = FloeWrite
 static void rec_free_grid(GridWriter& g) { (void)hipFree(g.store); g = GridWriter{}; }
 static void rec_free_all(sz_ctx* c) {
   for (int w = 0; w < REC_WRITERS; w++) { rec_free_floe(c->rec.floe[w]); rec_free_grid(c->rec.grid[w]); }
-  (void)hipFree(c->rec.grid_work.p); (void)hipFree(c->rec.entry_work.p);
+  (void)hipFree(c->rec.grid_work.p); (void)hipFree(c->rec.entry_work.p); (void)hipFree(c->rec.part_work.p);
   c->rec = Recorder{};
 }
-static int rec_setter_checks(sz_ctx* c, int32_t writer, int32_t dt_out) {
+// the setters of the single context (tile = false) and of a tiled one (sz_tile_set_*): the same arguments and checks, each kind refuses the other's context
+static int rec_setter_checks(sz_ctx* c, int32_t writer, int32_t dt_out, bool tile) {
   if (!c) return SZ_E_ARG;
   if (writer < 0 || writer >= REC_WRITERS) { c->err = "output writer index out of range (0..3)"; return SZ_E_ARG; }
   if (dt_out < 0) { c->err = "output interval must not be negative (0 turns the writer off)"; return SZ_E_ARG; }
-  if (c->S.tiled) { c->err = "the output recorder serves single contexts only"; return SZ_E_STATE; }
+  if (c->S.tiled && !tile) { c->err = "sz_set_floe_output / sz_set_grid_output serve single contexts only: a tiled context takes sz_tile_set_floe_output / sz_tile_set_grid_output"; return SZ_E_STATE; }
+  if (!c->S.tiled && tile) { c->err = "sz_tile_set_floe_output / sz_tile_set_grid_output need a tiled context (sz_tile_enable): a single context takes sz_set_floe_output / sz_set_grid_output"; return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SZ_OK;
 }
-int sz_set_floe_output(sz_ctx* c, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes) {
-  if (int rc = rec_setter_checks(c, writer, dt_out)) return rc;
+static int rec_set_floe(sz_ctx* c, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes, bool tile) {
+  if (int rc = rec_setter_checks(c, writer, dt_out, tile)) return rc;
   if (dt_out > 0 && (columns_mask == 0 || (columns_mask >> FR_NBITS) != 0)) { c->err = "sz_set_floe_output: the mask selects no column group, or one that does not exist (sz_debug_frame_bits)"; return SZ_E_ARG; }
   if (dt_out > 0 && arena_bytes < (int64_t)FR_HEADER) { c->err = "sz_set_floe_output: the arena holds no frame"; return SZ_E_ARG; }
   FloeWriter& w = c->rec.floe[writer];
   rec_free_floe(w);
   if (dt_out > 0) {
     HIPCHK(c, hipMalloc((void**)&w.arena, (size_t)arena_bytes));
-    w.dt = dt_out; w.mask = columns_mask; w.bytes = (size_t)arena_bytes;
+    w.dt = dt_out; w.mask = columns_mask; w.bytes = (size_t)arena_bytes; w.tile = tile;
   }
   c->rec.refresh();
   return SZ_OK;
 }
+static int rec_set_grid(sz_ctx* c, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double* xg, const double* yg, int32_t nout,
+                        const int32_t* outputs, int32_t max_frames, bool tile);
+int sz_set_floe_output(sz_ctx* c, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes) { return rec_set_floe(c, writer, dt_out, columns_mask, arena_bytes, false); }
+int sz_tile_set_floe_output(sz_ctx* c, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes) { return rec_set_floe(c, writer, dt_out, columns_mask, arena_bytes, true); }
 int sz_set_grid_output(sz_ctx* c, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double* xg, const double* yg, int32_t nout,
-                       const int32_t* outputs, int32_t max_frames) {
-  if (int rc = rec_setter_checks(c, writer, dt_out)) return rc;
+                       const int32_t* outputs, int32_t max_frames) { return rec_set_grid(c, writer, dt_out, nx, ny, xg, yg, nout, outputs, max_frames, false); }
+int sz_tile_set_grid_output(sz_ctx* c, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double* xg, const double* yg, int32_t nout,
+                            const int32_t* outputs, int32_t max_frames) { return rec_set_grid(c, writer, dt_out, nx, ny, xg, yg, nout, outputs, max_frames, true); }
+static int rec_set_grid(sz_ctx* c, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double* xg, const double* yg, int32_t nout,
+                        const int32_t* outputs, int32_t max_frames, bool tile) {
+  if (int rc = rec_setter_checks(c, writer, dt_out, tile)) return rc;
   if (dt_out > 0) {
     if (int rc = eul_check_lines(c, nx, ny, xg, yg)) return rc;
     if (nout < 1 || !outputs || max_frames < 1) return SZ_E_ARG;
@@ -3411,7 +3426,7 @@ int sz_set_grid_output(sz_ctx* c, int32_t writer, int32_t dt_out, int32_t nx, in
   rec_free_grid(g);
   if (dt_out > 0) {
     HIPCHK(c, hipMalloc((void**)&g.store, (size_t)max_frames * nout * nx * ny * sizeof(double)));
-    g.dt = dt_out; g.nx = nx; g.ny = ny; g.max_frames = max_frames;
+    g.dt = dt_out; g.nx = nx; g.ny = ny; g.max_frames = max_frames; g.tile = tile;
     g.xg.assign(xg, xg + nx + 1); g.yg.assign(yg, yg + ny + 1); g.outputs.assign(outputs, outputs + nout);
     if (int rc = work_reserve(c, c->rec.grid_work, eul_grid_bytes(nx, ny))) return rc;
   }
@@ -3427,9 +3442,10 @@ static int rec_pack(sz_ctx* c, FloeWriter& w, int tstep, int V) {
   for (int k = 0; k < MIG_NTAB; k++) F.col[k] = src.p[k];
   for (int k = 0; k < FR_NSEC; k++) F.off[k] = L.off[k];
   F.dst = w.arena + w.used; F.tstep = tstep; F.M = M; F.N = N; F.V = V;
+  F.key_off = 0; F.spare[0] = F.spare[1] = F.spare[2] = 0;
   const long long widest = std::max<long long>(4ll * M, V);
-  hipLaunchKernelGGL(sz_k_frame_pack, dim3(grid_for(widest, FP_TPB, 256), FP_SLICES), dim3(FP_TPB), 0, c->stream, c->S, F);
-  w.frames.push_back({ w.used, tstep, M, N, V });
+  hipLaunchKernelGGL(sz_k_frame_pack<false>, dim3(grid_for(widest, FP_TPB, 256), FP_SLICES), dim3(FP_TPB), 0, c->stream, c->S, F);
+  w.frames.push_back({ w.used, tstep, M, N, V, {} });
   w.used += (size_t)L.total;
   return SZ_OK;
 }
@@ -3496,12 +3512,9 @@ int sz_floe_frame_info(sz_ctx* c, int32_t writer, int32_t k, int64_t* tstep, int
   if (n_ghost_links) *n_ghost_links = f->M - f->N;
   return SZ_OK;
 }
-int sz_download_floe_frame(sz_ctx* c, int32_t writer, int32_t k, sz_floe_columns* f) {
-  const FloeFrame* fr = rec_floe_frame(c, writer, k);
-  if (!fr || !f) return SZ_E_ARG;
-  const FloeWriter& w = c->rec.floe[writer];
-  const FrameLayout L(w.mask, fr->M, fr->N, fr->V);
-  const long long M = fr->M, V = fr->V, G = fr->M - fr->N;
+// a frame of M rows (N parents), V ring points in layout L at d_frame: down in one copy, its sections into the non-NULL members of f
+static int rec_frame_down(sz_ctx* c, const char* who, const FrameLayout& L, long long M, long long N, long long V, const char* d_frame, sz_floe_columns* f) {
+  const long long G = M - N;
   struct Part { void* dst; int sec; long long bytes; };
   std::vector<Part> parts;
   const ColTable<double*> dst = host_columns(*f);
@@ -3509,16 +3522,23 @@ int sz_download_floe_frame(sz_ctx* c, int32_t writer, int32_t k, sz_floe_columns
   parts.push_back({ f->id, FR_ID, M * 8 }); parts.push_back({ f->ghost_id, FR_GHOST_ID, M * 8 }); parts.push_back({ f->status, FR_STATUS, M * 4 });
   parts.push_back({ f->vert_off, FR_VOFF, (M + 1) * 4 }); parts.push_back({ f->vx, FR_VX, V * 8 }); parts.push_back({ f->vy, FR_VY, V * 8 });
   parts.push_back({ f->ghost_off, FR_GOFF, (M + 1) * 4 }); parts.push_back({ f->ghost_idx, FR_GIDX, G * 4 });
-  for (const Part& p : parts) if (p.dst && L.off[p.sec] < 0) { c->err = "sz_download_floe_frame: a member is asked for that the writer's mask did not record"; return SZ_E_ARG; }
-  if (f->sub_off || f->sx || f->sy) { c->err = "sz_download_floe_frame: sub-floe points are not recorded"; return SZ_E_ARG; }
+  for (const Part& p : parts) if (p.dst && L.off[p.sec] < 0) { c->err = std::string(who) + ": a member is asked for that the writer's mask did not record"; return SZ_E_ARG; }
+  if (f->sub_off || f->sx || f->sy) { c->err = std::string(who) + ": sub-floe points are not recorded"; return SZ_E_ARG; }
+  if (!d_frame) return SZ_OK;          // (the members were only checked)
   (void)hipSetDevice(c->device);
   // the frame comes down in one copy
   std::vector<char>& host = c->rec.host;
   host.resize((size_t)L.total);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(host.data(), w.arena + fr->at, (size_t)L.total, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(host.data(), d_frame, (size_t)L.total, hipMemcpyDeviceToHost));
   for (const Part& p : parts) if (p.dst && p.bytes > 0) memcpy(p.dst, host.data() + L.off[p.sec], (size_t)p.bytes);
   return SZ_OK;
+}
+int sz_download_floe_frame(sz_ctx* c, int32_t writer, int32_t k, sz_floe_columns* f) {
+  const FloeFrame* fr = rec_floe_frame(c, writer, k);
+  if (!fr || !f) return SZ_E_ARG;
+  const FloeWriter& w = c->rec.floe[writer];
+  return rec_frame_down(c, "sz_download_floe_frame", FrameLayout(w.mask, fr->M, fr->N, fr->V), fr->M, fr->N, fr->V, w.arena + fr->at, f);
 }
 int sz_download_grid_frame(sz_ctx* c, int32_t writer, int32_t k, int32_t* tstep, double* data) {
   if (!c) return SZ_E_ARG;
@@ -3537,6 +3557,265 @@ int sz_clear_frames(sz_ctx* c) {
   for (int w = 0; w < REC_WRITERS; w++) { c->rec.floe[w].frames.clear(); c->rec.floe[w].used = 0; c->rec.grid[w].tsteps.clear(); }
   c->rec.full = false;
   return SZ_OK;
+}
+
+}  // extern "C"
+// ---------------------------------------------------------------- output recorder on tiled contexts (sz_record_tile.hpp; DESIGN.md §9i, "Tiled contexts")
+// Host code of the tiled recorder, here and not in sz_tile_host.hpp because it is built from the helpers above (the workspace chunks, eul_*,
+// rec_frame_down); TileStops::record and sz_tile_run reach tile_record / tile_rec_agree_settings through the declarations there.
+namespace {
+constexpr int REC_BIT_FULL = 1 << 30;          // beside the device error bits in the word of the record point's gather
+// k ints of every rank on every rank, rank-major (k <= 8; the count-matrix area of d_gather, as comm_sizes borrows it between box gathers)
+int tile_gather_ints(sz_ctx* c, const int* local, int k, int* all) {
+  const int n = c->comm_n;
+  if (n == 1) { memcpy(all, local, (size_t)k * sizeof(int)); return SZ_OK; }
+  int *d_row = (int*)(c->d_gather + Gather::MAT), *d_all = d_row + Gather::RANKS;
+  HIPCHK(c, hipMemcpyAsync(d_row, local, (size_t)k * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (const int rc = comm_allgather(c, d_row, d_all, (size_t)k, NCCL_INT32, sizeof(int))) return rc;
+  HIPCHK(c, hipMemcpyAsync(all, d_all, (size_t)k * n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SZ_OK;
+}
+static_assert(2 * REC_WRITERS <= 8 && Gather::RANKS + 8 * Gather::RANKS <= Gather::RANKS * Gather::RANKS, "tile_gather_ints would leave the count-matrix area");
+// FNV-1a over what a writer was set with
+struct Digest {
+  unsigned h = 2166136261u;
+  void add(const void* p, size_t n) { for (size_t k = 0; k < n; k++) { h ^= ((const unsigned char*)p)[k]; h *= 16777619u; } }
+  template <class T> void val(const T& v) { add(&v, sizeof(T)); }
+};
+}  // namespace
+// The first act of a tiled batch with writers set, before any other collective: one gather of a digest of every writer's settings (interval, mask;
+// interval, grid lines, output codes, max_frames).  Ranks that were set differently would cut their batches differently and wait for each other
+// in different collectives: every rank returns SZ_E_STATE instead, naming the first writer that differs.
+static int tile_rec_agree_settings(sz_ctx* c) {
+  const Recorder& R = c->rec;
+  int mine[2 * REC_WRITERS], all[2 * REC_WRITERS * Gather::RANKS];
+  for (int w = 0; w < REC_WRITERS; w++) {
+    Digest f, g;
+    f.val(R.floe[w].dt); f.val(R.floe[w].mask); f.val(R.floe[w].tile);
+    const GridWriter& G = R.grid[w];
+    g.val(G.dt); g.val(G.nx); g.val(G.ny); g.val(G.max_frames); g.val(G.tile);
+    g.add(G.xg.data(), G.xg.size() * sizeof(double)); g.add(G.yg.data(), G.yg.size() * sizeof(double)); g.add(G.outputs.data(), G.outputs.size() * sizeof(int));
+    mine[w] = (int)f.h; mine[REC_WRITERS + w] = (int)g.h;
+  }
+  if (const int rc = tile_gather_ints(c, mine, 2 * REC_WRITERS, all)) return rc;
+  for (int w = 0; w < 2 * REC_WRITERS; w++)
+    for (int r = 1; r < c->comm_n; r++)
+      if (all[2 * REC_WRITERS * r + w] != all[w]) {
+        c->err = std::string("sz_tile_run: ") + (w < REC_WRITERS ? "floe" : "grid") + " output writer " + std::to_string(w % REC_WRITERS) + " is set differently on rank " + std::to_string(r) +
+                 " than on rank 0 (sz_tile_set_floe_output / sz_tile_set_grid_output are to be called alike on every rank): no step was run";
+        return SZ_E_STATE;
+      }
+  return SZ_OK;
+}
+namespace {
+// one tile frame: the single frame's launch with the key slice behind it
+int tile_rec_pack(sz_ctx* c, FloeWriter& w, int tstep, int V, const std::vector<int>& ranks, long long n_global) {
+  const int M = c->hostM, N = c->hostN;
+  const TileFrameLayout L(w.mask, M, N, V);
+  FramePack F;
+  const ColTable<double*> src = state_columns(c->S);
+  for (int k = 0; k < MIG_NTAB; k++) F.col[k] = src.p[k];
+  for (int k = 0; k < FR_NSEC; k++) F.off[k] = L.off[k];
+  F.dst = w.arena + w.used; F.tstep = tstep; F.M = M; F.N = N; F.V = V;
+  F.key_off = L.key; F.spare[0] = n_global; F.spare[1] = c->comm_rank; F.spare[2] = c->comm_n;
+  const long long widest = std::max<long long>(4ll * M, V);
+  hipLaunchKernelGGL(sz_k_frame_pack<true>, dim3(grid_for(widest, FP_TPB, 256), FP_SLICES + 1), dim3(FP_TPB), 0, c->stream, c->S, F);
+  w.frames.push_back({ w.used, tstep, M, N, V, ranks });
+  w.used += (size_t)L.total;
+  return SZ_OK;
+}
+}  // namespace
+// write_data! of output step tstep on a tiled context, collectively (TileStops::record): halo rows and ghosts dropped, sz_add_ghosts -- the
+// ghosts of the owned parents, which depend on each parent alone --, the counters, ONE gather of {error / full bits, M, N, V} per rank (an error
+// or a full writer of one rank is every rank's; the counts stay with the frame: the merge needs no collective to size its slots), one keyed
+// pack launch per due floe writer; per due grid writer this rank's per-cell sums into one buffer, ONE all-reduce over it, the averages, the
+// selected outputs into the store; sz_remove_ghosts.  A failure of the runtime itself (SZ_E_HIP) is returned alone, as everywhere on tiles.
+static int tile_record(sz_ctx* c, int tstep, int* full) {
+  Recorder& R = c->rec;
+  *full = 0;
+  bool fdue[REC_WRITERS], gdue[REC_WRITERS], any = false, any_grid = false;
+  for (int w = 0; w < REC_WRITERS; w++) {
+    fdue[w] = step_due(R.floe[w].dt, tstep); gdue[w] = step_due(R.grid[w].dt, tstep);
+    any = any || fdue[w] || gdue[w]; any_grid = any_grid || gdue[w];
+  }
+  if (!any) return SZ_OK;
+  const int n = c->comm_n;
+  (void)hipSetDevice(c->device);
+  int h[C_COUNT] = { 0 };
+  tile_cleanup(c);
+  int rc = sz_add_ghosts(c);
+  if (rc == SZ_E_HIP) return rc;
+  const int err_bits = rc ? (c->last_err_bits ? c->last_err_bits & ~REC_BIT_FULL : 1) : 0;
+  if (!rc && (rc = fetch_counters(c, h))) return rc;
+  const int M = c->hostM, N = c->hostN, V = h[C_NV];
+  bool room = true;
+  for (int w = 0; w < REC_WRITERS && !err_bits; w++) {
+    if (fdue[w] && R.floe[w].used + (size_t)TileFrameLayout(R.floe[w].mask, M, N, V).total > R.floe[w].bytes) room = false;
+    if (gdue[w] && (int)R.grid[w].tsteps.size() >= R.grid[w].max_frames) room = false;
+  }
+  const int mine[4] = { err_bits | (room ? 0 : REC_BIT_FULL), M, N, V };
+  std::vector<int> all((size_t)4 * Gather::RANKS, 0), ranks((size_t)3 * n);
+  if ((rc = tile_gather_ints(c, mine, 4, all.data()))) return rc;
+  int bits = 0, who = -1; long long n_global = 0;
+  for (int r = 0; r < n; r++) {
+    if ((all[4 * r] & ~REC_BIT_FULL) && who < 0) who = r;
+    bits |= all[4 * r];
+    for (int q = 0; q < 3; q++) ranks[3 * r + q] = all[4 * r + 1 + q];
+    n_global += all[4 * r + 2];
+  }
+  if (bits & ~REC_BIT_FULL) {
+    if (!err_bits) {          // (else this rank's own message stands)
+      (void)sz_remove_ghosts(c);
+      c->err = "rank " + std::to_string(who) + " of the tiled run reported device error bits at an output step (this rank is clean; all ranks stop together)";
+    }
+    return SZ_E_CAPACITY;
+  }
+  c->err.clear();
+  if (bits & REC_BIT_FULL) { *full = 1; R.full = true; return sz_remove_ghosts(c); }
+  for (int w = 0; w < REC_WRITERS; w++) if (fdue[w] && (rc = tile_rec_pack(c, R.floe[w], tstep, V, ranks, n_global))) return rc;
+  if (any_grid) {
+    size_t need_grid = 0, need_part = 0;
+    for (int w = 0; w < REC_WRITERS; w++) if (gdue[w]) { need_grid += eul_grid_bytes(R.grid[w].nx, R.grid[w].ny); need_part += (size_t)EUL_PARTIAL * R.grid[w].nx * R.grid[w].ny * sizeof(double); }
+    if ((rc = work_reserve(c, R.grid_work, need_grid)) || (rc = work_reserve(c, R.part_work, need_part))) return rc;
+    // every due writer's grid arrays out of the one workspace chunk (they live until the averages are made), its sums behind the last writer's
+    EulGrid E[REC_WRITERS]; double* part[REC_WRITERS] = { nullptr };
+    Pool gp = work_pool(R.grid_work);
+    size_t at = 0;
+    for (int w = 0; w < REC_WRITERS && !rc; w++) {
+      if (!gdue[w]) continue;
+      const GridWriter& g = R.grid[w];
+      int nent = 0; size_t need = 0;
+      if ((rc = eul_grid(c, g.nx, g.ny, g.xg.data(), g.yg.data(), gp, E[w])) || (rc = eul_count(c, E[w], nent)) || (rc = eul_fill_bytes(c, E[w], nent, &need)) ||
+          (rc = work_reserve(c, R.entry_work, need))) break;
+      Pool ep = work_pool(R.entry_work);
+      rc = eul_fill(c, ep, E[w], nent);
+      work_keep(R.entry_work, ep);
+      if (rc) break;
+      const int ncell = g.nx * g.ny;
+      part[w] = (double*)R.part_work.p + at; at += (size_t)EUL_PARTIAL * ncell;
+      hipLaunchKernelGGL(sz_k_eul_partial, dim3(grid_for(ncell, 64)), dim3(64), 0, c->stream, c->S, E[w], nent, part[w]);
+    }
+    work_keep(R.grid_work, gp);
+    if (rc) return rc;
+    if ((rc = sz_comm_allreduce(c, R.part_work.p, (int64_t)at))) return rc;
+    for (int w = 0; w < REC_WRITERS; w++) {
+      if (!gdue[w]) continue;
+      GridWriter& g = R.grid[w];
+      const size_t ncell = (size_t)g.nx * g.ny, nout = g.outputs.size();
+      hipLaunchKernelGGL(sz_k_eul_finish, dim3(grid_for((long long)ncell, 64)), dim3(64), 0, c->stream, E[w], (const double*)part[w]);
+      double* dst = g.store + g.tsteps.size() * nout * ncell;
+      for (size_t k = 0; k < nout; k++)
+        HIPCHK(c, hipMemcpyAsync(dst + k * ncell, E[w].data + (size_t)g.outputs[k] * ncell, ncell * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      g.tsteps.push_back(tstep);
+    }
+  }
+  return sz_remove_ghosts(c);
+}
+extern "C" {
+static const FloeFrame* tile_floe_frame(sz_ctx* c, int32_t writer, int32_t k, const char* who) {
+  const FloeFrame* fr = rec_floe_frame(c, writer, k);
+  if (fr && (!c->rec.floe[writer].tile || fr->ranks.empty())) { c->err = std::string(who) + ": not a frame of a tiled context's writer (sz_tile_set_floe_output)"; return nullptr; }
+  return fr;
+}
+int sz_tile_floe_frame_keys(sz_ctx* c, int32_t writer, int32_t k, int64_t* keys) {
+  const FloeFrame* fr = tile_floe_frame(c, writer, k, "sz_tile_floe_frame_keys");
+  if (!fr || !keys) return SZ_E_ARG;
+  const FloeWriter& w = c->rec.floe[writer];
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (fr->M > 0) HIPCHK(c, hipMemcpy(keys, w.arena + fr->at + TileFrameLayout(w.mask, fr->M, fr->N, fr->V).key, (size_t)fr->M * sizeof(long long), hipMemcpyDeviceToHost));
+  return SZ_OK;
+}
+int sz_tile_floe_frame_info(sz_ctx* c, int32_t writer, int32_t k, int64_t* tstep, int64_t* M, int64_t* N, int64_t* n_ring_points, int64_t* n_ghost_links) {
+  const FloeFrame* fr = tile_floe_frame(c, writer, k, "sz_tile_floe_frame_info");
+  if (!fr) return SZ_E_ARG;
+  long long tot[3] = { 0, 0, 0 };
+  for (size_t r = 0; r < fr->ranks.size() / 3; r++) for (int q = 0; q < 3; q++) tot[q] += fr->ranks[3 * r + q];
+  if (tstep) *tstep = fr->tstep;
+  if (M) *M = tot[0];
+  if (N) *N = tot[1];
+  if (n_ring_points) *n_ring_points = tot[2];
+  if (n_ghost_links) *n_ghost_links = tot[0] - tot[1];
+  return SZ_OK;
+}
+// The merged frame (collective): what each rank prepares alone -- the frame, the members asked for, the scratch -- is agreed first, so that nobody
+// is left in the gather; every rank's frame k in slots of the largest frame's size (known from the counts kept with the frame); the merge of
+// sz_record_tile.hpp on the ranks that asked for the frame; one copy down.
+int sz_tile_download_floe_frame(sz_ctx* c, int32_t writer, int32_t k, sz_floe_columns* f) {
+  static const char who[] = "sz_tile_download_floe_frame";
+  if (!c) return SZ_E_ARG;
+  if (int rc = tiled_ready(c, who)) return rc;
+  (void)hipSetDevice(c->device);
+  const int n = c->comm_n, me = c->comm_rank;
+  int rc = SZ_OK;
+  const FloeFrame* fr = tile_floe_frame(c, writer, k, who);
+  if (!fr) rc = SZ_E_ARG;
+  else if ((int)fr->ranks.size() != 3 * n) { c->err = std::string(who) + ": the frame was recorded by another number of ranks"; rc = SZ_E_STATE; }
+  // ---- this rank alone: the layouts of all ranks' frames and of the merged one, the scratch
+  long long slot = 8, Mg = 0, Ng = 0, Vg = 0;
+  std::vector<long long> sec((size_t)n * (FR_NSEC + 1), -1); std::vector<int> row0((size_t)n + 1, 0), npar((size_t)n, 0);
+  const unsigned long long mask = fr ? c->rec.floe[writer].mask : 1;
+  if (!rc) {
+    for (int r = 0; r < n; r++) slot = std::max(slot, TileFrameLayout(mask, fr->ranks[3 * r], fr->ranks[3 * r + 1], fr->ranks[3 * r + 2]).total);
+    for (int r = 0; r < n; r++) {
+      const TileFrameLayout L(mask, fr->ranks[3 * r], fr->ranks[3 * r + 1], fr->ranks[3 * r + 2]);
+      for (int s = 0; s < FR_NSEC; s++) sec[(size_t)r * (FR_NSEC + 1) + s] = L.off[s] < 0 ? -1 : r * slot + L.off[s];
+      sec[(size_t)r * (FR_NSEC + 1) + FR_NSEC] = r * slot + L.key;
+      row0[r] = (int)Mg; npar[r] = fr->ranks[3 * r + 1];
+      Mg += fr->ranks[3 * r]; Ng += fr->ranks[3 * r + 1]; Vg += fr->ranks[3 * r + 2];
+    }
+    row0[n] = (int)Mg;
+    if (Mg > 0x7fffffffll || Vg > 0x7fffffffll) { c->err = std::string(who) + ": the merged frame has more rows or ring points than an int holds"; rc = SZ_E_CAPACITY; }
+    else if (fr->M != fr->ranks[3 * me] || fr->N != fr->ranks[3 * me + 1] || fr->V != fr->ranks[3 * me + 2]) { c->err = std::string(who) + ": the frame was recorded by another rank of the communicator"; rc = SZ_E_STATE; }
+  }
+  const FrameLayout Lg(mask, Mg, Ng, Vg);
+  if (!rc && f) rc = rec_frame_down(c, who, Lg, Mg, Ng, Vg, nullptr, f);          // (the members asked for: checked before anybody gathers)
+  Pool& P = c->rect_allocs;
+  reset_pool(P);
+  char *d_own = nullptr, *d_all = nullptr, *d_out = nullptr, *d_tmp = nullptr;
+  long long *d_sec = nullptr, *key_in = nullptr, *key_out = nullptr; int *d_row0 = nullptr, *d_npar = nullptr, *val_in = nullptr, *src = nullptr, *pos = nullptr, *nv = nullptr, *ng = nullptr;
+  size_t tmp_bytes = 0;
+  const size_t Mc = (size_t)std::max<long long>(Mg, 1);
+  if (!rc) (void)((rc = dalloc(c, &d_own, (size_t)slot, P)) || (rc = dalloc(c, &d_all, (size_t)slot * n, P)));
+  if (!rc && f) {
+    size_t b1 = 0, b2 = 0;
+    if (hipSuccess != rocprim::radix_sort_pairs(nullptr, b1, (const long long*)nullptr, (long long*)nullptr, (const int*)nullptr, (int*)nullptr, Mc, 0u, 43u, c->stream) ||
+        hipSuccess != rocprim::exclusive_scan(nullptr, b2, (const int*)nullptr, (int*)nullptr, 0, Mc + 1, rocprim::plus<int>(), c->stream)) { c->err = std::string(who) + ": rocprim would not size its scratch"; rc = SZ_E_HIP; }
+    tmp_bytes = std::max(b1, b2);
+    if (!rc) (void)((rc = dalloc(c, &d_out, (size_t)Lg.total, P)) || (rc = dalloc(c, &d_tmp, tmp_bytes, P)) || (rc = dalloc(c, &d_sec, sec.size(), P)) || (rc = dalloc(c, &d_row0, row0.size(), P)) ||
+                    (rc = dalloc(c, &d_npar, npar.size(), P)) || (rc = dalloc(c, &key_in, Mc, P)) || (rc = dalloc(c, &key_out, Mc, P)) || (rc = dalloc(c, &val_in, Mc, P)) ||
+                    (rc = dalloc(c, &src, Mc, P)) || (rc = dalloc(c, &pos, Mc, P)) || (rc = dalloc(c, &nv, Mc + 1, P)) || (rc = dalloc(c, &ng, Mc + 1, P)));
+  }
+  // ---- the agreement on what each prepared alone, then the gather
+  int first = 0;
+  if (const int rc2 = comm_agree_rc(c, who, rc, &first)) return rc2;
+  if (first) return rc ? rc : first;
+  const FloeWriter& w = c->rec.floe[writer];
+  const size_t mine_bytes = (size_t)TileFrameLayout(mask, fr->M, fr->N, fr->V).total;
+  HIPCHK(c, hipMemcpyAsync(d_own, w.arena + fr->at, mine_bytes, hipMemcpyDeviceToDevice, c->stream));
+  if ((rc = comm_allgather(c, d_own, d_all, (size_t)slot / 8, NCCL_FLOAT64, sizeof(double)))) return rc;
+  if (!f) return SZ_OK;
+  // ---- the merge
+  HIPCHK(c, hipMemcpyAsync(d_sec, sec.data(), sec.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_row0, row0.data(), row0.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_npar, npar.data(), npar.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  RectArgs A{};
+  A.all = d_all; A.sec = d_sec; A.row0 = d_row0; A.npar = d_npar; A.src = src; A.pos = pos; A.nv = nv; A.ng = ng; A.out = d_out;
+  for (int s = 0; s < FR_NSEC; s++) A.off[s] = Lg.off[s];
+  A.nranks = n; A.Mg = (int)Mg; A.Ng = (int)Ng; A.Vg = (int)Vg; A.tstep = fr->tstep;
+  const int nb = grid_for(Mg + 1, RECT_TPB, 2048);
+  if (Mg > 0) {
+    hipLaunchKernelGGL(sz_k_rect_keys, dim3(nb), dim3(RECT_TPB), 0, c->stream, A, key_in, val_in);
+    HIPCHK(c, rocprim::radix_sort_pairs((void*)d_tmp, tmp_bytes, (const long long*)key_in, key_out, (const int*)val_in, src, (size_t)Mg, 0u, 43u, c->stream));
+  }
+  hipLaunchKernelGGL(sz_k_rect_counts, dim3(nb), dim3(RECT_TPB), 0, c->stream, A);
+  if (Lg.off[FR_VOFF] >= 0) HIPCHK(c, rocprim::exclusive_scan((void*)d_tmp, tmp_bytes, (const int*)nv, (int*)(d_out + Lg.off[FR_VOFF]), 0, (size_t)Mg + 1, rocprim::plus<int>(), c->stream));
+  if (Lg.off[FR_GOFF] >= 0) HIPCHK(c, rocprim::exclusive_scan((void*)d_tmp, tmp_bytes, (const int*)ng, (int*)(d_out + Lg.off[FR_GOFF]), 0, (size_t)Mg + 1, rocprim::plus<int>(), c->stream));
+  hipLaunchKernelGGL(sz_k_rect_scatter, dim3(grid_for(std::max<long long>(4 * Mg, Vg), RECT_TPB, 256), FP_SLICES), dim3(RECT_TPB), 0, c->stream, A);
+  rc = rec_frame_down(c, who, Lg, Mg, Ng, Vg, d_out, f);
+  trim_pool(P);
+  return rc;
 }
 
 // what simplify_floes! (simplification.jl:339-378) would find to do, without downloading a floe

@@ -19,6 +19,7 @@
 #include "sz_ridgeraft_tile.hpp"
 #include "sz_splice.hpp"
 #include "sz_record.hpp"
+#include "sz_record_tile.hpp"
 
 using namespace sz;
 
@@ -189,6 +190,7 @@ struct sz_ctx {
   bool tile_split_gl = false;
   // output recorder (sz_set_floe_output / sz_set_grid_output; sz_record.hpp): the writers, their frames in HBM, the workspace of the averages
   Recorder rec;
+  Pool rect_allocs;                 // scratch of sz_tile_download_floe_frame (sz_record_tile.hpp): the gathered slots, the sort's arrays, the merged frame; kept between calls
   bool last_stopped = false;        // the last batch of resident steps ended on a stop request (tag, fracture candidate), not at its last step
   bool maybe_tagged = false;        // a parent may be non-active on the device (an upload said so, a batch ended on a tag, a process-mode call ran):
                                     // the next batch then runs its first step on its own (see sz_step)

@@ -2,7 +2,7 @@
 // write_data! runs at the start of a step, right behind add_ghosts! (simulation.jl:102-105).  With a writer registered (sz_set_floe_output,
 // sz_set_grid_output) sz_step cuts its batch BEFORE every output step (sz_stops.hpp: StopRules::out_dts, the hook record()) and, at the cut:
 // detaches ghosts a process call left attached, sz_add_ghosts, one sz_k_frame_pack launch per due floe writer, the averages of
-// calc_eulerian_data! per due grid writer, sz_remove_ghosts -- and goes on.  Nothing crosses to the host but the counters.  Single contexts only.
+// calc_eulerian_data! per due grid writer, sz_remove_ghosts -- and goes on.  Nothing crosses to the host but the counters.  (Tiled contexts: below.)
 //
 // A FLOE FRAME is the list as add_ghosts! leaves it, in the columns the writer's mask selects.  The mask has one bit per column group of
 // sz_floe_columns, in struct order (frame_bit_names below): bits 0..27 the double columns (the three tensors 4 doubles per floe), 28 id,
@@ -17,6 +17,11 @@
 // A GRID FRAME is nout * nx * ny doubles in the layout of sz_eulerian_data, in a store of max_frames frames; its timestep is kept on the host.
 // Limits: 4 floe and 4 grid writers; a frame that finds no room (the arena, max_frames) is not taken: the batch ends in front of that step with
 // `full` set (sz_output_frames), and no writer gets a frame of a step that not all due writers have room for.
+// TILED CONTEXTS (sz_tile_set_floe_output / sz_tile_set_grid_output; the record point is tile_record in sz_tile_host.hpp, the merge of the ranks'
+// frames sz_record_tile.hpp): a TILE FRAME is the same layout over the rank's own rows -- its owned parents and their ghosts, ghost_idx in local
+// row numbers -- with one more section behind the selected ones, so that the layout above is untouched: key, int64 [M], the row's order key
+// (State::okey: a parent's global number, a ghost's (pass << 40) + 4 * parent key + k).  The three spare header words carry {N_global, rank,
+// nranks}.  The rows of all ranks sorted by key are the single context's frame of that step.
 #pragma once
 #include "sz_kernels.hpp"
 #include "sz_columns.hpp"
@@ -56,16 +61,27 @@ struct FramePack {
   long long off[FR_NSEC];
   char* dst;                      // the frame's start in the arena
   int tstep, M, N, V;             // the host's counts behind sz_add_ghosts: every store lies inside the layout made from them
+  long long key_off;              // a tile frame: where its key section lies (behind FrameLayout::total), and the three spare header words
+  long long spare[3];             // {N_global, rank, nranks}
 };
 
 constexpr int FP_TPB = 256;
-constexpr int FP_SLICES = MIG_NTAB + 5;      // blockIdx.y: one slice per mask bit
+constexpr int FP_SLICES = MIG_NTAB + 5;      // blockIdx.y: one slice per mask bit (a tile frame: one more, the keys)
 
 // One launch gathers a frame: slice y < MIG_NTAB double column y over all rows; then id, ghost_id, status; the rings (offsets made
 // frame-relative, vxy de-interleaved); the header and the ghost links (one workgroup: the offsets are a prefix sum over the parents' counts).
+// KEYED (tile frames): slice FP_SLICES copies the order keys, and the header's spare words are F.spare; nothing else differs.
+template <bool KEYED>
 __global__ void __launch_bounds__(FP_TPB) sz_k_frame_pack(State S, FramePack F) {
   const int y = blockIdx.y, M = F.M, N = F.N;
   const long long t0 = (long long)blockIdx.x * FP_TPB + threadIdx.x, stride = (long long)gridDim.x * FP_TPB;
+  if constexpr (KEYED) {
+    if (y == FP_SLICES) {
+      long long* out = (long long*)(F.dst + F.key_off);
+      for (long long r = t0; r < M; r += stride) out[r] = S.okey[r];
+      return;
+    }
+  }
   auto src_row = [&](int r) { if (r < N) return r; const int p = S.parent[r]; return p >= 0 && p < N ? p : r; };
   if (y < MIG_NTAB) {
     if (F.off[y] < 0) return;
@@ -96,7 +112,8 @@ __global__ void __launch_bounds__(FP_TPB) sz_k_frame_pack(State S, FramePack F) 
     const int G = M - N, t = threadIdx.x;
     if (t == 0) {
       long long* h = (long long*)F.dst;
-      h[0] = F.tstep; h[1] = M; h[2] = N; h[3] = F.V; h[4] = G; h[5] = h[6] = h[7] = 0;
+      h[0] = F.tstep; h[1] = M; h[2] = N; h[3] = F.V; h[4] = G;
+      if constexpr (KEYED) { h[5] = F.spare[0]; h[6] = F.spare[1]; h[7] = F.spare[2]; } else h[5] = h[6] = h[7] = 0;
     }
     if (F.off[FR_GOFF] < 0) return;
     int *goff = (int*)(F.dst + F.off[FR_GOFF]), *gidx = (int*)(F.dst + F.off[FR_GIDX]);
@@ -128,14 +145,17 @@ __global__ void __launch_bounds__(FP_TPB) sz_k_frame_pack(State S, FramePack F) 
 
 // host side of one writer each; the device memory is the recorder's own (hipMalloc / hipFree when a writer is set, re-set or cleared away),
 // so frames outlive uploads and row edits
-struct FloeFrame { size_t at; int tstep, M, N, V; };
+struct FloeFrame {
+  size_t at; int tstep, M, N, V;
+  std::vector<int> ranks;         // a tile frame: {M, N, V} of every rank's frame of this step, as gathered at the record point
+};
 struct FloeWriter {
-  int dt = 0; unsigned long long mask = 0;
+  int dt = 0; unsigned long long mask = 0; bool tile = false;      // tile: set through sz_tile_set_floe_output
   char* arena = nullptr; size_t bytes = 0, used = 0;
   std::vector<FloeFrame> frames;
 };
 struct GridWriter {
-  int dt = 0, nx = 0, ny = 0, max_frames = 0;
+  int dt = 0, nx = 0, ny = 0, max_frames = 0; bool tile = false;      // tile: set through sz_tile_set_grid_output
   std::vector<double> xg, yg; std::vector<int> outputs;
   double* store = nullptr;        // [max_frames][nout][nx][ny]
   std::vector<int> tsteps;
@@ -146,11 +166,18 @@ struct Recorder {
   FloeWriter floe[REC_WRITERS]; GridWriter grid[REC_WRITERS];
   int dts[2 * REC_WRITERS] = { 0 };          // StopRules::out_dts: floe writers, then grid writers
   bool any = false, full = false;
+  bool any_tile = false, any_single = false; // ... set through the tile setters / through the single context's
   RecWork grid_work, entry_work;             // EulGrid's per-cell arrays; its entries and the sort's scratch
+  RecWork part_work;                         // tile frames: the per-cell partial sums of all grid writers due at a step, one behind the other
   std::vector<char> host;                    // a frame on its way down
   void refresh() {
-    any = false;
-    for (int w = 0; w < REC_WRITERS; w++) { dts[w] = floe[w].dt; dts[REC_WRITERS + w] = grid[w].dt; any = any || floe[w].dt > 0 || grid[w].dt > 0; }
+    any = any_tile = any_single = false;
+    for (int w = 0; w < REC_WRITERS; w++) {
+      dts[w] = floe[w].dt; dts[REC_WRITERS + w] = grid[w].dt;
+      any_tile = any_tile || (floe[w].dt > 0 && floe[w].tile) || (grid[w].dt > 0 && grid[w].tile);
+      any_single = any_single || (floe[w].dt > 0 && !floe[w].tile) || (grid[w].dt > 0 && !grid[w].tile);
+    }
+    any = any_tile || any_single;
   }
 };
 

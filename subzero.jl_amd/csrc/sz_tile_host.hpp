@@ -89,7 +89,7 @@ int sz_tile_enable(sz_ctx* c, const int64_t* gidx, double halo_capacity_factor, 
   leave_resident(c);
   State& S = c->S;
   if (c->hostM != c->hostN) { c->err = "sz_tile_enable needs a ghost-free upload"; return SZ_E_STATE; }
-  if (c->rec.any) { c->err = "sz_tile_enable: an output writer is set, and the recorder serves single contexts only (sz_set_floe_output / sz_set_grid_output with dt_out = 0)"; return SZ_E_STATE; }
+  if (c->rec.any_single) { c->err = "sz_tile_enable: an output writer of a single context is set (sz_set_floe_output / sz_set_grid_output with dt_out = 0 turn it off; a tiled context takes sz_tile_set_floe_output / sz_tile_set_grid_output)"; return SZ_E_STATE; }
   std::vector<long long>& ok = c->tile_gidx;
   ok.assign(c->hostN, 0);
   for (int i = 0; i < c->hostN; i++) ok[i] = gidx[i];
@@ -1915,6 +1915,12 @@ static int tile_rr_step(sz_ctx* c, int tstep, int dt, int coupling_dt, int flags
   c->rr_draws += nd;
   return tile_rr_second_half(c, tstep, dt, coupling_dt, flags, any_tag);
 }
+}  // namespace
+// the tiled recorder (sz_api.hip, behind the single context's: it is built from the same helpers): the record point, and the agreement on the
+// writers' settings in front of a batch
+static int tile_record(sz_ctx* c, int tstep, int* full);
+static int tile_rec_agree_settings(sz_ctx* c);
+namespace {
 // The passes of the stop schedule (sz_stops.hpp) on a tiled context: collective, each agrees what it returns.  The only reader of tile_stop_raised.
 struct TileStops {
   sz_ctx* c; int dt, coupling_dt, flags;
@@ -1934,7 +1940,7 @@ struct TileStops {
   int segment(int len, int t0, int* ran, int* tag) {
     c->tile_stop_raised = 0; agreed = false;
     const int rc = drive(len, t0, ran);
-    *tag = *ran < len || c->tile_stop_raised == len;
+    *tag = !(flags & SZ_NO_STOP) && (*ran < len || c->tile_stop_raised == len);          // (a batch that runs through is only cut and recorded: no tag is looked at)
     return rc;
   }
   // pending = the lists keep their halo rows and ghosts, sz_tile_step_finish runs the rest
@@ -1955,8 +1961,8 @@ struct TileStops {
   }
   // done = the next segment starts from the compacted tiles (boxes, halo capacities and peers are gathered again at its first exchange)
   int remove(int* ok) { int nr = 0, nd = 0; return tile_remove_pass(c, ok, &nr, &nd); }
-  // (never asked: a tiled context has no output recorder, its rules carry no output interval)
-  int record(int, int* full) { *full = 0; return SZ_OK; }
+  // write_data! of an output step (sz_record.hpp, "tiled contexts"): every rank's tile frame of its owned rows, the grid frames summed over the ranks
+  int record(int tstep, int* full) { return tile_record(c, tstep, full); }
 };
 }  // namespace
 
@@ -1968,6 +1974,7 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   if (!c) return SZ_E_STATE;
   if (c->rr_pending >= 0) { c->err = "sz_tile_run: a ridge / raft step is pending (sz_ridgeraft_pending): sz_tile_step_finish runs its second half first"; return SZ_E_STATE; }
   if (c->rr_on && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled ridge / raft candidates gather the ghost keys and the entries over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
+  if (c->rec.any_tile && (c->comm_n < 1 || c->tile_margin <= 0)) { c->err = "tiled output writers gather the ranks' frame counts and sum the grid frames over the ranks: needs sz_tile_setup and a communicator"; return SZ_E_STATE; }
   if (int rc = tiled_ready(c, "sz_tile_run")) return rc;
   if (nsteps < 0) return SZ_E_ARG;
   c->rr_draws = 0;
@@ -1982,6 +1989,18 @@ int sz_tile_run(sz_ctx* c, int32_t nsteps, int32_t tstep0, int32_t dt, int32_t c
   // Two-way coupling across tiles has no tag stop of its own to hang a pass on: removal is not engaged there, the other three
   // refused above.  SZ_NO_STOP batches and contexts with none of the four set take the drivers as they are.
   TileStops ops = { c, dt, coupling_dt, flags };
+  const bool rec = c->rec.any_tile && nsteps > 0;
+  c->rec.full = false;
+  if (rec) {
+    // With an output writer set every batch takes the schedule, which then also cuts before the output steps and records their frames; a batch
+    // that runs through (SZ_NO_STOP) carries the output intervals alone in its rules, as on the single context.
+    const bool two_way = c->two_way;
+    if (two_way) { c->err = "tiled two-way coupling with an output writer set: its per-step all-reduce path has no tested cut: sz_tile_set_floe_output / sz_tile_set_grid_output with dt_out = 0"; return SZ_E_STATE; }
+    if (int rc = tile_rec_agree_settings(c)) return rc;
+    StopRules rules = (flags & SZ_NO_STOP) ? StopRules{ 0, 0, nullptr, 0, false, false } : tile_stop_rules(*c);
+    rules.out_dts = c->rec.dts; rules.n_out = 2 * REC_WRITERS;
+    return run_with_stops(rules, ops, nsteps, tstep0, steps_done);
+  }
   if ((!c->rm_on && !frac && !weld && !rr) || (flags & SZ_NO_STOP) || c->two_way || nsteps <= 0) return ops.drive(nsteps, tstep0, steps_done);
   return run_with_stops(tile_stop_rules(*c), ops, nsteps, tstep0, steps_done);
 }

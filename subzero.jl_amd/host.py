@@ -539,25 +539,26 @@ class World:
                 total += pad(4 * (M + 1)) + pad(4 * (M - N))
         return total
 
-    def set_floe_output(self, writer, dt_out, columns=None, arena_bytes=1 << 26):
+    def set_floe_output(self, writer, dt_out, columns=None, arena_bytes=1 << 26, _tile=False):
         """a FloeOutputWriter with Δtout = dt_out (0: off) that records the column groups `columns` (names out of capi.FRAME_BITS, or a ready
-        mask; None: all) into an arena of arena_bytes on the device"""
+        mask; None: all) into an arena of arena_bytes on the device.  (_tile: through the setter of tiled contexts -- TiledWorld's call.)"""
         mask = columns if isinstance(columns, int) else self.frame_mask(columns)
-        self._chk(self.L.sz_set_floe_output(self.h, int(writer), int(dt_out), int(mask), int(arena_bytes)))
+        fn = self.L.sz_tile_set_floe_output if _tile else self.L.sz_set_floe_output
+        self._chk(fn(self.h, int(writer), int(dt_out), int(mask), int(arena_bytes)))
         self._floe_masks = getattr(self, "_floe_masks", {})
         self._floe_masks[int(writer)] = int(mask)
 
-    def set_grid_output(self, writer, dt_out, xg=None, yg=None, outputs=None, max_frames=64):
+    def set_grid_output(self, writer, dt_out, xg=None, yg=None, outputs=None, max_frames=64, _tile=False):
         """a GridOutputWriter with Δtout = dt_out (0: off) on the grid lines xg, yg for the outputs named (EUL_OUTPUTS, default all), with room
-        for max_frames frames on the device"""
+        for max_frames frames on the device.  (_tile: through the setter of tiled contexts -- TiledWorld's call.)"""
         names = list(self.EUL_OUTPUTS if outputs is None else outputs)
         for n in names:
             if n not in self.EUL_OUTPUTS:
                 raise SzError(f"{n} is not a known grid output")
         codes = np.array([self.EUL_OUTPUTS.index(n) for n in names], _I32)
         xg = np.ascontiguousarray(xg if xg is not None else [0.0, 1.0], np.float64); yg = np.ascontiguousarray(yg if yg is not None else [0.0, 1.0], np.float64)
-        self._chk(self.L.sz_set_grid_output(self.h, int(writer), int(dt_out), len(xg) - 1, len(yg) - 1, capi.ptr(xg), capi.ptr(yg), len(names),
-                                            capi.ptr(codes, capi._ip), int(max_frames)))
+        fn = self.L.sz_tile_set_grid_output if _tile else self.L.sz_set_grid_output
+        self._chk(fn(self.h, int(writer), int(dt_out), len(xg) - 1, len(yg) - 1, capi.ptr(xg), capi.ptr(yg), len(names), capi.ptr(codes, capi._ip), int(max_frames)))
         self._grid_writers = getattr(self, "_grid_writers", {})
         self._grid_writers[int(writer)] = (len(names), len(xg) - 1, len(yg) - 1)
 
@@ -568,11 +569,16 @@ class World:
         self._chk(self.L.sz_output_frames(self.h, capi.ptr(nf, capi._ip), capi.ptr(ng, capi._ip), C.byref(full)))
         return [int(v) for v in nf], [int(v) for v in ng], bool(full.value)
 
-    def floe_frame(self, writer, k, members=None):
+    def floe_frame(self, writer, k, members=None, _merged=False):
         """floe frame k of a writer: a dict with tstep, M, N and the recorded columns as arrays in the layout of load_columns (the rings as
-        vert_off, vx, vy; the ghost links as ghost_off, ghost_idx).  members: struct members to ask for instead of everything recorded."""
+        vert_off, vx, vy; the ghost links as ghost_off, ghost_idx).  members: struct members to ask for instead of everything recorded.
+        (_merged: the merged frame of a tiled run, collectively -- TiledWorld.floe_frame's call.)"""
         info = [C.c_int64(0) for _ in range(5)]
-        self._chk(self.L.sz_floe_frame_info(self.h, int(writer), int(k), *(C.byref(v) for v in info)))
+        info_fn, down_fn = (self.L.sz_tile_floe_frame_info, self.L.sz_tile_download_floe_frame) if _merged else (self.L.sz_floe_frame_info, self.L.sz_download_floe_frame)
+        rc = info_fn(self.h, int(writer), int(k), *(C.byref(v) for v in info))
+        if rc and _merged:
+            down_fn(self.h, int(writer), int(k), None)          # (the peers are in the collective: take part, so that every rank raises)
+        self._chk(rc)
         tstep, M, N, V, G = (int(v.value) for v in info)
         if members is None:
             members = []
@@ -602,7 +608,7 @@ class World:
         for n, a in col.items():
             keep.append(a)
             setattr(f, n, capi.ptr(a.reshape(-1), capi._lp if a.dtype == _I64 else capi._ip if a.dtype == _I32 else capi._dp))
-        self._chk(self.L.sz_download_floe_frame(self.h, int(writer), int(k), C.byref(f)))
+        self._chk(down_fn(self.h, int(writer), int(k), C.byref(f)))
         for n in ("vx", "vy"):
             if n in col:
                 col[n] = col[n][:V]

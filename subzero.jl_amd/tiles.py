@@ -727,6 +727,45 @@ class TiledWorld:
                 self._max_rmax = max(self._max_rmax, float(np.max(col["rmax"])))
         return int(ng.value), n
 
+    # ---- output frames of a tiled run (sz_tile_set_floe_output / sz_tile_set_grid_output, sz_tile_download_floe_frame: library backends)
+    def set_floe_output(self, writer, dt_out, columns=None, arena_bytes=1 << 26):
+        """World.set_floe_output for this rank's tile (the same arguments on every rank).  run() then goes on past the writer's output steps and
+        records there: every rank keeps the frame of its own rows -- its owned floes and their ghosts -- with their order keys."""
+        self._library_only("set_floe_output")
+        self.world.set_floe_output(writer, dt_out, columns, arena_bytes, _tile=True)
+
+    def set_grid_output(self, writer, dt_out, xg=None, yg=None, outputs=None, max_frames=64):
+        """World.set_grid_output for this rank's tile (the same arguments on every rank): every rank holds every grid frame, summed over the ranks"""
+        self._library_only("set_grid_output")
+        self.world.set_grid_output(writer, dt_out, xg, yg, outputs, max_frames, _tile=True)
+
+    def output_frames(self):
+        """World.output_frames: the same numbers on every rank (`full` is agreed between the ranks)"""
+        return self.world.output_frames()
+
+    def clear_frames(self):
+        self.world.clear_frames()
+
+    def floe_frame_local(self, writer, k, members=None):
+        """this rank's tile frame k of a writer (local): World.floe_frame over its own rows -- M, N and ghost_idx are local -- plus `key`, the
+        order key of every row: a parent's global number, a ghost's (pass << 40) + 4 * parent key + k"""
+        w = self.world
+        fr = w.floe_frame(writer, k, members)
+        key = np.zeros(max(fr["M"], 1), np.int64)
+        w._chk(w.L.sz_tile_floe_frame_keys(w.h, int(writer), int(k), capi.ptr(key, capi._lp)))
+        fr["key"] = key[:fr["M"]].copy()
+        return fr
+
+    def floe_frame(self, writer, k, members=None):
+        """floe frame k of a writer over the global list (collective: every rank calls it alike): the rows of all ranks merged by order key inside
+        the library -- World.floe_frame of the single context's recorded run, bit for bit in every member"""
+        self._library_only("floe_frame")
+        return self.world.floe_frame(writer, k, members, _merged=True)
+
+    def grid_frame(self, writer, k):
+        """grid frame k of a writer: (tstep, array [nout, nx, ny]), the same on every rank"""
+        return self.world.grid_frame(writer, k)
+
     def ridgeraft_draws(self):
         """the per-floe draws of the ridge / raft steps the last run() ran through, over the global list: the same number on every rank"""
         return self._rr_draws
