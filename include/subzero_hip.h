@@ -764,12 +764,27 @@ int sz_simplify_check(sz_ctx *ctx, int32_t max_vertices, double min_floe_area, d
    context, sz_tile_enable returns SZ_E_STATE on a context with a writer set through them (a tiled context has setters of its own, below).
    sz_set_floe_output: columns_mask has one bit per column group of sz_floe_columns, in struct order (sz_debug_frame_bits): bits 0..27 the 28
      double columns cx .. strain (tensors 4 per floe), 28 id, 29 ghost_id, 30 status, 31 the rings (vert_off + vx + vy), 32 the ghost links
-     (ghost_off + ghost_idx).  NOT recorded: the sub-floe points, floe.interactions and status.fuse_idx -- a host writer that wants them keeps
-     cutting its own batches.  Frames are appended to one arena of arena_bytes in device memory.
+     (ghost_off + ghost_idx).  The ragged members -- floe.interactions and the sub-floe points -- are the lists of sz_set_floe_output_lists,
+     below.  Frames are appended to one arena of arena_bytes in device memory.
      A FLOE FRAME is what sz_add_ghosts followed by sz_download_floes of the selected columns gives at the start of the step, with one rule made
      explicit: a ghost is a deep copy of its parent (collisions.jl:881-901, floe_utils.jl:138), so a ghost row carries the parent's bits in
      every recorded column except cx, cy, the ring and ghost_id (the device keeps only the collision columns on ghost rows; the pack reads the
      others from the parent row).  vert_off is frame-relative; a ghost row's ghost_off span is empty.
+   sz_set_floe_output_lists: the ragged members floe writer `writer` records beside its columns, SZ_FRAME_INTERACTIONS | SZ_FRAME_SUBPOINTS; to be
+     called after sz_set_floe_output, which resets them to 0; frees that writer's frames.  Their sections lie behind the column sections: the
+     layout of a frame without lists is what it was, and a writer without lists costs no launch, scan or synchronisation more.  With the lists
+     a frame is everything a Floe holds on the device at write_data! time: a fresh context can be restarted from it.
+     INTERACTIONS: inter_off int32 [M + 1] and rows double [R][7].  A parent row carries floe.interactions of the last step that ran, with the
+     bits sz_download_interactions gives at that cut BEFORE sz_add_ghosts: the floeidx column as the reference stores it -- a partner that was
+     an inline ghost of that step is N + the rank of its order key among that step's ghost keys + 1; where that call would translate nothing
+     (a process-mode call ran since, the host uploaded the rows) the rows are kept untranslated, as it would.  A ghost row's span is empty:
+     deepcopy_floe (floe_utils.jl:120-161) passes no interactions, the copy gets zeros(0, 7) and num_inters = 0.
+     SUB-FLOE POINTS: sub_off int32 [M + 1], sx, sy [S], centred as stored: a parent row's own points with the bits of sz_download_subpoints; a
+     ghost row carries its parent's (deepcopy_floe copies them).
+     status.fuse_idx has no section: it is non-empty only on a row tagged `fuse` (collisions.jl:367-368, 801-806), and a batch that honours tags
+     never begins a step with such a row -- the recorded status column says so.
+     Refusals: bits other than the two, SZ_E_ARG; a writer that is off, SZ_E_STATE; a tiled context or a writer of sz_tile_set_floe_output,
+     SZ_E_STATE (tile frames record no lists yet).  The room check of a frame uses its full size, lists included.
    sz_set_grid_output: the arguments of sz_eulerian_data (evenly spaced grid lines, nout >= 1 of the SZ_EUL_* codes) and room for max_frames
      frames.  A GRID FRAME is the nout * nx * ny doubles sz_eulerian_data gives on the same list, bit for bit, and its timestep.  The averages run
      in a workspace the recorder keeps (sized when the writer is set, grown on demand): a recorded output step allocates nothing once warm.
@@ -777,17 +792,23 @@ int sz_simplify_check(sz_ctx *ctx, int32_t max_vertices, double min_floe_area, d
    ends in front of it with SZ_OK, *steps_done not counting it, and `full` set until the next sz_step or sz_clear_frames.
    Draining: sz_output_frames: frames held per writer (n_floe, n_grid: 4 entries each, may be NULL) and full.  sz_floe_frame_info: the header of
    floe frame k {tstep, M, N, n_ring_points, n_ghost_links}.  sz_download_floe_frame: every non-NULL member of cols that was recorded is filled
-   (sized from sz_floe_frame_info; ghost_idx n_ghost_links entries); a non-NULL member that was not recorded -- sub_off, sx, sy always --
-   returns SZ_E_ARG and nothing is written.  sz_download_grid_frame: tstep and data[nout][nx][ny] (either may be NULL).  A frame or writer
+   (sized from sz_floe_frame_info; ghost_idx n_ghost_links entries; sub_off M + 1 and sx, sy n_sub_points entries, when the frame recorded
+   the sub-floe points); a non-NULL member that was not recorded returns SZ_E_ARG and nothing is written.  sz_floe_frame_lists_info: the totals
+   of frame k's list sections (0 for a section not recorded).  sz_download_floe_frame_interactions: the signature of sz_download_interactions,
+   on frame k: off M + 1 entries, rows n_inter_rows * 7 (rows may be NULL); SZ_E_ARG on a frame without the section.  sz_download_grid_frame: tstep and data[nout][nx][ny] (either may be NULL).  A frame or writer
    that does not exist: SZ_E_ARG.  Frames survive sz_upload_floes, sz_splice_floes and sz_remove_floes, so a host that edits at a stop drains
    whenever it likes; they are freed by sz_clear_frames (all writers, the writers stay set), by setting that writer again and by sz_destroy. */
 int sz_set_floe_output(sz_ctx *ctx, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes);
+enum { SZ_FRAME_INTERACTIONS = 1, SZ_FRAME_SUBPOINTS = 2 };
+int sz_set_floe_output_lists(sz_ctx *ctx, int32_t writer, uint32_t lists);
 int sz_set_grid_output(sz_ctx *ctx, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double *xg, const double *yg,
                        int32_t nout, const int32_t *outputs, int32_t max_frames);
 int sz_output_frames(sz_ctx *ctx, int32_t *n_floe, int32_t *n_grid, int32_t *full);
 int sz_floe_frame_info(sz_ctx *ctx, int32_t writer, int32_t k, int64_t *tstep, int64_t *M, int64_t *N, int64_t *n_ring_points,
                        int64_t *n_ghost_links);
 int sz_download_floe_frame(sz_ctx *ctx, int32_t writer, int32_t k, sz_floe_columns *cols);
+int sz_floe_frame_lists_info(sz_ctx *ctx, int32_t writer, int32_t k, int64_t *n_inter_rows, int64_t *n_sub_points);
+int sz_download_floe_frame_interactions(sz_ctx *ctx, int32_t writer, int32_t k, int32_t *off, double *rows);
 int sz_download_grid_frame(sz_ctx *ctx, int32_t writer, int32_t k, int32_t *tstep, double *data);
 int sz_clear_frames(sz_ctx *ctx);
 

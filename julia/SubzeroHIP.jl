@@ -205,6 +205,7 @@ mutable struct HIPEngine
     min_floe_height::Float64
     host_rows::Vector{Int}       # per host row the row it had at the last upload! (the device removes floes: origin, pull_state!)
     rec_floe::Vector{Tuple{Int, UInt64}}   # device floe writer k + 1 -> (index in sim.writers.floewriters, its column mask); set_floe_output!
+                                           # (the lists a writer records follow from its outputs: frame_lists)
     rec_grid::Vector{Int}        # device grid writer k + 1 -> index in sim.writers.gridwriters; set_grid_output!
 end
 
@@ -1101,10 +1102,10 @@ rows and adds the dissolved mass to its copy of `ocean.dissolved`, inside a batc
 `remove_floes!(eng)`.  The host's rows follow at the next `pull_state!`, which deletes the rows `origin(eng)` no longer names.
 
 Output (`device_output = true`; off by default, this file has not been run): every GridOutputWriter and every FloeOutputWriter whose outputs a
-device frame holds (`FRAME_OUTPUTS`) is registered with the recorder (`set_floe_output!`, `set_grid_output!`; four of each at most).  Batches
-then run past those writers' output steps -- `sz_step` cuts before the step, records the frames on the device and goes on -- and
-`drain_frames!` writes them through the writers' own files after each batch.  Every other writer (checkpoint, initial state, a floe writer that
-asks for `interactions` and the like, a fifth writer) keeps the cut on the host, where only those writers write.
+frame serves (`frame_covers`: every field of `Floe`, so the default `FloeOutputWriter(Δtout)` too) is registered with the recorder
+(`set_floe_output!`, `set_grid_output!`; four of each at most).  Batches then run past those writers' output steps -- `sz_step` cuts before
+the step, records the frames on the device and goes on -- and `drain_frames!` writes them through the writers' own files after each batch.
+Every other writer (checkpoint, initial state, a fifth writer) keeps the cut on the host, where only those writers write.
 """
 function run_resident!(sim, eng::HIPEngine; start_tstep::Integer = 0, batch::Integer = 500, device_output::Bool = false)
     # (the candidates are read from the step's own interaction rows: sz_step refuses ridge / raft without SZ_COLLISIONS_ON)
@@ -1585,9 +1586,7 @@ const FRAME_BITS = (:cx, :cy, :rmax, :area, :height, :mass, :moment, :alpha, :u,
                     :p_dxidt, :fxOA, :fyOA, :trqOA, :hflx_factor, :overarea, :coll_fx, :coll_fy, :coll_trq, :stress_accum, :stress_instant,
                     :strain, :id, :ghost_id, :status, :rings, :ghost_links)
 frame_mask(groups) = reduce(|, (UInt64(1) << (findfirst(==(g), FRAME_BITS) - 1) for g in groups); init = UInt64(0))
-# FloeOutputWriter outputs a frame can give, and the column groups each needs.  Not recorded, so not here: :status (its fuse_idx), :poly and
-# :angles (derived on the host), the sub-floe points, :parent_ids, :interactions, :num_inters, :damage -- a writer that asks for one of those
-# keeps the host's cut
+# FloeOutputWriter outputs a frame's columns give as they are, and the column groups each needs.  The other fields of Floe: the tables below
 const FRAME_OUTPUTS = Dict{Symbol, Vector{Symbol}}(
     :centroid => [:cx, :cy], :coords => [:rings], :height => [:height], :area => [:area], :mass => [:mass], :rmax => [:rmax],
     :moment => [:moment], :α => [:alpha], :u => [:u], :v => [:v], :ξ => [:xi], :id => [:id], :ghost_id => [:ghost_id],
@@ -1595,7 +1594,44 @@ const FRAME_OUTPUTS = Dict{Symbol, Vector{Symbol}}(
     :overarea => [:overarea], :collision_force => [:coll_fx, :coll_fy], :collision_trq => [:coll_trq], :stress_accum => [:stress_accum],
     :stress_instant => [:stress_instant], :strain => [:strain], :p_dxdt => [:p_dxdt], :p_dydt => [:p_dydt], :p_dudt => [:p_dudt],
     :p_dvdt => [:p_dvdt], :p_dξdt => [:p_dxidt], :p_dαdt => [:p_dalphadt])
-frame_covers(w) = all(o -> haskey(FRAME_OUTPUTS, o), w.outputs)
+# The lists of sz_set_floe_output_lists, bit 0 first (SZ_FRAME_INTERACTIONS, SZ_FRAME_SUBPOINTS)
+const FRAME_LISTS = (:interactions, :subpoints)
+# Outputs a frame serves through more than a copy of a column: output => (column groups, lists)
+#   :interactions, :num_inters   the interactions section; the matrix written is rows 1:num_inters (the reference's file can also hold stale
+#                                rows past num_inters -- the matrix only grows, collisions.jl:290-296 -- which no reader may use)
+#   :status                      Status(tag, Int[]): fuse_idx is non-empty only on a row tagged `fuse`, and a batch that honours tags never
+#                                begins a step with one (an error if a frame shows one)
+#   :poly                        Subzero.make_polygon of the recorded ring
+const FRAME_DERIVED_OUTPUTS = Dict{Symbol, Tuple{Vector{Symbol}, Vector{Symbol}}}(
+    :interactions => (Symbol[], [:interactions]), :num_inters => (Symbol[], [:interactions]),
+    :status => ([:status], Symbol[]), :poly => ([:rings], Symbol[]))
+# Outputs taken from the HOST's own floes, matched by the recorded id (each needs the :id group): nothing in a batch changes them, a ghost
+# carries its parent's id, and matching by id survives removals on the device.  The sub-floe points are deliberately not pulled through the
+# frame's section here -- about 16 MB per frame at 10 000 floes of data that is constant between host edits; the section is for hosts that
+# keep no floe list, and for restarts.  parent_ids: emptied after the first frame written for an output step, as write_floe_data! does
+# (output.jl:570).
+const FRAME_HOST_OUTPUTS = (:angles, :damage, :parent_ids, :x_subfloe_points, :y_subfloe_points)
+frame_covers(w) = all(o -> haskey(FRAME_OUTPUTS, o) || haskey(FRAME_DERIVED_OUTPUTS, o) || o in FRAME_HOST_OUTPUTS, w.outputs)
+# the column groups and the lists word a writer's outputs need
+function frame_needs(outputs)
+    groups, lists = Symbol[], UInt32(0)
+    for o in outputs
+        if haskey(FRAME_OUTPUTS, o)
+            append!(groups, FRAME_OUTPUTS[o])
+        elseif haskey(FRAME_DERIVED_OUTPUTS, o)
+            g, l = FRAME_DERIVED_OUTPUTS[o]
+            append!(groups, g)
+            for name in l
+                lists |= UInt32(1) << (findfirst(==(name), FRAME_LISTS) - 1)
+            end
+        else
+            push!(groups, :id)
+        end
+    end
+    isempty(groups) && push!(groups, :id)          # (a mask selects at least one group)
+    return frame_mask(groups), lists
+end
+frame_lists(w) = frame_needs(w.outputs)[2]
 const EUL_CODES = Dict(name => Int32(k - 1) for (k, name) in enumerate(
     (:u_grid, :v_grid, :dudt_grid, :dvdt_grid, :overarea_grid, :mass_grid, :area_grid, :height_grid, :si_frac_grid, :stress_xx_grid,
      :stress_yx_grid, :stress_xy_grid, :stress_yy_grid, :stress_eig_grid, :strain_ux_grid, :strain_vx_grid, :strain_uy_grid, :strain_vy_grid)))
@@ -1603,15 +1639,17 @@ const EUL_CODES = Dict(name => Int32(k - 1) for (k, name) in enumerate(
 """
     set_floe_output!(eng, sim, i; arena_bytes = 1 << 28) -> Bool
 
-Register `sim.writers.floewriters[i]` with the device recorder (at most 4): its Δtout and the column groups its outputs need.  `false`, and
-nothing registered, when the writer asks for an output a frame does not hold.
+Register `sim.writers.floewriters[i]` with the device recorder (at most 4): its Δtout, the column groups and the lists its outputs need
+(`frame_needs`; the `id` group where an output is served from the host's floes).  `false`, and nothing registered, when the writer asks for
+an output a frame does not serve.
 """
 function set_floe_output!(eng::HIPEngine, sim, i::Integer; arena_bytes::Integer = 1 << 28)
     w = sim.writers.floewriters[i]
     (frame_covers(w) && length(eng.rec_floe) < 4) || return false
-    mask = frame_mask(g for o in w.outputs for g in FRAME_OUTPUTS[o])
+    mask, lists = frame_needs(w.outputs)
     check(eng, @ccall lib.sz_set_floe_output(eng.ctx::Ptr{Cvoid}, Int32(length(eng.rec_floe))::Int32, Int32(w.Δtout)::Int32, mask::UInt64,
                                              Int64(arena_bytes)::Int64)::Cint)
+    lists != 0 && check(eng, @ccall lib.sz_set_floe_output_lists(eng.ctx::Ptr{Cvoid}, Int32(length(eng.rec_floe))::Int32, lists::UInt32)::Cint)
     push!(eng.rec_floe, (Int(i), mask))
     return true
 end
@@ -1636,6 +1674,16 @@ end
 tensor(t, i) = [t[4i-3] t[4i-2]; t[4i-1] t[4i]]          # 11, 12, 21, 22
 # one output of a FloeOutputWriter from the columns of a frame, as StructArrays.component(floes, output) would give it
 function frame_component(o::Symbol, c::Dict{Symbol, Vector}, M::Int)
+    if o === :interactions          # rows 1:num_inters of every floe (c[:inter_rows][1]: 7 x R, a row of the matrix per column)
+        rows = c[:inter_rows][1]
+        return [permutedims(rows[:, c[:inter_off][i]+1:c[:inter_off][i+1]]) for i in 1:M]
+    end
+    o === :num_inters && return [Int(c[:inter_off][i+1] - c[:inter_off][i]) for i in 1:M]
+    if o === :status          # (tags: active = 1, remove = 2, fuse = 3 -- SZ_ACTIVE .. SZ_FUSE, floe.jl:8-12)
+        any(==(Int32(3)), c[:status]) && error("a frame began a step with a floe tagged fuse: its fuse_idx is not recorded")
+        return [Subzero.Status(Subzero.StatusTag(Int(t)), Int[]) for t in c[:status]]
+    end
+    o === :poly && return [Subzero.make_polygon([[[c[:vx][k], c[:vy][k]] for k in c[:vert_off][i]+1:c[:vert_off][i+1]]]) for i in 1:M]
     o === :centroid && return [[c[:cx][i], c[:cy][i]] for i in 1:M]
     o === :coords && return [[[[c[:vx][k], c[:vy][k]] for k in c[:vert_off][i]+1:c[:vert_off][i+1]]] for i in 1:M]
     o === :ghosts && return [Int[c[:ghost_idx][k] + 1 for k in c[:ghost_off][i]+1:c[:ghost_off][i+1]] for i in 1:M]
@@ -1655,8 +1703,10 @@ a frame that found no room.
 function drain_frames!(eng::HIPEngine, sim)
     nf, ng, full = zeros(Int32, 4), zeros(Int32, 4), Ref{Int32}(0)
     check(eng, @ccall lib.sz_output_frames(eng.ctx::Ptr{Cvoid}, nf::Ptr{Int32}, ng::Ptr{Int32}, full::Ptr{Int32})::Cint)
+    emptied = Set{Int}()          # output steps whose parent_ids have been written once (output.jl:570)
     for (slot, (i, mask)) in enumerate(eng.rec_floe), k in 0:nf[slot]-1
         w = sim.writers.floewriters[i]
+        lists = frame_lists(w)
         info = [Ref{Int64}(0) for _ in 1:5]
         check(eng, @ccall lib.sz_floe_frame_info(eng.ctx::Ptr{Cvoid}, Int32(slot - 1)::Int32, Int32(k)::Int32, info[1]::Ptr{Int64},
                                                  info[2]::Ptr{Int64}, info[3]::Ptr{Int64}, info[4]::Ptr{Int64}, info[5]::Ptr{Int64})::Cint)
@@ -1683,11 +1733,30 @@ function drain_frames!(eng::HIPEngine, sim)
             check(eng, @ccall lib.sz_download_floe_frame(eng.ctx::Ptr{Cvoid}, Int32(slot - 1)::Int32, Int32(k)::Int32,
                                                          cols::Ref{SzFloeColumns})::Cint)
         end
+        if lists & 1 != 0
+            nr, ns = Ref{Int64}(0), Ref{Int64}(0)
+            check(eng, @ccall lib.sz_floe_frame_lists_info(eng.ctx::Ptr{Cvoid}, Int32(slot - 1)::Int32, Int32(k)::Int32, nr::Ptr{Int64},
+                                                           ns::Ptr{Int64})::Cint)
+            ioff, irows = zeros(Int32, M + 1), zeros(Float64, 7, max(Int(nr[]), 1))
+            check(eng, @ccall lib.sz_download_floe_frame_interactions(eng.ctx::Ptr{Cvoid}, Int32(slot - 1)::Int32, Int32(k)::Int32,
+                                                                      ioff::Ptr{Int32}, irows::Ptr{Float64})::Cint)
+            c[:inter_off], c[:inter_rows] = ioff, [irows]
+        end
+        # outputs of the host's own floes, by the recorded id (a ghost: its parent's)
+        floes = sim.model.floes
+        row_of = Dict(id => r for (r, id) in enumerate(floes.id))
+        host_rows = any(in(FRAME_HOST_OUTPUTS), w.outputs) ? [row_of[Int(id)] for id in c[:id]] : Int[]
         Subzero.jldopen(w.filepath, "a+") do file
             for o in w.outputs
-                Subzero.write_field(file, string(o, "/", tstep), frame_component(o, c, M))
+                if o in FRAME_HOST_OUTPUTS
+                    v = o === :parent_ids && tstep in emptied ? [Int[] for _ in host_rows] : [getproperty(floes, o)[r] for r in host_rows]
+                    Subzero.write_field(file, string(o, "/", tstep), v)
+                else
+                    Subzero.write_field(file, string(o, "/", tstep), frame_component(o, c, M))
+                end
             end
         end
+        :parent_ids in w.outputs && push!(emptied, tstep)
     end
     for (slot, i) in enumerate(eng.rec_grid), k in 0:ng[slot]-1
         w = sim.writers.gridwriters[i]

@@ -98,11 +98,16 @@ EXPORTS = [
     "sz_clear_frames", "sz_debug_next_segment_out", "sz_debug_frame_bits",
     "sz_tile_set_floe_output", "sz_tile_set_grid_output", "sz_tile_floe_frame_keys", "sz_tile_floe_frame_info", "sz_tile_download_floe_frame",
     "sz_debug_totals_mode", "sz_debug_fx_totals", "sz_debug_fx_word",
+    "sz_set_floe_output_lists", "sz_floe_frame_lists_info", "sz_download_floe_frame_interactions",
 ]
 
 # the column groups of sz_set_floe_output's mask, bit 0 first (sz_debug_frame_bits; tests/test_output_stops_cpu.py holds the list to the library's)
 FRAME_BITS = DCOLS + TCOLS + ["id", "ghost_id", "status", "rings", "ghost_links"]
 FRAME_MEMBERS = {"rings": ["vert_off", "vx", "vy"], "ghost_links": ["ghost_off", "ghost_idx"]}      # groups of more than one struct member
+# the ragged members of sz_set_floe_output_lists, bit 0 first (SZ_FRAME_INTERACTIONS, SZ_FRAME_SUBPOINTS), and the struct members / keys of
+# World.floe_frame they bring
+FRAME_LISTS = ["interactions", "subpoints"]
+FRAME_LIST_MEMBERS = {"interactions": ["inter_off", "inter_rows"], "subpoints": ["sub_off", "sx", "sy"]}
 REC_WRITERS = 4
 
 EUL_PARTIAL = 17      # SZ_EUL_PARTIAL: per-cell partial fields of sz_eulerian_partial
@@ -256,6 +261,9 @@ def load(build_if_missing=True):
     L.sz_floe_frame_info.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _lp, _lp, _lp, _lp, _lp]
     L.sz_download_floe_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SzFloeColumns)]
     L.sz_download_grid_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp]
+    L.sz_set_floe_output_lists.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
+    L.sz_floe_frame_lists_info.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _lp, _lp]
+    L.sz_download_floe_frame_interactions.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp]
     L.sz_clear_frames.argtypes = [C.c_void_p]
     L.sz_tile_set_floe_output.argtypes = L.sz_set_floe_output.argtypes
     L.sz_tile_set_grid_output.argtypes = L.sz_set_grid_output.argtypes

@@ -3380,6 +3380,7 @@ static void rec_free_grid(GridWriter& g) { (void)hipFree(g.store); g = GridWrite
 static void rec_free_all(sz_ctx* c) {
   for (int w = 0; w < REC_WRITERS; w++) { rec_free_floe(c->rec.floe[w]); rec_free_grid(c->rec.grid[w]); }
   (void)hipFree(c->rec.grid_work.p); (void)hipFree(c->rec.entry_work.p); (void)hipFree(c->rec.part_work.p);
+  (void)hipFree(c->rec.list_work.p);
   c->rec = Recorder{};
 }
 // the setters of the single context (tile = false) and of a tiled one (sz_tile_set_*): the same arguments and checks, each kind refuses the other's context
@@ -3410,6 +3411,18 @@ static int rec_set_grid(sz_ctx* c, int32_t writer, int32_t dt_out, int32_t nx, i
                         const int32_t* outputs, int32_t max_frames, bool tile);
 int sz_set_floe_output(sz_ctx* c, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes) { return rec_set_floe(c, writer, dt_out, columns_mask, arena_bytes, false); }
 int sz_tile_set_floe_output(sz_ctx* c, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes) { return rec_set_floe(c, writer, dt_out, columns_mask, arena_bytes, true); }
+int sz_set_floe_output_lists(sz_ctx* c, int32_t writer, uint32_t lists) {
+  if (!c) return SZ_E_ARG;
+  if (writer < 0 || writer >= REC_WRITERS) { c->err = "output writer index out of range (0..3)"; return SZ_E_ARG; }
+  if (lists & ~FR_LIST_ALL) { c->err = "sz_set_floe_output_lists: a list that does not exist (SZ_FRAME_INTERACTIONS | SZ_FRAME_SUBPOINTS)"; return SZ_E_ARG; }
+  FloeWriter& w = c->rec.floe[writer];
+  if (c->S.tiled || w.tile) { c->err = "sz_set_floe_output_lists: tile frames record no lists yet (single contexts, writers of sz_set_floe_output)"; return SZ_E_STATE; }
+  if (w.dt == 0) { c->err = "sz_set_floe_output_lists: the writer is off (sz_set_floe_output first)"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  w.frames.clear(); w.used = 0; w.lists = lists;
+  return SZ_OK;
+}
 int sz_set_grid_output(sz_ctx* c, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double* xg, const double* yg, int32_t nout,
                        const int32_t* outputs, int32_t max_frames) { return rec_set_grid(c, writer, dt_out, nx, ny, xg, yg, nout, outputs, max_frames, false); }
 int sz_tile_set_grid_output(sz_ctx* c, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double* xg, const double* yg, int32_t nout,
@@ -3471,6 +3484,75 @@ static int rec_grid(sz_ctx* c, GridWriter& g, int tstep) {
   g.tsteps.push_back(tstep);
   return SZ_OK;
 }
+// The workspace of the lists (Recorder::list_work), carved for a context of capM rows: the sorted keys, the keys on their way up, the counts and
+// the scanned offsets of both lists, the sort's scratch.  Sized by the capacity, not by the counts, so that what is sorted before sz_add_ghosts
+// stays where it is when the counts are known.
+struct ListWork {
+  long long *keys, *keys_in; int *n_inter, *n_sub, *ioff, *soff; void* tmp; size_t tmp_bytes;
+};
+static int rec_list_work(sz_ctx* c, ListWork& W) {
+  const size_t cap = (size_t)c->S.capM + 2, ints = (cap * sizeof(int) + 7) & ~(size_t)7;
+  size_t tb = 0;
+  HIPCHK(c, rocprim::radix_sort_keys(nullptr, tb, (long long*)nullptr, (long long*)nullptr, cap, 0, 64, c->stream));
+  tb = (tb + 255) & ~(size_t)255;
+  if (int rc = work_reserve(c, c->rec.list_work, 2 * cap * sizeof(long long) + 4 * ints + tb)) return rc;
+  char* p = c->rec.list_work.p;
+  W.keys = (long long*)p; p += cap * sizeof(long long); W.keys_in = (long long*)p; p += cap * sizeof(long long);
+  W.n_inter = (int*)p; p += ints; W.n_sub = (int*)p; p += ints; W.ioff = (int*)p; p += ints; W.soff = (int*)p; p += ints;
+  W.tmp = p; W.tmp_bytes = tb;
+  return SZ_OK;
+}
+// the order keys of the last step's inline ghosts, sorted, into the workspace: what the interactions section translates partners with.  To be
+// called BEFORE sz_add_ghosts, which clears gi_valid and reuses the key table.  Keys not fetched yet are sorted where they are, on the device
+// (gi_pending stays: nothing is fetched); keys the host holds already are uploaded.  *nkeys == 0: nothing to translate, as
+// sz_download_interactions would translate nothing.
+static int rec_list_keys(sz_ctx* c, int* nkeys) {
+  *nkeys = 0;
+  if (!c->gi_valid) return SZ_OK;
+  ListWork W;
+  if (int rc = rec_list_work(c, W)) return rc;
+  const int G = c->gi_pending ? c->gi_pending_n : (int)c->gi_keys.size();
+  if (G <= 0 || G > c->S.capM) return SZ_OK;
+  const long long* src = c->S.gkeys + (size_t)c->gi_pending_slot * c->S.capM;
+  if (!c->gi_pending) {
+    HIPCHK(c, hipMemcpyAsync(W.keys_in, c->gi_keys.data(), (size_t)G * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    src = W.keys_in;
+  }
+  size_t tb = 0;
+  HIPCHK(c, rocprim::radix_sort_keys(nullptr, tb, src, W.keys, (size_t)G, 0, 64, c->stream));
+  if (tb > W.tmp_bytes) { c->err = "the recorder's key sort needs more scratch than its workspace holds"; return SZ_E_STATE; }
+  HIPCHK(c, rocprim::radix_sort_keys(W.tmp, tb, src, W.keys, (size_t)G, 0, 64, c->stream));
+  *nkeys = G;
+  return SZ_OK;
+}
+// the counts of both lists over the rows behind sz_add_ghosts and their scans; the totals go into two spare words of the counter block and
+// reach the host with the counter fetch the record point does anyway
+static int rec_list_scans(sz_ctx* c, unsigned lists) {
+  ListWork W;
+  if (int rc = rec_list_work(c, W)) return rc;
+  const int M = c->hostM, N = c->hostN;
+  hipLaunchKernelGGL(sz_k_frame_list_counts, dim3(grid_for(M + 1, FP_TPB, 256)), dim3(FP_TPB), 0, c->stream, c->S, lists & FR_LIST_INTER ? W.n_inter : nullptr,
+                     lists & FR_LIST_SUB ? W.n_sub : nullptr, M, N);
+  if (lists & FR_LIST_INTER) scan(c, W.n_inter, W.ioff, M, -1, M, C_SCRATCH0);
+  if (lists & FR_LIST_SUB) scan(c, W.n_sub, W.soff, M, -1, M, C_SCRATCH1);
+  return SZ_OK;
+}
+// the list sections of the frame rec_pack has just appended to w: one launch
+static int rec_pack_lists(sz_ctx* c, FloeWriter& w, long long R, long long S, int nkeys) {
+  ListWork W;
+  if (int rc = rec_list_work(c, W)) return rc;
+  FloeFrame& fr = w.frames.back();
+  const long long base = FrameLayout(w.mask, fr.M, fr.N, fr.V).total;
+  fr.lists = w.lists; fr.R = w.lists & FR_LIST_INTER ? R : 0; fr.S = w.lists & FR_LIST_SUB ? S : 0;
+  const ListLayout L(base, fr.lists, fr.M, fr.R, fr.S);
+  FrameLists F;
+  for (int k = 0; k < FL_NSEC; k++) F.off[k] = L.off[k];
+  F.dst = w.arena + fr.at; F.ioff = W.ioff; F.soff = W.soff; F.keys = W.keys; F.nkeys = nkeys; F.M = fr.M; F.N = fr.N; F.lists = fr.lists; F.R = fr.R; F.S = fr.S;
+  const long long widest = std::max<long long>(std::max<long long>(7 * fr.R, fr.S), fr.M + 1);
+  hipLaunchKernelGGL(sz_k_frame_lists, dim3(grid_for(widest, FP_TPB, 256), 2), dim3(FP_TPB), 0, c->stream, c->S, F);
+  w.used = fr.at + (size_t)L.total;
+  return SZ_OK;
+}
 // write_data! of output step tstep, in front of the segment that starts there (run_with_stops).  *full: a due writer has no room for its
 // frame -- nothing is recorded for this step, the batch ends in front of it.
 static int rec_record(sz_ctx* c, int tstep, int* full) {
@@ -3480,14 +3562,25 @@ static int rec_record(sz_ctx* c, int tstep, int* full) {
   for (int w = 0; w < REC_WRITERS; w++) { fdue[w] = step_due(R.floe[w].dt, tstep); gdue[w] = step_due(R.grid[w].dt, tstep); any = any || fdue[w] || gdue[w]; }
   if (!any) return SZ_OK;
   for (int w = 0; w < REC_WRITERS; w++) if (gdue[w] && (int)R.grid[w].tsteps.size() >= R.grid[w].max_frames) { *full = 1; R.full = true; return SZ_OK; }
-  int rc, h[C_COUNT];
+  int rc, h[C_COUNT], nkeys = 0;
   (void)hipSetDevice(c->device);
+  unsigned lists = 0;          // the lists some due writer records: a writer without lists adds no launch, no scan and no synchronisation
+  for (int w = 0; w < REC_WRITERS; w++) if (fdue[w]) lists |= R.floe[w].lists;
+  if ((lists & FR_LIST_INTER) && (rc = rec_list_keys(c, &nkeys))) return rc;
+  const char* const keys_in = R.list_work.p;
   if ((c->ghosts_staged || c->hostM != c->hostN) && (rc = sz_remove_ghosts(c))) return rc;          // (ghosts a process-mode call left attached: a batch drops them too)
-  if ((rc = sz_add_ghosts(c)) || (rc = fetch_counters(c, h))) return rc;
+  if ((rc = sz_add_ghosts(c)) || (lists && (rc = rec_list_scans(c, lists))) || (rc = fetch_counters(c, h))) return rc;
+  if (nkeys > 0 && R.list_work.p != keys_in) { c->err = "the recorder's workspace moved under the sorted ghost keys (sz_add_ghosts grew the list)"; return SZ_E_STATE; }
   const int V = h[C_NV];
+  const long long nR = lists & FR_LIST_INTER ? h[C_SCRATCH0] : 0, nS = lists & FR_LIST_SUB ? h[C_SCRATCH1] : 0;
+  auto frame_total = [&](const FloeWriter& fw) {
+    const long long base = FrameLayout(fw.mask, c->hostM, c->hostN, V).total;
+    return (size_t)(fw.lists ? ListLayout(base, fw.lists, c->hostM, nR, nS).total : base);
+  };
   for (int w = 0; w < REC_WRITERS; w++)
-    if (fdue[w] && R.floe[w].used + (size_t)FrameLayout(R.floe[w].mask, c->hostM, c->hostN, V).total > R.floe[w].bytes) { *full = 1; R.full = true; }
-  for (int w = 0; w < REC_WRITERS && !*full; w++) if (fdue[w] && (rc = rec_pack(c, R.floe[w], tstep, V))) return rc;
+    if (fdue[w] && R.floe[w].used + frame_total(R.floe[w]) > R.floe[w].bytes) { *full = 1; R.full = true; }
+  for (int w = 0; w < REC_WRITERS && !*full; w++)
+    if (fdue[w] && ((rc = rec_pack(c, R.floe[w], tstep, V)) || (R.floe[w].lists && (rc = rec_pack_lists(c, R.floe[w], nR, nS, nkeys))))) return rc;
   for (int w = 0; w < REC_WRITERS && !*full; w++) if (gdue[w] && (rc = rec_grid(c, R.grid[w], tstep))) return rc;
   return sz_remove_ghosts(c);
 }
@@ -3513,7 +3606,9 @@ int sz_floe_frame_info(sz_ctx* c, int32_t writer, int32_t k, int64_t* tstep, int
   return SZ_OK;
 }
 // a frame of M rows (N parents), V ring points in layout L at d_frame: down in one copy, its sections into the non-NULL members of f
-static int rec_frame_down(sz_ctx* c, const char* who, const FrameLayout& L, long long M, long long N, long long V, const char* d_frame, sz_floe_columns* f) {
+// LL (a frame with the sub-floe points section): sub_off, sx, sy come down too, S points, in copies of their own
+static int rec_frame_down(sz_ctx* c, const char* who, const FrameLayout& L, long long M, long long N, long long V, const char* d_frame, sz_floe_columns* f,
+                          const ListLayout* LL = nullptr, long long S = 0) {
   const long long G = M - N;
   struct Part { void* dst; int sec; long long bytes; };
   std::vector<Part> parts;
@@ -3523,7 +3618,8 @@ static int rec_frame_down(sz_ctx* c, const char* who, const FrameLayout& L, long
   parts.push_back({ f->vert_off, FR_VOFF, (M + 1) * 4 }); parts.push_back({ f->vx, FR_VX, V * 8 }); parts.push_back({ f->vy, FR_VY, V * 8 });
   parts.push_back({ f->ghost_off, FR_GOFF, (M + 1) * 4 }); parts.push_back({ f->ghost_idx, FR_GIDX, G * 4 });
   for (const Part& p : parts) if (p.dst && L.off[p.sec] < 0) { c->err = std::string(who) + ": a member is asked for that the writer's mask did not record"; return SZ_E_ARG; }
-  if (f->sub_off || f->sx || f->sy) { c->err = std::string(who) + ": sub-floe points are not recorded"; return SZ_E_ARG; }
+  const bool subs = LL && LL->off[FL_SOFF] >= 0;
+  if ((f->sub_off || f->sx || f->sy) && !subs) { c->err = std::string(who) + ": this frame did not record the sub-floe points (sz_set_floe_output_lists)"; return SZ_E_ARG; }
   if (!d_frame) return SZ_OK;          // (the members were only checked)
   (void)hipSetDevice(c->device);
   // the frame comes down in one copy
@@ -3532,13 +3628,39 @@ static int rec_frame_down(sz_ctx* c, const char* who, const FrameLayout& L, long
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(host.data(), d_frame, (size_t)L.total, hipMemcpyDeviceToHost));
   for (const Part& p : parts) if (p.dst && p.bytes > 0) memcpy(p.dst, host.data() + L.off[p.sec], (size_t)p.bytes);
+  if (subs) {
+    if (f->sub_off) HIPCHK(c, hipMemcpy(f->sub_off, d_frame + LL->off[FL_SOFF], (size_t)(M + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    if (f->sx && S > 0) HIPCHK(c, hipMemcpy(f->sx, d_frame + LL->off[FL_SX], (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    if (f->sy && S > 0) HIPCHK(c, hipMemcpy(f->sy, d_frame + LL->off[FL_SY], (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+  }
   return SZ_OK;
 }
 int sz_download_floe_frame(sz_ctx* c, int32_t writer, int32_t k, sz_floe_columns* f) {
   const FloeFrame* fr = rec_floe_frame(c, writer, k);
   if (!fr || !f) return SZ_E_ARG;
   const FloeWriter& w = c->rec.floe[writer];
-  return rec_frame_down(c, "sz_download_floe_frame", FrameLayout(w.mask, fr->M, fr->N, fr->V), fr->M, fr->N, fr->V, w.arena + fr->at, f);
+  const FrameLayout L(w.mask, fr->M, fr->N, fr->V);
+  const ListLayout LL(L.total, fr->lists, fr->M, fr->R, fr->S);
+  return rec_frame_down(c, "sz_download_floe_frame", L, fr->M, fr->N, fr->V, w.arena + fr->at, f, &LL, fr->S);
+}
+int sz_floe_frame_lists_info(sz_ctx* c, int32_t writer, int32_t k, int64_t* n_inter_rows, int64_t* n_sub_points) {
+  const FloeFrame* f = rec_floe_frame(c, writer, k);
+  if (!f) return SZ_E_ARG;
+  if (n_inter_rows) *n_inter_rows = f->R;
+  if (n_sub_points) *n_sub_points = f->S;
+  return SZ_OK;
+}
+int sz_download_floe_frame_interactions(sz_ctx* c, int32_t writer, int32_t k, int32_t* off, double* rows) {
+  const FloeFrame* fr = rec_floe_frame(c, writer, k);
+  if (!fr || !off) return SZ_E_ARG;
+  if (!(fr->lists & FR_LIST_INTER)) { c->err = "sz_download_floe_frame_interactions: this frame did not record the interactions (sz_set_floe_output_lists)"; return SZ_E_ARG; }
+  const FloeWriter& w = c->rec.floe[writer];
+  const ListLayout LL(FrameLayout(w.mask, fr->M, fr->N, fr->V).total, fr->lists, fr->M, fr->R, fr->S);
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(off, w.arena + fr->at + LL.off[FL_IOFF], (size_t)(fr->M + 1) * sizeof(int), hipMemcpyDeviceToHost));
+  if (rows && fr->R > 0) HIPCHK(c, hipMemcpy(rows, w.arena + fr->at + LL.off[FL_IROWS], (size_t)fr->R * 7 * sizeof(double), hipMemcpyDeviceToHost));
+  return SZ_OK;
 }
 int sz_download_grid_frame(sz_ctx* c, int32_t writer, int32_t k, int32_t* tstep, double* data) {
   if (!c) return SZ_E_ARG;

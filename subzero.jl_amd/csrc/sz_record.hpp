@@ -6,8 +6,21 @@
 //
 // A FLOE FRAME is the list as add_ghosts! leaves it, in the columns the writer's mask selects.  The mask has one bit per column group of
 // sz_floe_columns, in struct order (frame_bit_names below): bits 0..27 the double columns (the three tensors 4 doubles per floe), 28 id,
-// 29 ghost_id, 30 status, 31 the rings (vert_off + vx + vy), 32 the ghost links (ghost_off + ghost_idx).  Not recorded: the sub-floe points,
-// floe.interactions and status.fuse_idx -- a writer that wants those keeps cutting its own batches.
+// 29 ghost_id, 30 status, 31 the rings (vert_off + vx + vy), 32 the ghost links (ghost_off + ghost_idx).
+// THE LISTS (sz_set_floe_output_lists, opt-in per writer; sz_k_frame_lists below): the ragged members of a floe, in sections BEHIND the selected
+// column sections, so that the layout of a frame without them is untouched (the move TileFrameLayout made for its keys):
+//   interactions  inter_off int32 [M + 1], inter_rows double [R][7].  A parent row carries floe.interactions of the last step that ran, with the
+//                 bits sz_download_interactions gives at that cut BEFORE sz_add_ghosts: the floeidx column as the reference stores it -- a partner
+//                 that was an inline ghost of that step is N + the rank of its order key among that step's ghost keys + 1 (the keys are sorted on
+//                 the device, or the host's fetched copy is uploaded, before sz_add_ghosts clears gi_valid and reuses the key table); where that
+//                 call would translate nothing (gi_valid false: a process-mode call ran, the host uploaded the rows) the rows are kept as they
+//                 are.  A ghost row's span is EMPTY whatever inter_cnt says on rows >= N: deepcopy_floe (floe_utils.jl:120-161) passes no
+//                 interactions, the copy gets zeros(0, 7) and num_inters = 0.
+//   subpoints     sub_off int32 [M + 1], sx [S], sy [S], centred as stored.  A parent row carries its own points with the bits of
+//                 sz_download_subpoints; a ghost row its root parent's (deepcopy_floe copies them; State::parent names the row).
+// status.fuse_idx has no section: it is non-empty only on a row tagged `fuse` (collisions.jl:367-368, 801-806), and a batch that honours tags
+// never begins a step with such a row -- a host reads the recorded status column and knows.
+// The three spare header words of a frame with lists are {lists, R, S}.
 // A ghost is a deep copy of its parent (collisions.jl:881-901, floe_utils.jl:138), translated: the device keeps only the collision columns on a
 // ghost row, so the pack reads every column of a ghost row from the row State::parent names -- cx, cy, the ring and ghost_id apart, which are
 // the ghost's own.  A ghost row has no ghost links of its own (its ghost_off span is empty), as sz_download_floes reports it.
@@ -143,14 +156,101 @@ __global__ void __launch_bounds__(FP_TPB) sz_k_frame_pack(State S, FramePack F) 
   }
 }
 
+// ---- the lists (sz_set_floe_output_lists): which, and where their sections lie -- behind FrameLayout::total, each padded to 8 bytes
+constexpr unsigned FR_LIST_INTER = 1, FR_LIST_SUB = 2, FR_LIST_ALL = 3;
+constexpr int FL_IOFF = 0, FL_IROWS = 1, FL_SOFF = 2, FL_SX = 3, FL_SY = 4, FL_NSEC = 5;
+struct ListLayout {
+  long long off[FL_NSEC]; long long total;          // total: the whole frame's, columns included
+  ListLayout(long long base, unsigned lists, long long M, long long R, long long S) {
+    long long at = base;
+    auto take = [&](int sec, bool on, long long bytes) { off[sec] = on ? at : -1; if (on) at += (bytes + 7) & ~7ll; };
+    const bool in = lists & FR_LIST_INTER, sub = lists & FR_LIST_SUB;
+    take(FL_IOFF, in, (M + 1) * 4); take(FL_IROWS, in, R * 7 * 8);
+    take(FL_SOFF, sub, (M + 1) * 4); take(FL_SX, sub, S * 8); take(FL_SY, sub, S * 8);
+    total = at;
+  }
+};
+
+// per row of the list behind sz_add_ghosts its interaction rows and sub-floe points (entry M: 0): what the two scans turn into offsets.
+// A null pointer: that list is not wanted.
+__global__ void __launch_bounds__(FP_TPB) sz_k_frame_list_counts(State S, int* n_inter, int* n_sub, int M, int N) {
+  for (int r = blockIdx.x * FP_TPB + threadIdx.x; r <= M; r += gridDim.x * FP_TPB) {
+    if (n_inter) n_inter[r] = r < N ? min(max(S.inter_cnt[r], 0), S.rowcap) : 0;          // (a ghost row: empty, whatever inter_cnt says there)
+    if (n_sub) {
+      int p = r < N ? r : -1;
+      if (r >= N && r < M) { const int q = S.parent[r]; p = q >= 0 && q < N ? q : -1; }
+      n_sub[r] = p >= 0 ? max(S.soff[p + 1] - S.soff[p], 0) : 0;
+    }
+  }
+}
+
+// what one launch of sz_k_frame_lists is told
+struct FrameLists {
+  char* dst;                      // the frame's start in the arena
+  long long off[FL_NSEC];
+  const int *ioff, *soff;         // the scanned counts, M + 1 entries each (the recorder's workspace)
+  const long long* keys;          // the order keys of the last step's inline ghosts, sorted; nkeys == 0: nothing is translated
+  int nkeys, M, N;
+  unsigned lists;
+  long long R, S;                 // the host's totals, fetched with the counters: every store lies inside the layout made from them
+};
+
+// The payload of the lists, element-parallel: blockIdx.y = 0 the interactions, one thread per output double; 1 the sub-floe points, one thread
+// per point.  The owning row is found by bisection in the scanned offsets, which the same slice copies into the frame; stores are coalesced,
+// reads contiguous within a row.  The floeidx column (column 0) of a row whose partner was an inline ghost holds 1 + the ghost's order key
+// (> 2^40): it becomes N + rank among the sorted keys + 1, as sz_download_interactions renumbers it on the host; a key that is not among them
+// stays.  No atomic decides a position: two packs of one state give the same bits.
+__global__ void __launch_bounds__(FP_TPB) sz_k_frame_lists(State S, FrameLists F) {
+  const int M = F.M, N = F.N;
+  const long long t0 = (long long)blockIdx.x * FP_TPB + threadIdx.x, stride = (long long)gridDim.x * FP_TPB;
+  if (blockIdx.y == 0) {
+    if (t0 == 0) { long long* h = (long long*)F.dst; h[5] = F.lists; h[6] = F.R; h[7] = F.S; }
+    if (F.off[FL_IOFF] < 0) return;
+    int* off = (int*)(F.dst + F.off[FL_IOFF]);
+    double* out = (double*)(F.dst + F.off[FL_IROWS]);
+    for (long long r = t0; r <= M; r += stride) off[r] = F.ioff[r];
+    const double lim = (double)((long long)1 << 40);
+    for (long long e = t0; e < 7 * F.R; e += stride) {
+      const long long row = e / 7; const int k = (int)(e - 7 * row);
+      int lo = 0, hi = N;                         // the last parent i with ioff[i] <= row: the one that owns it (empty parents share an offset)
+      while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (F.ioff[mid] <= row) lo = mid; else hi = mid; }
+      const long long q = row - F.ioff[lo];
+      double v = q >= 0 && q < S.rowcap && lo < N ? S.inter_rows[((size_t)lo * S.rowcap + (size_t)q) * 7 + k] : 0.0;
+      if (k == 0 && F.nkeys > 0 && v > lim) {
+        const long long key = (long long)v - 1;
+        int a = 0, b = F.nkeys;                   // lower bound
+        while (a < b) { const int mid = (a + b) >> 1; if (F.keys[mid] < key) a = mid + 1; else b = mid; }
+        if (a < F.nkeys && F.keys[a] == key) v = (double)(N + a + 1);
+      }
+      out[e] = v;
+    }
+  } else {
+    if (F.off[FL_SOFF] < 0) return;
+    int* off = (int*)(F.dst + F.off[FL_SOFF]);
+    double *sx = (double*)(F.dst + F.off[FL_SX]), *sy = (double*)(F.dst + F.off[FL_SY]);
+    for (long long r = t0; r <= M; r += stride) off[r] = F.soff[r];
+    for (long long p = t0; p < F.S; p += stride) {
+      int lo = 0, hi = M;                         // the last row with soff[row] <= p
+      while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (F.soff[mid] <= p) lo = mid; else hi = mid; }
+      int src = lo < N ? lo : -1;
+      if (lo >= N && lo < M) { const int q = S.parent[lo]; src = q >= 0 && q < N ? q : -1; }
+      const long long q = src >= 0 ? (long long)S.soff[src] + (p - F.soff[lo]) : -1;
+      const bool ok = src >= 0 && q >= S.soff[src] && q < S.soff[src + 1] && q < S.capS;
+      sx[p] = ok ? S.sx[q] : 0.0; sy[p] = ok ? S.sy[q] : 0.0;
+    }
+  }
+}
+
 // host side of one writer each; the device memory is the recorder's own (hipMalloc / hipFree when a writer is set, re-set or cleared away),
 // so frames outlive uploads and row edits
 struct FloeFrame {
   size_t at; int tstep, M, N, V;
   std::vector<int> ranks;         // a tile frame: {M, N, V} of every rank's frame of this step, as gathered at the record point
+  unsigned lists = 0; long long R = 0, S = 0;          // the lists it holds, their totals: interaction rows, sub-floe points
 };
 struct FloeWriter {
   int dt = 0; unsigned long long mask = 0; bool tile = false;      // tile: set through sz_tile_set_floe_output
+  unsigned lists = 0;             // sz_set_floe_output_lists
   char* arena = nullptr; size_t bytes = 0, used = 0;
   std::vector<FloeFrame> frames;
 };
@@ -168,6 +268,7 @@ struct Recorder {
   bool any = false, full = false;
   bool any_tile = false, any_single = false; // ... set through the tile setters / through the single context's
   RecWork grid_work, entry_work;             // EulGrid's per-cell arrays; its entries and the sort's scratch
+  RecWork list_work;                         // the lists: sorted ghost keys, counts and scanned offsets, the sort's scratch (ListWork)
   RecWork part_work;                         // tile frames: the per-cell partial sums of all grid writers due at a step, one behind the other
   std::vector<char> host;                    // a frame on its way down
   void refresh() {

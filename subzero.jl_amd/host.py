@@ -518,9 +518,19 @@ class World:
         return sum(1 << capi.FRAME_BITS.index(n) for n in set(names))
 
     @staticmethod
-    def frame_bytes(mask, M, N, V):
+    def frame_lists(lists=None):
+        """the `lists` word of sz_set_floe_output_lists for names out of capi.FRAME_LISTS (None: none; a ready word passes through)"""
+        if lists is None or isinstance(lists, int):
+            return int(lists or 0)
+        for n in lists:
+            if n not in capi.FRAME_LISTS:
+                raise SzError(f"{n} is not a list of a floe frame")
+        return sum(1 << capi.FRAME_LISTS.index(n) for n in set(lists))
+
+    @staticmethod
+    def frame_bytes(mask, M, N, V, lists=0, R=0, S=0):
         """what a floe frame of M rows (N parents) and V ring points takes of its writer's arena (FrameLayout, csrc/sz_record.hpp): a header of
-        64 bytes, then the selected sections, each padded to 8 bytes"""
+        64 bytes, then the selected sections, each padded to 8 bytes; behind them the lists (ListLayout): R interaction rows, S sub-floe points"""
         def pad(b):
             return (b + 7) // 8 * 8
         total = 64
@@ -537,16 +547,28 @@ class World:
                 total += pad(4 * (M + 1)) + 16 * V
             else:
                 total += pad(4 * (M + 1)) + pad(4 * (M - N))
+        lists = World.frame_lists(lists)
+        if lists & 1:
+            total += pad(4 * (M + 1)) + 56 * R
+        if lists & 2:
+            total += pad(4 * (M + 1)) + 16 * S
         return total
 
-    def set_floe_output(self, writer, dt_out, columns=None, arena_bytes=1 << 26, _tile=False):
+    def set_floe_output(self, writer, dt_out, columns=None, arena_bytes=1 << 26, _tile=False, lists=None):
         """a FloeOutputWriter with Δtout = dt_out (0: off) that records the column groups `columns` (names out of capi.FRAME_BITS, or a ready
-        mask; None: all) into an arena of arena_bytes on the device.  (_tile: through the setter of tiled contexts -- TiledWorld's call.)"""
+        mask; None: all) into an arena of arena_bytes on the device, and the ragged members `lists` (names out of capi.FRAME_LISTS; None: none)
+        behind them.  (_tile: through the setter of tiled contexts -- TiledWorld's call.)"""
         mask = columns if isinstance(columns, int) else self.frame_mask(columns)
+        word = self.frame_lists(lists)
         fn = self.L.sz_tile_set_floe_output if _tile else self.L.sz_set_floe_output
         self._chk(fn(self.h, int(writer), int(dt_out), int(mask), int(arena_bytes)))
         self._floe_masks = getattr(self, "_floe_masks", {})
         self._floe_masks[int(writer)] = int(mask)
+        self._floe_lists = getattr(self, "_floe_lists", {})
+        self._floe_lists[int(writer)] = 0
+        if word:
+            self._chk(self.L.sz_set_floe_output_lists(self.h, int(writer), word))
+            self._floe_lists[int(writer)] = word
 
     def set_grid_output(self, writer, dt_out, xg=None, yg=None, outputs=None, max_frames=64, _tile=False):
         """a GridOutputWriter with Δtout = dt_out (0: off) on the grid lines xg, yg for the outputs named (EUL_OUTPUTS, default all), with room
@@ -571,7 +593,8 @@ class World:
 
     def floe_frame(self, writer, k, members=None, _merged=False):
         """floe frame k of a writer: a dict with tstep, M, N and the recorded columns as arrays in the layout of load_columns (the rings as
-        vert_off, vx, vy; the ghost links as ghost_off, ghost_idx).  members: struct members to ask for instead of everything recorded.
+        vert_off, vx, vy; the ghost links as ghost_off, ghost_idx; of a writer with lists inter_off, inter_rows [R, 7] and sub_off, sx, sy).
+        members: struct members (and inter_off / inter_rows) to ask for instead of everything recorded.
         (_merged: the merged frame of a tiled run, collectively -- TiledWorld.floe_frame's call.)"""
         info = [C.c_int64(0) for _ in range(5)]
         info_fn, down_fn = (self.L.sz_tile_floe_frame_info, self.L.sz_tile_download_floe_frame) if _merged else (self.L.sz_floe_frame_info, self.L.sz_download_floe_frame)
@@ -580,13 +603,24 @@ class World:
             down_fn(self.h, int(writer), int(k), None)          # (the peers are in the collective: take part, so that every rank raises)
         self._chk(rc)
         tstep, M, N, V, G = (int(v.value) for v in info)
+        R = S = 0
+        if not _merged:
+            tot = [C.c_int64(0), C.c_int64(0)]
+            self._chk(self.L.sz_floe_frame_lists_info(self.h, int(writer), int(k), *(C.byref(v) for v in tot)))
+            R, S = (int(v.value) for v in tot)
         if members is None:
             members = []
             for b, n in enumerate(capi.FRAME_BITS):
                 if self._floe_masks[int(writer)] >> b & 1:
                     members += capi.FRAME_MEMBERS.get(n, [n])
+            for b, n in enumerate(capi.FRAME_LISTS):
+                if getattr(self, "_floe_lists", {}).get(int(writer), 0) >> b & 1:
+                    members += capi.FRAME_LIST_MEMBERS[n]
+        inter = [n for n in members if n in ("inter_off", "inter_rows")]
         col = {}
         for n in members:
+            if n in inter:
+                continue
             if n in capi.DCOLS:
                 col[n] = np.zeros(M)
             elif n in capi.TCOLS:
@@ -597,8 +631,10 @@ class World:
                 col[n] = np.zeros(M, _I32)
             elif n in ("vert_off", "ghost_off", "sub_off"):
                 col[n] = np.zeros(M + 1, _I32)
-            elif n in ("vx", "vy", "sx", "sy"):
+            elif n in ("vx", "vy"):
                 col[n] = np.zeros(max(V, 1))
+            elif n in ("sx", "sy"):
+                col[n] = np.zeros(max(S, 1))
             elif n == "ghost_idx":
                 col[n] = np.zeros(max(G, 1), _I32)
             else:
@@ -612,6 +648,16 @@ class World:
         for n in ("vx", "vy"):
             if n in col:
                 col[n] = col[n][:V]
+        for n in ("sx", "sy"):
+            if n in col:
+                col[n] = col[n][:S]
+        if inter:
+            off = np.zeros(M + 1, _I32); rows = np.zeros((max(R, 1), 7))
+            self._chk(self.L.sz_download_floe_frame_interactions(self.h, int(writer), int(k), capi.ptr(off, capi._ip), capi.ptr(rows) if "inter_rows" in inter else None))
+            if "inter_off" in inter:
+                col["inter_off"] = off
+            if "inter_rows" in inter:
+                col["inter_rows"] = rows[:R]
         if "ghost_idx" in col:
             col["ghost_idx"] = col["ghost_idx"][:G]
         col.update(tstep=tstep, M=M, N=N)

@@ -728,10 +728,13 @@ class TiledWorld:
         return int(ng.value), n
 
     # ---- output frames of a tiled run (sz_tile_set_floe_output / sz_tile_set_grid_output, sz_tile_download_floe_frame: library backends)
-    def set_floe_output(self, writer, dt_out, columns=None, arena_bytes=1 << 26):
+    def set_floe_output(self, writer, dt_out, columns=None, arena_bytes=1 << 26, lists=None):
         """World.set_floe_output for this rank's tile (the same arguments on every rank).  run() then goes on past the writer's output steps and
-        records there: every rank keeps the frame of its own rows -- its owned floes and their ghosts -- with their order keys."""
+        records there: every rank keeps the frame of its own rows -- its owned floes and their ghosts -- with their order keys.  Tile frames
+        record no lists yet: `lists` is refused."""
         self._library_only("set_floe_output")
+        if lists:
+            raise capi.SzError("tile frames record no lists yet: set_floe_output of a tiled run takes no `lists`")
         self.world.set_floe_output(writer, dt_out, columns, arena_bytes, _tile=True)
 
     def set_grid_output(self, writer, dt_out, xg=None, yg=None, outputs=None, max_frames=64):

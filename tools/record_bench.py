@@ -4,6 +4,9 @@ remove_ghosts.  Three worlds step through the same NB-step blocks with an output
     plain     one run() per block, no output
     hand      a run() up to each output step, then the four calls
     recorded  one run() per block with the writers set, then the frames drained (downloaded) and cleared
+Two more worlds take the ragged members too (sz_set_floe_output_lists: floe.interactions and the sub-floe points):
+    hand+lists      the hand cut, with interactions() in front of add_ghosts and subpoints() behind the column download
+    recorded+lists  the recorded run with both lists set; its drain downloads the list sections too
 Each block ends in a device synchronise (run() returns after one), so the host clock around a block is its wall time; the cost of ONE output
 step is (block - plain block) / output steps in the block, which includes what the cut itself costs the batch.  The blocks alternate between
 the worlds and are repeated; every repeat is printed, then the median.
@@ -58,16 +61,29 @@ def block_hand(w, t):
     return calls
 
 
+def block_hand_lists(w, t):
+    for s in range(t, t + NB, DT_OUT):
+        w.interactions()          # (before add_ghosts, which forgets how the last step's ghosts were numbered)
+        w.add_ghosts()
+        w._pull()
+        w.subpoints()
+        w.eulerian_data(xg, yg)
+        w.remove_ghosts()
+        assert w.run(DT_OUT, s, dt, **run) == DT_OUT
+
+
 def block_recorded(w, t):
     assert w.run(NB, t, dt, **run) == NB
 
 
-def drain(w):
+def drain(w, sizes=None):
     nf, ng, full = w.output_frames()
     assert nf[0] == ng[0] == NB // DT_OUT and not full
     for k in range(nf[0]):
-        w.floe_frame(0, k)
+        fr = w.floe_frame(0, k)
         w.grid_frame(0, k)
+        if sizes is not None:
+            sizes.append(w.frame_bytes(w.frame_mask(None), fr["M"], fr["N"], len(fr["vx"]), LISTS, len(fr["inter_rows"]), len(fr["sx"])))
     w.clear_frames()
 
 
@@ -75,26 +91,35 @@ P, H = world(), world()
 R = world()
 R.set_floe_output(0, DT_OUT, arena_bytes=1 << 28)
 R.set_grid_output(0, DT_OUT, xg, yg, max_frames=NB // DT_OUT)
+LISTS = ["interactions", "subpoints"]
+HL, RL = world(), world()
+RL.set_floe_output(0, DT_OUT, arena_bytes=1 << 28, lists=LISTS)          # (4 frames of ~20 MB each a block: the default arena of 64 MiB ends `full` at the 4th)
+RL.set_grid_output(0, DT_OUT, xg, yg, max_frames=NB // DT_OUT)
 nout = NB // DT_OUT
-rows = []
+rows, frame_sizes = [], []
 t = WARM
 for rep in range(args.repeats + 1):          # (the first repeat warms every shape of the timed window and is not counted)
     t0 = time.perf_counter(); block_plain(P, t); tp = time.perf_counter() - t0
     t0 = time.perf_counter(); calls = block_hand(H, t); th = time.perf_counter() - t0
     t0 = time.perf_counter(); block_recorded(R, t); tr = time.perf_counter() - t0
     t0 = time.perf_counter(); drain(R); td = time.perf_counter() - t0
+    t0 = time.perf_counter(); block_hand_lists(HL, t); thl = time.perf_counter() - t0
+    t0 = time.perf_counter(); block_recorded(RL, t); trl = time.perf_counter() - t0
+    t0 = time.perf_counter(); drain(RL, frame_sizes); tdl = time.perf_counter() - t0
     t += NB
     if rep == 0:
         continue
     row = dict(plain_ms_per_step=tp / NB * 1e3, hand_step_ms=(th - tp) / nout * 1e3, hand_calls_ms=calls / nout * 1e3,
-               recorded_step_ms=(tr - tp) / nout * 1e3, drain_ms_per_frame_pair=td / nout * 1e3)
+               recorded_step_ms=(tr - tp) / nout * 1e3, drain_ms_per_frame_pair=td / nout * 1e3,
+               hand_lists_step_ms=(thl - tp) / nout * 1e3, recorded_lists_step_ms=(trl - tp) / nout * 1e3, drain_lists_ms_per_frame_pair=tdl / nout * 1e3)
     rows.append(row)
     print(f"repeat {rep}: " + "  ".join(f"{k} {v:.3f}" for k, v in row.items()), flush=True)
 print(f"floes {args.floes}, grid 100x100, {args.repeats} repeats of {NB} steps with {nout} output steps each; median:")
 for k in rows[0]:
     print(f"  {k}: {statistics.median(r[k] for r in rows):.3f}")
-# the three ways end in the same state
+print(f"  floe frame with both lists: {statistics.median(frame_sizes) / 1e6:.2f} MB (median of {len(frame_sizes)})")
+# the ways end in the same state
 from subzero_jl_amd import capi
-same = all(np.array_equal(P.get(n), R.get(n)) and np.array_equal(P.get(n), H.get(n)) for n in capi.DCOLS)
+same = all(np.array_equal(P.get(n), W.get(n)) for n in capi.DCOLS for W in (R, H, HL, RL))
 print("final states equal:", same)
 assert same
