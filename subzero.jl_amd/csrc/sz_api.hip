@@ -928,6 +928,21 @@ int sz_upload_floes(sz_ctx* c, int64_t M64, int64_t N64, const sz_floe_columns* 
   if (!c || !f || M64 < 0 || N64 < 0 || N64 > M64 || !f->vert_off || !f->vx || !f->vy || !f->cx || !f->cy) return SZ_E_ARG;
   if (!c->have_domain) { c->err = "sz_set_domain must be called before sz_upload_floes"; return SZ_E_STATE; }
   if (M64 > N64 && (!f->ghost_off || !f->ghost_idx || !f->ghost_id)) { c->err = "M > N needs ghost_off/ghost_idx/ghost_id"; return SZ_E_ARG; }
+  {
+    // Rings no kernel holds are refused here, by name, before anything of the last upload is dropped (the kernels' own guards -- ERR_CAP_RING --
+    // stay behind this): ring sizes and edge indices travel as bytes, and the ghost passes copy a parent's ring in one wavefront's registers.
+    int big = 0;
+    for (int64_t i = 0; i < M64; i++) big = std::max(big, f->vert_off[i + 1] - f->vert_off[i]);
+    if (big > NARROW_CAP2) {
+      c->err = "a ring has " + std::to_string(big) + " points: more than the " + std::to_string(NARROW_CAP2) + " the narrow phase's largest variant holds";
+      return SZ_E_CAPACITY;
+    }
+    if (big > GHOST_RING_WIDE && (c->S.any_periodic_ew || c->S.any_periodic_ns)) {
+      c->err = "a ring has " + std::to_string(big) + " points in a domain with a periodic direction: the ghost passes copy rings of at most " +
+               std::to_string(GHOST_RING_WIDE) + " points (rings of up to " + std::to_string(NARROW_CAP2) + " need non-periodic boundaries)";
+      return SZ_E_CAPACITY;
+    }
+  }
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->gi_pending && c->gi_valid) { int rc0 = gi_fetch(c); if (rc0) return rc0; }      // (the key tables go with the pool; the rows may stay)

@@ -466,6 +466,9 @@ __device__ __forceinline__ void rig_store(State& S, int lane, int f, int vo, int
 // asked for in ONE batch -- the scalar columns one per lane, the ring one point per lane -- and stored afterwards.
 // The up to three ghosts are named registers (no indexed arrays: those went to scratch memory): G0 is the E/W ghost, or the
 // N/S ghost of a parent that has no E/W one; G1 the N/S ghost of G0 and G2 the parent's own N/S ghost (corner parents).
+// Ring points of a parent whose ghosts these passes can make: one per lane of a wavefront, two in the WIDE variant.  sz_upload_floes
+// refuses longer rings in a domain with a periodic direction (the narrow phase itself takes up to NARROW_CAP2 points).
+constexpr int GHOST_RING = 64, GHOST_RING_WIDE = 128;
 template <bool WIDE>
 __device__ __forceinline__ void ghost_fill_parent(State& S, const GridGeo& geo, int lane, int i, int fl, int4 sc, int4 T, int M0, int NV0, int bin,
                                                   int vo, int n, const double* wall) {
@@ -489,7 +492,7 @@ __device__ __forceinline__ void ghost_fill_parent(State& S, const GridGeo& geo, 
   const long long oki = S.tiled ? okp : 0;
   State::Fam* const F = S.fam + i;            // the family record of the Dict rule (pair_allowed_fam), as the inline ghost maker leaves it
   if (ngh_old != 0) { if (lane == 0) atomicOr(&S.cnt[C_ERR], ERR_GHOSTS_PER_PARENT); return; }
-  if (n > (WIDE ? 128 : 64)) { if (lane == 0) atomicOr(&S.cnt[C_ERR], ERR_CAP_RING); return; }
+  if (n > (WIDE ? GHOST_RING_WIDE : GHOST_RING)) { if (lane == 0) atomicOr(&S.cnt[C_ERR], ERR_CAP_RING); return; }
   // ---- the two passes, in registers; a ghost is stored as soon as nothing is derived from it any more (at most two
   // ghosts and the parent are live at a time)
   auto put = [&](const R& G, int g, int vb, int gid, long long key) {
