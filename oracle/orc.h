@@ -78,6 +78,11 @@ int    orc_ipoints_flat(int na, const double *ax, const double *ay,
                         int nb, const double *bx, const double *by,
                         int max_pts, double *px, double *py);
 
+/* area of ring ∩ [x0, x1] x [y0, y1] by Sutherland-Hodgman against closed half-planes, in window-relative coordinates (orc_world.c): what
+   the grid paths (two-way coupling, Eulerian averages) clip with; exact where a ring only touches a grid line */
+double orc_rect_area(const orc_ring *ring, double x0, double x1, double y0, double y1);
+double orc_rect_area_flat(int n, const double *x, const double *y, double x0, double x1, double y0, double y1);
+
 /* ------------------------------------------------------------------ world */
 typedef struct orc_world orc_world;
 

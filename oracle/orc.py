@@ -59,6 +59,7 @@ def lib():
                      "orc_clip_flat", "orc_ipoints_flat", "orc_cell_count", "orc_shift_cell_idx", "orc_which_vertices_match_points",
                      "orc_in_bounds", "orc_find_interp_knots"):
             getattr(L, name).restype = C.c_int
+        L.orc_rect_area_flat.restype = C.c_double
     return _LIB
 
 
@@ -79,6 +80,13 @@ def clip(a, b, max_regions=16, max_pts=4096):
                             _p(off, _ip), _p(rx), _p(ry))
     assert n >= 0, "oracle clip capacity exceeded"
     return [np.stack([rx[off[k]:off[k + 1]], ry[off[k]:off[k + 1]]], 1) for k in range(n)]
+
+
+def rect_area(ring, x0, x1, y0, y1):
+    """area of the closed ring ((n,2) array) inside [x0, x1] x [y0, y1]: orc_rect_area, the clip of the grid paths"""
+    r = _d(ring)
+    x, y = _d(r[:, 0]), _d(r[:, 1])
+    return float(lib().orc_rect_area_flat(len(x), _p(x), _p(y), *(C.c_double(v) for v in (x0, x1, y0, y1))))
 
 
 def which_vertices_match_points(points, region):

@@ -976,6 +976,48 @@ void orc_cell_entry(const orc_world *w, int xidx, int yidx, int k, double *out6)
   const cell_ent *e = &w->cells[(size_t)(xidx - 1) * (size_t)(w->Ny + 1) + (size_t)(yidx - 1)].e[k];
   out6[0] = e->floe; out6[1] = e->dx; out6[2] = e->dy; out6[3] = e->tx; out6[4] = e->ty; out6[5] = e->n;
 }
+/* area of ring ∩ [x0, x1] x [y0, y1]: Sutherland-Hodgman, one closed half-plane after the other (x >= 0, x <= w, y >= 0, y <= h in
+   coordinates relative to the window's corner) on stored polygons, then the shoelace sum.  The grid paths use it in place of orc_intersection
+   against a rectangle, whose trace goes wrong where one vertex of a ring touches an edge of the other.  A ring that leaves
+   the window in pieces comes out as one polygon whose bridging edges run along the window's boundary there and back and cancel in the sum. */
+static int rect_stage(const orc_pt *in, int n, orc_pt *out, int axis, double c, int upper) {
+  int m = 0;
+  for (int k = 0; k < n; k++) {
+    const orc_pt a = in[k], b = in[k + 1 < n ? k + 1 : 0];
+    const double va = axis ? a.y : a.x, vb = axis ? b.y : b.x;
+    const int ia = upper ? va <= c : va >= c, ib = upper ? vb <= c : vb >= c;
+    if (ia != ib) {
+      const double t = (c - va) / (vb - va);
+      if (axis) { out[m].x = a.x + t * (b.x - a.x); out[m].y = c; }
+      else      { out[m].x = c; out[m].y = a.y + t * (b.y - a.y); }
+      m++;
+    }
+    if (ib) out[m++] = b;
+  }
+  return m;
+}
+double orc_rect_area(const orc_ring *ring, double x0, double x1, double y0, double y1) {
+  const double w = x1 - x0, h = y1 - y0;
+  int n = ring->n - 1;                         /* open ring */
+  if (n < 3 || !(w > 0) || !(h > 0)) return 0.0;
+  /* a stage emits at most two points per edge */
+  orc_pt *p = (orc_pt *)malloc((size_t)16 * (size_t)n * sizeof(orc_pt)), *q = (orc_pt *)malloc((size_t)16 * (size_t)n * sizeof(orc_pt));
+  for (int k = 0; k < n; k++) { p[k].x = ring->p[k].x - x0; p[k].y = ring->p[k].y - y0; }
+  n = rect_stage(p, n, q, 0, 0.0, 0);
+  n = rect_stage(q, n, p, 0, w, 1);
+  n = rect_stage(p, n, q, 1, 0.0, 0);
+  n = rect_stage(q, n, p, 1, h, 1);
+  double s = 0.0;
+  for (int k = 0; k < n; k++) { const orc_pt a = p[k], b = p[k + 1 < n ? k + 1 : 0]; s += a.x * b.y - b.x * a.y; }
+  free(p); free(q);
+  return 0.5 * fabs(s);
+}
+double orc_rect_area_flat(int n, const double *x, const double *y, double x0, double x1, double y0, double y1) {
+  orc_ring r; orc_ring_init(&r); orc_ring_from_xy(&r, n, x, y);
+  const double a = orc_rect_area(&r, x0, x1, y0, y1);
+  orc_ring_free(&r);
+  return a;
+}
 /* calc_two_way_coupling!, coupling.jl:1617-1680 */
 void orc_calc_two_way_coupling(orc_world *w) {
   int per_x = w->b[ORC_EAST].kind == ORC_PERIODIC, per_y = w->b[ORC_NORTH].kind == ORC_PERIODIC;
@@ -984,26 +1026,20 @@ void orc_calc_two_way_coupling(orc_world *w) {
 #pragma omp parallel for schedule(dynamic, 16) num_threads(w->nthreads)
 #endif
   for (int ix = 1; ix <= w->Nx + 1; ix++) {
-    orc_ring cell, moved; orc_regions rg;
-    orc_ring_init(&cell); orc_ring_init(&moved); orc_regions_init(&rg);
+    orc_ring moved;
+    orc_ring_init(&moved);
     for (int iy = 1; iy <= w->Ny + 1; iy++) {
       size_t q = (size_t)(ix - 1) * (size_t)(w->Ny + 1) + (size_t)(iy - 1);
       double tx = 0.0, ty = 0.0, si = 0.0;
       const struct cell_list *c = &w->cells[q];
       if (c->n > 0) {
         double bb[4]; orc_center_cell_coords(w, ix, iy, per_y, per_x, bb);
-        /* _make_bounding_box_polygon: (xmin,ymin) (xmin,ymax) (xmax,ymax) (xmax,ymin) (xmin,ymin) */
-        cell.n = 0;
-        orc_ring_push(&cell, bb[0], bb[2]); orc_ring_push(&cell, bb[0], bb[3]); orc_ring_push(&cell, bb[1], bb[3]);
-        orc_ring_push(&cell, bb[1], bb[2]); orc_ring_push(&cell, bb[0], bb[2]);
         for (int k = 0; k < c->n; k++) {
           const cell_ent *e = &c->e[k];
           const floe_t *f = &w->f[e->floe];
           moved.n = 0;
           for (int v = 0; v < f->poly.n; v++) orc_ring_push(&moved, f->poly.p[v].x + e->dx, f->poly.p[v].y + e->dy);
-          orc_intersection(&cell, &moved, &rg);
-          double a = 0.0;
-          for (int r = 0; r < rg.n; r++) a += orc_area(&rg.r[r]);
+          const double a = orc_rect_area(&moved, bb[0], bb[1], bb[2], bb[3]);          /* intersect_polys(cell_poly, floe_poly), summed */
           if (a > 0) {
             tx += (e->tx / e->n) * a; ty += (e->ty / e->n) * a; si += a;
           }
@@ -1018,7 +1054,7 @@ void orc_calc_two_way_coupling(orc_world *w) {
       w->tau_x[q] = tx; w->tau_y[q] = ty; w->si_frac[q] = si;
       w->hf[q] = w->dt_couple * w->k_ice / (w->rho_i * w->L_ice) * (w->t_ocn[q] - w->t_atm[q]);
     }
-    orc_ring_free(&cell); orc_ring_free(&moved); orc_regions_free(&rg);
+    orc_ring_free(&moved);
   }
 }
 
@@ -1027,21 +1063,17 @@ void orc_calc_two_way_coupling(orc_world *w) {
    data[k][ix][iy] at (k * nx + ix) * ny + iy, k in the order of ORC_EUL_* (orc.h); cell (ix, iy) is
    [xg[ix], xg[ix+1]] x [yg[iy], yg[iy+1]] (writer.data[j, i, k] with j = ix + 1, i = iy + 1).
    Topography (the cell polygon minus the topography, :829-832) is restated through the set identity
-   area(floe ∩ (cell \ topo)) = area(floe ∩ cell) - sum_t area((floe ∩ cell) ∩ topo_t), valid for topography
-   elements that do not overlap one another (the reference's diff_polys lives in GeometryOps). */
-static double regions_area(const orc_regions *rg) {
-  double a = 0.0;
-  for (int r = 0; r < rg->n; r++) a += orc_area(&rg->r[r]);
-  return a;
-}
+   area(floe ∩ (cell \ topo)) = area(floe ∩ cell) - sum_t area((floe ∩ topo_t) ∩ cell), valid for topography
+   elements that do not overlap one another (the reference's diff_polys lives in GeometryOps).  The rectangle is
+   applied last and always through orc_rect_area: the general clip only meets floe against element. */
 void orc_calc_eulerian_data(const orc_world *w, int nx, int ny, const double *xg, const double *yg, double *data) {
   const double dx = xg[1] - xg[0], dy = yg[1] - yg[0];
   const double cell_rmax = sqrt(dx * dx + dy * dy);
   const int M = w->M;
   int *idx = (int *)malloc((size_t)(M > 0 ? M : 1) * sizeof(int));
   double *pic = (double *)malloc((size_t)(M > 0 ? M : 1) * sizeof(double));
-  orc_ring cell; orc_regions rg, rg2;
-  orc_ring_init(&cell); orc_regions_init(&rg); orc_regions_init(&rg2);
+  orc_regions rg;
+  orc_regions_init(&rg);
   for (int ix = 0; ix < nx; ix++) for (int iy = 0; iy < ny; iy++) {
     double *out[ORC_EUL_COUNT];
     for (int k = 0; k < ORC_EUL_COUNT; k++) { out[k] = &data[((size_t)k * nx + ix) * ny + iy]; *out[k] = 0.0; }
@@ -1054,22 +1086,18 @@ void orc_calc_eulerian_data(const orc_world *w, int nx, int ny, const double *xg
       if (d < 0) idx[n++] = i;
     }
     if (n == 0) continue;
-    cell.n = 0;
-    orc_ring_push(&cell, xg[ix], yg[iy]); orc_ring_push(&cell, xg[ix], yg[iy + 1]); orc_ring_push(&cell, xg[ix + 1], yg[iy + 1]);
-    orc_ring_push(&cell, xg[ix + 1], yg[iy]); orc_ring_push(&cell, xg[ix], yg[iy]);
-    double cell_area = orc_area(&cell);
-    for (int t = 0; t < w->ntopo; t++) {
-      orc_intersection(&cell, &w->topo[t].poly, &rg);
-      cell_area -= regions_area(&rg);
-    }
+    const double cx0 = xg[ix], cx1 = xg[ix + 1], cy0 = yg[iy], cy1 = yg[iy + 1];
+    double cell_area = (cx1 - cx0) * (cy1 - cy0);
+    for (int t = 0; t < w->ntopo; t++) cell_area -= orc_rect_area(&w->topo[t].poly, cx0, cx1, cy0, cy1);
     if (!(cell_area > 0)) continue;          /* length(cell_poly_list) == 0, :834-837 */
     int m = 0;
     for (int k = 0; k < n; k++) {
       const floe_t *f = &w->f[idx[k]];
-      orc_intersection(&f->poly, &cell, &rg);
-      double a = regions_area(&rg);
-      for (int t = 0; t < w->ntopo && a > 0; t++)
-        for (int r = 0; r < rg.n; r++) { orc_intersection(&rg.r[r], &w->topo[t].poly, &rg2); a -= regions_area(&rg2); }
+      double a = orc_rect_area(&f->poly, cx0, cx1, cy0, cy1);
+      for (int t = 0; t < w->ntopo && a > 0; t++) {
+        orc_intersection(&f->poly, &w->topo[t].poly, &rg);
+        for (int r = 0; r < rg.n; r++) a -= orc_rect_area(&rg.r[r], cx0, cx1, cy0, cy1);
+      }
       if (a > 0) { idx[m] = idx[k]; pic[m] = a; m++; }
     }
     double area_tot = 0.0, mass_tot = 0.0;
@@ -1098,7 +1126,7 @@ void orc_calc_eulerian_data(const orc_world *w, int nx, int ny, const double *xg
     }
     for (int k = 0; k < ORC_EUL_COUNT; k++) *out[k] = s[k];
   }
-  orc_ring_free(&cell); orc_regions_free(&rg); orc_regions_free(&rg2); free(idx); free(pic);
+  orc_regions_free(&rg); free(idx); free(pic);
 }
 /* what simplify_floes! (simplification.jl:339-378) would have to do: out4 = floes tagged remove, floes tagged
    fuse, floes with more than max_vertices ring points (smooth_floes!, :66: GI.npoint counts the closing point),

@@ -3277,7 +3277,7 @@ int eul_grid(sz_ctx* c, int32_t nx, int32_t ny, const double* xg, const double* 
       (rc = dalloc(c, &E.cell_area, ncell, pool)) || (rc = dalloc(c, &E.data, (size_t)EUL_COUNT * ncell, pool))) return rc;
   H2D(d_xg, xg, nx + 1, double); H2D(d_yg, yg, ny + 1, double);
   E.xg = d_xg; E.yg = d_yg;
-  hipLaunchKernelGGL(sz_k_eul_cell_area, dim3(grid_for(ncell, 64 / EU_G, 8192)), dim3(64), 0, c->stream, c->S, E);
+  hipLaunchKernelGGL(sz_k_eul_cell_area, dim3(grid_for(ncell, 256, 8192)), dim3(256), 0, c->stream, c->S, E);
   return SZ_OK;
 }
 // entries: counted ...

@@ -310,6 +310,8 @@ int sync_and_check(sz_ctx* c, int* cnt_out = nullptr) {
              "device capacity/consistency error bits 0x%x (ring=1 crossings=2 regions=4 rows=8 trace=16 neighbours=32 "
              "pairs=64 elems=128 inter=256 floes=512 verts=1024 cells=2048 ghosts/parent=4096 scan=8192 halo-drift=16384 fixed-point-range=32768)", h[C_ERR]);
     c->err = buf;
+    if (h[C_ERR] & ERR_CAP_CELLS)
+      c->err += "; cells: the sub-floe points of one floe fall into more than " + std::to_string(FC_CAP) + " distinct centre cells, or number more than the forcing kernel stages per floe";
     int z = 0; (void)hipMemcpy(c->S.cnt + C_ERR, &z, sizeof(int), hipMemcpyHostToDevice);
     return SZ_E_CAPACITY;
   }

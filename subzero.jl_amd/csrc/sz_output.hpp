@@ -2,7 +2,8 @@
 //   calc_eulerian_data! (output.jl:793-914): floe data averaged on the GridOutputWriter's grid, and the
 //   "nothing to simplify" test of simplify_floes! (simplification.jl:66, 287-290).
 // The Eulerian averages are the third floe ∩ rectangle clip workload after the contact path and the two-way
-// coupling, and reuse the same group-cooperative clipper:
+// coupling; the rectangle is cut with the two-way coupling's half-plane pipeline, the group-cooperative clipper is
+// kept for floe against topography element:
 //   sz_k_eul_entries   per floe: the output cells its ring box reaches -> entries keyed  cell * M + floe.  The
 //                      reference's candidate test (cell centre within rmax + cell diagonal of the centroid,
 //                      :808-819) only prefilters: entries without area are dropped afterwards (:851-852), and
@@ -12,7 +13,7 @@
 //   sz_k_eul_area      per entry: area of floe ∩ cell, minus what topography covers of it
 //   sz_k_eul_reduce    per cell: the 18 averages (:855-905)
 // Topography: the reference subtracts it from the cell polygon (diff_polys) before clipping; here the same areas
-// come from area(f ∩ (c \ t)) = area(f ∩ c) - sum_t area((f ∩ c) ∩ t) for elements that do not overlap one another.
+// come from area(f ∩ (c \ t)) = area(f ∩ c) - sum_t area((f ∩ t) ∩ c) for elements that do not overlap one another.
 #pragma once
 #include "sz_kernels.hpp"
 #include "sz_twoway.hpp"      // RectClip: the rectangle pipeline
@@ -71,68 +72,46 @@ __global__ void sz_k_eul_entries(State S, EulGrid E, int fill) {
   }
 }
 
+// With topography the rectangle is applied last and always through the rectangle pipeline: the general clip<> only ever meets floe against
+// element.  (It used to meet cell against floe as well, and where a single vertex of the floe touched the cell's edge from outside its tie
+// rule -- DESIGN §3.2 -- answered with the whole cell.)  Only that clip holds rings in LDS: EU_CAP bounds the floes and elements whose boxes
+// meet, nothing else.
 constexpr int EU_G = 16, EU_CAP = 64, EU_KC = 32, EU_RC = 128, EU_RM = 8;
-struct EulMem {
-  GroupMem<EU_CAP, EU_KC, EU_RC, EU_RM> g;
-  double sx[EU_RC], sy[EU_RC];      // regions of floe ∩ cell while they are clipped against topography
-  int soff[EU_RM + 1];
-};
-// _make_bounding_box_polygon: (xmin,ymin) (xmin,ymax) (xmax,ymax) (xmax,ymin) (xmin,ymin)
-template <class MEM>
-__device__ __forceinline__ void eul_cell_ring(MEM& m, int gl, double xmin, double xmax, double ymin, double ymax) {
-  if (gl < 5) { m.ax[gl] = (gl == 2 || gl == 3) ? xmax : xmin; m.ay[gl] = (gl == 1 || gl == 2) ? ymax : ymin; }
+using EulMem = GroupMem<EU_CAP, EU_KC, EU_RC, EU_RM>;
+// area of (ring of `nopen` distinct points, handed out by pt(k, x, y) in window coordinates) ∩ [0, w] x [0, h]
+template <class F>
+__device__ __forceinline__ double eul_rect_area(int nopen, double w, double h, F&& pt) {
+  RectClip rc;
+  rc.w = w; rc.h = h; rc.acc = 0.0; rc.hout = false;
+  rc.ox0 = rc.oy0 = rc.oxp = rc.oyp = 0.0;
+  for (int k = 0; k < 4; k++) { rc.have[k] = false; rc.fx[k] = rc.fy[k] = rc.px[k] = rc.py[k] = 0.0; }
+  for (int k = 0; k < nopen; k++) { double x, y; pt(k, x, y); rc.feed<0>(x, y); }
+  return rc.finish();
 }
-// area of (ring a of m, n points, box ba) ∩ topography element te; 0 if the boxes miss
-template <class MEM>
-__device__ __forceinline__ double eul_clip_topo(const State& S, MEM& m, int gl, int n, const Box& ba, int te, Stamps& st, bool& cap_err) {
-  const int e = 4 + te;
-  const Box bt{ S.ebb[4 * e], S.ebb[4 * e + 1], S.ebb[4 * e + 2], S.ebb[4 * e + 3] };
-  if (ba.x1 < bt.x0 || bt.x1 < ba.x0 || ba.y1 < bt.y0 || bt.y1 < ba.y0) return 0.0;
-  const int eo = S.eoff[e], ne = S.eoff[e + 1] - eo;
-  if (ne > EU_CAP) { cap_err = true; return 0.0; }
-  gsync();
-  for (int k = gl; k < ne; k += EU_G) { m.bx[k] = S.ex[eo + k]; m.by[k] = S.ey[eo + k]; }
-  gsync();
-  const int oa = ring_signed_area(m.ax, m.ay, n) >= 0.0 ? 1 : -1;
-  clip<EU_G>(m, gl, 0.0, 0.0, n, oa, ne, (int)S.eosign[e], 0, ba, bt, st);
-  gsync();
-  double a = 0.0;
-  const int nreg = m.nreg[0];
-  for (int r = 0; r < nreg; r++) a += m.rarea[0][r];
-  return a;
-}
-__global__ void __launch_bounds__(64) sz_k_eul_cell_area(State S, EulGrid E) {
-  constexpr int GPB = 64 / EU_G;
-  __shared__ EulMem mem[GPB];
-  const int gl = threadIdx.x % EU_G, gi = threadIdx.x / EU_G;
-  auto& m = mem[gi].g;
+// per cell, one thread: the cell minus what each element covers of it
+__global__ void __launch_bounds__(256) sz_k_eul_cell_area(State S, EulGrid E) {
   const int ncell = E.nx * E.ny, ntopo = S.nelem - 4;
-  if (gl == 0) { m.err = 0; m.ntracefail = 0; }
-  Stamps st; STAMP_INIT(st);
-  bool cap_err = false;
-  for (int q0 = blockIdx.x * GPB; q0 < ncell; q0 += gridDim.x * GPB) {
-    const int q = q0 + gi;
-    if (q >= ncell) continue;
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < ncell; q += gridDim.x * blockDim.x) {
     const int ix = q / E.ny, iy = q % E.ny;
     const double xmin = E.xg[ix], xmax = E.xg[ix + 1], ymin = E.yg[iy], ymax = E.yg[iy + 1];
-    const Box bc{ xmin, xmax, ymin, ymax };
-    gsync();
-    eul_cell_ring(m, gl, xmin, xmax, ymin, ymax);
-    gsync();
-    double a = fabs(ring_signed_area(m.ax, m.ay, 5));
-    for (int te = 0; te < ntopo; te++) a -= eul_clip_topo(S, m, gl, 5, bc, te, st, cap_err);
-    if (gl == 0) E.cell_area[q] = a;
+    const double w = xmax - xmin, h = ymax - ymin;
+    double a = w * h;
+    for (int te = 0; te < ntopo; te++) {
+      const int e = 4 + te;
+      if (xmax < S.ebb[4 * e] || S.ebb[4 * e + 1] < xmin || ymax < S.ebb[4 * e + 2] || S.ebb[4 * e + 3] < ymin) continue;
+      const int eo = S.eoff[e], ne = S.eoff[e + 1] - eo;
+      a -= eul_rect_area(ne - 1, w, h, [&](int k, double& x, double& y) { x = S.ex[eo + k] - xmin; y = S.ey[eo + k] - ymin; });
+    }
+    E.cell_area[q] = a;
   }
-  gsync();
-  if (gl == 0 && (cap_err || m.err)) atomicOr(&S.cnt[C_ERR], (cap_err ? ERR_CAP_RING : 0) | (m.err & (ERR_CAP_XING | ERR_CAP_REGION)));
-  if (gl == 0 && m.ntracefail) atomicAdd(&S.cnt[C_TRACE_FAIL], m.ntracefail);
 }
+// per entry, one lane group: floe ∩ cell by the rectangle pipeline (every lane runs it on the same points: no lane waits for another), then
+// per element whose box meets the floe's part of the cell the regions of clip(floe, element), each cut to the cell by the pipeline again
 __global__ void __launch_bounds__(64) sz_k_eul_area(State S, EulGrid E, int nent) {
   constexpr int GPB = 64 / EU_G;
   __shared__ EulMem mem[GPB];
   const int gl = threadIdx.x % EU_G, gi = threadIdx.x / EU_G;
-  auto& mm = mem[gi];
-  auto& m = mm.g;
+  auto& m = mem[gi];
   const int ntopo = S.nelem - 4;
   if (gl == 0) { m.err = 0; m.ntracefail = 0; }
   Stamps st; STAMP_INIT(st);
@@ -144,49 +123,30 @@ __global__ void __launch_bounds__(64) sz_k_eul_area(State S, EulGrid E, int nent
     const int i = (int)(key % (unsigned long long)E.M), q = (int)(key / (unsigned long long)E.M);
     const int ix = q / E.ny, iy = q % E.ny;
     const double xmin = E.xg[ix], xmax = E.xg[ix + 1], ymin = E.yg[iy], ymax = E.yg[iy + 1];
+    const double w = xmax - xmin, h = ymax - ymin;
     const int bo = S.voff[i], nb = S.voff[i + 1] - bo;
-    gsync();
-    if (nb > EU_CAP) { cap_err = true; if (gl == 0) E.pic[t] = 0.0; continue; }
-    eul_cell_ring(m, gl, xmin, xmax, ymin, ymax);
-    for (int k = gl; k < nb; k += EU_G) { const double2 p = S.vxy[bo + k]; m.bx[k] = p.x; m.by[k] = p.y; }
-    gsync();
-    const Box bc{ xmin, xmax, ymin, ymax };
-    const Box bf{ S.bbx0[i], S.bbx1[i], S.bby0[i], S.bby1[i] };
-    const int oc = ring_signed_area(m.ax, m.ay, 5) >= 0.0 ? 1 : -1;
-    // regions into buffer 1: it keeps the ring of a contained floe / cell too
-    clip<EU_G>(m, gl, 0.0, 0.0, 5, oc, nb, (int)S.osign[i], 1, bc, bf, st);
-    gsync();
-    double a = 0.0;
-    const int nreg = m.nreg[1];
-    for (int r = 0; r < nreg; r++) a += m.rarea[1][r];
-    if (ntopo > 0 && a > 0) {
+    double a = eul_rect_area(nb - 1, w, h, [&](int k, double& x, double& y) { const double2 p = S.vxy[bo + k]; x = p.x - xmin; y = p.y - ymin; });
+    if (a > 0) {
+      const Box bf{ S.bbx0[i], S.bbx1[i], S.bby0[i], S.bby1[i] };
       const Box bq{ fmax(xmin, bf.x0), fmin(xmax, bf.x1), fmax(ymin, bf.y0), fmin(ymax, bf.y1) };
-      bool any = false;
+      bool have_floe = false;
       for (int te = 0; te < ntopo; te++) {
         const int e = 4 + te;
-        any |= !(bq.x1 < S.ebb[4 * e] || S.ebb[4 * e + 1] < bq.x0 || bq.y1 < S.ebb[4 * e + 2] || S.ebb[4 * e + 3] < bq.y0);
-      }
-      if (any) {
-        // the second clip reuses the region buffers: park the regions first
-        const int tot = m.roff[1][nreg];
-        for (int k = gl; k < tot; k += EU_G) { mm.sx[k] = m.reg[1][0][k]; mm.sy[k] = m.reg[1][1][k]; }
-        if (gl <= nreg) mm.soff[gl] = m.roff[1][gl];
+        const Box bt{ S.ebb[4 * e], S.ebb[4 * e + 1], S.ebb[4 * e + 2], S.ebb[4 * e + 3] };
+        if (bq.x1 < bt.x0 || bt.x1 < bq.x0 || bq.y1 < bt.y0 || bt.y1 < bq.y0) continue;
+        const int eo = S.eoff[e], ne = S.eoff[e + 1] - eo;
+        if (nb > EU_CAP || ne > EU_CAP) { cap_err = true; a = 0.0; break; }
         gsync();
+        if (!have_floe) { for (int k = gl; k < nb; k += EU_G) { const double2 p = S.vxy[bo + k]; m.ax[k] = p.x; m.ay[k] = p.y; } have_floe = true; }
+        for (int k = gl; k < ne; k += EU_G) { m.bx[k] = S.ex[eo + k]; m.by[k] = S.ey[eo + k]; }
+        gsync();
+        // regions into buffer 1: it keeps the ring of a contained floe / element too
+        clip<EU_G>(m, gl, 0.0, 0.0, nb, (int)S.osign[i], ne, (int)S.eosign[e], 1, bf, bt, st);
+        gsync();
+        const int nreg = m.nreg[1];
         for (int r = 0; r < nreg; r++) {
-          const int s0 = mm.soff[r], n = mm.soff[r + 1] - s0;
-          if (n > EU_CAP) { cap_err = true; continue; }
-          double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
-          for (int k = gl; k < n; k += EU_G) {
-            const double x = mm.sx[s0 + k], y = mm.sy[s0 + k];
-            x0 = fmin(x0, x); x1 = fmax(x1, x); y0 = fmin(y0, y); y1 = fmax(y1, y);
-          }
-          const Box br{ gmin<EU_G>(x0), gmax<EU_G>(x1), gmin<EU_G>(y0), gmax<EU_G>(y1) };
-          for (int te = 0; te < ntopo; te++) {
-            gsync();
-            for (int k = gl; k < n; k += EU_G) { m.ax[k] = mm.sx[s0 + k]; m.ay[k] = mm.sy[s0 + k]; }
-            gsync();
-            a -= eul_clip_topo(S, m, gl, n, br, te, st, cap_err);
-          }
+          const int s0 = m.roff[1][r], n = m.roff[1][r + 1] - s0;
+          a -= eul_rect_area(n - 1, w, h, [&](int k, double& x, double& y) { x = m.reg[1][0][s0 + k] - xmin; y = m.reg[1][1][s0 + k] - ymin; });
         }
       }
     }
