@@ -784,7 +784,8 @@ int sz_simplify_check(sz_ctx *ctx, int32_t max_vertices, double min_floe_area, d
      status.fuse_idx has no section: it is non-empty only on a row tagged `fuse` (collisions.jl:367-368, 801-806), and a batch that honours tags
      never begins a step with such a row -- the recorded status column says so.
      Refusals: bits other than the two, SZ_E_ARG; a writer that is off, SZ_E_STATE; a tiled context or a writer of sz_tile_set_floe_output,
-     SZ_E_STATE (tile frames record no lists yet).  The room check of a frame uses its full size, lists included.
+     SZ_E_STATE (tile frames record no lists yet through this setter: sz_tile_set_floe_output_lists, below).  The room check of a frame uses
+     its full size, lists included.
    sz_set_grid_output: the arguments of sz_eulerian_data (evenly spaced grid lines, nout >= 1 of the SZ_EUL_* codes) and room for max_frames
      frames.  A GRID FRAME is the nout * nx * ny doubles sz_eulerian_data gives on the same list, bit for bit, and its timestep.  The averages run
      in a workspace the recorder keeps (sized when the writer is set, grown on demand): a recorded output step allocates nothing once warm.
@@ -836,7 +837,26 @@ int sz_clear_frames(sz_ctx *ctx);
    travel between device buffers (RCCL) and are merged on the device; the merged frame comes down in one copy.
    sz_tile_run refuses, with SZ_E_STATE and no step run: writers whose settings differ between the ranks (one gather of a digest, before any
    other collective: the message names the writer); two-way coupling with a tile writer set; a context without sz_tile_setup and a
-   communicator.  sz_step on a context with tile writers set returns SZ_E_STATE: sz_tile_run records. */
+   communicator.  sz_step on a context with tile writers set returns SZ_E_STATE: sz_tile_run records.
+   THE LISTS IN TILE FRAMES.  sz_tile_set_floe_output_lists: sz_set_floe_output_lists for a writer of sz_tile_set_floe_output (called after it,
+   which resets the lists; frees the writer's frames; the same word on every rank: it is part of the digest).  SZ_E_ARG: unknown bits, a bad
+   writer; SZ_E_STATE: a writer that is off or was not set through the tile setter.  The merged frame of a tiled run with lists is the single
+   context's frame with lists of the same step, bit for bit, the list sections included.  A tile frame then carries, behind its keys: the sorted
+   order keys of the rows the LAST step had behind the owned parents (halo floes, their ghosts, the owned floes' ghosts; interactions only) and
+   the single frame's list sections over its own rows -- a ghost row its parent's points and no interactions; the partner column UNTRANSLATED: a
+   floe's global number + 1, or the order key + 1 of a ghost of the last step (> 2^40), or a negative boundary / topography code.  The merge
+   turns a key + 1 into N_global + (rank of the key among the sorted DISTINCT ghost keys of all ranks' tables) + 1 -- the single context's
+   number, since the union of the ranks' ghosts of a step is its ghost list of that step; a key found nowhere stays.  The record point adds
+   {R, S, table entries, rows-lost} to its one all-gather, and no other collective.  WHERE THE ROWS ARE NOT THE LAST STEP'S on some rank -- a
+   frame recorded behind sz_tile_migrate (which drops the rows) before a collision step has run, or behind a list-based tile step (sz_tile_step,
+   a ridge / raft step: its ghost keys are not kept) -- every rank records that frame with SZ_FRAME_INTERACTIONS cleared in its `lists` word;
+   the points are still recorded.  sz_tile_floe_frame_lists_info (local): the `lists` word of frame k and the MERGED frame's totals.
+   sz_tile_download_floe_frame fills sub_off / sx / sy when asked for and recorded.  sz_tile_download_floe_frame_interactions: COLLECTIVE, the
+   signature of sz_download_floe_frame_interactions on the merged frame (off M + 1, rows n_inter_rows * 7); off and rows may be NULL on a rank
+   that only takes part; a frame whose interactions bit was cleared returns SZ_E_STATE on every rank, the message naming the migration (or the
+   list-based step); a frame of a writer without the list SZ_E_ARG.  The local calls work on a tile frame with lists: sz_floe_frame_lists_info
+   and sz_download_floe_frame give this rank's own totals and points, sz_download_floe_frame_interactions its rows with the partner column
+   untranslated, sz_tile_floe_frame_list_keys the key table (*n entries; keys may be NULL). */
 int sz_tile_set_floe_output(sz_ctx *ctx, int32_t writer, int32_t dt_out, uint64_t columns_mask, int64_t arena_bytes);
 int sz_tile_set_grid_output(sz_ctx *ctx, int32_t writer, int32_t dt_out, int32_t nx, int32_t ny, const double *xg, const double *yg,
                             int32_t nout, const int32_t *outputs, int32_t max_frames);
@@ -844,6 +864,10 @@ int sz_tile_floe_frame_keys(sz_ctx *ctx, int32_t writer, int32_t k, int64_t *key
 int sz_tile_floe_frame_info(sz_ctx *ctx, int32_t writer, int32_t k, int64_t *tstep, int64_t *M, int64_t *N, int64_t *n_ring_points,
                             int64_t *n_ghost_links);
 int sz_tile_download_floe_frame(sz_ctx *ctx, int32_t writer, int32_t k, sz_floe_columns *cols);
+int sz_tile_set_floe_output_lists(sz_ctx *ctx, int32_t writer, uint32_t lists);
+int sz_tile_floe_frame_lists_info(sz_ctx *ctx, int32_t writer, int32_t k, uint32_t *lists, int64_t *n_inter_rows, int64_t *n_sub_points);
+int sz_tile_download_floe_frame_interactions(sz_ctx *ctx, int32_t writer, int32_t k, int32_t *off, double *rows);
+int sz_tile_floe_frame_list_keys(sz_ctx *ctx, int32_t writer, int32_t k, int64_t *n, int64_t *keys);
 
 /* test hook: which_vertices_match_points(points, region) (floe_utils.jl:331-352) as the narrow phase evaluates it, on
    given points (<= 64) and a given closed region ring; idx = sorted 0-based vertex indices */

@@ -99,6 +99,7 @@ EXPORTS = [
     "sz_tile_set_floe_output", "sz_tile_set_grid_output", "sz_tile_floe_frame_keys", "sz_tile_floe_frame_info", "sz_tile_download_floe_frame",
     "sz_debug_totals_mode", "sz_debug_fx_totals", "sz_debug_fx_word",
     "sz_set_floe_output_lists", "sz_floe_frame_lists_info", "sz_download_floe_frame_interactions",
+    "sz_tile_set_floe_output_lists", "sz_tile_floe_frame_lists_info", "sz_tile_download_floe_frame_interactions", "sz_tile_floe_frame_list_keys",
 ]
 
 # the column groups of sz_set_floe_output's mask, bit 0 first (sz_debug_frame_bits; tests/test_output_stops_cpu.py holds the list to the library's)
@@ -270,6 +271,10 @@ def load(build_if_missing=True):
     L.sz_tile_floe_frame_keys.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _lp]
     L.sz_tile_floe_frame_info.argtypes = L.sz_floe_frame_info.argtypes
     L.sz_tile_download_floe_frame.argtypes = L.sz_download_floe_frame.argtypes
+    L.sz_tile_set_floe_output_lists.argtypes = L.sz_set_floe_output_lists.argtypes
+    L.sz_tile_floe_frame_lists_info.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), _lp, _lp]
+    L.sz_tile_download_floe_frame_interactions.argtypes = L.sz_download_floe_frame_interactions.argtypes
+    L.sz_tile_floe_frame_list_keys.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _lp, _lp]
     L.sz_debug_next_segment_out.argtypes = [C.c_int32] * 6 + [_ip, C.c_int32, _ip, _ip]
     L.sz_debug_frame_bits.restype = C.c_char_p
     L.sz_debug_frame_bits.argtypes = []

@@ -1068,6 +1068,7 @@ int sz_upload_floes(sz_ctx* c, int64_t M64, int64_t N64, const sz_floe_columns* 
   }
   // (an upload may bring ghosts, and floes without sub-floe points; its largest rmax is the host's, and no other rank's is known: no hint)
   if ((rc = field_placed(c, N, M - N, V, f->sub_off ? N : 0, gl_est, rmax_max, 0.0))) return rc;
+  c->tile_inter_state = TILE_INTER_NONE;          // (whatever rows stay are the host's to answer for: nothing is translated)
   c->upload_M = M; c->upload_V = V;
   return SZ_OK;
 }
@@ -3431,8 +3432,21 @@ int sz_set_floe_output_lists(sz_ctx* c, int32_t writer, uint32_t lists) {
   if (writer < 0 || writer >= REC_WRITERS) { c->err = "output writer index out of range (0..3)"; return SZ_E_ARG; }
   if (lists & ~FR_LIST_ALL) { c->err = "sz_set_floe_output_lists: a list that does not exist (SZ_FRAME_INTERACTIONS | SZ_FRAME_SUBPOINTS)"; return SZ_E_ARG; }
   FloeWriter& w = c->rec.floe[writer];
-  if (c->S.tiled || w.tile) { c->err = "sz_set_floe_output_lists: tile frames record no lists yet (single contexts, writers of sz_set_floe_output)"; return SZ_E_STATE; }
+  if (c->S.tiled || w.tile) { c->err = "sz_set_floe_output_lists: tile frames record no lists yet (single contexts, writers of sz_set_floe_output) through this setter: a writer of sz_tile_set_floe_output takes sz_tile_set_floe_output_lists"; return SZ_E_STATE; }
   if (w.dt == 0) { c->err = "sz_set_floe_output_lists: the writer is off (sz_set_floe_output first)"; return SZ_E_STATE; }
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  w.frames.clear(); w.used = 0; w.lists = lists;
+  return SZ_OK;
+}
+// the lists of a tiled context's writer (behind sz_tile_set_floe_output, which resets them; the same word on every rank: tile_rec_agree_settings)
+int sz_tile_set_floe_output_lists(sz_ctx* c, int32_t writer, uint32_t lists) {
+  if (!c) return SZ_E_ARG;
+  if (writer < 0 || writer >= REC_WRITERS) { c->err = "output writer index out of range (0..3)"; return SZ_E_ARG; }
+  if (lists & ~FR_LIST_ALL) { c->err = "sz_tile_set_floe_output_lists: a list that does not exist (SZ_FRAME_INTERACTIONS | SZ_FRAME_SUBPOINTS)"; return SZ_E_ARG; }
+  FloeWriter& w = c->rec.floe[writer];
+  if (w.dt == 0) { c->err = "sz_tile_set_floe_output_lists: the writer is off (sz_tile_set_floe_output first)"; return SZ_E_STATE; }
+  if (!c->S.tiled || !w.tile) { c->err = "sz_tile_set_floe_output_lists: not a writer of sz_tile_set_floe_output (a single context's writer takes sz_set_floe_output_lists)"; return SZ_E_STATE; }
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   w.frames.clear(); w.used = 0; w.lists = lists;
@@ -3562,7 +3576,7 @@ static int rec_pack_lists(sz_ctx* c, FloeWriter& w, long long R, long long S, in
   const ListLayout L(base, fr.lists, fr.M, fr.R, fr.S);
   FrameLists F;
   for (int k = 0; k < FL_NSEC; k++) F.off[k] = L.off[k];
-  F.dst = w.arena + fr.at; F.ioff = W.ioff; F.soff = W.soff; F.keys = W.keys; F.nkeys = nkeys; F.M = fr.M; F.N = fr.N; F.lists = fr.lists; F.R = fr.R; F.S = fr.S;
+  F.dst = w.arena + fr.at; F.ioff = W.ioff; F.soff = W.soff; F.keys = W.keys; F.nkeys = nkeys; F.M = fr.M; F.N = fr.N; F.lists = fr.lists; F.R = fr.R; F.S = fr.S; F.keep_spare = 0;
   const long long widest = std::max<long long>(std::max<long long>(7 * fr.R, fr.S), fr.M + 1);
   hipLaunchKernelGGL(sz_k_frame_lists, dim3(grid_for(widest, FP_TPB, 256), 2), dim3(FP_TPB), 0, c->stream, c->S, F);
   w.used = fr.at + (size_t)L.total;
@@ -3650,12 +3664,19 @@ static int rec_frame_down(sz_ctx* c, const char* who, const FrameLayout& L, long
   }
   return SZ_OK;
 }
+// where the list sections of a frame lie: behind the columns; in a tile frame behind its keys and its key table
+static ListLayout rec_list_layout(const FloeWriter& w, const FloeFrame& fr) {
+  if (w.tile && !fr.ranks.empty()) {
+    return ListLayout(TileListLayout(w.mask, fr.lists, fr.M, fr.N, fr.V, fr.R, fr.S, fr.K).base, fr.lists, fr.M, fr.R, fr.S);
+  }
+  return ListLayout(FrameLayout(w.mask, fr.M, fr.N, fr.V).total, fr.lists, fr.M, fr.R, fr.S);
+}
 int sz_download_floe_frame(sz_ctx* c, int32_t writer, int32_t k, sz_floe_columns* f) {
   const FloeFrame* fr = rec_floe_frame(c, writer, k);
   if (!fr || !f) return SZ_E_ARG;
   const FloeWriter& w = c->rec.floe[writer];
   const FrameLayout L(w.mask, fr->M, fr->N, fr->V);
-  const ListLayout LL(L.total, fr->lists, fr->M, fr->R, fr->S);
+  const ListLayout LL = rec_list_layout(w, *fr);
   return rec_frame_down(c, "sz_download_floe_frame", L, fr->M, fr->N, fr->V, w.arena + fr->at, f, &LL, fr->S);
 }
 int sz_floe_frame_lists_info(sz_ctx* c, int32_t writer, int32_t k, int64_t* n_inter_rows, int64_t* n_sub_points) {
@@ -3670,7 +3691,7 @@ int sz_download_floe_frame_interactions(sz_ctx* c, int32_t writer, int32_t k, in
   if (!fr || !off) return SZ_E_ARG;
   if (!(fr->lists & FR_LIST_INTER)) { c->err = "sz_download_floe_frame_interactions: this frame did not record the interactions (sz_set_floe_output_lists)"; return SZ_E_ARG; }
   const FloeWriter& w = c->rec.floe[writer];
-  const ListLayout LL(FrameLayout(w.mask, fr->M, fr->N, fr->V).total, fr->lists, fr->M, fr->R, fr->S);
+  const ListLayout LL = rec_list_layout(w, *fr);
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(off, w.arena + fr->at + LL.off[FL_IOFF], (size_t)(fr->M + 1) * sizeof(int), hipMemcpyDeviceToHost));
@@ -3721,7 +3742,7 @@ struct Digest {
   template <class T> void val(const T& v) { add(&v, sizeof(T)); }
 };
 }  // namespace
-// The first act of a tiled batch with writers set, before any other collective: one gather of a digest of every writer's settings (interval, mask;
+// The first act of a tiled batch with writers set, before any other collective: one gather of a digest of every writer's settings (interval, mask, lists;
 // interval, grid lines, output codes, max_frames).  Ranks that were set differently would cut their batches differently and wait for each other
 // in different collectives: every rank returns SZ_E_STATE instead, naming the first writer that differs.
 static int tile_rec_agree_settings(sz_ctx* c) {
@@ -3729,7 +3750,7 @@ static int tile_rec_agree_settings(sz_ctx* c) {
   int mine[2 * REC_WRITERS], all[2 * REC_WRITERS * Gather::RANKS];
   for (int w = 0; w < REC_WRITERS; w++) {
     Digest f, g;
-    f.val(R.floe[w].dt); f.val(R.floe[w].mask); f.val(R.floe[w].tile);
+    f.val(R.floe[w].dt); f.val(R.floe[w].mask); f.val(R.floe[w].tile); f.val(R.floe[w].lists);
     const GridWriter& G = R.grid[w];
     g.val(G.dt); g.val(G.nx); g.val(G.ny); g.val(G.max_frames); g.val(G.tile);
     g.add(G.xg.data(), G.xg.size() * sizeof(double)); g.add(G.yg.data(), G.yg.size() * sizeof(double)); g.add(G.outputs.data(), G.outputs.size() * sizeof(int));
@@ -3762,9 +3783,54 @@ int tile_rec_pack(sz_ctx* c, FloeWriter& w, int tstep, int V, const std::vector<
   w.used += (size_t)L.total;
   return SZ_OK;
 }
+// The lists of a tile frame (sz_tile_set_floe_output_lists).  The order keys of the last step's rows behind the owned parents -- its halo floes,
+// their ghosts and the owned floes' ghosts, as the inline tile steps leave them in S.gkeys -- sorted into the recorder's workspace: what the
+// merge translates ghost partners with.  Called BEFORE sz_add_ghosts, as rec_list_keys is.  *nkeys == 0: nothing to translate.
+int tile_rec_list_keys(sz_ctx* c, int* nkeys) {
+  *nkeys = 0;
+  if (c->tile_inter_state != TILE_INTER_TABLE) return SZ_OK;
+  ListWork W;
+  if (int rc = rec_list_work(c, W)) return rc;
+  const int G = c->tile_keys_n;
+  if (G <= 0 || G > c->S.capM) return SZ_OK;
+  const long long* src = c->S.gkeys + (size_t)c->tile_keys_slot * c->S.capM;
+  size_t tb = 0;
+  HIPCHK(c, rocprim::radix_sort_keys(nullptr, tb, src, W.keys, (size_t)G, 0, 64, c->stream));
+  if (tb > W.tmp_bytes) { c->err = "the recorder's key sort needs more scratch than its workspace holds"; return SZ_E_STATE; }
+  HIPCHK(c, rocprim::radix_sort_keys(W.tmp, tb, src, W.keys, (size_t)G, 0, 64, c->stream));
+  *nkeys = G;
+  return SZ_OK;
+}
+// the list sections of the tile frame tile_rec_pack has just appended to w: the key table copied, one launch of the single frame's list kernel
+// with nothing translated.  lists: the writer's, without the interactions where some rank's rows were not the last step's (lost: why);
+// lranks: {R, S, K} of every rank for the union of the due writers' lists
+int tile_rec_pack_lists(sz_ctx* c, FloeWriter& w, unsigned lists, int nkeys, const std::vector<int>& lranks, int lost) {
+  ListWork W;
+  if (int rc = rec_list_work(c, W)) return rc;
+  FloeFrame& fr = w.frames.back();
+  const bool in = lists & FR_LIST_INTER, sub = lists & FR_LIST_SUB;
+  const int me = c->comm_rank;
+  fr.lists = lists; fr.inter_lost = (w.lists & FR_LIST_INTER) ? lost : 0;
+  fr.lranks = lranks;
+  for (size_t r = 0; r < fr.lranks.size() / 3; r++) { if (!in) fr.lranks[3 * r] = fr.lranks[3 * r + 2] = 0; if (!sub) fr.lranks[3 * r + 1] = 0; }
+  fr.R = fr.lranks[3 * me]; fr.S = fr.lranks[3 * me + 1]; fr.K = in ? nkeys : 0;
+  const TileListLayout L(w.mask, lists, fr.M, fr.N, fr.V, fr.R, fr.S, fr.K);
+  char* dst = w.arena + fr.at;
+  if (fr.K > 0) HIPCHK(c, hipMemcpyAsync(dst + L.lkey, W.keys, (size_t)fr.K * sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
+  if (lists) {
+    FrameLists F;
+    for (int k = 0; k < FL_NSEC; k++) F.off[k] = L.off[k];
+    F.dst = dst; F.ioff = W.ioff; F.soff = W.soff; F.keys = nullptr; F.nkeys = 0; F.M = fr.M; F.N = fr.N; F.lists = lists; F.R = fr.R; F.S = fr.S; F.keep_spare = 1;
+    const long long widest = std::max<long long>(std::max<long long>(7 * fr.R, fr.S), fr.M + 1);
+    hipLaunchKernelGGL(sz_k_frame_lists, dim3(grid_for(widest, FP_TPB, 256), 2), dim3(FP_TPB), 0, c->stream, c->S, F);
+  }
+  w.used = fr.at + (size_t)L.total;
+  return SZ_OK;
+}
 }  // namespace
 // write_data! of output step tstep on a tiled context, collectively (TileStops::record): halo rows and ghosts dropped, sz_add_ghosts -- the
-// ghosts of the owned parents, which depend on each parent alone --, the counters, ONE gather of {error / full bits, M, N, V} per rank (an error
+// ghosts of the owned parents, which depend on each parent alone --, the counters, ONE gather of {error / full bits, M, N, V} per rank (with lists due also
+// {R, S, key-table entries, rows-lost}: the key table is sorted in front of sz_add_ghosts, the counts and scans of the lists run behind it; an error
 // or a full writer of one rank is every rank's; the counts stay with the frame: the merge needs no collective to size its slots), one keyed
 // pack launch per due floe writer; per due grid writer this rank's per-cell sums into one buffer, ONE all-reduce over it, the averages, the
 // selected outputs into the store; sz_remove_ghosts.  A failure of the runtime itself (SZ_E_HIP) is returned alone, as everywhere on tiles.
@@ -3780,27 +3846,53 @@ static int tile_record(sz_ctx* c, int tstep, int* full) {
   const int n = c->comm_n;
   (void)hipSetDevice(c->device);
   int h[C_COUNT] = { 0 };
+  // the lists some due writer records (the same word on every rank: the settings were agreed).  A writer without lists adds no launch, no scan,
+  // no synchronisation, and the gather carries its four words
+  unsigned lists = 0;
+  for (int w = 0; w < REC_WRITERS; w++) if (fdue[w]) lists |= R.floe[w].lists;
+  int rc = SZ_OK, nkeys = 0, lost = 0;
+  if (lists & FR_LIST_INTER) {
+    lost = c->tile_inter_state == TILE_INTER_MIGRATED || c->tile_inter_state == TILE_INTER_LISTED ? c->tile_inter_state : 0;
+    if (!lost && (rc = tile_rec_list_keys(c, &nkeys)) == SZ_E_HIP) return rc;
+  }
+  const char* const keys_in = R.list_work.p;
   tile_cleanup(c);
-  int rc = sz_add_ghosts(c);
+  if (!rc) rc = sz_add_ghosts(c);
   if (rc == SZ_E_HIP) return rc;
+  if (!rc && lists && (rc = rec_list_scans(c, lost ? lists & ~FR_LIST_INTER : lists)) == SZ_E_HIP) return rc;
+  if (!rc && nkeys > 0 && R.list_work.p != keys_in) {
+    (void)sz_remove_ghosts(c);          // (the ghosts are in the list: an error return leaves the parents alone, as the other ways out do)
+    c->err = "the recorder's workspace moved under the sorted ghost keys (sz_add_ghosts grew the list)"; rc = SZ_E_STATE;
+  }
   const int err_bits = rc ? (c->last_err_bits ? c->last_err_bits & ~REC_BIT_FULL : 1) : 0;
   if (!rc && (rc = fetch_counters(c, h))) return rc;
   const int M = c->hostM, N = c->hostN, V = h[C_NV];
+  const int nR = (lists & FR_LIST_INTER) && !lost ? h[C_SCRATCH0] : 0, nS = lists & FR_LIST_SUB ? h[C_SCRATCH1] : 0;
+  auto frame_total = [&](const FloeWriter& fw) {
+    if (!fw.lists) return (size_t)TileFrameLayout(fw.mask, M, N, V).total;
+    return (size_t)TileListLayout(fw.mask, lost ? fw.lists & ~FR_LIST_INTER : fw.lists, M, N, V, nR, nS, nkeys).total;
+  };
+  // (the local full size: where only a PEER's rows are lost the frame will be smaller than checked -- conservative; the migration and the
+  //  drivers set the state alike on every rank, so in practice the ranks agree on `lost` before the gather says so)
   bool room = true;
   for (int w = 0; w < REC_WRITERS && !err_bits; w++) {
-    if (fdue[w] && R.floe[w].used + (size_t)TileFrameLayout(R.floe[w].mask, M, N, V).total > R.floe[w].bytes) room = false;
+    if (fdue[w] && R.floe[w].used + frame_total(R.floe[w]) > R.floe[w].bytes) room = false;
     if (gdue[w] && (int)R.grid[w].tsteps.size() >= R.grid[w].max_frames) room = false;
   }
-  const int mine[4] = { err_bits | (room ? 0 : REC_BIT_FULL), M, N, V };
-  std::vector<int> all((size_t)4 * Gather::RANKS, 0), ranks((size_t)3 * n);
-  if ((rc = tile_gather_ints(c, mine, 4, all.data()))) return rc;
+  const int nw = lists ? 8 : 4;
+  const int mine[8] = { err_bits | (room ? 0 : REC_BIT_FULL), M, N, V, nR, nS, nkeys, lost };
+  std::vector<int> all((size_t)nw * Gather::RANKS, 0), ranks((size_t)3 * n), lranks(lists ? (size_t)3 * n : 0, 0);          // (without lists: what was allocated before)
+  if ((rc = tile_gather_ints(c, mine, nw, all.data()))) return rc;
   int bits = 0, who = -1; long long n_global = 0;
   for (int r = 0; r < n; r++) {
-    if ((all[4 * r] & ~REC_BIT_FULL) && who < 0) who = r;
-    bits |= all[4 * r];
-    for (int q = 0; q < 3; q++) ranks[3 * r + q] = all[4 * r + 1 + q];
-    n_global += all[4 * r + 2];
+    if ((all[nw * r] & ~REC_BIT_FULL) && who < 0) who = r;
+    bits |= all[nw * r];
+    for (int q = 0; q < 3; q++) ranks[3 * r + q] = all[nw * r + 1 + q];
+    n_global += all[nw * r + 2];
+    if (lists) { for (int q = 0; q < 3; q++) lranks[3 * r + q] = all[nw * r + 4 + q]; if (!lost) lost = all[nw * r + 7]; }
   }
+  // (rows that are not the last step's on one rank: no rank records the interactions of this frame -- the points stay)
+  if (lost) { nkeys = 0; for (int r = 0; r < n; r++) lranks[3 * r] = lranks[3 * r + 2] = 0; }
   if (bits & ~REC_BIT_FULL) {
     if (!err_bits) {          // (else this rank's own message stands)
       (void)sz_remove_ghosts(c);
@@ -3810,7 +3902,11 @@ static int tile_record(sz_ctx* c, int tstep, int* full) {
   }
   c->err.clear();
   if (bits & REC_BIT_FULL) { *full = 1; R.full = true; return sz_remove_ghosts(c); }
-  for (int w = 0; w < REC_WRITERS; w++) if (fdue[w] && (rc = tile_rec_pack(c, R.floe[w], tstep, V, ranks, n_global))) return rc;
+  for (int w = 0; w < REC_WRITERS; w++) {
+    if (!fdue[w]) continue;
+    if ((rc = tile_rec_pack(c, R.floe[w], tstep, V, ranks, n_global))) return rc;
+    if (R.floe[w].lists && (rc = tile_rec_pack_lists(c, R.floe[w], lost ? R.floe[w].lists & ~FR_LIST_INTER : R.floe[w].lists, nkeys, lranks, lost))) return rc;
+  }
   if (any_grid) {
     size_t need_grid = 0, need_part = 0;
     for (int w = 0; w < REC_WRITERS; w++) if (gdue[w]) { need_grid += eul_grid_bytes(R.grid[w].nx, R.grid[w].ny); need_part += (size_t)EUL_PARTIAL * R.grid[w].nx * R.grid[w].ny * sizeof(double); }
@@ -3878,61 +3974,94 @@ int sz_tile_floe_frame_info(sz_ctx* c, int32_t writer, int32_t k, int64_t* tstep
 }
 // The merged frame (collective): what each rank prepares alone -- the frame, the members asked for, the scratch -- is agreed first, so that nobody
 // is left in the gather; every rank's frame k in slots of the largest frame's size (known from the counts kept with the frame); the merge of
-// sz_record_tile.hpp on the ranks that asked for the frame; one copy down.
-int sz_tile_download_floe_frame(sz_ctx* c, int32_t writer, int32_t k, sz_floe_columns* f) {
-  static const char who[] = "sz_tile_download_floe_frame";
+// sz_record_tile.hpp on the ranks that asked for the frame; one copy down.  inter: the call is sz_tile_download_floe_frame_interactions, and
+// off / rows take the merged interactions instead of f the columns and points.  A rank that passes neither only takes part.
+static int tile_frame_merged(sz_ctx* c, const char* who, int32_t writer, int32_t k, sz_floe_columns* f, bool inter, int32_t* off, double* rows) {
   if (!c) return SZ_E_ARG;
   if (int rc = tiled_ready(c, who)) return rc;
   (void)hipSetDevice(c->device);
   const int n = c->comm_n, me = c->comm_rank;
+  const bool take = inter ? off != nullptr : f != nullptr;
   int rc = SZ_OK;
   const FloeFrame* fr = tile_floe_frame(c, writer, k, who);
   if (!fr) rc = SZ_E_ARG;
-  else if ((int)fr->ranks.size() != 3 * n) { c->err = std::string(who) + ": the frame was recorded by another number of ranks"; rc = SZ_E_STATE; }
+  else if ((int)fr->ranks.size() != 3 * n || (fr->lists && (int)fr->lranks.size() != 3 * n)) { c->err = std::string(who) + ": the frame was recorded by another number of ranks"; rc = SZ_E_STATE; }
+  else if (inter && !(fr->lists & FR_LIST_INTER)) {
+    if (fr->inter_lost == TILE_INTER_MIGRATED) { c->err = std::string(who) + ": this frame holds no interactions: it was recorded behind sz_tile_migrate, which drops the rows, before a collision step had made new ones"; rc = SZ_E_STATE; }
+    else if (fr->inter_lost == TILE_INTER_LISTED) { c->err = std::string(who) + ": this frame holds no interactions: the step in front of it was a list-based tile step (sz_tile_step, a ridge / raft step), whose ghost keys are not kept"; rc = SZ_E_STATE; }
+    else { c->err = std::string(who) + ": this frame did not record the interactions (sz_tile_set_floe_output_lists)"; rc = SZ_E_ARG; }
+  }
   // ---- this rank alone: the layouts of all ranks' frames and of the merged one, the scratch
-  long long slot = 8, Mg = 0, Ng = 0, Vg = 0;
-  std::vector<long long> sec((size_t)n * (FR_NSEC + 1), -1); std::vector<int> row0((size_t)n + 1, 0), npar((size_t)n, 0);
+  const unsigned lists = fr && !rc ? fr->lists : 0;
+  long long slot = 8, Mg = 0, Ng = 0, Vg = 0, Rg = 0, Sg = 0, Kt = 0;
+  std::vector<long long> sec((size_t)n * RECT_NSEC, -1); std::vector<int> row0((size_t)n + 1, 0), npar((size_t)n, 0), lcnt((size_t)3 * n, 0), kbase((size_t)n + 1, 0);
   const unsigned long long mask = fr ? c->rec.floe[writer].mask : 1;
   if (!rc) {
-    for (int r = 0; r < n; r++) slot = std::max(slot, TileFrameLayout(mask, fr->ranks[3 * r], fr->ranks[3 * r + 1], fr->ranks[3 * r + 2]).total);
+    auto layout = [&](int r) { return TileListLayout(mask, lists, fr->ranks[3 * r], fr->ranks[3 * r + 1], fr->ranks[3 * r + 2], lists ? fr->lranks[3 * r] : 0, lists ? fr->lranks[3 * r + 1] : 0, lists ? fr->lranks[3 * r + 2] : 0); };
+    // What travels: the whole frame -- or, for the interactions, only the part of it that call reads: the keys, the key table, inter_off and the
+    // rows lie one behind the other in a tile frame (TileFrameLayout::key .. the end of ListLayout's FL_IROWS), in front of the points
+    auto part = [&](int r, long long* from, long long* to) {
+      const TileListLayout T = layout(r);
+      *from = inter ? TileFrameLayout(mask, fr->ranks[3 * r], fr->ranks[3 * r + 1], fr->ranks[3 * r + 2]).key : 0;
+      *to = inter ? T.off[FL_IROWS] + 56ll * std::max(fr->lranks[3 * r], 0) : T.total;
+    };
+    for (int r = 0; r < n; r++) { long long a, b; part(r, &a, &b); slot = std::max(slot, b - a); }
     for (int r = 0; r < n; r++) {
       const TileFrameLayout L(mask, fr->ranks[3 * r], fr->ranks[3 * r + 1], fr->ranks[3 * r + 2]);
-      for (int s = 0; s < FR_NSEC; s++) sec[(size_t)r * (FR_NSEC + 1) + s] = L.off[s] < 0 ? -1 : r * slot + L.off[s];
-      sec[(size_t)r * (FR_NSEC + 1) + FR_NSEC] = r * slot + L.key;
+      long long* t = &sec[(size_t)r * RECT_NSEC];
+      long long from, to; part(r, &from, &to);
+      auto at = [&](long long off) { return off < from || off >= to ? -1 : r * slot + off - from; };
+      for (int s = 0; s < FR_NSEC; s++) t[s] = L.off[s] < 0 ? -1 : at(L.off[s]);
+      t[RS_KEY] = at(L.key);
+      if (lists) {
+        const TileListLayout T = layout(r);
+        t[RS_LKEY] = T.lkey < 0 ? -1 : at(T.lkey);
+        for (int s = 0; s < FL_NSEC; s++) t[RS_LIST + s] = T.off[s] < 0 ? -1 : at(T.off[s]);
+        for (int q = 0; q < 3; q++) lcnt[3 * r + q] = std::max(fr->lranks[3 * r + q], 0);
+        Rg += lcnt[3 * r]; Sg += lcnt[3 * r + 1];
+      }
+      kbase[r] = (int)Kt; Kt += lcnt[3 * r + 2];
       row0[r] = (int)Mg; npar[r] = fr->ranks[3 * r + 1];
       Mg += fr->ranks[3 * r]; Ng += fr->ranks[3 * r + 1]; Vg += fr->ranks[3 * r + 2];
     }
-    row0[n] = (int)Mg;
-    if (Mg > 0x7fffffffll || Vg > 0x7fffffffll) { c->err = std::string(who) + ": the merged frame has more rows or ring points than an int holds"; rc = SZ_E_CAPACITY; }
+    row0[n] = (int)Mg; kbase[n] = (int)Kt;
+    if (Mg > 0x7fffffffll || Vg > 0x7fffffffll || 7 * Rg > 0x7fffffffll || Sg > 0x7fffffffll || Kt > 0x7fffffffll) { c->err = std::string(who) + ": the merged frame has more rows, ring points or list entries than an int holds"; rc = SZ_E_CAPACITY; }
     else if (fr->M != fr->ranks[3 * me] || fr->N != fr->ranks[3 * me + 1] || fr->V != fr->ranks[3 * me + 2]) { c->err = std::string(who) + ": the frame was recorded by another rank of the communicator"; rc = SZ_E_STATE; }
   }
   const FrameLayout Lg(mask, Mg, Ng, Vg);
-  if (!rc && f) rc = rec_frame_down(c, who, Lg, Mg, Ng, Vg, nullptr, f);          // (the members asked for: checked before anybody gathers)
+  const ListLayout LLg(Lg.total, lists, Mg, Rg, Sg);
+  if (!rc && f && !inter) rc = rec_frame_down(c, who, Lg, Mg, Ng, Vg, nullptr, f, &LLg, Sg);          // (the members asked for: checked before anybody gathers)
   Pool& P = c->rect_allocs;
   reset_pool(P);
   char *d_own = nullptr, *d_all = nullptr, *d_out = nullptr, *d_tmp = nullptr;
-  long long *d_sec = nullptr, *key_in = nullptr, *key_out = nullptr; int *d_row0 = nullptr, *d_npar = nullptr, *val_in = nullptr, *src = nullptr, *pos = nullptr, *nv = nullptr, *ng = nullptr;
+  long long *d_sec = nullptr, *key_in = nullptr, *key_out = nullptr, *kcat = nullptr, *ksort = nullptr;
+  int *d_row0 = nullptr, *d_npar = nullptr, *val_in = nullptr, *src = nullptr, *pos = nullptr, *nv = nullptr, *ng = nullptr, *d_lcnt = nullptr, *d_kbase = nullptr, *ni = nullptr, *ns = nullptr,
+      *kflag = nullptr, *drank = nullptr;
   size_t tmp_bytes = 0;
-  const size_t Mc = (size_t)std::max<long long>(Mg, 1);
+  const size_t Mc = (size_t)std::max<long long>(Mg, 1), Kc = (size_t)std::max<long long>(Kt, 1);
   if (!rc) (void)((rc = dalloc(c, &d_own, (size_t)slot, P)) || (rc = dalloc(c, &d_all, (size_t)slot * n, P)));
-  if (!rc && f) {
-    size_t b1 = 0, b2 = 0;
+  if (!rc && take) {
+    size_t b1 = 0, b2 = 0, b3 = 0;
     if (hipSuccess != rocprim::radix_sort_pairs(nullptr, b1, (const long long*)nullptr, (long long*)nullptr, (const int*)nullptr, (int*)nullptr, Mc, 0u, 43u, c->stream) ||
-        hipSuccess != rocprim::exclusive_scan(nullptr, b2, (const int*)nullptr, (int*)nullptr, 0, Mc + 1, rocprim::plus<int>(), c->stream)) { c->err = std::string(who) + ": rocprim would not size its scratch"; rc = SZ_E_HIP; }
-    tmp_bytes = std::max(b1, b2);
-    if (!rc) (void)((rc = dalloc(c, &d_out, (size_t)Lg.total, P)) || (rc = dalloc(c, &d_tmp, tmp_bytes, P)) || (rc = dalloc(c, &d_sec, sec.size(), P)) || (rc = dalloc(c, &d_row0, row0.size(), P)) ||
+        hipSuccess != rocprim::exclusive_scan(nullptr, b2, (const int*)nullptr, (int*)nullptr, 0, std::max(Mc, lists ? Kc : 0) + 1, rocprim::plus<int>(), c->stream) ||
+        (lists && hipSuccess != rocprim::radix_sort_keys(nullptr, b3, (const long long*)nullptr, (long long*)nullptr, Kc, 0u, 64u, c->stream))) { c->err = std::string(who) + ": rocprim would not size its scratch"; rc = SZ_E_HIP; }
+    tmp_bytes = std::max(std::max(b1, b2), b3);
+    if (!rc) (void)((rc = dalloc(c, &d_out, (size_t)LLg.total, P)) || (rc = dalloc(c, &d_tmp, tmp_bytes, P)) || (rc = dalloc(c, &d_sec, sec.size(), P)) || (rc = dalloc(c, &d_row0, row0.size(), P)) ||
                     (rc = dalloc(c, &d_npar, npar.size(), P)) || (rc = dalloc(c, &key_in, Mc, P)) || (rc = dalloc(c, &key_out, Mc, P)) || (rc = dalloc(c, &val_in, Mc, P)) ||
                     (rc = dalloc(c, &src, Mc, P)) || (rc = dalloc(c, &pos, Mc, P)) || (rc = dalloc(c, &nv, Mc + 1, P)) || (rc = dalloc(c, &ng, Mc + 1, P)));
+    if (!rc && lists) (void)((rc = dalloc(c, &d_lcnt, lcnt.size(), P)) || (rc = dalloc(c, &d_kbase, kbase.size(), P)) || (rc = dalloc(c, &ni, Mc + 1, P)) || (rc = dalloc(c, &ns, Mc + 1, P)) ||
+                             (rc = dalloc(c, &kcat, Kc, P)) || (rc = dalloc(c, &ksort, Kc, P)) || (rc = dalloc(c, &kflag, Kc + 1, P)) || (rc = dalloc(c, &drank, Kc + 1, P)));
   }
   // ---- the agreement on what each prepared alone, then the gather
   int first = 0;
   if (const int rc2 = comm_agree_rc(c, who, rc, &first)) return rc2;
   if (first) return rc ? rc : first;
   const FloeWriter& w = c->rec.floe[writer];
-  const size_t mine_bytes = (size_t)TileFrameLayout(mask, fr->M, fr->N, fr->V).total;
-  HIPCHK(c, hipMemcpyAsync(d_own, w.arena + fr->at, mine_bytes, hipMemcpyDeviceToDevice, c->stream));
+  const TileListLayout Tm(mask, lists, fr->M, fr->N, fr->V, fr->R, fr->S, fr->K);
+  const long long mine_from = inter ? TileFrameLayout(mask, fr->M, fr->N, fr->V).key : 0, mine_to = inter ? Tm.off[FL_IROWS] + 56ll * fr->R : Tm.total;
+  if (mine_to > mine_from) HIPCHK(c, hipMemcpyAsync(d_own, w.arena + fr->at + mine_from, (size_t)(mine_to - mine_from), hipMemcpyDeviceToDevice, c->stream));
   if ((rc = comm_allgather(c, d_own, d_all, (size_t)slot / 8, NCCL_FLOAT64, sizeof(double)))) return rc;
-  if (!f) return SZ_OK;
+  if (!take) return SZ_OK;
   // ---- the merge
   HIPCHK(c, hipMemcpyAsync(d_sec, sec.data(), sec.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_row0, row0.data(), row0.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -3946,13 +4075,66 @@ int sz_tile_download_floe_frame(sz_ctx* c, int32_t writer, int32_t k, sz_floe_co
     hipLaunchKernelGGL(sz_k_rect_keys, dim3(nb), dim3(RECT_TPB), 0, c->stream, A, key_in, val_in);
     HIPCHK(c, rocprim::radix_sort_pairs((void*)d_tmp, tmp_bytes, (const long long*)key_in, key_out, (const int*)val_in, src, (size_t)Mg, 0u, 43u, c->stream));
   }
-  hipLaunchKernelGGL(sz_k_rect_counts, dim3(nb), dim3(RECT_TPB), 0, c->stream, A);
-  if (Lg.off[FR_VOFF] >= 0) HIPCHK(c, rocprim::exclusive_scan((void*)d_tmp, tmp_bytes, (const int*)nv, (int*)(d_out + Lg.off[FR_VOFF]), 0, (size_t)Mg + 1, rocprim::plus<int>(), c->stream));
-  if (Lg.off[FR_GOFF] >= 0) HIPCHK(c, rocprim::exclusive_scan((void*)d_tmp, tmp_bytes, (const int*)ng, (int*)(d_out + Lg.off[FR_GOFF]), 0, (size_t)Mg + 1, rocprim::plus<int>(), c->stream));
-  hipLaunchKernelGGL(sz_k_rect_scatter, dim3(grid_for(std::max<long long>(4 * Mg, Vg), RECT_TPB, 256), FP_SLICES), dim3(RECT_TPB), 0, c->stream, A);
-  rc = rec_frame_down(c, who, Lg, Mg, Ng, Vg, d_out, f);
+  // (a call moves what it returns: the interactions call neither the columns nor the points, the column call neither the key tables nor the rows)
+  if (!inter) hipLaunchKernelGGL(sz_k_rect_counts, dim3(nb), dim3(RECT_TPB), 0, c->stream, A);
+  if (!inter && Lg.off[FR_VOFF] >= 0) HIPCHK(c, rocprim::exclusive_scan((void*)d_tmp, tmp_bytes, (const int*)nv, (int*)(d_out + Lg.off[FR_VOFF]), 0, (size_t)Mg + 1, rocprim::plus<int>(), c->stream));
+  if (!inter && Lg.off[FR_GOFF] >= 0) HIPCHK(c, rocprim::exclusive_scan((void*)d_tmp, tmp_bytes, (const int*)ng, (int*)(d_out + Lg.off[FR_GOFF]), 0, (size_t)Mg + 1, rocprim::plus<int>(), c->stream));
+  if (!inter) hipLaunchKernelGGL(sz_k_rect_scatter, dim3(grid_for(std::max<long long>(4 * Mg, Vg), RECT_TPB, 256), FP_SLICES), dim3(RECT_TPB), 0, c->stream, A);
+  const bool want_in = inter && (lists & FR_LIST_INTER), want_sub = !inter && (lists & FR_LIST_SUB) && f && (f->sub_off || f->sx || f->sy);
+  if (want_in || want_sub) {
+    HIPCHK(c, hipMemcpyAsync(d_lcnt, lcnt.data(), lcnt.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_kbase, kbase.data(), kbase.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    A.lists = lists; A.lcnt = d_lcnt; A.kbase = d_kbase; A.ni = ni; A.ns = ns; A.dkeys = ksort; A.drank = drank;
+    for (int s = 0; s < FL_NSEC; s++) A.loff[s] = LLg.off[s];
+    if (!want_in) A.loff[FL_IOFF] = A.loff[FL_IROWS] = -1;
+    if (!want_sub) A.loff[FL_SOFF] = A.loff[FL_SX] = A.loff[FL_SY] = -1;
+    A.Kt = want_in ? (int)Kt : 0; A.Rg = (int)Rg; A.Sg = (int)Sg; A.list0 = want_in ? 0 : 1;
+    if (A.Kt > 0) {
+      hipLaunchKernelGGL(sz_k_rect_lkeys, dim3(grid_for(Kt, RECT_TPB, 2048)), dim3(RECT_TPB), 0, c->stream, A, kcat);
+      HIPCHK(c, rocprim::radix_sort_keys((void*)d_tmp, tmp_bytes, (const long long*)kcat, ksort, (size_t)Kt, 0u, 64u, c->stream));
+      hipLaunchKernelGGL(sz_k_rect_kflags, dim3(grid_for(Kt + 1, RECT_TPB, 2048)), dim3(RECT_TPB), 0, c->stream, (const long long*)ksort, kflag, (int)Kt);
+      HIPCHK(c, rocprim::exclusive_scan((void*)d_tmp, tmp_bytes, (const int*)kflag, drank, 0, (size_t)Kt + 1, rocprim::plus<int>(), c->stream));
+    }
+    hipLaunchKernelGGL(sz_k_rect_list_counts, dim3(nb), dim3(RECT_TPB), 0, c->stream, A);
+    if (want_in) HIPCHK(c, rocprim::exclusive_scan((void*)d_tmp, tmp_bytes, (const int*)ni, (int*)(d_out + LLg.off[FL_IOFF]), 0, (size_t)Mg + 1, rocprim::plus<int>(), c->stream));
+    if (want_sub) HIPCHK(c, rocprim::exclusive_scan((void*)d_tmp, tmp_bytes, (const int*)ns, (int*)(d_out + LLg.off[FL_SOFF]), 0, (size_t)Mg + 1, rocprim::plus<int>(), c->stream));
+    hipLaunchKernelGGL(sz_k_rect_lists, dim3(grid_for(want_in ? 7 * Rg : Sg, RECT_TPB, 256), 1), dim3(RECT_TPB), 0, c->stream, A);
+  }
+  if (!inter) rc = rec_frame_down(c, who, Lg, Mg, Ng, Vg, d_out, f, &LLg, Sg);
+  else {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(off, d_out + LLg.off[FL_IOFF], (size_t)(Mg + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    if (rows && Rg > 0) HIPCHK(c, hipMemcpy(rows, d_out + LLg.off[FL_IROWS], (size_t)Rg * 7 * sizeof(double), hipMemcpyDeviceToHost));
+  }
   trim_pool(P);
   return rc;
+}
+int sz_tile_download_floe_frame(sz_ctx* c, int32_t writer, int32_t k, sz_floe_columns* f) { return tile_frame_merged(c, "sz_tile_download_floe_frame", writer, k, f, false, nullptr, nullptr); }
+int sz_tile_download_floe_frame_interactions(sz_ctx* c, int32_t writer, int32_t k, int32_t* off, double* rows) {
+  return tile_frame_merged(c, "sz_tile_download_floe_frame_interactions", writer, k, nullptr, true, off, rows);
+}
+// the lists of the MERGED frame and their totals, from the counts kept with the frame (local)
+int sz_tile_floe_frame_lists_info(sz_ctx* c, int32_t writer, int32_t k, uint32_t* lists, int64_t* n_inter_rows, int64_t* n_sub_points) {
+  const FloeFrame* fr = tile_floe_frame(c, writer, k, "sz_tile_floe_frame_lists_info");
+  if (!fr) return SZ_E_ARG;
+  long long tot[2] = { 0, 0 };
+  for (size_t r = 0; r < fr->lranks.size() / 3; r++) for (int q = 0; q < 2; q++) tot[q] += fr->lranks[3 * r + q];
+  if (lists) *lists = fr->lists;
+  if (n_inter_rows) *n_inter_rows = tot[0];
+  if (n_sub_points) *n_sub_points = tot[1];
+  return SZ_OK;
+}
+// the key table of tile frame k (local): *n its entries, keys (may be NULL) the sorted order keys of the last step's rows behind the owned parents
+int sz_tile_floe_frame_list_keys(sz_ctx* c, int32_t writer, int32_t k, int64_t* n, int64_t* keys) {
+  const FloeFrame* fr = tile_floe_frame(c, writer, k, "sz_tile_floe_frame_list_keys");
+  if (!fr || !n) return SZ_E_ARG;
+  *n = fr->K;
+  if (!keys || fr->K <= 0) return SZ_OK;
+  const FloeWriter& w = c->rec.floe[writer];
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(keys, w.arena + fr->at + TileListLayout(w.mask, fr->lists, fr->M, fr->N, fr->V, fr->R, fr->S, fr->K).lkey, (size_t)fr->K * sizeof(long long), hipMemcpyDeviceToHost));
+  return SZ_OK;
 }
 
 // what simplify_floes! (simplification.jl:339-378) would find to do, without downloading a floe

@@ -191,6 +191,11 @@ struct sz_ctx {
   // output recorder (sz_set_floe_output / sz_set_grid_output; sz_record.hpp): the writers, their frames in HBM, the workspace of the averages
   Recorder rec;
   Pool rect_allocs;                 // scratch of sz_tile_download_floe_frame (sz_record_tile.hpp): the gathered slots, the sort's arrays, the merged frame; kept between calls
+  // tile frames with lists (sz_tile_set_floe_output_lists): what the partner column of floe.interactions on this tile can be translated with.
+  // TILE_INTER_NONE: the rows are as placed (an upload: nothing to translate); _TABLE: the last step was an inline tile step, its order keys are
+  // tile_keys_n entries of S.gkeys' half tile_keys_slot; _LISTED: it was a list-based tile step (sz_tile_step, a ridge / raft step), whose key
+  // table nobody keeps; _MIGRATED: sz_tile_migrate dropped the rows.  Set by the migration and by every collision step of a tile.
+  int tile_inter_state = 0, tile_keys_n = 0, tile_keys_slot = 0;
   bool last_stopped = false;        // the last batch of resident steps ended on a stop request (tag, fracture candidate), not at its last step
   bool maybe_tagged = false;        // a parent may be non-active on the device (an upload said so, a batch ended on a tag, a process-mode call ran):
                                     // the next batch then runs its first step on its own (see sz_step)

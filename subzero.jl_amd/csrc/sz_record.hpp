@@ -30,6 +30,7 @@
 // A GRID FRAME is nout * nx * ny doubles in the layout of sz_eulerian_data, in a store of max_frames frames; its timestep is kept on the host.
 // Limits: 4 floe and 4 grid writers; a frame that finds no room (the arena, max_frames) is not taken: the batch ends in front of that step with
 // `full` set (sz_output_frames), and no writer gets a frame of a step that not all due writers have room for.
+// (sz_tile_set_floe_output_lists: a tile frame's lists lie behind its key section, sz_record_tile.hpp.)
 // TILED CONTEXTS (sz_tile_set_floe_output / sz_tile_set_grid_output; the record point is tile_record in sz_tile_host.hpp, the merge of the ranks'
 // frames sz_record_tile.hpp): a TILE FRAME is the same layout over the rank's own rows -- its owned parents and their ghosts, ghost_idx in local
 // row numbers -- with one more section behind the selected ones, so that the layout above is untouched: key, int64 [M], the row's order key
@@ -158,6 +159,9 @@ __global__ void __launch_bounds__(FP_TPB) sz_k_frame_pack(State S, FramePack F) 
 
 // ---- the lists (sz_set_floe_output_lists): which, and where their sections lie -- behind FrameLayout::total, each padded to 8 bytes
 constexpr unsigned FR_LIST_INTER = 1, FR_LIST_SUB = 2, FR_LIST_ALL = 3;
+// a tiled context: what the partner column of its interaction rows can be translated with (sz_ctx::tile_inter_state), and why a tile frame
+// lost its interactions bit (FloeFrame::inter_lost: _LISTED, _MIGRATED)
+constexpr int TILE_INTER_NONE = 0, TILE_INTER_TABLE = 1, TILE_INTER_LISTED = 2, TILE_INTER_MIGRATED = 3;
 constexpr int FL_IOFF = 0, FL_IROWS = 1, FL_SOFF = 2, FL_SX = 3, FL_SY = 4, FL_NSEC = 5;
 struct ListLayout {
   long long off[FL_NSEC]; long long total;          // total: the whole frame's, columns included
@@ -193,6 +197,7 @@ struct FrameLists {
   int nkeys, M, N;
   unsigned lists;
   long long R, S;                 // the host's totals, fetched with the counters: every store lies inside the layout made from them
+  int keep_spare;                 // a tile frame: the spare header words stay {N_global, rank, nranks} (its totals are kept with the frame on the host)
 };
 
 // The payload of the lists, element-parallel: blockIdx.y = 0 the interactions, one thread per output double; 1 the sub-floe points, one thread
@@ -204,7 +209,7 @@ __global__ void __launch_bounds__(FP_TPB) sz_k_frame_lists(State S, FrameLists F
   const int M = F.M, N = F.N;
   const long long t0 = (long long)blockIdx.x * FP_TPB + threadIdx.x, stride = (long long)gridDim.x * FP_TPB;
   if (blockIdx.y == 0) {
-    if (t0 == 0) { long long* h = (long long*)F.dst; h[5] = F.lists; h[6] = F.R; h[7] = F.S; }
+    if (t0 == 0 && !F.keep_spare) { long long* h = (long long*)F.dst; h[5] = F.lists; h[6] = F.R; h[7] = F.S; }
     if (F.off[FL_IOFF] < 0) return;
     int* off = (int*)(F.dst + F.off[FL_IOFF]);
     double* out = (double*)(F.dst + F.off[FL_IROWS]);
@@ -247,6 +252,10 @@ struct FloeFrame {
   size_t at; int tstep, M, N, V;
   std::vector<int> ranks;         // a tile frame: {M, N, V} of every rank's frame of this step, as gathered at the record point
   unsigned lists = 0; long long R = 0, S = 0;          // the lists it holds, their totals: interaction rows, sub-floe points
+  // a tile frame of a writer with lists (sz_tile_set_floe_output_lists): K = the entries of its key-table section; lranks = {R, S, K} of every
+  // rank's frame of this step, as gathered at the record point; inter_lost = why the interactions bit of `lists` was cleared on every rank
+  // (TILE_INTER_*; 0: it was not)
+  long long K = 0; std::vector<int> lranks; int inter_lost = 0;
 };
 struct FloeWriter {
   int dt = 0; unsigned long long mask = 0; bool tile = false;      // tile: set through sz_tile_set_floe_output

@@ -71,6 +71,7 @@ static int tile_step_body(sz_ctx* c, const void* d_recv, int32_t nranks, int32_t
   //  inside the step here, assembling rows only)
   const bool facc_on = coll && c->facc_buf != nullptr;
   S.facc = facc_on ? c->facc_buf : nullptr; S.kexp = force_scale_exp(c); c->reduce_mode = facc_on ? 1 : 0; c->acc_mode = facc_on ? 1 : 0;
+  if (first && coll) c->tile_inter_state = TILE_INTER_LISTED;          // (the rows name this step's ghosts by order key, and no table of them is kept)
   if (first && coll) stage_ghosts(c, true, sg, gl);
   if (first && coll) collisions(c, -1, dt, periodic && !sg, sg);
   if (second) {
@@ -548,6 +549,7 @@ int tile_migrate_device(sz_ctx* c, int px, int py, const int32_t* owner_override
   free_pool(old_sub);
   c->max_ring = std::max(c->max_ring, ring_in); c->max_sub = std::max(c->max_sub, sub_in);
   c->inter_lost = false; c->inter_any = true;
+  c->tile_inter_state = TILE_INTER_MIGRATED;          // (a tile frame with lists says so: no rows of a last step to record)
   if ((rc = tiling.again(c, ngid.data(), owner_override ? 0 : px, py))) return rc;
   trim_pool(pool.v);
   if (n_owned) *n_owned = Nn;
@@ -663,6 +665,7 @@ int tile_migrate_host(sz_ctx* c, int32_t px, int32_t py, const int32_t* owner_ov
   f.id = (int64_t*)nid.data(); f.status = nstatus.data(); f.vert_off = nvoff.data(); f.vx = nvx.data(); f.vy = nvy.data(); f.sub_off = nsoff.data(); f.sx = nsx.data(); f.sy = nsy.data();
   if ((rc = sz_upload_floes(c, Nn, Nn, &f))) return rc;
   c->inter_lost = false; c->inter_any = true;
+  c->tile_inter_state = TILE_INTER_MIGRATED;          // (a tile frame with lists says so: no rows of a last step to record)
   HIPCHK(c, hipMemsetAsync(S.inter_cnt, 0, ((size_t)S.capM + 1) * sizeof(int), c->stream));          // (no rows until the next collision call)
   if ((rc = tiling.again(c, ngid.data(), owner_override ? 0 : px, py))) return rc;
   if (n_owned) *n_owned = Nn;
@@ -1857,6 +1860,7 @@ static int tile_run_inline(sz_ctx* c, int nsteps, int tstep0, int dt, int coupli
   frc.use(last_set(done)); frc.keep = true;          // the forcing outputs of the last step that ran (see `beside` above)
   if (done < nsteps) c->grid_live = false;          // stopped early: cells hold floes of a step that did not come
   c->inter_any = true; c->inter_lost = false;
+  if (done > 0) { c->tile_inter_state = TILE_INTER_TABLE; c->tile_keys_n = h[C_NGHOSTS]; c->tile_keys_slot = (done - 1) & 1; }      // (the rows' ghost partners: that step's key table)
   // status.fuse_idx of the step that ended the batch (as sz_step: only that step can have produced fuse pairs)
   if (done > 0 && (h[C_STOP] > 0 || (flags & SZ_NO_STOP))) {
     c->gi_pending_n = h[C_NGHOSTS]; c->gi_pending_slot = (done - 1) & 1; c->gi_pending = true;

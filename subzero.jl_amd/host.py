@@ -566,6 +566,8 @@ class World:
         self._floe_masks[int(writer)] = int(mask)
         self._floe_lists = getattr(self, "_floe_lists", {})
         self._floe_lists[int(writer)] = 0
+        self._floe_tile = getattr(self, "_floe_tile", {})
+        self._floe_tile[int(writer)] = bool(_tile)
         if word:
             self._chk(self.L.sz_set_floe_output_lists(self.h, int(writer), word))
             self._floe_lists[int(writer)] = word
@@ -603,18 +605,26 @@ class World:
             down_fn(self.h, int(writer), int(k), None)          # (the peers are in the collective: take part, so that every rank raises)
         self._chk(rc)
         tstep, M, N, V, G = (int(v.value) for v in info)
-        R = S = 0
-        if not _merged:
-            tot = [C.c_int64(0), C.c_int64(0)]
+        tot = [C.c_int64(0), C.c_int64(0)]
+        lists = getattr(self, "_floe_lists", {}).get(int(writer), 0)
+        if _merged:          # (the lists a tile frame really holds: a frame behind a migration has lost its interactions)
+            word = C.c_uint32(0)
+            self._chk(self.L.sz_tile_floe_frame_lists_info(self.h, int(writer), int(k), C.byref(word), *(C.byref(v) for v in tot)))
+            lists = int(word.value)
+        else:
+            if getattr(self, "_floe_tile", {}).get(int(writer)):
+                word = C.c_uint32(0)
+                self._chk(self.L.sz_tile_floe_frame_lists_info(self.h, int(writer), int(k), C.byref(word), None, None))
+                lists = int(word.value)
             self._chk(self.L.sz_floe_frame_lists_info(self.h, int(writer), int(k), *(C.byref(v) for v in tot)))
-            R, S = (int(v.value) for v in tot)
+        R, S = (int(v.value) for v in tot)
         if members is None:
             members = []
             for b, n in enumerate(capi.FRAME_BITS):
                 if self._floe_masks[int(writer)] >> b & 1:
                     members += capi.FRAME_MEMBERS.get(n, [n])
             for b, n in enumerate(capi.FRAME_LISTS):
-                if getattr(self, "_floe_lists", {}).get(int(writer), 0) >> b & 1:
+                if lists >> b & 1:
                     members += capi.FRAME_LIST_MEMBERS[n]
         inter = [n for n in members if n in ("inter_off", "inter_rows")]
         col = {}
@@ -644,7 +654,8 @@ class World:
         for n, a in col.items():
             keep.append(a)
             setattr(f, n, capi.ptr(a.reshape(-1), capi._lp if a.dtype == _I64 else capi._ip if a.dtype == _I32 else capi._dp))
-        self._chk(down_fn(self.h, int(writer), int(k), C.byref(f)))
+        if col or not (_merged and inter):          # (a merged call for the interactions alone is ONE collective: no gather of the whole frames in front of it)
+            self._chk(down_fn(self.h, int(writer), int(k), C.byref(f)))
         for n in ("vx", "vy"):
             if n in col:
                 col[n] = col[n][:V]
@@ -653,7 +664,8 @@ class World:
                 col[n] = col[n][:S]
         if inter:
             off = np.zeros(M + 1, _I32); rows = np.zeros((max(R, 1), 7))
-            self._chk(self.L.sz_download_floe_frame_interactions(self.h, int(writer), int(k), capi.ptr(off, capi._ip), capi.ptr(rows) if "inter_rows" in inter else None))
+            inter_fn = self.L.sz_tile_download_floe_frame_interactions if _merged else self.L.sz_download_floe_frame_interactions
+            self._chk(inter_fn(self.h, int(writer), int(k), capi.ptr(off, capi._ip), capi.ptr(rows) if "inter_rows" in inter else None))
             if "inter_off" in inter:
                 col["inter_off"] = off
             if "inter_rows" in inter:
@@ -661,6 +673,8 @@ class World:
         if "ghost_idx" in col:
             col["ghost_idx"] = col["ghost_idx"][:G]
         col.update(tstep=tstep, M=M, N=N)
+        if getattr(self, "_floe_tile", {}).get(int(writer)) and self._floe_lists.get(int(writer), 0):
+            col["lists"] = lists          # (a tile frame of a writer with lists: the frame's own word -- TiledWorld.floe_frame, floe_frame_local)
         return col
 
     def grid_frame(self, writer, k):

@@ -730,12 +730,47 @@ class TiledWorld:
     # ---- output frames of a tiled run (sz_tile_set_floe_output / sz_tile_set_grid_output, sz_tile_download_floe_frame: library backends)
     def set_floe_output(self, writer, dt_out, columns=None, arena_bytes=1 << 26, lists=None):
         """World.set_floe_output for this rank's tile (the same arguments on every rank).  run() then goes on past the writer's output steps and
-        records there: every rank keeps the frame of its own rows -- its owned floes and their ghosts -- with their order keys.  Tile frames
-        record no lists yet: `lists` is refused."""
+        records there: every rank keeps the frame of its own rows -- its owned floes and their ghosts -- with their order keys.  `lists` is
+        refused here: the lists of a tile writer are set through set_floe_output_lists, behind this call."""
         self._library_only("set_floe_output")
         if lists:
-            raise capi.SzError("tile frames record no lists yet: set_floe_output of a tiled run takes no `lists`")
+            raise capi.SzError("tile frames record no lists yet through set_floe_output: set_floe_output_lists(writer, lists) behind it sets them")
         self.world.set_floe_output(writer, dt_out, columns, arena_bytes, _tile=True)
+
+    def set_floe_output_lists(self, writer, lists):
+        """the ragged members (names out of capi.FRAME_LISTS; the same on every rank) a tile writer records behind its columns: called after
+        set_floe_output, which resets them; frees the writer's frames.  The merged frame then holds inter_off, inter_rows, sub_off, sx, sy as
+        World.floe_frame of a single context's writer with the same lists does, bit for bit"""
+        self._library_only("set_floe_output_lists")
+        w = self.world
+        word = w.frame_lists(lists)
+        w._chk(w.L.sz_tile_set_floe_output_lists(w.h, int(writer), word))
+        w._floe_lists[int(writer)] = word
+
+    @staticmethod
+    def tile_frame_bytes(mask, M, N, V, lists=0, R=0, S=0, K=0):
+        """what a tile frame of M local rows (N owned parents), V ring points takes of its writer's arena (TileFrameLayout / TileListLayout,
+        csrc/sz_record_tile.hpp): World.frame_bytes, the M order keys, and with lists the K entries of the last step's key table (interactions
+        only) and the list sections of R interaction rows and S sub-floe points"""
+        lists = World.frame_lists(lists)
+        plain = World.frame_bytes(mask, M, N, V)
+        return plain + 8 * M + (8 * K if lists & 1 else 0) + World.frame_bytes(mask, M, N, V, lists, R, S) - plain
+
+    def frame_list_keys(self, writer, k):
+        """the key table of this rank's tile frame k (local): the sorted order keys of the rows the last step had behind the owned parents"""
+        w = self.world
+        n = C.c_int64(0)
+        w._chk(w.L.sz_tile_floe_frame_list_keys(w.h, int(writer), int(k), C.byref(n), None))
+        keys = np.zeros(max(int(n.value), 1), np.int64)
+        w._chk(w.L.sz_tile_floe_frame_list_keys(w.h, int(writer), int(k), C.byref(n), capi.ptr(keys, capi._lp)))
+        return keys[:int(n.value)].copy()
+
+    def floe_frame_lists_info(self, writer, k):
+        """(lists word, interaction rows, sub-floe points) of the MERGED frame k (local: from the counts kept with the frame)"""
+        w = self.world
+        word = C.c_uint32(0); tot = [C.c_int64(0), C.c_int64(0)]
+        w._chk(w.L.sz_tile_floe_frame_lists_info(w.h, int(writer), int(k), C.byref(word), *(C.byref(v) for v in tot)))
+        return int(word.value), int(tot[0].value), int(tot[1].value)
 
     def set_grid_output(self, writer, dt_out, xg=None, yg=None, outputs=None, max_frames=64):
         """World.set_grid_output for this rank's tile (the same arguments on every rank): every rank holds every grid frame, summed over the ranks"""
@@ -751,7 +786,9 @@ class TiledWorld:
 
     def floe_frame_local(self, writer, k, members=None):
         """this rank's tile frame k of a writer (local): World.floe_frame over its own rows -- M, N and ghost_idx are local -- plus `key`, the
-        order key of every row: a parent's global number, a ghost's (pass << 40) + 4 * parent key + k"""
+        order key of every row: a parent's global number, a ghost's (pass << 40) + 4 * parent key + k.  Of a writer with lists also this rank's
+        own lists -- the partner column of inter_rows untranslated: global number + 1, or order key + 1 of a ghost of the last step -- and
+        `lists`, the word of the lists the frame holds"""
         w = self.world
         fr = w.floe_frame(writer, k, members)
         key = np.zeros(max(fr["M"], 1), np.int64)
@@ -761,7 +798,8 @@ class TiledWorld:
 
     def floe_frame(self, writer, k, members=None):
         """floe frame k of a writer over the global list (collective: every rank calls it alike): the rows of all ranks merged by order key inside
-        the library -- World.floe_frame of the single context's recorded run, bit for bit in every member"""
+        the library -- World.floe_frame of the single context's recorded run, bit for bit in every member, the lists of a writer with lists
+        included; such a frame also has `lists`, the word of the lists it holds (a frame recorded right behind migrate() has lost its interactions)"""
         self._library_only("floe_frame")
         return self.world.floe_frame(writer, k, members, _merged=True)
 

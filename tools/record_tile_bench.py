@@ -11,8 +11,17 @@ The cost of ONE output step is (block - plain block) / output steps in the block
 warms every shape and is not counted; every repeat is printed, then the median.
 `--off-rounds R --parent-tree PATH`: ms/step of a run with NO writer set, on this tree and on another built checkout (the parent commit's:
 its package and library), in fresh rank processes each, alternating, R rounds: the writer-off path must cost what it cost before.
+`--off-writer`: the same with a floe writer WITHOUT lists set (all column groups, an output step every DT_OUT steps): the recorded step of a
+writer without lists must cost what it cost before, too.
+`--lists`: the arm with both lists (sz_tile_set_floe_output_lists) instead of the arms above, floe writers only, in the same repeats:
+    plain      no output
+    recorded   a floe writer without lists
+    lists      a floe writer with interactions and sub-floe points (arena 256 MiB: the block must not end `full`)
+    hand       the cut by hand that also downloads interactions (before add_ghosts) and sub-floe points on every rank
+    drain / drain_lists   per frame: the merged download of the frame without / with lists; with lists two collectives, timed apart too: the
+                          columns with the points, and the interactions (which gathers only the keys, the key tables and the rows)
 
-    python tools/record_tile_bench.py [--floes 10000] [--repeats 5] [--off-rounds 0] [--parent-tree PATH] [--off-steps 200]
+    python tools/record_tile_bench.py [--floes 10000] [--repeats 5] [--lists] [--off-rounds 0] [--off-writer] [--parent-tree PATH] [--off-steps 200]
 """
 import argparse
 import datetime
@@ -93,7 +102,86 @@ def _worker_steps(rank, port, floes, repeats, q):
         dist.destroy_process_group()
 
 
-def _worker_off(rank, port, floes, steps, tree, q):
+def _worker_lists(rank, port, floes, repeats, q):
+    import torch.distributed as dist
+    from subzero_jl_amd import fields
+    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=WORLD, timeout=datetime.timedelta(seconds=300))
+    try:
+        cfg = fields.make_config(n_floes=floes, seed=12345)
+        dt = cfg["dt"]
+        P, H, R0, RL, X = (_tiled(cfg, rank, dist) for _ in range(5))          # (X: see below)
+        R0.set_floe_output(0, DT_OUT, arena_bytes=1 << 28)
+        RL.set_floe_output(0, DT_OUT, arena_bytes=1 << 28)
+        RL.set_floe_output_lists(0, ["interactions", "subpoints"])
+        nout = NB // DT_OUT
+
+        def timed(fn):
+            dist.barrier()
+            t0 = time.perf_counter(); fn(); return time.perf_counter() - t0
+
+        def hand(t):
+            for s in range(t, t + NB, DT_OUT):
+                H.sync(); H.world.interactions()
+                H.world.add_ghosts(); H.world._host_stale = True; H.world._pull(); H.world.subpoints(); H.world.remove_ghosts()
+                assert H.run(DT_OUT, s, dt, **RUN) == DT_OUT
+            H.sync()
+
+        ROWS = ["inter_off", "inter_rows"]
+
+        def drain(w, split=None):
+            """every frame down, merged; split: the seconds of the column-and-points call and of the interactions call, each a collective"""
+            nf, ng, full = w.output_frames()
+            assert nf[0] == nout and not full, (nf, full)
+            sizes = []
+            for k in range(nout):
+                if split is None:
+                    fr = w.floe_frame(0, k)
+                else:
+                    t0 = time.perf_counter()
+                    fr = w.floe_frame(0, k, members=COLS)
+                    t1 = time.perf_counter()
+                    fr.update(w.floe_frame(0, k, members=ROWS))
+                    split[0] += t1 - t0; split[1] += time.perf_counter() - t1
+                sizes.append(sum(v.nbytes for v in fr.values() if isinstance(v, np.ndarray)))
+            w.clear_frames()
+            return sizes
+
+        from subzero_jl_amd import capi
+        COLS = [m for g in capi.FRAME_BITS for m in capi.FRAME_MEMBERS.get(g, [g])] + capi.FRAME_LIST_MEMBERS["subpoints"]
+
+        rows, t, bytes0, bytesL = [], WARM, 0, 0
+        for rep in range(repeats + 1):
+            # the block that follows the drain of the large frames runs at a third of its speed whichever world it is (§9i: the single-context
+            # arm saw the same): a world that is not measured takes it
+            X.run(NB, t, dt, **RUN); X.sync()
+            tp = timed(lambda: (P.run(NB, t, dt, **RUN), P.sync()))
+            t0 = timed(lambda: (R0.run(NB, t, dt, **RUN), R0.sync()))
+            tl = timed(lambda: (RL.run(NB, t, dt, **RUN), RL.sync()))
+            th = timed(lambda: hand(t))
+            box = {}
+            td0 = timed(lambda: box.update(a=drain(R0)))
+            split = [0.0, 0.0]
+            tdl = timed(lambda: box.update(b=drain(RL, split)))
+            bytes0, bytesL = max(box["a"]), max(box["b"])
+            t += NB
+            if rep == 0:
+                continue
+            rows.append(dict(plain_ms_per_step=tp / NB * 1e3, recorded_step_ms=(t0 - tp) / nout * 1e3, lists_step_ms=(tl - tp) / nout * 1e3,
+                             hand_lists_step_ms=(th - tp) / nout * 1e3, merged_download_ms=td0 / nout * 1e3, merged_download_lists_ms=tdl / nout * 1e3,
+                             of_it_columns_and_points_ms=split[0] / nout * 1e3, of_it_interactions_ms=split[1] / nout * 1e3))
+            q.put(f"rank {rank} repeat {rep}: " + "  ".join(f"{k} {v:.3f}" for k, v in rows[-1].items()))
+        same = all(np.array_equal(P.owned(n), w.owned(n)) for w in (R0, RL, H) for n in ("cx", "cy", "u", "v", "xi"))
+        q.put(f"rank {rank} of {WORLD} sharing one GPU over the host channel (wall times of a rehearsal), {floes} floes ({len(P.gidx)} owned), "
+              f"{repeats} repeats of {NB} steps with {nout} output steps each; merged frame {bytes0} bytes without lists, {bytesL} with; median (min .. max): "
+              + "  ".join(f"{k} {statistics.median(r[k] for r in rows):.3f} ({min(r[k] for r in rows):.3f} .. {max(r[k] for r in rows):.3f})" for k in rows[0])
+              + f"; final states equal: {same}")
+        q.put(None)
+    finally:
+        dist.destroy_process_group()
+
+
+def _worker_off(rank, port, floes, steps, tree, writer, q):
     if tree:
         sys.path.insert(0, tree)          # (in front of this tree: the other checkout's package and the library beside it)
     import torch.distributed as dist
@@ -103,6 +191,8 @@ def _worker_off(rank, port, floes, steps, tree, q):
     try:
         cfg = fields.make_config(n_floes=floes, seed=12345)
         tw = _tiled(cfg, rank, dist)
+        if writer:
+            tw.set_floe_output(0, DT_OUT, arena_bytes=1 << 29)
         dist.barrier()
         t0 = time.perf_counter()
         assert tw.run(steps, WARM, cfg["dt"], **RUN) == steps
@@ -148,17 +238,24 @@ def main():
     ap.add_argument("--off-rounds", type=int, default=0)
     ap.add_argument("--off-steps", type=int, default=200)
     ap.add_argument("--parent-tree", default="")
+    ap.add_argument("--lists", action="store_true")
+    ap.add_argument("--off-writer", action="store_true")
+    ap.add_argument("--alternate-order", action="store_true", help="--off-rounds: the tree that runs first changes from round to round")
+    ap.add_argument("--parent-first", action="store_true", help="--off-rounds: the parent's tree runs first in every round (the order is a suspect of its own)")
     a = ap.parse_args()
     if a.repeats > 0:
-        _ranks(_worker_steps, a.floes, a.repeats)
+        _ranks(_worker_lists if a.lists else _worker_steps, a.floes, a.repeats)
     if a.off_rounds > 0:
         arms = {"this build": "", "parent build": os.path.abspath(a.parent_tree)} if a.parent_tree else {"this build": ""}
+        if a.parent_first:
+            arms = dict(reversed(list(arms.items())))
         got = {k: [] for k in arms}
-        for _ in range(a.off_rounds):
-            for name, tree in arms.items():
-                got[name].append(max(_ranks(_worker_off, a.floes, a.off_steps, tree)))          # (the slower rank: the ranks step together)
+        for rnd in range(a.off_rounds):
+            for name, tree in (list(arms.items()) if not (a.alternate_order and rnd % 2) else list(arms.items())[::-1]):
+                got[name].append(max(_ranks(_worker_off, a.floes, a.off_steps, tree, a.off_writer)))          # (the slower rank: the ranks step together)
+        what = f"a floe writer without lists set (an output step every {DT_OUT} steps)" if a.off_writer else "no writer set"
         for name, v in got.items():
-            print(f"no writer set, {name}: ms/step over {a.off_steps} steps, {WORLD} ranks sharing one GPU (wall times of a rehearsal), median {statistics.median(v):.4f} "
+            print(f"{what}, {name}: ms/step over {a.off_steps} steps, {WORLD} ranks sharing one GPU (wall times of a rehearsal), median {statistics.median(v):.4f} "
                   f"(all: {' '.join(f'{x:.4f}' for x in v)})", flush=True)
 
 
